@@ -9,8 +9,10 @@ A step = one `partial_evaluate(table, 0, r)` pass (evaluation_form.rs:61-106) ov
           (Prover::prove rounds, prover.rs:46-63; one all-reduce per pass) and the 2^24-term MSM slice-sharded N ways
           (multilinear_kzg.rs:37-42; one all-gather of N points) beside it under "config5_strong".  `--scaling weak` makes the
           headline a 2^24 table per GPU instead; by default that run is the secondary key "weak".
-The line also carries "msm" (one 2^24-term MSM per GPU) and, at N = 1, "configs": BASELINE configs 2, 3 and 4 timed and checked.
-Everything that is timed is checked afterwards: the fold against the oracle on sampled entries, every proof through the
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line (and write the outputs of the
+last step under `--dump-outputs DIR`).  Everything else is behind `--full`: with it the line also carries "msm" (one 2^24-term
+MSM per GPU), at N = 1 "configs" (BASELINE configs 1 to 4) and "paths", the CPU baselines, and at N > 1 the legs named above.
+Everything that `--full` times is checked afterwards: the fold against the oracle on sampled entries, every proof through the
 verifier's equations, every MSM through the O(N) identity of its structured bases.
 
 `python bench.py --gpus N` with WORLD_SIZE unset starts the N ranks itself (child processes, one per GPU, before anything
@@ -45,6 +47,11 @@ def parse_args():
     ap.add_argument("--log-n", type=int, default=24)
     ap.add_argument("--scaling", choices=("weak", "strong"), default=None,
                     help="N > 1 only; default strong = BASELINE config 5 (ONE table sharded N ways)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline fold: the post-timing check, CPU baselines, MSM, config-5 legs, BASELINE configs and paths, "
+                         "the weak-scaling leg at N > 1 (the --no-* switches below select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's fold output) as DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-msm", action="store_true", help="skip the per-GPU 2^log-n MSM leg")
     ap.add_argument("--no-config5", action="store_true", help="skip the config-5 legs (sharded proof + sharded MSM)")
@@ -455,6 +462,10 @@ def run_rank(env, args, zk):
             result["roofline"]["traffic_source"] = (f"profiles/{rnd}/fold_2p24_pmc.json (committed summary of separate rocprofv3 --pmc FETCH_SIZE / "
                                                     "WRITE_SIZE passes, FETCH doubled per the gfx950 note; not re-measured in this run)")
             break
+    if args.dump_outputs and rank == 0:
+        dump_fold_outputs(args.dump_outputs, out)
+    if not args.full:                                        # a plain run: the headline alone
+        return result
     if rank == 0 and not args.no_cpu_baseline:
         # what was timed is a correct fold: sampled outputs of the last launch against the oracle on the host mirror of the inputs
         result["post_check"] = post_check_fold(zk, field, out, r, seed, first, stride, half)
@@ -504,6 +515,20 @@ def run_rank(env, args, zk):
     if watchdog:
         watchdog.cancel()
     return result
+
+
+def dump_fold_outputs(path, out, rows=1 << 16, seed=0x5EED00D0):
+    """--dump-outputs: the output table of the last timed partial_evaluate, as its caller receives it (Montgomery limbs).  The whole table
+    (2^(log-n - 1) x 32 B) is too large to write, so: a fixed seeded sample of its rows, each as 8 little-endian 32-bit limbs, their row
+    indices, and over ALL rows the sum of each 16-bit piece of the 256-bit word (below 2^(log-n + 16): exact).  float64, every value exact."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    vals = out.evaluated_values                              # (n / 2, 4) uint64
+    n = vals.shape[0]
+    idx = np.arange(n) if n <= rows else np.sort(np.random.default_rng(seed).choice(n, rows, replace=False))
+    np.save(os.path.join(path, "fold_out_sample.npy"), vals[idx].view(np.uint32).astype(np.float64))
+    np.save(os.path.join(path, "fold_out_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "fold_out_piece_sums.npy"), vals.view(np.uint16).sum(axis=0, dtype=np.uint64).astype(np.float64))
 
 
 def secondary_legs_watchdog(env, args, result):

@@ -31,6 +31,11 @@ def test_rank_count_must_be_a_power_of_two():
     assert p.returncode != 0 and "power of two" in (p.stderr + p.stdout)
 
 
+def test_full_and_dump_outputs_are_options():
+    p = run(["--help"])
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+
+
 def last_json(stdout):
     lines = [l for l in stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, stdout[-2000:]
@@ -38,8 +43,44 @@ def last_json(stdout):
 
 
 @pytest.mark.gpu
+def test_plain_line_is_the_headline_and_dumps_the_timed_fold(tmp_path, oracle):
+    # without --full: the headline keys and nothing of the legs behind --full; --dump-outputs writes the last step's fold output, the same
+    # bytes in two runs, equal to the oracle's fold of the host mirror of the bench's table
+    import numpy as np
+    import __graft_entry__ as G
+    dumps = []
+    for k in range(2):
+        d_dir = tmp_path / f"run{k}"
+        p = run(["--steps", "3", "--warmup", "1", "--log-n", "16", "--dump-outputs", str(d_dir)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = last_json(p.stdout)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+            assert key in d, key
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "u32"
+        for key in ("post_check", "cpu_baseline", "msm", "config5_strong", "configs", "paths"):
+            assert key not in d, key
+        files = sorted(f.name for f in d_dir.iterdir())
+        assert files == ["fold_out_piece_sums.npy", "fold_out_sample.npy", "fold_out_sample_index.npy"], files
+        arrs = {f: np.load(d_dir / f) for f in files}
+        assert all(a.dtype == np.float64 for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        dumps.append(arrs)
+    assert all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
+    zk = G.import_package()
+    from zkmle_amd import _lib
+    n = 1 << 16
+    table, r = np.zeros((n, 4), np.uint64), np.zeros(4, np.uint64)
+    _lib.check(zk.lib().zk_host_fill_random(0, 0x5EED0005, 0, n, _lib.p64(table)))     # bench.py SEED_TABLE, one rank
+    _lib.check(zk.lib().zk_host_fill_random(0, 0x5EED0005, n, 1, _lib.p64(r)))
+    want = oracle.partial_evaluate(0, table, 0, r)
+    got = dumps[0]
+    assert np.array_equal(got["fold_out_sample_index.npy"], np.arange(n // 2))            # the whole output fits the sample at 2^16
+    assert np.array_equal(got["fold_out_sample.npy"].astype(np.uint32), np.ascontiguousarray(want).view(np.uint32))
+    assert np.array_equal(got["fold_out_piece_sums.npy"], np.ascontiguousarray(want).view(np.uint16).sum(axis=0, dtype=np.uint64).astype(np.float64))
+
+
+@pytest.mark.gpu
 def test_one_gpu_line_has_the_contract_keys():
-    p = run(["--steps", "5", "--warmup", "2", "--log-n", "16", "--msm-reps", "1", "--no-configs"])
+    p = run(["--full", "--steps", "5", "--warmup", "2", "--log-n", "16", "--msm-reps", "1", "--no-configs"])
     assert p.returncode == 0, p.stderr[-2000:]
     d = last_json(p.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "prewarm_s", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
@@ -63,7 +104,7 @@ def test_one_gpu_line_has_the_contract_keys():
 def test_one_gpu_line_times_every_named_path_and_config():
     # the functions north_star names beyond the fold and the MSM (evaluate, setup, commit, open_and_prove, dense gkr::prove) and BASELINE configs 1-4,
     # each timed AND checked; sizes follow --log-n where they are not fixed by BASELINE
-    p = run(["--steps", "5", "--warmup", "2", "--log-n", "16", "--msm-reps", "1", "--no-msm", "--no-config5"])
+    p = run(["--full", "--steps", "5", "--warmup", "2", "--log-n", "16", "--msm-reps", "1", "--no-msm", "--no-config5"])
     assert p.returncode == 0, p.stderr[-2000:]
     d = last_json(p.stdout)
     pa, cf = d["paths"], d["configs"]
@@ -82,7 +123,7 @@ def test_one_gpu_line_times_every_named_path_and_config():
 @pytest.mark.gpu
 def test_eight_rank_rehearsal_is_strong_scaling_of_one_table():
     # BASELINE config 5's split on one GPU: 8 ranks as threads of the bench process (a one-GPU box allows 6 processes on its card)
-    p = run(["--gpus", "8", "--rehearse", "--steps", "4", "--warmup", "1", "--log-n", "16", "--msm-reps", "1", "--no-cpu-baseline"])
+    p = run(["--full", "--gpus", "8", "--rehearse", "--steps", "4", "--warmup", "1", "--log-n", "16", "--msm-reps", "1", "--no-cpu-baseline"])
     assert p.returncode == 0, p.stderr[-2000:]
     d = last_json(p.stdout)
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["config"]["entries_per_gpu"] == (1 << 16) // 8
@@ -114,7 +155,7 @@ def test_config5_at_its_stated_size_eight_ranks_one_2p24_table():
     # BASELINE config 5 as stated -- ONE 2^24-entry table and ONE 2^24-term MSM split 8 ways -- inside the suite: the 8 ranks are threads sharing the
     # one GPU (not a scaling measurement); what the line checks must hold: the verifier's equations on the sharded proof, the same MSM point on every
     # rank, the O(N) identity of the 2^24 MSM
-    p = run(["--gpus", "8", "--rehearse", "--log-n", "24", "--steps", "20", "--warmup", "5", "--msm-reps", "1", "--no-cpu-baseline", "--no-weak"])
+    p = run(["--full", "--gpus", "8", "--rehearse", "--log-n", "24", "--steps", "20", "--warmup", "5", "--msm-reps", "1", "--no-cpu-baseline", "--no-weak"])
     assert p.returncode == 0, p.stderr[-2000:]
     d = last_json(p.stdout)
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["config"]["entries_per_gpu"] == (1 << 24) // 8 and "failed_legs" not in d
@@ -128,12 +169,12 @@ def test_config5_at_its_stated_size_eight_ranks_one_2p24_table():
 def test_a_stuck_secondary_leg_does_not_take_the_headline_with_it():
     # N > 1: the legs after the headline run collectives; past ZK_BENCH_LEG_DEADLINE the line is printed with what has finished (bench.py
     # secondary_legs_watchdog).  Here the deadline is shorter than the legs take, on the 8-rank rehearsal.
-    p = run(["--gpus", "8", "--rehearse", "--steps", "4", "--warmup", "1", "--log-n", "18", "--msm-reps", "1", "--no-cpu-baseline"],
+    p = run(["--full", "--gpus", "8", "--rehearse", "--steps", "4", "--warmup", "1", "--log-n", "18", "--msm-reps", "1", "--no-cpu-baseline"],
             env={"ZK_BENCH_LEG_DEADLINE": "0.05"})
     assert p.returncode == 0, p.stderr[-2000:]
     d = last_json(p.stdout)
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["value"] > 0 and "roofline" in d
     assert any("watchdog" in leg for leg in d["failed_legs"])
-    p = run(["--gpus", "8", "--rehearse", "--steps", "4", "--warmup", "1", "--log-n", "18", "--msm-reps", "1", "--no-cpu-baseline", "--require-rccl"],
+    p = run(["--full", "--gpus", "8", "--rehearse", "--steps", "4", "--warmup", "1", "--log-n", "18", "--msm-reps", "1", "--no-cpu-baseline", "--require-rccl"],
             env={"ZK_BENCH_LEG_DEADLINE": "0.05"})
     assert p.returncode != 0
