@@ -10,12 +10,12 @@
 // 2^m sums) instead of m.  Same field elements in the messages, same bytes absorbed, same challenges.
 #pragma once
 #include "dev_transcript.cuh"
+#include "round_schedule.h"
 
 namespace zk {
 
 // kMultiMax (mle_kernels.cuh) = 8 rounds per exchange of a grid-wide pass: 2^8 segment sums go to the mailbox's `big` area, 8 challenges
-// come back, one answer line each.  The one-workgroup tail runs up to six rounds per exchange (its sums and challenges live in LDS).
-constexpr int kTailMultiMax = 6;
+// come back, one answer line each.  The one-workgroup tail runs up to kTailMultiMax = 6 rounds per exchange (round_schedule.h basic_tail_step).
 
 // ---- the exchange inside the producer ----------------------------------------------------------------------------------------
 // r2 ran a one-workgroup kernel (multi_finish_kernel) behind every pass: reduce the partials, post, wait for the challenges.  r3: the
@@ -151,7 +151,7 @@ template <class F> __global__ void __launch_bounds__(64) multi_finish_kernel(Mul
     multi_publish_and_wait<F>(f, lane);
 }
 
-// Every round of a table of <= kTailLen entries (none of them started), one workgroup: per exchange up to kMultiMax rounds -- segment sums,
+// Every round of a table of <= kTailLen entries (none of them started), one workgroup: per exchange basic_tail_step rounds -- segment sums,
 // post, the challenges, the folds level by level -- until 2^m <= 16 entries are left, which go to the host as they are (the "segment sums"
 // of one-entry segments) and finish there.  The first level folds `in` into `buf` (the caller's table stays intact), the rest in place.
 struct BasicTailArgs {
@@ -171,8 +171,7 @@ template <class F> __global__ void __launch_bounds__(kTailBlock) basic_tail_kern
     size_t cl = a.len, cs = a.chal_slot;
     uint64_t seq = a.seq0;
     while (cl >= 2) {
-        const unsigned lg = 31u - (unsigned)__builtin_clz((unsigned)cl);
-        const unsigned m = lg < (unsigned)kTailMultiMax ? lg : (unsigned)kTailMultiMax, nseg = 1u << m;
+        const unsigned m = basic_tail_step(cl), nseg = 1u << m;
         const size_t seglen = cl >> m;
         if (seglen == 1) {
             if (tid < nseg) ev[tid] = fe_load<F>(src, tid);

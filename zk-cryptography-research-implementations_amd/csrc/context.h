@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string>
 
 #include "../../include/zkmle.h"
@@ -62,6 +63,11 @@ void pool_free(void *p);
 
 inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
 inline unsigned ilog2(size_t x) { unsigned k = 0; while (x >>= 1) k++; return k; }
+// ZK_PROOF_TRACE=1 (measurement only): host clock and in-kernel stamps of a proof's phases on stderr
+inline bool proof_trace() {
+    static const bool v = [] { const char *e = getenv("ZK_PROOF_TRACE"); return e && e[0] == '1'; }();
+    return v;
+}
 inline int field_limbs64(int field) { return field == ZK_FQ381 ? 6 : (field >= 0 && field <= 3 ? 4 : -1); }
 
 }  // namespace zk

@@ -12,6 +12,7 @@
 // Round messages: basic sumcheck prover.rs:50-58 (two sums, big-endian), GKR sumcheck
 // sumcheck_gkr_protocol.rs:41-55 (Lagrange coefficients over 0..d, little-endian).
 #pragma once
+#include "round_schedule.h"
 #include "sumcheck_kernels.cuh"
 
 #ifndef TS          // timing hooks, defined by tools/microbench_finish.hip only
@@ -632,9 +633,8 @@ template <class F> __global__ void __launch_bounds__(64) gkr_link_wait_kernel(Li
 // Below ~2^11 entries a round is pure latency (one lane's chain of ~16 dependent products + the transcript step); as two
 // launches per round it costs ~36 us, most of it launch, partial-sum round trip and a second reduction.  One workgroup keeps
 // the sponge in LDS, folds + evaluates (lane i owns pair index i), reduces straight to the evaluations, runs the
-// transcript step in wave 0 and broadcasts the challenge through LDS.  Same arithmetic, same bytes absorbed.
-constexpr int kTailBlock = 512;
-constexpr size_t kTailLen = 4 * (size_t)kTailBlock;
+// transcript step in wave 0 and broadcasts the challenge through LDS.  Same arithmetic, same bytes absorbed.  Rounds per exchange: tail_step
+// (round_schedule.h), the schedule the host's requests follow.
 constexpr int kTailSplit = 512;      // (pair index, table) lanes of a split round: 2 x 32 B each in LDS
 
 struct TailArgs {
@@ -657,7 +657,7 @@ struct TailArgs {
     // folded by the first one before anything else
     int pending2;
     // two_rounds (host-assisted step, two-factor products; 0 = never): while the tables have at most this many (product, quad) pairs, TWO rounds per
-    // exchange (see the kernel)
+    // exchange (round_schedule.h tail_step; see the kernel)
     int two_rounds;
 };
 #define ZK_TAIL_STAMP(k) do { if (a.trace && tid == 0) a.trace[6 * j + (k)] = wall_clock64(); } while (0)
@@ -751,7 +751,7 @@ __global__ void __launch_bounds__(kTailBlock) sumcheck_tail_kernel(TailArgs a) {
     const unsigned wv = tid >> 6;
     for (;;) {
         if constexpr (NFAC == 2) {
-            while (mb && a.two_rounds && cl >= 8 && (size_t)a.nprod * (cl / 8) <= (size_t)a.two_rounds) {
+            while (tail_takes_two(cl, a.nprod, mb ? a.two_rounds : 0)) {    // tail_step 2
                 const size_t ol = cl / 2, qq = ol / 4, o2 = ol / 2;
                 char *d1 = (char *)a.buf[j & 1], *d2 = (char *)a.buf[(j + 1) & 1];
                 ZK_TAIL_STAMP(0);
@@ -856,7 +856,7 @@ __global__ void __launch_bounds__(kTailBlock) sumcheck_tail_kernel(TailArgs a) {
                 j += 2;
             }
         }
-        if (cl < 4) break;
+        if (cl < 4) break;                                   // tail_step 0, else 1:
         // fold by r AND evaluate the next round (sumcheck_kernels.cuh)
         const size_t q = cl / 4, ol = cl / 2;
         char *dst = (char *)a.buf[j & 1];

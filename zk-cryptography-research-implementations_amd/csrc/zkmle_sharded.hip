@@ -22,6 +22,7 @@
 
 #include "context.h"
 #include "mle_kernels.cuh"
+#include "round_schedule.h"
 #include "transcript.h"
 
 using namespace zk;
@@ -383,11 +384,10 @@ int sharded_rounds(zk_comm *c, int field, int mode, const zk_table *const *tabs,
     const size_t nrounds = ilog2(L) + ilog2(G);
     if (G > 1024 || !is_pow2(G)) return ZK_E_ARG;
     // ZK_PROOF_TRACE=1 (measurement): host clock of this call's phases on stderr
-    static const bool trace = [] { const char *e = getenv("ZK_PROOF_TRACE"); return e && e[0] == '1'; }();
     struct Clock {
         bool on; double t0, last; static double now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; }
         void mark(const char *what) { if (!on) return; const double t = now(); fprintf(stderr, "[proof trace] %-28s +%7.1f us (%8.1f)\n", what, t - last, t - t0); last = t; }
-    } clk{trace, Clock::now(), 0};
+    } clk{proof_trace(), Clock::now(), 0};
     clk.last = clk.t0;
     zk_rounds *r = nullptr;
     ZK_TRY(zk_rounds_new(field, mode, nprod, nfac, nrounds, t, &r));
@@ -414,7 +414,6 @@ int sharded_rounds(zk_comm *c, int field, int mode, const zk_table *const *tabs,
     DevBuf limbs;
     ZK_TRY(limbs.alloc(zk_rounds_limbs_len(r) * 8));
     uint64_t *lp = (uint64_t *)limbs.p;
-    const size_t kTail = 2048;                                           // kTailLen (dev_transcript.cuh): one-launch replicated tail
     TableSet ping, pong;
     std::vector<const zk_table *> cur(tabs, tabs + ntab);
     bool absorbed = false;                                               // the evaluations of `cur` are in the transcript
@@ -424,16 +423,12 @@ int sharded_rounds(zk_comm *c, int field, int mode, const zk_table *const *tabs,
         // basic sumcheck, several rounds per pass and per all-reduce (basic_multi.cuh): the top-bit segments of the global table are
         // the top-bit segments of every rank's shard, so the 2^m segment sums add up over the ranks like the two half sums do
         const size_t W = (size_t)field_limbs64(field) * 2 + 1;
-        auto pass = [&](size_t global_len) {                               // the rounds left, spread evenly over the passes they need
-            const unsigned left = (unsigned)(ilog2(global_len) - ilog2(kTail)), passes = (left + kmax - 1) / kmax;
-            return (left + passes - 1) / passes;
-        };
         const zk_table *one = tabs[0];
-        if (L * G > kTail) {
+        if (L * G > kTailLen) {                                            // down to the one-launch replicated tail
             ZK_TRY(ping.alloc(field, L / 2, 1));
             ZK_TRY(pong.alloc(field, L / 4 ? L / 4 : 1, 1));
             TableSet *dst = &ping, *other = &pong;
-            unsigned m = pass(L * G);
+            unsigned m = rounds_per_pass(L * G, (int)kmax);
             // one rank: nothing to all-reduce -- every pass's last workgroup runs the exchange itself (limbs = null)
             uint64_t *xl = G > 1 ? lp : nullptr;
             ZK_TRY(zk_rounds_multi_evals(r, one, m, xl));
@@ -443,7 +438,7 @@ int sharded_rounds(zk_comm *c, int field, int mode, const zk_table *const *tabs,
                     ZK_TRY(zk_rounds_multi_absorb(r, lp, m));
                 }                                                          // (one rank: no exchange ran, none is counted -- zk_comm_stats)
                 const size_t n = L >> m;
-                const unsigned mn = n * G > kTail ? pass(n * G) : 0u;
+                const unsigned mn = n * G > kTailLen ? (unsigned)rounds_per_pass(n * G, (int)kmax) : 0u;
                 ZK_TRY(zk_rounds_multi_fold_evals(r, one, dst->t[0], m, mn, xl));
                 one = dst->t[0];
                 TableSet *x = dst; dst = other; other = x;
@@ -469,7 +464,7 @@ int sharded_rounds(zk_comm *c, int field, int mode, const zk_table *const *tabs,
         ZK_TRY(zk_rounds_multi_tail(r, &view));
         return collect_agreed();
     }
-    if (L * G > kTail) {
+    if (L * G > kTailLen) {
         ZK_TRY(ping.alloc(field, L / 2, ntab));
         ZK_TRY(pong.alloc(field, L / 4 ? L / 4 : 1, ntab));
         ZK_TRY(zk_rounds_evals(r, cur.data(), lp));
@@ -477,7 +472,7 @@ int sharded_rounds(zk_comm *c, int field, int mode, const zk_table *const *tabs,
         ZK_TRY(zk_rounds_absorb(r, lp));
         absorbed = true;
         TableSet *dst = &ping, *other = &pong;
-        while (L * G > kTail) {                                          // local rounds: fold + next evaluations, all-reduce, transcript
+        while (L * G > kTailLen) {                                          // local rounds: fold + next evaluations, all-reduce, transcript
             ZK_TRY(zk_rounds_fold_evals(r, cur.data(), dst->t.data(), lp));
             ZK_TRY(c->all_reduce_i64(lp, round_words));
             ZK_TRY(zk_rounds_absorb(r, lp));

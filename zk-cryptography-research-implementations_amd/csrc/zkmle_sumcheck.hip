@@ -18,6 +18,7 @@
 #include "dev_transcript.cuh"
 #include "basic_multi.cuh"
 #include "fold_multi.h"
+#include "round_schedule.h"
 #include "sumcheck_kernels.cuh"
 #include "transcript.h"
 #include "univariate.h"
@@ -251,82 +252,69 @@ template <class F> struct DeviceRounds {
         Fe<F> ev[kMaxPts];
         for (int t = 0; t < q.npts; t++) ev[t] = mb_get(mb->ev + 12 * t);
         if (q.derive1) ev[1] = fe_sub<F>(running_claim, ev[0]);                // the producer skipped the point 1 (dev_transcript.cuh kDerive1)
-        Fe<F> r;
         if (q.mode == 0) {                                                     // prover.rs:50-58: the two half sums, big-endian
             if (q.with_claim) {
                 hs[q.claim_slot] = fe_add<F>(ev[0], ev[1]);                    // :28
                 htr->template append_be<F>(hs[q.claim_slot]);                  // :40-41
             }
             for (int t = 0; t < q.npts; t++) htr->template append_be<F>(ev[t]);
-            r = htr->template random_challenge_as_field_element<F>();
+            const Fe<F> r = htr->template random_challenge_as_field_element<F>();
             publish_challenge(seq, r);
             for (int t = 0; t < q.npts; t++) hs[q.msg_slot + t] = ev[t];
+            hs[q.chal_slot] = r;
             running_claim = fe_add<F>(ev[0], fe_mul<F>(r, fe_sub<F>(ev[1], ev[0])));
-        } else {                                                               // sumcheck_gkr_protocol.rs:46-55: Lagrange coefficients, little-endian
-            if (q.with_claim) htr->template append_be<F>(hs[q.claim_slot]);    // :35
-            // coefficient d as the canonical integer straight away: evaluations (stored form) x the basis as canonical integers
-            const size_t n2 = (size_t)q.npts * q.npts;
-            uint8_t bytes[kMaxPts * 4 * F::N];
-            for (int d = 0; d < q.npts; d++) {
-                Fe<F> cc = fe_mul<F>(ev[0], hbasis[n2 + d]);
-                for (int i = 1; i < q.npts; i++) cc = fe_add<F>(cc, fe_mul<F>(ev[i], hbasis[n2 + (size_t)i * q.npts + d]));
-                memcpy(bytes + (size_t)d * 4 * F::N, cc.l, 4 * F::N);          // univariate_to_bytes :145-150: little-endian limbs as they lie (LE host)
-            }
-            htr->append(bytes, (size_t)q.npts * 4 * F::N);
-            r = htr->template random_challenge_as_field_element<F>();
+        } else {
+            if (q.with_claim) htr->template append_be<F>(hs[q.claim_slot]);    // sumcheck_gkr_protocol.rs:35
+            const Fe<F> r = gkr_step(ev, q.npts);
             publish_challenge(seq, r);
-            Fe<F> c[kMaxPts];
-            for (int d = 0; d < q.npts; d++) {
-                c[d] = fe_mul<F>(ev[0], hbasis[d]);
-                for (int i = 1; i < q.npts; i++) c[d] = fe_add<F>(c[d], fe_mul<F>(ev[i], hbasis[(size_t)i * q.npts + d]));
-                hs[q.msg_slot + d] = c[d];
-            }
-            Fe<F> acc = c[q.npts - 1];
-            for (int d = q.npts - 2; d >= 0; d--) acc = fe_add<F>(fe_mul<F>(acc, r), c[d]);
-            running_claim = acc;
+            gkr_keep(ev, q.npts, r, q.msg_slot, q.chal_slot);
         }
-        hs[q.chal_slot] = r;
     }
-    // one transcript step of a two-factor GKR round from its evaluations at 0, 1, infinity (sumcheck_gkr_protocol.rs:46-55): absorbs the coefficients
-    // (canonical, little-endian) and samples the challenge -- only what the challenge depends on; keep_gkr3 does the bookkeeping afterwards
-    Fe<F> step_gkr3(const Fe<F> (&ev)[3]) {
-        const size_t n2 = 9;
-        uint8_t bytes[3 * 4 * F::N];
-        for (int d = 0; d < 3; d++) {
+    // one transcript step of a GKR round from its npts evaluations (sumcheck_gkr_protocol.rs:46-55): absorbs the Lagrange coefficients (canonical,
+    // little-endian) and samples the challenge -- only what the challenge depends on; gkr_keep does the bookkeeping after the answer is out.
+    // Inlined, so that the two-round exchange's constant npts = 3 unrolls it.
+    __attribute__((always_inline)) Fe<F> gkr_step(const Fe<F> *ev, int npts) {
+        // coefficient d as the canonical integer straight away: evaluations (stored form) x the basis as canonical integers
+        const size_t n2 = (size_t)npts * npts;
+        uint8_t bytes[kMaxPts * 4 * F::N];
+        for (int d = 0; d < npts; d++) {
             Fe<F> cc = fe_mul<F>(ev[0], hbasis[n2 + d]);
-            for (int i = 1; i < 3; i++) cc = fe_add<F>(cc, fe_mul<F>(ev[i], hbasis[n2 + (size_t)i * 3 + d]));
-            memcpy(bytes + (size_t)d * 4 * F::N, cc.l, 4 * F::N);
+            for (int i = 1; i < npts; i++) cc = fe_add<F>(cc, fe_mul<F>(ev[i], hbasis[n2 + (size_t)i * npts + d]));
+            memcpy(bytes + (size_t)d * 4 * F::N, cc.l, 4 * F::N);              // univariate_to_bytes :145-150: little-endian limbs as they lie (LE host)
         }
-        htr->append(bytes, sizeof bytes);
+        htr->append(bytes, (size_t)npts * 4 * F::N);
         return htr->template random_challenge_as_field_element<F>();
     }
-    // the proof's copy of that round (coefficients in the stored form, the challenge) and the running claim
-    void keep_gkr3(const Fe<F> (&ev)[3], const Fe<F> &r, size_t msg_slot, size_t chal_slot) {
-        Fe<F> c[3];
-        for (int d = 0; d < 3; d++) {
+    // the proof's copy of that round (coefficients in the stored form, the challenge) and the running claim, the message at r
+    __attribute__((always_inline)) void gkr_keep(const Fe<F> *ev, int npts, const Fe<F> &r, size_t msg_slot, size_t chal_slot) {
+        Fe<F> c[kMaxPts];
+        for (int d = 0; d < npts; d++) {
             c[d] = fe_mul<F>(ev[0], hbasis[d]);
-            for (int i = 1; i < 3; i++) c[d] = fe_add<F>(c[d], fe_mul<F>(ev[i], hbasis[(size_t)i * 3 + d]));
+            for (int i = 1; i < npts; i++) c[d] = fe_add<F>(c[d], fe_mul<F>(ev[i], hbasis[(size_t)i * npts + d]));
             hs[msg_slot + d] = c[d];
         }
         hs[chal_slot] = r;
-        running_claim = fe_add<F>(fe_mul<F>(fe_add<F>(fe_mul<F>(c[2], r), c[1]), r), c[0]);
+        Fe<F> acc = c[npts - 1];
+        for (int d = npts - 2; d >= 0; d--) acc = fe_add<F>(fe_mul<F>(acc, r), c[d]);
+        running_claim = acc;
     }
     // TWO rounds of a two-factor GKR sumcheck from the nine sums the tail posts (dev_transcript.cuh, sumcheck_tail_kernel): round A's evaluations are sums of
     // them; round B's are polynomials in round A's challenge with those sums as coefficients.  q.s[0] = slots per round.  The kernel is spinning: both
-    // challenges go out before any bookkeeping.
-    void serve_round2(const Req &q, uint64_t seq) {
+    // challenges go out before any bookkeeping.  False (nothing answered): not a request of three-point rounds.
+    bool serve_round2(const Req &q, uint64_t seq) {
+        if (q.npts != 3) return false;
         Fe<F> S[9];
         for (int t = 0; t < 9; t++) S[t] = mb_get(mb->big + 12 * t);
         const Fe<F> &P0 = S[0], &P1 = S[1], &Q0 = S[2], &Q1 = S[3], &D0 = S[4], &D1 = S[5], &EE = S[6], &FF = S[7], &GG = S[8];
         const size_t per = q.s[0];
         const Fe<F> evA[3] = {fe_add<F>(P0, P1), fe_add<F>(Q0, Q1), fe_add<F>(D0, D1)};
-        const Fe<F> rA = step_gkr3(evA);
+        const Fe<F> rA = gkr_step(evA, 3);
         auto quad = [&](const Fe<F> &k0, const Fe<F> &k1, const Fe<F> &k2) {          // k0 + rA (k1 - k0 - k2) + rA^2 k2
             const Fe<F> mid = fe_sub<F>(fe_sub<F>(k1, k0), k2);
             return fe_add<F>(fe_mul<F>(fe_add<F>(fe_mul<F>(k2, rA), mid), rA), k0);
         };
         const Fe<F> evB[3] = {quad(P0, Q0, D0), quad(P1, Q1, D1), quad(EE, FF, GG)};
-        const Fe<F> rB = step_gkr3(evB);
+        const Fe<F> rB = gkr_step(evB, 3);
         const Fe<F> both[2] = {rA, rB};
         for (int i = 0; i < 2; i++)
             for (int k = 0; k < F::N; k++) __atomic_store_n(&mb->ans8[i][1 + k], both[i].l[k], __ATOMIC_RELAXED);
@@ -334,8 +322,9 @@ template <class F> struct DeviceRounds {
             __atomic_store_n(&mb->ans8[i][0], (uint32_t)seq, __ATOMIC_RELEASE);
             __atomic_store_n(&mb->ans8[i][15], (uint32_t)seq, __ATOMIC_RELEASE);
         }
-        keep_gkr3(evA, rA, q.msg_slot, q.chal_slot);
-        keep_gkr3(evB, rB, q.msg_slot + per, q.chal_slot + per);
+        gkr_keep(evA, 3, rA, q.msg_slot, q.chal_slot);
+        gkr_keep(evB, 3, rB, q.msg_slot + per, q.chal_slot + per);
+        return true;
     }
     // basic sumcheck, q.npts rounds from the 2^npts segment sums of the current table (basic_multi.cuh): the basic sumcheck on the
     // table of the sums, S -- round i sends its two half sums and folds its top variable by the challenge
@@ -416,7 +405,7 @@ template <class F> struct DeviceRounds {
             if (q.kind == kRound) serve_round(q, seq);           // publishes its answer itself, as early as it can
             else {
                 if (q.kind == kMulti) serve_multi(q, seq);
-                else if (q.kind == kRound2) serve_round2(q, seq);
+                else if (q.kind == kRound2) { if (!serve_round2(q, seq)) { service_rc = ZK_E_ARG; break; } }
                 else if (q.kind == kLink) serve_link(q);
                 else for (int k = 0; k < q.ntab; k++) hs[q.fin_slot + k] = mb_get(mb->fin + 12 * k);
                 __atomic_store_n(&mb->cpu_seq, seq, __ATOMIC_RELEASE);
@@ -430,6 +419,22 @@ template <class F> struct DeviceRounds {
     void push_req(const Req &q) {
         std::lock_guard<std::mutex> lk(req_mu);
         reqs.push_back(q);
+    }
+    // one request per exchange, pushed in the order the kernels post
+    void push_round(int mode, int npts, int with_claim, size_t claim_slot, size_t msg_slot, size_t chal_slot, int derive1 = 0) {
+        push_req(Req{kRound, mode, npts, with_claim, derive1, 0, claim_slot, msg_slot, chal_slot});
+    }
+    // two three-point GKR rounds: messages at msg_slot, msg_slot + per; challenges at chal_slot, chal_slot + per
+    int push_round2(int npts, size_t msg_slot, size_t chal_slot, size_t per) {
+        if (npts != 3) return ZK_E_ARG;
+        push_req(Req{kRound2, 1, npts, 0, 0, 0, 0, msg_slot, chal_slot, 0, {per}});
+        return ZK_OK;
+    }
+    // basic sumcheck, rounds round .. round + m - 1: slots of round k 1 + 3 k, 2 + 3 k (sums), 3 + 3 k (challenge), claim 0
+    void push_multi(int m, size_t round) { push_req(Req{kMulti, 0, m, round == 0 ? 1 : 0, 0, 0, 0, 1 + 3 * round, 3 + 3 * round, 0, {3}}); }
+    void push_final(int ntab, size_t fin_slot) { push_req(Req{kFinal, 0, 0, 0, 0, ntab, 0, 0, 0, fin_slot}); }
+    void push_link(size_t wb_src, size_t wc_src, size_t wb_slot, size_t wc_slot, size_t alpha_slot, size_t beta_slot, size_t claim_slot) {
+        push_req(Req{kLink, 1, 0, 0, 0, 0, 0, 0, 0, 0, {wb_src, wc_src, wb_slot, wc_slot, alpha_slot, beta_slot, claim_slot}});
     }
     size_t nreq() {
         std::lock_guard<std::mutex> lk(req_mu);
@@ -461,7 +466,7 @@ template <class F> struct DeviceRounds {
         a.claim_slot = claim_slot; a.msg_slot = msg_slot; a.chal_slot = chal_slot;
         a.prev_msg_slot = msg_slot - per; a.prev_chal_slot = chal_slot - per;
         if (host_mode) {                                    // the derivation moves to the host with the rest of the step
-            push_req(Req{kRound, mode, npts, with_claim, derive_prev, 0, claim_slot, msg_slot, chal_slot, 0, {0, 0, 0, 0, 0, 0, 0}});
+            push_round(mode, npts, with_claim, claim_slot, msg_slot, chal_slot, derive_prev);
             a.seq = nreq();
             a.flags = 0;
             derive_prev = 0;
@@ -480,34 +485,34 @@ template <class F> struct DeviceRounds {
     int round_fin(int grid, int npts, int mode, int with_claim, size_t claim_slot, size_t msg_slot, size_t chal_slot, int derive_prev, RoundFin *out,
                   bool expand = false) {
         if (!host_mode) return ZK_E_ARG;
-        push_req(Req{kRound, mode, npts, with_claim, derive_prev, 0, claim_slot, msg_slot, chal_slot, 0, {0, 0, 0, 0, 0, 0, 0}});
-        unsigned group = 32;
-        while ((unsigned)(grid + group - 1) / group > 200u) group *= 2;   // one 64-byte counter slot per group (context.h kSyncCounterBytes)
-        *out = RoundFin{(unsigned *)syncw, (uint64_t *)((char *)syncw + kSyncCounterBytes), npts, derive_prev, group, nullptr, mb_dev, (uint64_t)nreq(), proof(),
-                        chal_slot, expand ? uexp() : nullptr};
+        push_round(mode, npts, with_claim, claim_slot, msg_slot, chal_slot, derive_prev);
+        *out = RoundFin{(unsigned *)syncw, (uint64_t *)((char *)syncw + kSyncCounterBytes), npts, derive_prev, fin_group(grid), nullptr, mb_dev, (uint64_t)nreq(),
+                        proof(), chal_slot, expand ? uexp() : nullptr};
         return ZK_OK;
     }
     // a TWO-round exchange in the last workgroup of split2_round_kernel: nine sums out, the challenges of rounds `first` and `first + 1` back
     // (messages at msg_slot, msg_slot + per; challenges at chal_slot, chal_slot + per)
     int round2_fin(int grid, size_t msg_slot, size_t chal_slot, size_t per, RoundFin *out) {
         if (!host_mode) return ZK_E_ARG;
-        push_req(Req{kRound2, 1, 3, 0, 0, 0, 0, msg_slot, chal_slot, 0, {per, 0, 0, 0, 0, 0, 0}});
-        unsigned group = 32;
-        while ((unsigned)(grid + group - 1) / group > 200u) group *= 2;
-        *out = RoundFin{(unsigned *)syncw, (uint64_t *)((char *)syncw + kSyncCounterBytes), 9, 0, group, nullptr, mb_dev, (uint64_t)nreq(), proof(), chal_slot, nullptr, per};
+        ZK_TRY(push_round2(3, msg_slot, chal_slot, per));
+        *out = RoundFin{(unsigned *)syncw, (uint64_t *)((char *)syncw + kSyncCounterBytes), 9, 0, fin_group(grid), nullptr, mb_dev, (uint64_t)nreq(), proof(), chal_slot, nullptr, per};
         return ZK_OK;
     }
     // the same for a sharded table: the kernel's last workgroup leaves the npts sums as limb words for the all-reduce, nothing is posted
     RoundFin round_fin_limbs(int grid, int npts, int skip1, uint64_t *limbs_out) const {
+        return RoundFin{(unsigned *)syncw, (uint64_t *)((char *)syncw + kSyncCounterBytes), npts, skip1, fin_group(grid), limbs_out, nullptr, 0, nullptr, 0, nullptr};
+    }
+    // workgroups per arrival group of a producer of `grid` workgroups: one 64-byte counter slot per group (context.h kSyncCounterBytes)
+    static unsigned fin_group(int grid) {
         unsigned group = 32;
         while ((unsigned)(grid + group - 1) / group > 200u) group *= 2;
-        return RoundFin{(unsigned *)syncw, (uint64_t *)((char *)syncw + kSyncCounterBytes), npts, skip1, group, limbs_out, nullptr, 0, nullptr, 0, nullptr};
+        return group;
     }
     // host mode, basic sumcheck (basic_multi.cuh): rounds round .. round + m - 1 from the 2^m segment sums an all-reduce has left as limb
     // words (sharded table); slots of round k: 1 + 3 k, 2 + 3 k (sums), 3 + 3 k (challenge), claim 0
     int launch_multi(const uint64_t *limbs_in, int m, size_t round) {
         if (!host_mode || !limbs_in || m < 1 || m > kMultiMax) return ZK_E_ARG;
-        push_req(Req{kMulti, 0, m, round == 0 ? 1 : 0, 0, 0, 0, 1 + 3 * round, 3 + 3 * round, 0, {3, 0, 0, 0, 0, 0, 0}});
+        push_multi(m, round);
         MultiArgs a{limbs_in, m, mb_dev, (uint64_t)nreq(), proof(), 3 + 3 * round, 3};
         multi_finish_kernel<F><<<1, 64, 0, cur_stream()>>>(a);
         ZK_HIP(hipGetLastError());
@@ -518,10 +523,9 @@ template <class F> struct DeviceRounds {
     // for the all-reduce and posts nothing (launch_multi with limbs_in follows the collective).
     int multi_fin(int m, size_t round, MultiFin *out) {
         if (!host_mode || m < 1 || m > kMultiMax) return ZK_E_ARG;
-        push_req(Req{kMulti, 0, m, round == 0 ? 1 : 0, 0, 0, 0, 1 + 3 * round, 3 + 3 * round, 0, {3, 0, 0, 0, 0, 0, 0}});
+        push_multi(m, round);
         *out = MultiFin{(unsigned *)syncw, (uint64_t *)((char *)syncw + kSyncCounterBytes), m, nullptr, mb_dev, (uint64_t)nreq(), proof(), 3 + 3 * round, 3, nullptr};
-        static const bool trace = [] { const char *e = getenv("ZK_PROOF_TRACE"); return e && e[0] == '1'; }();
-        if (trace && nfin_traced < 8) {
+        if (proof_trace() && nfin_traced < 8) {
             if (!fin_trace.p) { ZK_TRY(fin_trace.alloc(8 * 4 * 8)); ZK_HIP(hipMemsetAsync(fin_trace.p, 0, 8 * 4 * 8, cur_stream())); }
             out->trace = (uint64_t *)fin_trace.p + 4 * nfin_traced++;
         }
@@ -532,11 +536,10 @@ template <class F> struct DeviceRounds {
     int launch_basic_tail(const void *in, void *buf, size_t len, size_t round) {
         if (!host_mode || len < 2 || len > kTailLen) return ZK_E_ARG;
         BasicTailArgs a{in, buf, len, mb_dev, (uint64_t)nreq() + 1, proof(), 3 + 3 * round, 3};
-        size_t rd = round;
-        for (size_t cl = len; cl >= 2;) {
-            const int lg = (int)ilog2(cl), m = lg < kTailMultiMax ? lg : kTailMultiMax;
-            push_req(Req{kMulti, 0, m, rd == 0 ? 1 : 0, 0, 0, 0, 1 + 3 * rd, 3 + 3 * rd, 0, {3, 0, 0, 0, 0, 0, 0}});
-            rd += (size_t)m;
+        for (size_t cl = len, rd = round; cl >= 2;) {                  // the kernel's own schedule (round_schedule.h)
+            const unsigned m = basic_tail_step(cl);
+            push_multi((int)m, rd);
+            rd += m;
             cl >>= m;
         }
         basic_tail_kernel<F><<<1, kTailBlock, 0, cur_stream()>>>(a);
@@ -564,25 +567,15 @@ template <class F> struct DeviceRounds {
         }
         if (host_mode) {
             a.seq0 = nreq() + 1;
-            size_t rd = round;
+            size_t rd = round, cl = len;
             if (first_evals)                                 // round `round` itself: the request round_fin() would have registered for a launch of its own
-                push_req(Req{kRound, mode, nfac + 1, with_claim, 0, 0, claim_slot, msg_base + per * rd, chal_base + per * rd, 0, {0, 0, 0, 0, 0, 0, 0}});
-            // the kernel's own schedule (dev_transcript.cuh): single rounds while the tables are long, two rounds per exchange once (product, quad) pairs fit a wave
-            size_t cl0 = len;
-            if (pending2) { cl0 = len / 2; rd++; }           // the kernel folds by the first pending challenge before its first exchange
-            for (size_t cl = cl0; cl >= 4;) {
-                if (a.two_rounds && cl >= 8 && (size_t)nprod * (cl / 8) <= (size_t)a.two_rounds) {
-                    push_req(Req{kRound2, mode, nfac + 1, 0, 0, 0, 0, msg_base + per * (rd + 1), chal_base + per * (rd + 1), 0, {per, 0, 0, 0, 0, 0, 0}});
-                    rd += 2;
-                    cl /= 4;
-                } else {
-                    rd++;
-                    push_req(Req{kRound, mode, nfac + 1, 0, 0, 0, 0, msg_base + per * rd, chal_base + per * rd, 0, {0, 0, 0, 0, 0, 0, 0}});
-                    cl /= 2;
-                }
+                push_round(mode, nfac + 1, with_claim, claim_slot, msg_base + per * rd, chal_base + per * rd);
+            if (pending2) { cl /= 2; rd++; }                 // the kernel's own schedule (round_schedule.h tail_step), entered as it enters it
+            for (int step; (step = tail_step(cl, nprod, a.two_rounds)) != 0; cl >>= step, rd += step) {
+                if (step == 2) ZK_TRY(push_round2(nfac + 1, msg_base + per * (rd + 1), chal_base + per * (rd + 1), per));
+                else push_round(mode, nfac + 1, 0, 0, msg_base + per * (rd + 1), chal_base + per * (rd + 1));
             }
-            const bool want_fin = fin_slot != ~(size_t)0;
-            push_req(Req{kFinal, mode, nfac + 1, 0, 0, want_fin ? nprod * nfac : 0, 0, 0, 0, want_fin ? fin_slot : 0, {0, 0, 0, 0, 0, 0, 0}});
+            push_final(fin_slot != ~(size_t)0 ? nprod * nfac : 0, fin_slot);
         }
         if (nfac == 1) sumcheck_tail_kernel<F, 1><<<1, kTailBlock, 0, cur_stream()>>>(a);
         else if (nfac == 2) sumcheck_tail_kernel<F, 2><<<1, kTailBlock, 0, cur_stream()>>>(a);
@@ -619,7 +612,7 @@ template <class F> struct DeviceRounds {
     }
     // the layer link of a GKR proof in host mode: the host answers with alpha and beta once the two tails' final values are in
     int launch_link_host(size_t wb_src, size_t wc_src, size_t wb_slot, size_t wc_slot, size_t alpha_slot, size_t beta_slot, size_t claim_slot) {
-        push_req(Req{kLink, 1, 0, 0, 0, 0, 0, 0, 0, 0, {wb_src, wc_src, wb_slot, wc_slot, alpha_slot, beta_slot, claim_slot}});
+        push_link(wb_src, wc_src, wb_slot, wc_slot, alpha_slot, beta_slot, claim_slot);
         LinkWaitArgs a{mb_dev, proof(), (uint64_t)nreq(), alpha_slot, beta_slot};
         gkr_link_wait_kernel<F><<<1, 64, 0, cur_stream()>>>(a);
         ZK_HIP(hipGetLastError());
@@ -628,7 +621,7 @@ template <class F> struct DeviceRounds {
     // the single synchronisation of the sumcheck: proof slots + sponge back to the host
     int collect(Transcript &tr) {
         if (host_mode) {
-            static const bool trace = [] { const char *e = getenv("ZK_PROOF_TRACE"); return e && e[0] == '1'; }();
+            const bool trace = proof_trace();
             const double tc0 = now_ms();
             const int rc = close_service();
             const double tc1 = now_ms();
@@ -677,15 +670,6 @@ static int multi_kmax() {                                  // ZK_BASIC_ROUNDS_PE
     }();
     return v;
 }
-// rounds of the next pass over a table of `global_len` entries (> kTailLen): never past the length the tail takes over at, and the rounds
-// left are spread evenly over the passes they need (13 rounds = 7 + 6 rather than 8 + 5: the host's share of an exchange grows with 2^m,
-// and the fold of 8 variables reads 256 streams per lane -- r3 sweep at 2^24 / 2^20, ms per proof: m <= 4 0.338 / 0.123, 5 0.346 / 0.120,
-// 6 0.330 / 0.121, 7 0.332 / 0.137 (7 + 2), 8 0.348 / 0.191)
-static int multi_pass_rounds(size_t global_len) {
-    const int left = (int)ilog2(global_len) - (int)ilog2(kTailLen), kmax = multi_kmax();
-    const int passes = (left + kmax - 1) / kmax;
-    return (left + passes - 1) / passes;
-}
 template <class F> int launch_seg_sums(const void *in, size_t len, int m, void *part, unsigned *bps_out, const MultiFin *fin = nullptr) {
     const size_t seglen = len >> m;
     const unsigned bps = multi_bps(seglen, m);
@@ -729,12 +713,12 @@ template <class F> int basic_prove(const zk_table *table, Transcript &tr, uint64
     // Every transcript step from here on runs on the device (dev_transcript.cuh): no host round trip per round.
     DeviceRounds<F> dr;
     ZK_TRY(dr.init(tr, std::vector<Fe<F>>(), 1 + 3 * (size_t)nvars));
+    const void *cur = table->dptr;
+    void *dst = bufA.p, *other = bufB.p;
+    size_t cl = len, round = 0;
     if (dr.host_mode) {                                                // several rounds per pass over the table (basic_multi.cuh)
-        const void *cur = table->dptr;
-        void *dst = bufA.p, *other = bufB.p;
-        size_t cl = len, round = 0;
         if (cl > kTailLen) {
-            int m = multi_pass_rounds(cl);
+            int m = rounds_per_pass(cl, multi_kmax());
             unsigned bps;
             MultiFin fin;
             // every pass's last workgroup runs the exchange on the segment sums the pass leaves: rounds round .. round + m - 1 (:50-58)
@@ -742,7 +726,7 @@ template <class F> int basic_prove(const zk_table *table, Transcript &tr, uint64
             ZK_TRY((launch_seg_sums<F>(cur, cl, m, part, &bps, &fin)));    // :74-89, by 2^m segments
             for (;;) {
                 const size_t n = cl >> m;
-                const int mn = n > kTailLen ? multi_pass_rounds(n) : 0;
+                const int mn = n > kTailLen ? rounds_per_pass(n, multi_kmax()) : 0;
                 const void *rp[kMultiMax];
                 for (int i = 0; i < m; i++) rp[i] = dr.slot_ptr(3 + 3 * (round + (size_t)i));
                 if (mn) ZK_TRY(dr.multi_fin(mn, round + (size_t)m, &fin));
@@ -759,41 +743,28 @@ template <class F> int basic_prove(const zk_table *table, Transcript &tr, uint64
             }
         }
         ZK_TRY(dr.launch_basic_tail(cur, dst, cl, round));
-        ZK_TRY(dr.collect(tr));
-        g_stats.ms_rounds = (float)(now_ms() - t1);
-        store_el<F>(claimed_sum, dr.slot(0));
-        for (unsigned rd = 0; rd < nvars; rd++) {
-            store_el<F>(round_polys + (size_t)(2 * rd) * L64, dr.slot(1 + 3 * (size_t)rd));
-            store_el<F>(round_polys + (size_t)(2 * rd + 1) * L64, dr.slot(2 + 3 * (size_t)rd));
-            if (challenges) store_el<F>(challenges + (size_t)rd * L64, dr.slot(3 + 3 * (size_t)rd));
+    } else {
+        {   // round-0 half sums (split_polynomial_and_sum_each :74-89); claimed sum = their sum (:28), absorbed first (:40-41)
+            size_t seg = len / 2;
+            int grid = reduce_grid_for(seg);
+            segment_sums_kernel<F><<<grid, kBlock, 0, cur_stream()>>>(table->dptr, seg, 2, part);
+            ZK_HIP(hipGetLastError());
+            ZK_TRY(dr.launch_finish(part, (size_t)grid, 2, 0, 1, 0, 1, 3));               // :50-58 of round 0
         }
-        return ZK_OK;
-    }
-    {   // round-0 half sums (split_polynomial_and_sum_each :74-89); claimed sum = their sum (:28), absorbed first (:40-41)
-        size_t seg = len / 2;
-        int grid = reduce_grid_for(seg);
-        segment_sums_kernel<F><<<grid, kBlock, 0, cur_stream()>>>(table->dptr, seg, 2, part);
-        ZK_HIP(hipGetLastError());
-        ZK_TRY(dr.launch_finish(part, (size_t)grid, 2, 0, 1, 0, 1, 3));               // :50-58 of round 0
-    }
-    const void *cur = table->dptr;
-    void *dst = bufA.p, *other = bufB.p;
-    size_t cl = len;
-    unsigned round = 0;
-    for (; cl > kTailLen; round++) {                                   // :46
-        const void *rp = dr.slot_ptr(3 + 3 * (size_t)round);           // this round's challenge (:58), on the device
-        size_t q = cl / 4;                                             // :61-63 fused with the next round's :50
-        int grid = reduce_grid_for(q);
-        fold_half_sums_kernel<F><<<grid, kBlock, 0, cur_stream()>>>(cur, dst, q, fe_zero<F>(), part, rp);
-        ZK_HIP(hipGetLastError());
-        ZK_TRY(dr.launch_finish(part, (size_t)grid, 2, 0, 0, 0, 1 + 3 * (size_t)(round + 1), 3 + 3 * (size_t)(round + 1)));
-        cur = dst;
-        void *nx = other;
-        other = dst;
-        dst = nx;
-        cl /= 2;
-    }
-    {   // rounds on <= kTailLen entries: one launch; the half sums are the evaluations at 0 and 1 of a 1-factor product
+        for (; cl > kTailLen; round++) {                               // :46
+            const void *rp = dr.slot_ptr(3 + 3 * round);               // this round's challenge (:58), on the device
+            size_t q = cl / 4;                                         // :61-63 fused with the next round's :50
+            int grid = reduce_grid_for(q);
+            fold_half_sums_kernel<F><<<grid, kBlock, 0, cur_stream()>>>(cur, dst, q, fe_zero<F>(), part, rp);
+            ZK_HIP(hipGetLastError());
+            ZK_TRY(dr.launch_finish(part, (size_t)grid, 2, 0, 0, 0, 1 + 3 * (round + 1), 3 + 3 * (round + 1)));
+            cur = dst;
+            void *nx = other;
+            other = dst;
+            dst = nx;
+            cl /= 2;
+        }
+        // rounds on <= kTailLen entries: one launch; the half sums are the evaluations at 0 and 1 of a 1-factor product
         SumPolyTables tabs{};
         tabs.in[0] = cur;
         ZK_TRY(dr.launch_tail(tabs, dst, other, 1, 1, cl, 0, round, 1, 3, 3, ~(size_t)0));
@@ -801,10 +772,10 @@ template <class F> int basic_prove(const zk_table *table, Transcript &tr, uint64
     ZK_TRY(dr.collect(tr));
     g_stats.ms_rounds = (float)(now_ms() - t1);
     store_el<F>(claimed_sum, dr.slot(0));
-    for (unsigned round = 0; round < nvars; round++) {
-        store_el<F>(round_polys + (size_t)(2 * round) * L64, dr.slot(1 + 3 * (size_t)round));
-        store_el<F>(round_polys + (size_t)(2 * round + 1) * L64, dr.slot(2 + 3 * (size_t)round));
-        if (challenges) store_el<F>(challenges + (size_t)round * L64, dr.slot(3 + 3 * (size_t)round));
+    for (size_t rd = 0; rd < nvars; rd++) {
+        store_el<F>(round_polys + (2 * rd) * L64, dr.slot(1 + 3 * rd));
+        store_el<F>(round_polys + (2 * rd + 1) * L64, dr.slot(2 + 3 * rd));
+        if (challenges) store_el<F>(challenges + rd * L64, dr.slot(3 + 3 * rd));
     }
     return ZK_OK;
 }
@@ -1001,18 +972,23 @@ template <class F> int gkr_rounds_enqueue(DeviceRounds<F> &dr, size_t s0, const 
             else memcpy(tabs.cval[k / nfac], const_host + (k / nfac) * L64, esz);
         }
     }
-    // The fused round of the two-factor lazy kernel folds by the challenge as a UNIFORM multiplier (ufield.cuh UniMul); the exchange that receives
-    // the challenge of a round whose fold is such a launch leaves it in that form (host-assisted step; otherwise the kernel's waves work it out).
-    const size_t tail_from0 = (nfac == 2 && nprod >= 2) ? kTailLen / 2 : kTailLen;
+    // The one-workgroup tail takes over at 2048 entries, at 1024 for two or more two-factor products: its round on 2048 entries is a
+    // chain of 14 products per lane (28 us measured, tools ZK_TAIL_TRACE), the grid-wide round + finish launch pair takes 19.
+    const size_t tail_from = (nfac == 2 && nprod >= 2) ? kTailLen / 2 : kTailLen;
     // ZK_GRID_TWO_ROUNDS=0: the short grid-wide rounds stay one round per launch (measurement / fallback switch)
     static const bool grid_two = [] { const char *e = getenv("ZK_GRID_TWO_ROUNDS"); return !(e && e[0] == '0'); }();
     static const size_t grid_two_max_q = [] { const char *e = getenv("ZK_GRID_TWO_BITS"); int b = e ? atoi(e) : 17; return (size_t)1 << (b < 6 ? 6 : (b > 24 ? 24 : b)); }();   // r4 sweep, 4 x 2^22 (15 / 16 / 17 / 18 / 19): 0.710 / 0.724 / 0.692 / 0.731 / 0.741 ms
     const bool two_regime_ok = grid_two && dr.host_mode && nfac == 2 && nprod == 2;
+    // the round on tables of `n` entries starts the grid-wide two-round launches (split2_round_kernel), which go on down to the tail.  Entered at
+    // an ODD log2 of the table length: the launches then end on 2^10 entries, which is where the one-workgroup tail is cheapest to enter.
+    auto grid_two_from = [&](size_t n) { return two_regime_ok && n >= 512 && n / 4 <= grid_two_max_q && (ilog2(n) & 1u); };
+    // The fused round of the two-factor lazy kernel folds by the challenge as a UNIFORM multiplier (ufield.cuh UniMul); the exchange that receives
+    // the challenge of a round whose fold is such a launch leaves it in that form (host-assisted step; otherwise the kernel's waves work it out).
     auto takes_uniform = [&](size_t cl_folded) {                     // cl_folded: the length of the tables that challenge folds
-        return dr.host_mode && nfac == 2 && LazyProducts<F>::value && cl_folded > tail_from0 && !fold_round_takes_split((int)nprod, (int)nfac, cl_folded / 4, true) &&
-               !(two_regime_ok && cl_folded >= 512 && cl_folded / 4 <= grid_two_max_q && (ilog2(cl_folded) & 1u));
+        return dr.host_mode && nfac == 2 && LazyProducts<F>::value && cl_folded > tail_from && !fold_round_takes_split((int)nprod, (int)nfac, cl_folded / 4, true) &&
+               !grid_two_from(cl_folded);
     };
-    const bool tail_takes_all = len <= tail_from0;                   // every round, the first one's evaluations included, in the one-workgroup tail
+    const bool tail_takes_all = len <= tail_from;                   // every round, the first one's evaluations included, in the one-workgroup tail
     if (!tail_takes_all) {   // round 0 evaluations
         size_t half = len / 2;
         int grid = reduce_grid_for(half);
@@ -1030,14 +1006,10 @@ template <class F> int gkr_rounds_enqueue(DeviceRounds<F> &dr, size_t s0, const 
     char *dst = (char *)bufA.p, *other = (char *)bufB.p;
     size_t cl = len;
     unsigned round = 0;
-    // The one-workgroup tail takes over at 2048 entries, at 1024 for two or more two-factor products: its round on 2048 entries is a
-    // chain of 14 products per lane (28 us measured, tools ZK_TAIL_TRACE), the grid-wide round + finish launch pair takes 19.
-    const size_t tail_from = (nfac == 2 && nprod >= 2) ? kTailLen / 2 : kTailLen;
     for (; cl > tail_from; round++) {                                  // :37
         const void *rp = dr.slot_ptr(s0 + per * round + npts);         // :55, on the device
         size_t ol = cl / 2, q = cl / 4;
-        // (entered at an ODD log2 of the table length: the launches then end on 2^10 entries, which is where the one-workgroup tail is cheapest to enter)
-        if (two_regime_ok && cl >= 512 && q <= grid_two_max_q && (ilog2(cl) & 1u)) {
+        if (grid_two_from(cl)) {
             // From here down to the tail: TWO rounds per launch and exchange (sumcheck_kernels.cuh split2_round_kernel).  The first launch folds by the one
             // pending challenge; every later one by the two its predecessor's exchange brought; the tail starts by folding with the first of its two.
             auto launch2 = [&](size_t in_len, size_t first_new_round, const void *rp0, const void *rp1) -> int {
@@ -1243,8 +1215,7 @@ template <class F> struct RoundsImpl : RoundsBase {
         a.claim_slot = 0; a.msg_slot = msg_base + per * round; a.chal_slot = chal_base + per * round;
         a.prev_msg_slot = a.msg_slot - per; a.prev_chal_slot = a.chal_slot - per;      // used with kDerive1 only (round >= 1)
         if (dr.host_mode) {                                  // the step runs on this rank's host (every rank's host does the same)
-            dr.push_req(typename DeviceRounds<F>::Req{DeviceRounds<F>::kRound, mode, (int)npts, a.with_claim, skipped1 ? 1 : 0, 0, a.claim_slot,
-                                                       a.msg_slot, a.chal_slot, 0, {0, 0, 0, 0, 0, 0, 0}});
+            dr.push_round(mode, (int)npts, a.with_claim, a.claim_slot, a.msg_slot, a.chal_slot, skipped1 ? 1 : 0);
             a.seq = dr.nreq();
             a.flags = 0;
         }
