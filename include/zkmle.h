@@ -101,6 +101,10 @@ int zk_mle_to_bytes(const zk_table *t, uint8_t *host_out);
 int zk_mle_scalar_mul(const zk_table *a, const uint64_t *scalar, zk_table *out, void *stream);
 int zk_mle_add(const zk_table *a, const zk_table *b, zk_table *out, void *stream);
 int zk_mle_sub_scalar(const zk_table *a, const uint64_t *scalar, zk_table *out, void *stream); /* multilinear_kzg.rs:74-78 */
+/* out = sum_j coeffs[j] * tables[j]  (k tables of equal length, 1 <= k <= 64; coeffs: k elements, Montgomery): scalar_mul :49 and
+ * add_polynomials :145 of k tables in one pass.  A table may be passed more than once; out must not overlap any of them.
+ * ZK_E_NVARS: unequal lengths; ZK_E_ARG: k = 0, k > 64, mixed fields, out too short or overlapping.  Extension: no reference counterpart. */
+int zk_mle_linear_combination(const zk_table *const *tables, size_t k, const uint64_t *coeffs, zk_table *out, void *stream);
 int zk_mle_tensor_add(const zk_table *wb, const zk_table *wc, zk_table *out, void *stream);
 int zk_mle_tensor_mul(const zk_table *wb, const zk_table *wc, zk_table *out, void *stream);
 /* iter().sum()  prover.rs:28 ; and split_polynomial_and_sum_each prover.rs:74-89 (out2: 2 elements) */
@@ -353,6 +357,20 @@ int zk_kzg_opening_key_free(zk_kzg_opening_key *k);
 int zk_kzg_opening_key_precompute(zk_kzg_opening_key *k, int window_bits, size_t min_points);
 int zk_kzg_open(const zk_table *poly, const zk_g1_bases *g1_powers, const zk_kzg_opening_key *key,
                 const uint64_t *opening, size_t nopen, size_t n_g2, uint64_t *evaluation, uint64_t *proofs);
+/* Open k polynomials (equal length 2^nopen, BLS12-381 Fr) at ONE point with ONE proof (extension: no reference counterpart).
+ * Transcript (t = NULL: a fresh Transcript::new()), in this order, as plain appends:
+ *   for j < k: x_j || y_j of commitment j, each the canonical 48-byte BIG-endian Fq integer (infinity: 96 zero bytes);
+ *   for i < nopen: opening[i] as field_element_to_bytes (32-byte canonical big-endian, sumcheck_gkr_protocol.rs:152);
+ *   for j < k: evaluations[j], same encoding;
+ *   then gamma = random_challenge_as_field_element() (fiat_shamir_transcript.rs:38).
+ * evaluations: k elements (f_j(opening)); proofs: nopen affine points = open_and_prove of sum_j gamma^j f_j;
+ * gamma (may be NULL): the sampled challenge.  commitments12: k affine points (zk_kzg_commit of each polynomial), bound by the
+ * transcript.  Preconditions and codes as zk_kzg_open, plus ZK_E_NVARS / ZK_E_ARG as zk_mle_linear_combination.  The first
+ * level's combination, quotient and fold are one pass over the k tables; the level MSMs are those of one zk_kzg_open. */
+int zk_kzg_batch_open(const zk_table *const *polys, size_t k, const uint64_t *commitments12,
+                      const zk_g1_bases *g1_powers, const zk_kzg_opening_key *key,
+                      const uint64_t *opening, size_t nopen, size_t n_g2, zk_transcript *t,
+                      uint64_t *evaluations, uint64_t *gamma, uint64_t *proofs);
 
 /* prove_succinct  gkr/src/succinct_gkr_protocol.rs:35-169 (BLS12-381 Fr): the GKR proof of
  * zk_gkr_prove plus commit(inputs) (:42-44) and the two openings at the last layer's rb / rc
@@ -380,6 +398,12 @@ int zk_kzg_setup_g2(const uint64_t *taus, size_t ntaus, uint64_t *out);
  * ng2 > nproofs (the reference indexes proofs[i] for every G2 power, :149-154) */
 int zk_kzg_verify(const uint64_t *commitment12, const uint64_t *opening_values, size_t nopen, const uint64_t *evaluation,
                   const uint64_t *proofs, size_t nproofs, const uint64_t *g2_powers, size_t ng2, int *ok);
+/* The verifier of zk_kzg_batch_open: replays the same transcript steps, then MultilinearKZG::verify (multilinear_kzg.rs:131-158)
+ * on C = sum gamma^j C_j, v = sum gamma^j v_j.  *ok = 1 / 0.  Length codes as zk_kzg_verify; k = 0 -> ZK_E_ARG.  Every status is
+ * returned before the transcript is touched.  Extension: no reference counterpart. */
+int zk_kzg_batch_verify(const uint64_t *commitments12, size_t k, const uint64_t *opening, size_t nopen,
+                        const uint64_t *evaluations, const uint64_t *proofs, size_t nproofs,
+                        const uint64_t *g2_powers, size_t ng2, zk_transcript *t, int *ok);
 
 /* verify_succinct  gkr/src/succinct_gkr_protocol.rs:172-285 (BLS12-381 Fr): GKR verification without the inputs, then the
  * two KZG openings of the committed input polynomial at the last layer's challenges */

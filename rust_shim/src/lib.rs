@@ -124,6 +124,13 @@ pub mod ffi {
         pub fn zk_rounds_collect(r: *mut c_void, t: *mut zk_transcript, claimed: *mut u64, messages: *mut u64, challenges: *mut u64,
                                  final_values: *mut u64) -> c_int;
         pub fn zk_rounds_free(r: *mut c_void) -> c_int;
+        // items beyond the reference (no counterpart there): the k-table linear combination and the batched KZG opening at one point
+        pub fn zk_mle_linear_combination(tables: *const *const zk_table, k: usize, coeffs: *const u64, out: *mut zk_table, stream: *mut c_void) -> c_int;
+        pub fn zk_kzg_batch_open(polys: *const *const zk_table, k: usize, commitments12: *const u64, g1: *const zk_g1_bases, key: *const c_void,
+                                 opening: *const u64, nopen: usize, n_g2: usize, t: *mut zk_transcript, evaluations: *mut u64, gamma: *mut u64,
+                                 proofs: *mut u64) -> c_int;
+        pub fn zk_kzg_batch_verify(commitments12: *const u64, k: usize, opening: *const u64, nopen: usize, evaluations: *const u64,
+                                   proofs: *const u64, nproofs: usize, g2_powers: *const u64, ng2: usize, t: *mut zk_transcript, ok: *mut c_int) -> c_int;
     }
 }
 
@@ -284,6 +291,16 @@ pub mod polynomials {
                     let (a, b) = (DeviceTable::<F>::upload(&poly1.evaluated_values), DeviceTable::<F>::upload(&poly2.evaluated_values));
                     let out = DeviceTable::<F>::alloc(a.len());
                     check(unsafe { ffi::zk_mle_add(a.h, b.h, out.h, std::ptr::null_mut()) });          // length mismatch -> the reference's panic text
+                    Self { evaluated_values: out.download() }
+                }
+                /// Beyond the reference (no counterpart there): sum_j coeffs[j] * polys[j] over k <= 64 polynomials of equal length in one
+                /// pass -- scalar_mul (:49) and add_polynomials (:145) of k tables at once.  Unequal lengths panic as "different number of variables".
+                pub fn linear_combination(polys: &[&MultilinearPolynomial<F>], coeffs: &[F]) -> Self {
+                    assert_eq!(polys.len(), coeffs.len(), "one coefficient per polynomial");
+                    let tabs: Vec<DeviceTable<F>> = polys.iter().map(|p| DeviceTable::<F>::upload(&p.evaluated_values)).collect();
+                    let ptrs: Vec<*const ffi::zk_table> = tabs.iter().map(|t| t.h as *const ffi::zk_table).collect();
+                    let out = DeviceTable::<F>::alloc(tabs.first().map(|t| t.len()).unwrap_or(1));
+                    check(unsafe { ffi::zk_mle_linear_combination(ptrs.as_ptr(), ptrs.len(), as_limbs(coeffs), out.h, std::ptr::null_mut()) });
                     Self { evaluated_values: out.download() }
                 }
                 fn tensor(w_b: &MultilinearPolynomial<F>, w_c: &MultilinearPolynomial<F>, mul: bool) -> MultilinearPolynomial<F> {
@@ -849,12 +866,17 @@ pub mod multilinear_kzg {
     pub mod multilinear_kzg {
         use super::trusted_setup::TrustedSetup;
         use crate::polynomials::multilinear::evaluation_form::MultilinearPolynomial;
+        use crate::transcripts::fiat_shamir::fiat_shamir_transcript::Transcript;
         use crate::*;
         /// multilinear_kzg.rs:10-14
         pub struct MultilinearKZG<F: ZkField, P: ZkPairing> { _phantom_f: std::marker::PhantomData<F>, _phantom_p: std::marker::PhantomData<P> }
         /// multilinear_kzg.rs:16-20
         #[derive(Clone, Debug)]
         pub struct MultilinearKZGProof<F: ZkField, P: ZkPairing> { pub evaluation: F, pub proofs: Vec<P::G1> }
+        /// Beyond the reference (no counterpart there): the proof of k polynomials opened at one point (zk_kzg_batch_open) -- their
+        /// evaluations, the transcript's gamma and the proof points of sum_j gamma^j f_j
+        #[derive(Clone, Debug)]
+        pub struct MultilinearKZGBatchProof<F: ZkField, P: ZkPairing> { pub evaluations: Vec<F>, pub gamma: F, pub proofs: Vec<P::G1> }
 
         impl<F: ZkField, P: ZkPairing> MultilinearKZG<F, P> {
             /// commit_to_polynomial (:25-45): one Pippenger MSM over the resident G1 powers
@@ -881,6 +903,35 @@ pub mod multilinear_kzg {
                 let mut ok: c_int = 0;
                 check(unsafe { ffi::zk_kzg_verify(c.as_ptr(), as_limbs(opening_values), opening_values.len(), el(&proof.evaluation),
                                                   prs.as_ptr(), proof.proofs.len(), g2.as_ptr(), trusted_setup.g2_powers_of_tau.len(), &mut ok) });
+                ok == 1
+            }
+            /// Beyond the reference (no counterpart there): open k polynomials at ONE point with ONE proof.  The commitments
+            /// (x || y, 48-byte big-endian each), the point and the k evaluations (32-byte big-endian) are appended to `transcript`,
+            /// gamma = random_challenge_as_field_element(), and sum_j gamma^j f_j is opened: one set of level MSMs whatever k is.
+            pub fn batch_open_and_prove(polynomials: &[&MultilinearPolynomial<F>], trusted_setup: &TrustedSetup<P>, opening_values: &[F],
+                                        commitments: &[P::G1], transcript: &mut Transcript) -> MultilinearKZGBatchProof<F, P> {
+                assert_eq!(polynomials.len(), commitments.len(), "one commitment per polynomial");
+                let tabs: Vec<DeviceTable<F>> = polynomials.iter().map(|p| DeviceTable::<F>::upload(&p.evaluated_values)).collect();
+                let ptrs: Vec<*const ffi::zk_table> = tabs.iter().map(|t| t.h as *const ffi::zk_table).collect();
+                let cs: Vec<u64> = commitments.iter().flat_map(|c| P::g1_to_limbs(c)).collect();
+                let (mut evs, mut gamma) = (vec![F::zero(); polynomials.len()], F::zero());
+                let mut proofs = vec![0u64; 12 * opening_values.len().max(1)];
+                check(unsafe { ffi::zk_kzg_batch_open(ptrs.as_ptr(), ptrs.len(), cs.as_ptr(), trusted_setup.device().g1, std::ptr::null(),
+                                                      as_limbs(opening_values), opening_values.len(), trusted_setup.g2_powers_of_tau.len(),
+                                                      transcript.h, evs.as_mut_ptr() as *mut u64, el_mut(&mut gamma), proofs.as_mut_ptr()) });
+                MultilinearKZGBatchProof { evaluations: evs, gamma, proofs: proofs.chunks(12).take(opening_values.len()).map(P::g1_from_limbs).collect() }
+            }
+            /// Beyond the reference: the verifier of batch_open_and_prove -- the same transcript steps, then verify (:131-158) on
+            /// C = sum_j gamma^j C_j and v = sum_j gamma^j v_j
+            pub fn batch_verify(trusted_setup: &TrustedSetup<P>, commitments: &[P::G1], opening_values: &[F], proof: &MultilinearKZGBatchProof<F, P>,
+                                transcript: &mut Transcript) -> bool {
+                let cs: Vec<u64> = commitments.iter().flat_map(|c| P::g1_to_limbs(c)).collect();
+                let prs: Vec<u64> = proof.proofs.iter().flat_map(|p| P::g1_to_limbs(p)).collect();
+                let g2: Vec<u64> = trusted_setup.g2_powers_of_tau.iter().flat_map(|q| P::g2_to_limbs(q)).collect();
+                let mut ok: c_int = 0;
+                check(unsafe { ffi::zk_kzg_batch_verify(cs.as_ptr(), commitments.len(), as_limbs(opening_values), opening_values.len(),
+                                                        as_limbs(&proof.evaluations), prs.as_ptr(), proof.proofs.len(), g2.as_ptr(),
+                                                        trusted_setup.g2_powers_of_tau.len(), transcript.h, &mut ok) });
                 ok == 1
             }
         }

@@ -77,6 +77,7 @@ def lib():
         "zk_mle_to_bytes": [vp, u8p],
         "zk_mle_scalar_mul": [vp, u64p, vp, vp],
         "zk_mle_add": [vp, vp, vp, vp],
+        "zk_mle_linear_combination": [C.POINTER(vp), sz, u64p, vp, vp],
         "zk_mle_sub_scalar": [vp, u64p, vp, vp],
         "zk_mle_tensor_add": [vp, vp, vp, vp],
         "zk_mle_tensor_mul": [vp, vp, vp, vp],

@@ -8,6 +8,7 @@
 // (half sums).
 #pragma once
 #include <stdlib.h>
+#include <string.h>
 
 #include "ufield.cuh"
 
@@ -589,6 +590,61 @@ template <class F> __global__ void __launch_bounds__(kBlock) fold_alpha_beta_ker
     }
 }
 
+// ---- linear combination of k tables: out[i] = sum_j c_j f_j[i] (scalar_mul :49 + add_polynomials :145, k at once) ----------------
+// One lane per output, the k inputs one after the other: the products of the weighted sum above (raw_mul_add: L^2 multiply-adds each,
+// no reduction) into 64-bit columns, one Montgomery reduction per output.
+// Bounds.  Columns: normalized after every kRawCarryEvery = 4 products (4 L 2^58 + 2^30 < 2^64 for L <= 14, as in foldk).  Value: the
+// entries are canonical (< p, every kernel of the library leaves canonical elements) and so are the coefficients, so the integer sum is
+// below k p^2 and raw_mont_reduce leaves k p (p / 2^(29 L)) + p, which is below 2 p -- the range u_reduce_once finishes -- for
+// k < 2^(29 L) / p: 141 for BLS12-381 Fr, 169 for both BN254 fields, 2^25 for BLS12-381 Fq.  So k <= kLinCombMax = 64 takes ONE
+// reduction per output and no intermediate one.
+// The coefficients are the same for every lane: they live in the kernel's argument block (constant memory) and each is read with one
+// uniform (scalar) load where it is used; the multiply-adds take it as their scalar operand.
+constexpr int kLinCombMax = 64;
+template <class F> struct LinCombArgs {
+    const void *t[kLinCombMax];         // the k tables (one table may appear more than once)
+    Fe<F> c[kLinCombMax];               // c_j R_u mod p (R_u = 2^(29 L)), canonical, 32-bit limbs: lincomb_coeff
+    int k;
+};
+// the coefficient in the scan's form: entry (x R_std) times (c R_u), divided by R_u once, is (c x) R_std -- the stored form of the product
+template <class F> ZK_HD Fe<F> lincomb_coeff(const Fe<F> &c_std) { return u_to_limbs32<F>(u_reduce_once<F>(u_from_std<F>(c_std))); }
+template <class F> __device__ __forceinline__ Fe<F> lincomb_at(const LinCombArgs<F> &a, size_t i) {
+    RawAcc<F> ra;
+#pragma unroll
+    for (int c = 0; c < 2 * UParams<F>::L; c++) ra.c[c] = 0;
+#pragma unroll 1
+    for (int j0 = 0; j0 < a.k; j0 += kRawCarryEvery) {
+        const int m = a.k - j0 < kRawCarryEvery ? a.k - j0 : kRawCarryEvery;       // uniform
+        Fe<F> x[kRawCarryEvery];
+#pragma unroll
+        for (int q = 0; q < kRawCarryEvery; q++)
+            if (q < m) x[q] = fe_load<F>(a.t[j0 + q], i);                          // all loads of the group in flight together
+#pragma unroll
+        for (int q = 0; q < kRawCarryEvery; q++)
+            if (q < m) raw_mul_add<F>(ra, u_from_limbs32<F>(x[q]), u_from_limbs32<F>(a.c[j0 + q]));
+        raw_normalize<F>(ra);
+    }
+    return u_to_limbs32<F>(u_reduce_once<F>(raw_mont_reduce<F>(ra)));
+}
+// LEVEL = false: out[i] = sum_j c_j f_j[i], i < n.
+// LEVEL = true (the first level of a batched KZG opening, multilinear_kzg.rs:74-119 on g = sum_j c_j f_j; n = half the table length):
+//   q[i] = g[i + n] - g[i]  (compute_quotient_polynomial :165-179 of g - v: the v cancels),  out[i] = (g[i] - v) + z0 q[i]  (the fold of
+//   g - v by z0, partial_evaluate(.., 0, z0)).  g and g - v are never stored: the pass reads the k tables once and writes two half tables.
+template <class F, bool LEVEL> __global__ void __launch_bounds__(kBlock) lincomb_kernel(LinCombArgs<F> a, void *__restrict__ out, size_t n,
+                                                                                       Fe<F> v, Fe<F> z0, void *__restrict__ q) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const Multiplier<F> mz(z0);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const Fe<F> lo = lincomb_at<F>(a, i);
+        if constexpr (LEVEL) {
+            const Fe<F> d = fe_sub<F>(lincomb_at<F>(a, i + n), lo);
+            fe_store<F>(q, i, d);
+            fe_store<F>(out, i, fe_add<F>(fe_sub<F>(lo, v), mz.times(d)));
+        } else {
+            fe_store<F>(out, i, lo);
+        }
+    }
+}
 // ---- element-wise and tensor operations --------------------------------------------------------------
 enum { OP_SCALAR_MUL = 0, OP_ADD = 1, OP_SUB_SCALAR = 2, OP_TO_CANONICAL_BE = 3, OP_HI_MINUS_LO = 4 };
 
@@ -640,5 +696,20 @@ inline int reduce_block_cap() {
     return v;
 }
 inline int reduce_grid_for(size_t work) { return grid_for(work, reduce_block_cap()); }
+
+// launch on `s`: tables = k device pointers, coeffs = k stored-form elements (u64 limbs)
+template <class F, bool LEVEL> inline hipError_t lincomb_launch(const void *const *tables, size_t k, const uint64_t *coeffs, void *out, size_t n,
+                                                               const Fe<F> &v, const Fe<F> &z0, void *q, hipStream_t s) {
+    LinCombArgs<F> a{};
+    for (size_t j = 0; j < k; j++) {
+        Fe<F> c;
+        memcpy(c.l, coeffs + j * (F::N / 2), 4 * F::N);
+        a.t[j] = tables[j];
+        a.c[j] = lincomb_coeff<F>(c);
+    }
+    a.k = (int)k;
+    lincomb_kernel<F, LEVEL><<<grid_for(n), kBlock, 0, s>>>(a, out, n, v, z0, q);
+    return hipGetLastError();
+}
 
 }  // namespace zk

@@ -142,6 +142,30 @@ class Transcript {
     Keccak256 h_;
 };
 
+// The Fiat-Shamir steps of a batched KZG opening (zk_kzg_batch_open / zk_kzg_batch_verify, include/zkmle.h), shared by prover and
+// verifier: the k commitments (affine, x || y, each the canonical 48-byte big-endian Fq integer; infinity = (0, 0) = 96 zero bytes),
+// the nopen opening values and the k evaluations (field_element_to_bytes), then gamma.  powers[j] = gamma^j, j < k.
+inline Fe<Fr381> kzg_batch_challenge(Transcript &t, const uint64_t *commitments12, size_t k, const uint64_t *opening, size_t nopen,
+                                     const uint64_t *evaluations, uint64_t *powers) {
+    for (size_t j = 0; j < 2 * k; j++) {
+        Fe<Fq381> x;
+        memcpy(x.l, commitments12 + 6 * j, 48);
+        t.append_be<Fq381>(x);
+    }
+    for (size_t i = 0; i < nopen + k; i++) {
+        Fe<Fr381> x;
+        memcpy(x.l, i < nopen ? opening + 4 * i : evaluations + 4 * (i - nopen), 32);
+        t.append_be<Fr381>(x);
+    }
+    const Fe<Fr381> gamma = t.random_challenge_as_field_element<Fr381>();
+    Fe<Fr381> p = fe_one<Fr381>();
+    for (size_t j = 0; j < k; j++) {
+        memcpy(powers + 4 * j, p.l, 32);
+        p = fe_mul<Fr381>(p, gamma);
+    }
+    return gamma;
+}
+
 }  // namespace zk
 
 struct zk_transcript {

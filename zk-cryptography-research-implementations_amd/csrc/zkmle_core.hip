@@ -255,6 +255,24 @@ int mle_fold_alpha_beta(const zk_table *in, size_t k, const uint64_t *alpha, con
 }
 
 
+int lincomb_check(const zk_table *const *tables, size_t k, const zk_table *out) {
+    if (!tables || k == 0 || k > (size_t)kLinCombMax) return ZK_E_ARG;
+    for (size_t j = 0; j < k; j++)
+        if (!tables[j] || tables[j]->field != tables[0]->field) return ZK_E_ARG;
+    const int limbs = field_limbs64(tables[0]->field);
+    if (limbs < 0) return ZK_E_ARG;
+    for (size_t j = 0; j < k; j++)
+        if (tables[j]->len != tables[0]->len) return ZK_E_NVARS;          // product_polynomial.rs:16-21's check for a combination
+    if (!out) return ZK_OK;
+    if (out->field != tables[0]->field || out->len < tables[0]->len) return ZK_E_ARG;
+    const size_t bytes = tables[0]->len * (size_t)limbs * 8;
+    const uintptr_t o = (uintptr_t)out->dptr;
+    for (size_t j = 0; j < k; j++) {                                  // the pass reads entry i of every table after writing entry i' < i of out
+        const uintptr_t t = (uintptr_t)tables[j]->dptr;
+        if (o < t + bytes && t < o + bytes) return ZK_E_ARG;
+    }
+    return ZK_OK;
+}
 }  // namespace zk
 
 using namespace zk;
@@ -511,6 +529,19 @@ int zk_mle_add(const zk_table *a, const zk_table *b, zk_table *out, void *stream
     if (a->len != b->len) return ZK_E_LEN_MISMATCH;      // evaluation_form.rs:149-153
     if (out->len < a->len) return ZK_E_ARG;
     return elementwise<OP_ADD>(a, b, nullptr, out, a->len, stream);
+}
+// scalar_mul :49 and add_polynomials :145 over k tables in one pass (lincomb_kernel).  Every status comes before the device check.
+int zk_mle_linear_combination(const zk_table *const *tables, size_t k, const uint64_t *coeffs, zk_table *out, void *stream) {
+    if (!coeffs || !out) return ZK_E_ARG;
+    ZK_TRY(zk::lincomb_check(tables, k, out));
+    ZK_TRY(require_device());
+    const void *ptrs[kLinCombMax];
+    for (size_t j = 0; j < k; j++) ptrs[j] = tables[j]->dptr;
+    const size_t len = tables[0]->len;
+    hipStream_t s = stream ? (hipStream_t)stream : cur_stream();
+    ZK_DISPATCH_FIELD(out->field, ZK_HIP((lincomb_launch<F, false>(ptrs, k, coeffs, out->dptr, len, fe_zero<F>(), fe_zero<F>(), nullptr, s))));
+    out->len = len;
+    return ZK_OK;
 }
 static int tensor_impl(const zk_table *wb, const zk_table *wc, zk_table *out, void *stream, bool mul) {
     if (!wb || !wc || !out || wb->field != wc->field || out->field != wb->field) return ZK_E_ARG;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "context.h"
+#include "transcript.h"
 #define ZK_MSM_LIGHT_KERNELS
 #include "eq_table.cuh"
 #include "msm_kernels.cuh"
@@ -784,6 +785,96 @@ int zk_kzg_open(const zk_table *poly, const zk_g1_bases *g1_powers, const zk_kzg
     return zk::kzg_open_core(poly, g1_powers, key, opening, nopen, nullptr, evaluation, proofs, nullptr);
 }
 
+// Where the quotient of each level of an opening goes: those of the batched (small) levels, zero-padded, in one scalar buffer
+// [j][2^small_bits] (level t = small_t0 + j at offset 2^nlev - 2^(nlev - j)); those of the large levels end to end in `bigq` (level i
+// at offset len - len / 2^i).  Levels t = 1 .. nbig take a plain MSM each.
+struct OpenQuotients {
+    const zk_kzg_opening_key *key = nullptr;
+    bool batched = false;
+    size_t nlev = 0, nbig = 0;
+    DevBuf smallq, bigq;
+    std::vector<size_t> big_off;
+    int alloc(const zk_kzg_opening_key *k, size_t nopen, size_t len) {
+        key = k;
+        batched = k->small_u != nullptr;
+        nlev = k->small_bits + 1;
+        nbig = batched ? k->small_t0 - 1 : nopen;
+        big_off.assign(nbig + 1, 0);
+        for (size_t i = 0; i < nbig; i++) big_off[i + 1] = big_off[i] + (len >> (i + 1));
+        if (batched) ZK_TRY(smallq.alloc((((size_t)1 << nlev) - 1) * 32));
+        if (nbig) ZK_TRY(bigq.alloc(len * 32));
+        return ZK_OK;
+    }
+    void *dst(size_t i) const {                                  // level t = i + 1
+        const size_t t = i + 1;
+        if (t > nbig) return (char *)smallq.p + (((size_t)1 << nlev) - ((size_t)1 << (nlev - (t - key->small_t0)))) * 32;
+        return (char *)bigq.p + big_off[i] * 32;
+    }
+};
+
+// levels from .. nopen - 1 of an opening (:86): quotient = hi half - lo half (compute_quotient_polynomial :165-179) into the level's slot,
+// then the fold by opening[i] (:113-119); `sub` holds the level's table and ends holding the last one
+static int open_levels(const OpenQuotients &oq, size_t from, size_t nopen, const uint64_t *opening, zk_table *&sub, zk_table *&nxt) {
+    int rc = ZK_OK;
+    for (size_t i = from; i < nopen && rc == ZK_OK; i++) {
+        const size_t half = sub->len / 2;
+        elementwise_kernel<Fr381, OP_HI_MINUS_LO><<<grid_for(half), kBlock, 0, cur_stream()>>>(sub->dptr, nullptr, oq.dst(i), half, fe_zero<Fr381>());
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return ZK_E_HIP; }
+        nxt->len = half;
+        rc = zk_mle_fold(sub, 0, opening + 4 * i, nxt, nullptr);
+        zk_table *tt = sub; sub = nxt; nxt = tt;
+    }
+    return rc;
+}
+
+// proof_i = sum_j [blown_up(q)[j]] B_j  (:96-107)  ==  sum_k [q[k]] B^(i+1)_k : task i < nbig; task nbig = the batched small levels.
+// The quotients must be complete (the caller's stream synchronised).
+static int open_msms(const OpenQuotients &oq, uint64_t *proofs) {
+    const zk_kzg_opening_key *key = oq.key;
+    const size_t nbig = oq.nbig, nlev = oq.nlev;
+    const size_t ntasks = nbig + (oq.batched ? 1 : 0);
+    auto run_task = [&](size_t k) -> int {
+        if (k < nbig) {
+            G1Xyzz pi;
+            ZK_TRY(msm_device((const char *)oq.bigq.p + oq.big_off[k] * 32, key->level[k + 1], oq.big_off[k + 1] - oq.big_off[k], 0, &pi, nullptr));
+            affine_to_u64(g1_to_affine(pi), proofs + 12 * k);
+            return ZK_OK;
+        }
+        std::vector<G1Xyzz> pis(nlev);
+        ZK_TRY(msm_core(oq.smallq.p, key->small_u, (size_t)1 << key->small_bits, (unsigned)nlev, true, key->small_c, pis.data(), nullptr));
+        for (size_t j = 0; j < nlev; j++) affine_to_u64(g1_to_affine(pis[j]), proofs + 12 * (key->small_t0 + j - 1));
+        return ZK_OK;
+    };
+    int rc = ZK_OK;
+    const unsigned nthreads = (unsigned)(ntasks < open_threads() ? ntasks : open_threads());
+    if (nthreads <= 1) {
+        for (size_t k = 0; k < ntasks && rc == ZK_OK; k++) rc = run_task(k);
+        return rc;
+    }
+    int dev = 0;
+    std::vector<hipStream_t> streams;
+    if (hipGetDevice(&dev) != hipSuccess) return ZK_E_HIP;
+    ZK_TRY(open_side_streams(dev, nthreads, streams));
+    std::atomic<size_t> next{0};
+    std::vector<int> rcs(nthreads, ZK_OK);
+    std::vector<std::string> errs(nthreads);
+    std::vector<std::thread> workers;
+    for (unsigned w = 0; w < nthreads; w++)
+        workers.emplace_back([&, w] {
+            if (hipSetDevice(dev) != hipSuccess) { rcs[w] = ZK_E_HIP; return; }
+            zk_set_stream((void *)streams[w]);
+            for (size_t k; (k = next.fetch_add(1)) < ntasks;) {           // largest MSM first (tasks are in level order)
+                int r = run_task(k);
+                if (r != ZK_OK) { rcs[w] = r; errs[w] = zk_last_error(); break; }
+            }
+        });
+    for (std::thread &th : workers) th.join();
+    for (unsigned w = 0; w < nthreads && rc == ZK_OK; w++)
+        if (rcs[w] != ZK_OK) { rc = rcs[w]; set_last_error(errs[w]); }
+    return rc;
+}
+
 // The body of open_and_prove.  `v_given` (may be null): the value to subtract instead of poly(opening) -- a rank of a sharded
 // opening passes the GLOBAL evaluation (its shard's own evaluation is something else), the replicated tail passes zero (its table is
 // already f - v).  `last` (may be null): the single entry left of f - v after all the folds.
@@ -808,71 +899,63 @@ extern "C++" int zk::kzg_open_core(const zk_table *poly, const zk_g1_bases *g1_p
     if (rc == ZK_OK) rc = table_alloc_pooled(ZK_FR381, poly->len, &sub);                        // pooled: a small opening is not two hipMalloc / hipFree pairs
     if (rc == ZK_OK) rc = zk_mle_sub_scalar(poly, evaluation, sub, nullptr);                    // :74-80
     if (rc == ZK_OK && poly->len >= 2) rc = table_alloc_pooled(ZK_FR381, poly->len / 2, &nxt);
-    // quotients of the batched (small) levels are collected, zero-padded, in one scalar buffer [j][2^small_bits];
-    // those of the large levels lie end to end in `bigq` (level i at offset len - len / 2^i)
-    const bool batched = key->small_u != nullptr && rc == ZK_OK;
-    const size_t nlev = key->small_bits + 1, small_total = ((size_t)1 << nlev) - 1;
-    const size_t nbig = batched ? key->small_t0 - 1 : nopen;          // levels t = 1 .. nbig take a plain MSM each
-    DevBuf smallq, bigq;
-    if (batched) rc = smallq.alloc(small_total * 32);
-    if (rc == ZK_OK && nbig) rc = bigq.alloc(poly->len * 32);
-    std::vector<size_t> big_off(nbig + 1, 0);
-    for (size_t i = 0; i < nopen && rc == ZK_OK; i++) {                                          // :86
-        size_t half = sub->len / 2;
-        const size_t t = i + 1;
-        const bool small = t > nbig;
-        // batched level j = t - small_t0 sits at offset 2^nlev - 2^(nlev - j) of the end-to-end scalar buffer
-        void *qdst = small ? (void *)((char *)smallq.p + (((size_t)1 << nlev) - ((size_t)1 << (nlev - (t - key->small_t0)))) * 32)
-                           : (void *)((char *)bigq.p + big_off[i] * 32);
-        if (!small) big_off[i + 1] = big_off[i] + half;
-        // quotient = hi half - lo half (compute_quotient_polynomial :165-179)
-        elementwise_kernel<Fr381, OP_HI_MINUS_LO><<<grid_for(half), kBlock, 0, cur_stream()>>>(sub->dptr, nullptr, qdst, half, fe_zero<Fr381>());
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); rc = ZK_E_HIP; break; }
-        nxt->len = half;
-        rc = zk_mle_fold(sub, 0, opening + 4 * i, nxt, nullptr);                                 // :113-119
-        zk_table *tt = sub; sub = nxt; nxt = tt;
-    }
+    OpenQuotients oq;
+    if (rc == ZK_OK) rc = oq.alloc(key, nopen, poly->len);
+    if (rc == ZK_OK) rc = open_levels(oq, 0, nopen, opening, sub, nxt);
     if (rc == ZK_OK && hipStreamSynchronize(cur_stream()) != hipSuccess) rc = ZK_E_HIP;
     if (rc == ZK_OK && last && zk_table_download(sub, last) != ZK_OK) rc = ZK_E_HIP;               // `sub` has one entry left
-    // proof_i = sum_j [blown_up(q)[j]] B_j  (:96-107)  ==  sum_k [q[k]] B^(i+1)_k : task i < nbig; task nbig = the batched small levels
-    const size_t ntasks = nbig + (batched ? 1 : 0);
-    auto run_task = [&](size_t k) -> int {
-        if (k < nbig) {
-            G1Xyzz pi;
-            ZK_TRY(msm_device((const char *)bigq.p + big_off[k] * 32, key->level[k + 1], big_off[k + 1] - big_off[k], 0, &pi, nullptr));
-            affine_to_u64(g1_to_affine(pi), proofs + 12 * k);
-            return ZK_OK;
+    if (rc == ZK_OK) rc = open_msms(oq, proofs);
+    zk_table_free(sub);
+    zk_table_free(nxt);
+    zk_kzg_opening_key_free(own);
+    return rc;
+}
+
+// Batched opening (extension: no reference counterpart): open_and_prove of g = sum_j gamma^j f_j with gamma from the transcript
+// (kzg_batch_challenge).  The first level of g - v -- the combination, its quotient and its fold by opening[0] -- is ONE pass over the k
+// tables (lincomb_kernel<Fr381, true>: g and g - v are never stored); levels 2 .. n and the level MSMs are those of kzg_open_core.
+int zk_kzg_batch_open(const zk_table *const *polys, size_t k, const uint64_t *commitments12, const zk_g1_bases *g1_powers,
+                      const zk_kzg_opening_key *key, const uint64_t *opening, size_t nopen, size_t n_g2, zk_transcript *t,
+                      uint64_t *evaluations, uint64_t *gamma, uint64_t *proofs) {
+    if (!commitments12 || !g1_powers || (!opening && nopen) || !evaluations || (!proofs && nopen)) return ZK_E_ARG;
+    ZK_TRY(lincomb_check(polys, k, nullptr));
+    if (polys[0]->field != ZK_FR381) return ZK_E_ARG;
+    if (nopen != n_g2) return ZK_E_KZG_LEN;                          // as zk_kzg_open
+    const size_t len = polys[0]->len;
+    if (!is_pow2(len)) return ZK_E_NOT_POW2;
+    if (ilog2(len) != nopen) return ZK_E_KZG_LEN;
+    if (len != g1_powers->n) return ZK_E_KZG_LEN;
+    ZK_TRY(require_device());
+    zk_kzg_opening_key *own = nullptr;
+    if (!key) {
+        ZK_TRY(zk_kzg_opening_key_new(g1_powers, &own));
+        key = own;
+    }
+    int rc = key->nvars != nopen ? ZK_E_KZG_LEN : ZK_OK;
+    for (size_t j = 0; j < k && rc == ZK_OK; j++) rc = zk_mle_evaluate(polys[j], opening, nopen, evaluations + 4 * j);
+    std::vector<uint64_t> powers(4 * k);
+    Fe<Fr381> v = fe_zero<Fr381>();
+    if (rc == ZK_OK) {
+        Transcript fresh;
+        const Fe<Fr381> g = kzg_batch_challenge(t ? t->t : fresh, commitments12, k, opening, nopen, evaluations, powers.data());
+        if (gamma) memcpy(gamma, g.l, 32);
+        for (size_t j = 0; j < k; j++) v = fe_add<Fr381>(v, fe_mul<Fr381>(load_el<Fr381>(powers.data() + 4 * j), load_el<Fr381>(evaluations + 4 * j)));
+    }
+    zk_table *sub = nullptr, *nxt = nullptr;
+    OpenQuotients oq;
+    if (rc == ZK_OK && nopen) {
+        rc = table_alloc_pooled(ZK_FR381, len / 2, &sub);
+        if (rc == ZK_OK && len >= 4) rc = table_alloc_pooled(ZK_FR381, len / 4, &nxt);
+        if (rc == ZK_OK) rc = oq.alloc(key, nopen, len);
+        if (rc == ZK_OK) {
+            const void *ptrs[kLinCombMax];
+            for (size_t j = 0; j < k; j++) ptrs[j] = polys[j]->dptr;
+            hipError_t e = lincomb_launch<Fr381, true>(ptrs, k, powers.data(), sub->dptr, len / 2, v, load_el<Fr381>(opening), oq.dst(0), cur_stream());
+            if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); rc = ZK_E_HIP; }
         }
-        std::vector<G1Xyzz> pis(nlev);
-        ZK_TRY(msm_core(smallq.p, key->small_u, (size_t)1 << key->small_bits, (unsigned)nlev, true, key->small_c, pis.data(), nullptr));
-        for (size_t j = 0; j < nlev; j++) affine_to_u64(g1_to_affine(pis[j]), proofs + 12 * (key->small_t0 + j - 1));
-        return ZK_OK;
-    };
-    const unsigned nthreads = (unsigned)(ntasks < open_threads() ? ntasks : open_threads());
-    if (rc == ZK_OK && nthreads <= 1) {
-        for (size_t k = 0; k < ntasks && rc == ZK_OK; k++) rc = run_task(k);
-    } else if (rc == ZK_OK) {
-        int dev = 0;
-        std::vector<hipStream_t> streams;
-        if (hipGetDevice(&dev) != hipSuccess) rc = ZK_E_HIP;
-        if (rc == ZK_OK) rc = open_side_streams(dev, nthreads, streams);
-        std::atomic<size_t> next{0};
-        std::vector<int> rcs(nthreads, ZK_OK);
-        std::vector<std::string> errs(nthreads);
-        std::vector<std::thread> workers;
-        for (unsigned w = 0; w < nthreads && rc == ZK_OK; w++)
-            workers.emplace_back([&, w] {
-                if (hipSetDevice(dev) != hipSuccess) { rcs[w] = ZK_E_HIP; return; }
-                zk_set_stream((void *)streams[w]);
-                for (size_t k; (k = next.fetch_add(1)) < ntasks;) {           // largest MSM first (tasks are in level order)
-                    int r = run_task(k);
-                    if (r != ZK_OK) { rcs[w] = r; errs[w] = zk_last_error(); break; }
-                }
-            });
-        for (std::thread &th : workers) th.join();
-        for (unsigned w = 0; w < nthreads && rc == ZK_OK; w++)
-            if (rcs[w] != ZK_OK) { rc = rcs[w]; set_last_error(errs[w]); }
+        if (rc == ZK_OK) rc = open_levels(oq, 1, nopen, opening, sub, nxt);
+        if (rc == ZK_OK && hipStreamSynchronize(cur_stream()) != hipSuccess) rc = ZK_E_HIP;
+        if (rc == ZK_OK) rc = open_msms(oq, proofs);
     }
     zk_table_free(sub);
     zk_table_free(nxt);

@@ -6,6 +6,7 @@
 
 #include "context.h"
 #include "pairing.h"
+#include "transcript.h"
 
 using namespace zk;
 using namespace zk::pairing;
@@ -105,6 +106,34 @@ int zk_kzg_verify(const uint64_t *commitment12, const uint64_t *opening_values, 
     }
     *ok = f12_eq(pairing_product(in), f12_one()) ? 1 : 0;   // :156
     return ZK_OK;
+}
+
+// zk_kzg_batch_open's verifier: the prover's transcript steps replayed (kzg_batch_challenge), then MultilinearKZG::verify on the
+// combination C = sum_j gamma^j C_j, v = sum_j gamma^j v_j (extension: no reference counterpart)
+int zk_kzg_batch_verify(const uint64_t *commitments12, size_t k, const uint64_t *opening, size_t nopen, const uint64_t *evaluations,
+                        const uint64_t *proofs, size_t nproofs, const uint64_t *g2_powers, size_t ng2, zk_transcript *t, int *ok) {
+    if (!commitments12 || !evaluations || !ok || k == 0 || (!opening && nopen) || (!proofs && nproofs) || (!g2_powers && ng2)) return ZK_E_ARG;
+    if (nopen != nproofs) return ZK_E_KZG_LEN;              // as zk_kzg_verify, before the transcript is touched
+    if (ng2 > nproofs) return ZK_E_KZG_LEN;
+    std::vector<uint64_t> powers(4 * k);
+    Transcript fresh;
+    kzg_batch_challenge(t ? t->t : fresh, commitments12, k, opening, nopen, evaluations, powers.data());
+    G1Xyzz c = g1_xyzz_inf();
+    Fe<Fr381> v = fe_zero<Fr381>();
+    for (size_t j = 0; j < k; j++) {
+        Fe<Fr381> pj, vj;
+        memcpy(pj.l, powers.data() + 4 * j, 32);
+        memcpy(vj.l, evaluations + 4 * j, 32);
+        v = fe_add<Fr381>(v, fe_mul<Fr381>(pj, vj));
+        const Fe<Fr381> e = fr_canonical(powers.data() + 4 * j);
+        c = g1_add(c, g1_mul_canonical(g1_load(commitments12 + 12 * j), e.l, 8));
+    }
+    const G1Affine ca = g1_to_affine(c);
+    uint64_t c12[12], v4[4];
+    fq_store(c12, ca.x);
+    fq_store(c12 + 6, ca.y);
+    memcpy(v4, v.l, 32);
+    return zk_kzg_verify(c12, opening, nopen, v4, proofs, nproofs, g2_powers, ng2, ok);
 }
 
 }  // extern "C"

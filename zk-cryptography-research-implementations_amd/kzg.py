@@ -37,6 +37,8 @@ def _decl():
         "zk_pairing": [u64p, u64p, u64p], "zk_pairing_product_is_one": [u64p, u64p, sz, C.POINTER(C.c_int)],
         "zk_kzg_setup_g2": [u64p, sz, u64p],
         "zk_kzg_verify": [u64p, u64p, sz, u64p, u64p, sz, u64p, sz, C.POINTER(C.c_int)],
+        "zk_kzg_batch_open": [C.POINTER(vp), sz, u64p, vp, vp, u64p, sz, sz, vp, u64p, u64p, u64p],
+        "zk_kzg_batch_verify": [u64p, sz, u64p, sz, u64p, u64p, sz, u64p, sz, vp, C.POINTER(C.c_int)],
     }
     for name, args in sigs.items():
         fn = getattr(lib, name)
@@ -172,6 +174,15 @@ class MultilinearKZGProof:                       # multilinear_kzg.rs:16-20
         self.proofs = proofs
 
 
+class MultilinearKZGBatchProof:
+    """zk_kzg_batch_open's proof of k polynomials at one point (extension: no reference counterpart): the k evaluations, the transcript's
+    gamma and the nopen proof points of sum_j gamma^j f_j"""
+    def __init__(self, evaluations, gamma, proofs):
+        self.evaluations = evaluations
+        self.gamma = gamma
+        self.proofs = proofs
+
+
 class MultilinearKZG:
     @staticmethod
     def commit_to_polynomial(polynomial, trusted_setup):       # :25-45
@@ -202,4 +213,42 @@ class MultilinearKZG:
         L.check(_decl().zk_kzg_verify(L.p64(np.ascontiguousarray(commitment, np.uint64)), L.p64(o) if o.size else L.p64(dummy), o.shape[0],
                                       L.p64(np.ascontiguousarray(proof.evaluation, np.uint64)), L.p64(prs) if prs.size else L.p64(dummy),
                                       prs.shape[0], L.p64(g2), g2.shape[0], C.byref(ok)))
+        return bool(ok.value)
+
+    @staticmethod
+    def batch_open_and_prove(polynomials, trusted_setup, opening_values, commitments, transcript=None):
+        """open k polynomials at ONE point with ONE proof (zk_kzg_batch_open): the commitments, the point and the evaluations are
+        absorbed into `transcript` (None: a fresh one), gamma is sampled, and sum_j gamma^j f_j is opened.  Extension: no reference
+        counterpart."""
+        polys = list(polynomials)
+        o = np.ascontiguousarray(opening_values, np.uint64).reshape(-1, 4)
+        cs = np.ascontiguousarray(commitments, np.uint64).reshape(-1, 12)
+        k = len(polys)
+        evs = np.zeros((max(k, 1), 4), np.uint64)
+        gamma = np.zeros(4, np.uint64)
+        proofs = np.zeros((max(o.shape[0], 1), 12), np.uint64)
+        nvars = polys[0].number_of_variables() if polys else -1
+        key = trusted_setup.opening_key() if (polys and o.shape[0] == nvars == trusted_setup.n_g2_powers_of_tau and
+                                              len(trusted_setup.g1_powers_of_tau) == len(polys[0])) else None
+        handles = (L.vp * max(k, 1))(*[p._h.value for p in polys])
+        optr = L.p64(o) if o.size else L.p64(gamma)
+        L.check(_decl().zk_kzg_batch_open(handles, k, L.p64(cs) if cs.size else L.p64(proofs), trusted_setup.g1_powers_of_tau._h, key,
+                                          optr, o.shape[0], trusted_setup.n_g2_powers_of_tau, transcript._h if transcript is not None else None,
+                                          L.p64(evs), L.p64(gamma), L.p64(proofs)))
+        return MultilinearKZGBatchProof(evs[:k], gamma, proofs[: o.shape[0]])
+
+    @staticmethod
+    def batch_verify(trusted_setup, commitments, opening_values, proof, transcript=None):
+        """zk_kzg_batch_verify: the transcript steps of batch_open_and_prove replayed, then verify on sum gamma^j C_j, sum gamma^j v_j"""
+        cs = np.ascontiguousarray(commitments, np.uint64).reshape(-1, 12)
+        o = np.ascontiguousarray(opening_values, np.uint64).reshape(-1, 4)
+        evs = np.ascontiguousarray(proof.evaluations, np.uint64).reshape(-1, 4)
+        prs = np.ascontiguousarray(proof.proofs, np.uint64).reshape(-1, 12)
+        g2 = trusted_setup.g2_powers_of_tau
+        ok = C.c_int(0)
+        dummy = np.zeros(24, np.uint64)
+        L.check(_decl().zk_kzg_batch_verify(L.p64(cs) if cs.size else L.p64(dummy), cs.shape[0], L.p64(o) if o.size else L.p64(dummy),
+                                            o.shape[0], L.p64(evs) if evs.size else L.p64(dummy), L.p64(prs) if prs.size else L.p64(dummy),
+                                            prs.shape[0], L.p64(g2), g2.shape[0], transcript._h if transcript is not None else None,
+                                            C.byref(ok)))
         return bool(ok.value)

@@ -174,6 +174,22 @@ class MultilinearPolynomial:
         return out
 
     @staticmethod
+    def linear_combination(polys, coeffs, stream=None):
+        """sum_j coeffs[j] * polys[j] in one pass (zk_mle_linear_combination): scalar_mul :49 and add_polynomials :145 of k <= 64 tables
+        of equal length.  Extension: no reference counterpart."""
+        polys = list(polys)
+        if not polys:
+            raise L.ZkError(L.ZK_E_ARG, "linear_combination needs at least one polynomial")
+        field = polys[0].field
+        c = np.ascontiguousarray(coeffs, np.uint64).reshape(-1, limbs(field))
+        if c.shape[0] != len(polys):
+            raise L.ZkError(L.ZK_E_ARG, "one coefficient per polynomial")
+        handles = (L.vp * len(polys))(*[p._h.value for p in polys])
+        out = MultilinearPolynomial.alloc(field, len(polys[0]))
+        L.check(L.lib().zk_mle_linear_combination(handles, len(polys), L.p64(c), out._h, stream))
+        return out
+
+    @staticmethod
     def polynomial_tensor_add(w_b, w_c, stream=None):       # :108
         out = MultilinearPolynomial.alloc(w_b.field, len(w_b) * len(w_c))
         L.check(L.lib().zk_mle_tensor_add(w_b._h, w_c._h, out._h, stream))
