@@ -320,7 +320,8 @@ def test_two_host_threads_prove_concurrently(zk):
 
 @pytest.mark.gpu
 def test_full_size_provers_size_independent_properties(zk):
-    """BASELINE config 5 sizes, where the oracle is too slow to run: a 2^24 basic sumcheck proof passes the verifier's round
+    """BASELINE config 5 sizes, checked by the verifier's side of the protocol (the byte-for-byte comparison of these sizes with the
+    oracle lives in tests/test_gpu_full_size_parity.py): a 2^24 basic sumcheck proof passes the verifier's round
     equations (p_k(0) + p_k(1) = previous claim, verifier.rs:47-64) recomputed here on the host with the oracle's field
     arithmetic, its last claim equals the table's evaluation at the challenges (:67-70, GPU evaluate cross-checked by a
     second, unfused fold chain), and a tampered round is rejected.  Same for a GKR sumcheck on 4 tables of 2^22."""
