@@ -145,6 +145,35 @@ int zk_keccak256(const uint8_t *data, size_t n, uint8_t out32[32]);
 int zk_transcript_export_state(const zk_transcript *t, uint64_t lanes25[25], uint32_t *fill);
 int zk_transcript_import_state(zk_transcript *t, const uint64_t lanes25[25], uint32_t fill);
 
+/* ---- Merkle commitment of a table (extension: the reference's merkle_tree/ crate is empty; csrc/merkle.cuh) ----------
+ * For a table of len = 2^d elements of any of the four fields:
+ *   leaf_i = Keccak256(0x00 || bytes(e_i))      bytes = convert_to_bytes of ONE element (evaluation_form.rs:35-43): the canonical
+ *                                               integer big-endian, 8 * limbs bytes (32 or 48)
+ *   node   = Keccak256(0x01 || left || right)   node j of level l + 1 hashes nodes 2j and 2j + 1 of level l;
+ *                                               level 0 = the leaves in table-index order
+ *   root   = the single node of level d; a one-entry table's root is leaf_0.
+ * Keccak256 is the transcript's: the ORIGINAL Keccak (pad 0x01 .. 0x80, rate 136), not SHA3-256.  Every input is 33, 49 or 65 bytes,
+ * one block, so a hash is one permutation; the kernels run one hash per GPU lane.  A length that is not a power of two returns
+ * ZK_E_NOT_POW2; NULL arguments and bad fields ZK_E_ARG.  Launches go on the calling thread's stream; one synchronisation per call.
+ * zk_mle_merkle_root returns nothing but the root (what the committed provers call): its levels go through one scratch block of the
+ * caching pool, 64 bytes x len (1 GiB for 2^24 entries), which the calling thread's pool keeps for the next call as it does every
+ * per-call scratch (zk_release_cached_memory).  zk_merkle_build keeps every level in HBM (64 bytes x len), which is what openings
+ * need; the tree is a long-lived allocation of its own (hipMalloc / hipFree), so zk_merkle_build and zk_merkle_free are NOT
+ * stream-ordered: the free may wait for the whole device, and the build's time includes the allocation. */
+int zk_mle_merkle_root(const zk_table *t, uint8_t root32[32]);
+typedef struct zk_merkle_tree zk_merkle_tree;
+int zk_merkle_build(const zk_table *t, zk_merkle_tree **out);
+int zk_merkle_free(zk_merkle_tree *m);
+size_t zk_merkle_depth(const zk_merkle_tree *m);
+int zk_merkle_root(const zk_merkle_tree *m, uint8_t root32[32]);
+/* the authentication paths of `nidx` entries, gathered by one kernel and one download: paths = nidx x depth x 32 bytes, for each
+ * index the leaf's sibling first, the root's child last.  An index >= len returns ZK_E_RANGE (nothing is written). */
+int zk_merkle_open(const zk_merkle_tree *m, const size_t *indices, size_t nidx, uint8_t *paths);
+/* HOST only, O(depth) hashes, needs no device: *ok = 1 when `element` (Montgomery limbs) at `index` hashes up `path` to root32.
+ * index >= 2^depth returns ZK_E_RANGE. */
+int zk_merkle_verify(int field, const uint8_t root32[32], size_t depth, size_t index, const uint64_t *element,
+                     const uint8_t *path, int *ok);
+
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */
 int zk_uni_lagrange_interpolate(int field, const uint64_t *xs, const uint64_t *ys, size_t n, uint64_t *out); /* :74 */
@@ -178,6 +207,17 @@ int zk_sumcheck_basic_prove_on(const zk_table *table, zk_transcript *transcript,
 /* Verifier::verify  verifier.rs:23-71 (its final `evaluate` is the same GPU fold); *ok = 1 / 0 */
 int zk_sumcheck_basic_verify(const zk_table *table, const uint64_t *claimed_sum,
                              const uint64_t *round_polys, size_t nrounds, int *ok);
+/* Prover::prove bound to the table's COMMITMENT (extension: no reference counterpart).  Exactly one change to prover.rs:35-71: the first
+ * append (:38-39) is the 32-byte Merkle root of the table (zk_mle_merkle_root, returned in root32) instead of the table's bytes.
+ * Claimed sum, round messages, challenges' derivation and the output layout are those of zk_sumcheck_basic_prove_on.  The sponge is
+ * sequential, so the reference's binding costs one host core 0.7 GB/s; the root is a few milliseconds of GPU work at 2^24 entries.
+ * transcript = NULL: a fresh Transcript::new().  zk_sumcheck_last_stats' ms_absorb reports the root's time. */
+int zk_sumcheck_basic_prove_committed(const zk_table *table, zk_transcript *transcript, uint8_t root32[32], uint64_t *claimed_sum,
+                                      uint64_t *round_polys, uint64_t *challenges);
+/* Verifier::verify (verifier.rs:23-71) for the committed proof: recomputes the root from the table on the GPU, *ok = 0 if root32 is given
+ * (it may be NULL) and differs, replays the transcript from the root and finishes with the GPU `evaluate`. */
+int zk_sumcheck_basic_verify_committed(const zk_table *table, const uint8_t *root32, const uint64_t *claimed_sum,
+                                       const uint64_t *round_polys, size_t nrounds, int *ok);
 
 /* ---- composed polynomials + GKR sumcheck ----------------------------------------------------------
  * A SumPolynomial (polynomials/src/composed/sum_polynomial.rs:7-9) of `nprod` ProductPolynomials
@@ -439,6 +479,13 @@ int zk_gkr_sparse_prove_compiled(int field, const zk_sparse_circuit *c, const ui
                                  uint64_t *circuit_output, uint64_t *claimed_sum, uint64_t *layer_claims,
                                  uint64_t *coeffs, uint64_t *challenges, uint64_t *wb_evals, uint64_t *wc_evals,
                                  uint64_t *output_challenges, float *ms_layers);
+/* the same proof with the output layer bound by its COMMITMENT (extension): the transcript's first append (gkr_protocol.rs:49) is the
+ * Merkle root of the output layer (zk_mle_merkle_root, returned in output_root32) instead of its bytes; the output challenges and
+ * everything after them follow from the transcript as before. */
+int zk_gkr_sparse_prove_committed(int field, const zk_sparse_circuit *c, const uint64_t *inputs, size_t ninputs,
+                                  uint64_t *circuit_output, uint64_t *claimed_sum, uint64_t *layer_claims,
+                                  uint64_t *coeffs, uint64_t *challenges, uint64_t *wb_evals, uint64_t *wc_evals,
+                                  uint64_t *output_challenges, float *ms_layers, uint8_t output_root32[32]);
 /* independent evaluation of the wiring predicates at a point (the verifier's O(#gates) work):
  * add_r = sum_{add gates} w_g eq(rb, left_g) eq(rc, right_g), same for mul, with
  * w_g = alpha eq(pa, out_g) + beta eq(pb, out_g)  (layer 0: alpha = 1, beta = 0, pa = output challenges). */

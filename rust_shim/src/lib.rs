@@ -131,6 +131,21 @@ pub mod ffi {
                                  proofs: *mut u64) -> c_int;
         pub fn zk_kzg_batch_verify(commitments12: *const u64, k: usize, opening: *const u64, nopen: usize, evaluations: *const u64,
                                    proofs: *const u64, nproofs: usize, g2_powers: *const u64, ng2: usize, t: *mut zk_transcript, ok: *mut c_int) -> c_int;
+        // beyond the reference as well: the Keccak-256 Merkle commitment of a table and the provers bound to its root
+        pub fn zk_mle_merkle_root(t: *const zk_table, root32: *mut u8) -> c_int;
+        pub fn zk_merkle_build(t: *const zk_table, out: *mut *mut c_void) -> c_int;
+        pub fn zk_merkle_free(m: *mut c_void) -> c_int;
+        pub fn zk_merkle_depth(m: *const c_void) -> usize;
+        pub fn zk_merkle_root(m: *const c_void, root32: *mut u8) -> c_int;
+        pub fn zk_merkle_open(m: *const c_void, indices: *const usize, nidx: usize, paths: *mut u8) -> c_int;
+        pub fn zk_merkle_verify(field: c_int, root32: *const u8, depth: usize, index: usize, element: *const u64, path: *const u8, ok: *mut c_int) -> c_int;
+        pub fn zk_sumcheck_basic_prove_committed(t: *const zk_table, transcript: *mut zk_transcript, root32: *mut u8, claimed: *mut u64, rounds: *mut u64,
+                                                 challenges: *mut u64) -> c_int;
+        pub fn zk_sumcheck_basic_verify_committed(t: *const zk_table, root32: *const u8, claimed: *const u64, rounds: *const u64, nrounds: usize,
+                                                  ok: *mut c_int) -> c_int;
+        pub fn zk_gkr_sparse_prove_committed(field: c_int, c: *const c_void, inputs: *const u64, ninputs: usize, circuit_output: *mut u64, claimed_sum: *mut u64,
+                                             layer_claims: *mut u64, coeffs: *mut u64, challenges: *mut u64, wb_evals: *mut u64, wc_evals: *mut u64,
+                                             output_challenges: *mut u64, ms_layers: *mut f32, output_root32: *mut u8) -> c_int;
     }
 }
 
@@ -511,6 +526,24 @@ pub mod sumcheck_protocol {
                     }
                 }
             }
+            impl<F: ZkField> Prover<F> {
+                /// Beyond the reference: `prove` with ONE change -- the transcript's first append (:38-39) is the 32-byte Keccak-256 Merkle root of
+                /// the table (returned beside the proof) instead of the table's bytes (zk_sumcheck_basic_prove_committed).
+                pub fn prove_committed(&mut self) -> (SumcheckProof<F>, [u8; 32]) {
+                    assert!(self.is_initialized, "Can't prove without init");
+                    let n = self.initial_polynomial.number_of_variables() as usize;
+                    let t = DeviceTable::<F>::upload(&self.initial_polynomial.evaluated_values);
+                    let (mut claimed, mut rounds, mut root) = (F::zero(), vec![F::zero(); 2 * n.max(1)], [0u8; 32]);
+                    check(unsafe { ffi::zk_sumcheck_basic_prove_committed(t.h, self.transcript.h, root.as_mut_ptr(), el_mut(&mut claimed), rounds.as_mut_ptr() as *mut u64,
+                                                                          std::ptr::null_mut()) });
+                    self.round_univariate_polynomials = rounds.chunks(2).take(n).map(MultilinearPolynomial::new).collect();
+                    (SumcheckProof {
+                        initial_polynomial: self.initial_polynomial.clone(),
+                        initial_claimed_sum: self.initial_claimed_sum,
+                        round_univariate_polynomials: self.round_univariate_polynomials.clone(),
+                    }, root)
+                }
+            }
             pub fn split_polynomial_and_sum_each<F: ZkField>(polynomial_evaluated_values: &Vec<F>) -> Vec<F> {   // :74-89
                 let t = DeviceTable::<F>::upload(polynomial_evaluated_values);
                 let mut out = vec![F::zero(); 2];
@@ -538,6 +571,17 @@ pub mod sumcheck_protocol {
                     let flat: Vec<F> = proof.round_univariate_polynomials.iter().flat_map(|p| p.evaluated_values.iter().cloned()).collect();
                     let mut ok: c_int = 0;
                     check(unsafe { ffi::zk_sumcheck_basic_verify(t.h, el(&proof.initial_claimed_sum), as_limbs(&flat), proof.round_univariate_polynomials.len(), &mut ok) });
+                    ok == 1
+                }
+                /// Beyond the reference: the verifier of `Prover::prove_committed`.  The root is recomputed from the proof's table on the GPU;
+                /// `root`, when given, must equal it.
+                pub fn verify_committed(&mut self, proof: SumcheckProof<F>, root: Option<&[u8; 32]>) -> bool {
+                    assert!(self.is_initialized, "Can't verify without init");
+                    let t = DeviceTable::<F>::upload(&proof.initial_polynomial.evaluated_values);
+                    let flat: Vec<F> = proof.round_univariate_polynomials.iter().flat_map(|p| p.evaluated_values.iter().cloned()).collect();
+                    let mut ok: c_int = 0;
+                    check(unsafe { ffi::zk_sumcheck_basic_verify_committed(t.h, root.map_or(std::ptr::null(), |r| r.as_ptr()), el(&proof.initial_claimed_sum), as_limbs(&flat),
+                                                                           proof.round_univariate_polynomials.len(), &mut ok) });
                     ok == 1
                 }
             }
@@ -936,4 +980,48 @@ pub mod multilinear_kzg {
             }
         }
     }
+}
+
+/// Beyond the reference (its `merkle_tree/` crate is empty): the Keccak-256 Merkle commitment of a table, hashed on the GPU one hash per lane.
+/// leaf_i = Keccak256(0x00 || e_i canonical big-endian), node = Keccak256(0x01 || left || right), root = the node of level log2(len).
+pub mod merkle_tree {
+    use crate::*;
+    /// root-only mode: nothing but the 32-byte root is kept (zk_mle_merkle_root)
+    pub fn merkle_root<F: ZkField>(evaluated_values: &Vec<F>) -> [u8; 32] {
+        let t = DeviceTable::<F>::upload(evaluated_values);
+        let mut root = [0u8; 32];
+        check(unsafe { ffi::zk_mle_merkle_root(t.h, root.as_mut_ptr()) });
+        root
+    }
+    /// every level resident in HBM (64 bytes per entry): what openings need
+    pub struct MerkleTree<F: ZkField> { h: *mut std::os::raw::c_void, _f: std::marker::PhantomData<F> }
+    impl<F: ZkField> MerkleTree<F> {
+        pub fn build(evaluated_values: &Vec<F>) -> Self {
+            let t = DeviceTable::<F>::upload(evaluated_values);
+            let mut h = std::ptr::null_mut();
+            check(unsafe { ffi::zk_merkle_build(t.h, &mut h) });
+            MerkleTree { h, _f: Default::default() }
+        }
+        pub fn depth(&self) -> usize { unsafe { ffi::zk_merkle_depth(self.h) } }
+        pub fn root(&self) -> [u8; 32] {
+            let mut root = [0u8; 32];
+            check(unsafe { ffi::zk_merkle_root(self.h, root.as_mut_ptr()) });
+            root
+        }
+        /// the authentication paths of `indices` (one kernel, one download): per index `depth` digests, the leaf's sibling first
+        pub fn open(&self, indices: &[usize]) -> Vec<Vec<[u8; 32]>> {
+            let d = self.depth();
+            let mut flat = vec![0u8; (indices.len() * d * 32).max(32)];
+            check(unsafe { ffi::zk_merkle_open(self.h, indices.as_ptr(), indices.len(), flat.as_mut_ptr()) });
+            (0..indices.len()).map(|q| (0..d).map(|l| { let mut x = [0u8; 32]; x.copy_from_slice(&flat[(q * d + l) * 32..(q * d + l + 1) * 32]); x }).collect()).collect()
+        }
+        /// host only: O(depth) hashes, no device
+        pub fn verify(root: &[u8; 32], index: usize, element: &F, path: &[[u8; 32]]) -> bool {
+            let flat: Vec<u8> = path.iter().flat_map(|x| x.iter().cloned()).collect();
+            let mut ok: c_int = 0;
+            check(unsafe { ffi::zk_merkle_verify(F::ID, root.as_ptr(), path.len(), index, el(element), if flat.is_empty() { root.as_ptr() } else { flat.as_ptr() }, &mut ok) });
+            ok == 1
+        }
+    }
+    impl<F: ZkField> Drop for MerkleTree<F> { fn drop(&mut self) { unsafe { ffi::zk_merkle_free(self.h); } } }
 }

@@ -14,6 +14,8 @@ from ._lib import FR381, FQ381, BN254_FQ, BN254_FR, ZkError, ReferencePanic, lib
 from .mle import MultilinearPolynomial, from_ints, to_ints, limbs  # noqa: F401
 from . import sumcheck  # noqa: F401
 from .sumcheck import Transcript, ProductPolynomial, SumPolynomial, Prover, Verifier  # noqa: F401
+from . import merkle  # noqa: F401
+from .merkle import MerkleTree, merkle_root  # noqa: F401
 from . import gkr  # noqa: F401
 from .gkr import Circuit, Gate, Layer, Operator  # noqa: F401
 from . import kzg  # noqa: F401
@@ -21,4 +23,4 @@ from .kzg import G1Bases, TrustedSetup, MultilinearKZG, MultilinearKZGProof, Mul
 from . import sharded  # noqa: F401
 
 __all__ = ["MultilinearPolynomial", "FR381", "FQ381", "BN254_FQ", "BN254_FR", "ZkError", "ReferencePanic",
-           "from_ints", "to_ints", "limbs", "lib", "library_path"]
+           "from_ints", "to_ints", "limbs", "lib", "library_path", "MerkleTree", "merkle_root"]

@@ -53,6 +53,7 @@ def lib():
     L.zk_version.restype = C.c_char_p
     L.zk_table_len.restype = sz
     L.zk_table_device_ptr.restype = vp
+    L.zk_merkle_depth.restype = sz
     sigs = {
         "zk_device_count": [C.POINTER(C.c_int)],
         "zk_init": [C.c_int],
@@ -91,11 +92,19 @@ def lib():
         "zk_fe_from_le_bytes_mod_order": [C.c_int, u8p, sz, u64p],
         "zk_vec_from_canonical": [C.c_int, u64p, sz, u64p],
         "zk_vec_to_canonical": [C.c_int, u64p, sz, u64p],
+        # Merkle commitment of a table (extension)
+        "zk_mle_merkle_root": [vp, u8p],
+        "zk_merkle_build": [vp, C.POINTER(vp)],
+        "zk_merkle_free": [vp],
+        "zk_merkle_depth": [vp],
+        "zk_merkle_root": [vp, u8p],
+        "zk_merkle_open": [vp, C.POINTER(sz), sz, u8p],
+        "zk_merkle_verify": [C.c_int, u8p, sz, sz, u64p, u8p, C.POINTER(C.c_int)],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)       # AttributeError = missing export: loud
         fn.argtypes = args
-        if name not in ("zk_table_len", "zk_table_device_ptr"):
+        if name not in ("zk_table_len", "zk_table_device_ptr", "zk_merkle_depth"):
             fn.restype = C.c_int
     _lib = L
     return L

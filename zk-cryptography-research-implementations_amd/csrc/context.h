@@ -84,6 +84,8 @@ class Transcript;
 // transcript.append(convert_to_bytes(table)) (evaluation_form.rs:35-43, prover.rs:38-39): the GPU converts Montgomery ->
 // canonical big-endian chunk by chunk into pinned host buffers while the host hashes the previous chunk (zkmle_sumcheck.hip)
 int transcript_absorb_table(Transcript &t, const zk_table *table);
+// the table's Keccak-256 Merkle root, root-only mode (zkmle_merkle.hip): what the committed provers append in place of the table's bytes
+int merkle_root_device(const zk_table *t, uint8_t root32[32]);
 // Proof slots shared by a proof made of several sumchecks (zkmle_sumcheck.hip): the sponge, the interpolation basis and every slot
 // (coefficients, challenges, final values, layer links) live in ONE device block; rounds() and link() only enqueue kernels on the
 // current stream, collect() is the single download.  Slot layout of rounds(): round k's nfac + 1 coefficients at s0 + per k, its

@@ -476,7 +476,7 @@ int build_layers(const zk_gate *gates, const size_t *gate_counts, size_t nlayers
 
 template <class F> int sparse_prove(std::vector<LayerDev> &layers, const uint64_t *inputs, size_t ninputs, uint64_t *circuit_output,
                                     uint64_t *claimed_sum, uint64_t *layer_claims, uint64_t *coeffs, uint64_t *challenges,
-                                    uint64_t *wb_evals, uint64_t *wc_evals, uint64_t *output_challenges, float *ms_layers) {
+                                    uint64_t *wb_evals, uint64_t *wc_evals, uint64_t *output_challenges, float *ms_layers, uint8_t *output_root32) {
     const size_t L64 = F::N / 2, esz = 4 * F::N;
     const size_t nlayers = layers.size();
     std::vector<uint32_t> out_bits_v(nlayers);
@@ -488,7 +488,13 @@ template <class F> int sparse_prove(std::vector<LayerDev> &layers, const uint64_
     ZK_TRY(zk_table_download(W[0].get(), circuit_output));
     zk_transcript tr;
     // transcript.append(w0 bytes) gkr_protocol.rs:49 (an output layer of one wire is one gate plus a zero pad, :43-47)
-    ZK_TRY(transcript_absorb_table(tr.t, W[0].get()));
+    // -- or, committed (zk_gkr_sparse_prove_committed), the output layer's Merkle root in place of its bytes
+    if (output_root32) {
+        ZK_TRY(merkle_root_device(W[0].get(), output_root32));
+        tr.t.append(output_root32, 32);
+    } else {
+        ZK_TRY(transcript_absorb_table(tr.t, W[0].get()));
+    }
     std::vector<uint64_t> ra((size_t)out_bits[0] * L64);
     for (uint32_t i = 0; i < out_bits[0]; i++) store_el<F>(ra.data() + i * L64, tr.t.random_challenge_as_field_element<F>());   // :50
     memcpy(output_challenges, ra.data(), ra.size() * 8);
@@ -747,7 +753,19 @@ int zk_gkr_sparse_prove_compiled(int field, const zk_sparse_circuit *c, const ui
     ZK_TRY(require_device());
     std::vector<LayerDev> &layers = const_cast<zk_sparse_circuit *>(c)->layers;   // read-only use of device buffers
     ZK_DISPATCH_FIELD(field, return sparse_prove<F>(layers, inputs, ninputs, circuit_output, claimed_sum, layer_claims, coeffs, challenges,
-                                                    wb_evals, wc_evals, output_challenges, ms_layers));
+                                                    wb_evals, wc_evals, output_challenges, ms_layers, nullptr));
+    return ZK_OK;
+}
+int zk_gkr_sparse_prove_committed(int field, const zk_sparse_circuit *c, const uint64_t *inputs, size_t ninputs, uint64_t *circuit_output,
+                                  uint64_t *claimed_sum, uint64_t *layer_claims, uint64_t *coeffs, uint64_t *challenges, uint64_t *wb_evals,
+                                  uint64_t *wc_evals, uint64_t *output_challenges, float *ms_layers, uint8_t output_root32[32]) {
+    if (!c || !inputs || !circuit_output || !claimed_sum || !layer_claims || !coeffs || !challenges || !output_challenges || !output_root32)
+        return ZK_E_ARG;
+    if (c->layers.size() > 1 && (!wb_evals || !wc_evals)) return ZK_E_ARG;
+    ZK_TRY(require_device());
+    std::vector<LayerDev> &layers = const_cast<zk_sparse_circuit *>(c)->layers;   // read-only use of device buffers
+    ZK_DISPATCH_FIELD(field, return sparse_prove<F>(layers, inputs, ninputs, circuit_output, claimed_sum, layer_claims, coeffs, challenges,
+                                                    wb_evals, wc_evals, output_challenges, ms_layers, output_root32));
     return ZK_OK;
 }
 int zk_gkr_sparse_wiring_eval(int field, const zk_gate *layer_gates, size_t ngates, uint32_t out_bits, uint32_t in_bits, const uint64_t *alpha,

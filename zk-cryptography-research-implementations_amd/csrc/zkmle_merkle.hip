@@ -1,0 +1,163 @@
+// zkmle_merkle.hip -- C ABI of the Keccak-256 Merkle commitment of a table (merkle.cuh): the root alone (what the committed provers bind
+// their transcript to), the whole tree resident in HBM with batched openings, and the host-side path check.  Extension: the reference
+// leaves `merkle_tree/` empty; the bytes are defined in include/zkmle.h.
+#include <string.h>
+
+#include <vector>
+
+#include "context.h"
+#include "merkle.cuh"
+#include "transcript.h"
+
+using namespace zk;
+
+struct zk_merkle_tree {
+    int field;
+    size_t len;
+    unsigned depth;
+    uint64_t *levels;       // 2 len - 1 digests: level l at digest offset 2 len - (2 len >> l), the root last
+};
+
+namespace {
+
+struct DevBuf {   // RAII block of the caching pool
+    void *p = nullptr;
+    ~DevBuf() { pool_free(p); }
+    int alloc(size_t bytes) { return pool_alloc(bytes, &p); }
+};
+
+inline unsigned merkle_grid(size_t work) {
+    size_t b = (work + kMerkleBlock - 1) / kMerkleBlock;
+    return (unsigned)(b < 1 ? 1 : b > ((size_t)1 << 20) ? (size_t)1 << 20 : b);
+}
+
+// `lv` holds n digests (a power of two); the levels above are written right behind it, the root at lv[2 n - 2]
+int hash_up(uint64_t *lv, size_t n) {
+    while (n > kMerkleFinish) {
+        merkle_node_kernel<<<merkle_grid(n / 2), kMerkleBlock, 0, cur_stream()>>>(lv, n / 2, lv + 4 * n);
+        ZK_HIP(hipGetLastError());
+        lv += 4 * n;
+        n /= 2;
+    }
+    if (n >= 2) {
+        merkle_finish_kernel<<<1, kMerkleBlock, 0, cur_stream()>>>(lv, (unsigned)n);
+        ZK_HIP(hipGetLastError());
+    }
+    return ZK_OK;
+}
+
+template <class F> int launch_leaves(const zk_table *t, uint64_t *out) {
+    merkle_leaf_kernel<F><<<merkle_grid(t->len), kMerkleBlock, 0, cur_stream()>>>(t->dptr, t->len, out);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+// Root-only mode: build mode on ONE scratch block of the caching pool, 2 len - 1 digests (64 B x len; cached by the calling thread's pool
+// after the call like every per-call scratch).  Nothing but the root leaves the device.
+template <class F> int root_only(const zk_table *t, uint8_t root32[32]) {
+    const size_t n = t->len;
+    DevBuf buf;
+    ZK_TRY(buf.alloc((2 * n - 1) * 32));
+    uint64_t *lv = (uint64_t *)buf.p;
+    ZK_TRY(launch_leaves<F>(t, lv));
+    ZK_TRY(hash_up(lv, n));
+    ZK_HIP(zk::memcpy_on_stream(root32, lv + 4 * (2 * n - 2), 32, hipMemcpyDeviceToHost));   // the call's one synchronisation
+    return ZK_OK;
+}
+
+// leaf and node hashes on the host (zk_merkle_verify; Keccak256 of transcript.h, pinned by the reference KATs)
+template <class F> void host_leaf(const uint64_t *element, uint8_t out[32]) {
+    uint8_t msg[1 + 4 * F::N];
+    Fe<F> e;
+    memcpy(e.l, element, 4 * F::N);
+    msg[0] = 0x00;
+    host_to_bytes_be<F>(e, msg + 1);
+    Keccak256 h;
+    h.update(msg, sizeof msg);
+    h.finalize_copy(out);
+}
+void host_node(const uint8_t *l, const uint8_t *r, uint8_t out[32]) {
+    uint8_t msg[65];
+    msg[0] = 0x01;
+    memcpy(msg + 1, l, 32);
+    memcpy(msg + 33, r, 32);
+    Keccak256 h;
+    h.update(msg, sizeof msg);
+    h.finalize_copy(out);
+}
+
+}  // namespace
+
+namespace zk {
+int merkle_root_device(const zk_table *t, uint8_t root32[32]) {
+    if (!t || !root32 || field_limbs64(t->field) < 0) return ZK_E_ARG;
+    if (!is_pow2(t->len)) return ZK_E_NOT_POW2;
+    ZK_TRY(require_device());
+    ZK_DISPATCH_FIELD(t->field, return root_only<F>(t, root32));
+    return ZK_OK;
+}
+}  // namespace zk
+
+extern "C" {
+
+int zk_mle_merkle_root(const zk_table *t, uint8_t root32[32]) { return merkle_root_device(t, root32); }
+
+int zk_merkle_build(const zk_table *t, zk_merkle_tree **out) {
+    if (!t || !out || field_limbs64(t->field) < 0) return ZK_E_ARG;
+    if (!is_pow2(t->len)) return ZK_E_NOT_POW2;
+    ZK_TRY(require_device());
+    void *d = nullptr;
+    ZK_HIP(hipMalloc(&d, (2 * t->len - 1) * 32));
+    zk_merkle_tree *m = new zk_merkle_tree{t->field, t->len, ilog2(t->len), (uint64_t *)d};
+    int rc = ZK_OK;
+    ZK_DISPATCH_FIELD(t->field, rc = launch_leaves<F>(t, m->levels));
+    if (rc == ZK_OK) rc = hash_up(m->levels, m->len);
+    if (rc == ZK_OK && hipStreamSynchronize(cur_stream()) != hipSuccess) { set_last_error("zk_merkle_build: the hash kernels failed"); rc = ZK_E_HIP; }
+    if (rc != ZK_OK) { zk_merkle_free(m); return rc; }
+    *out = m;
+    return ZK_OK;
+}
+int zk_merkle_free(zk_merkle_tree *m) {
+    if (!m) return ZK_OK;
+    if (m->levels) (void)hipFree(m->levels);
+    delete m;
+    return ZK_OK;
+}
+size_t zk_merkle_depth(const zk_merkle_tree *m) { return m ? m->depth : 0; }
+int zk_merkle_root(const zk_merkle_tree *m, uint8_t root32[32]) {
+    if (!m || !root32) return ZK_E_ARG;
+    ZK_HIP(zk::memcpy_on_stream(root32, m->levels + 4 * (2 * m->len - 2), 32, hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+int zk_merkle_open(const zk_merkle_tree *m, const size_t *indices, size_t nidx, uint8_t *paths) {
+    if (!m || (!indices && nidx) || (!paths && nidx && m->depth)) return ZK_E_ARG;
+    for (size_t q = 0; q < nidx; q++)
+        if (indices[q] >= m->len) return ZK_E_RANGE;
+    if (nidx == 0 || m->depth == 0) return ZK_OK;
+    static_assert(sizeof(size_t) == 8, "indices travel as 64-bit words");
+    DevBuf idx, out;
+    ZK_TRY(idx.alloc(nidx * 8));
+    ZK_TRY(out.alloc(nidx * m->depth * 32));
+    ZK_HIP(hipMemcpyAsync(idx.p, indices, nidx * 8, hipMemcpyHostToDevice, cur_stream()));
+    merkle_open_kernel<<<merkle_grid(nidx * m->depth), kMerkleBlock, 0, cur_stream()>>>(m->levels, m->len, m->depth, (const uint64_t *)idx.p, nidx,
+                                                                                     (uint64_t *)out.p);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(zk::memcpy_on_stream(paths, out.p, nidx * m->depth * 32, hipMemcpyDeviceToHost));   // one download
+    return ZK_OK;
+}
+
+int zk_merkle_verify(int field, const uint8_t root32[32], size_t depth, size_t index, const uint64_t *element, const uint8_t *path, int *ok) {
+    if (!root32 || !element || (!path && depth) || !ok || field_limbs64(field) < 0) return ZK_E_ARG;
+    if (depth >= 64 || (index >> depth) != 0) return ZK_E_RANGE;
+    uint8_t cur[32];
+    ZK_DISPATCH_FIELD(field, host_leaf<F>(element, cur));
+    for (size_t l = 0; l < depth; l++) {                       // the leaf's sibling first
+        const uint8_t *sib = path + 32 * l;
+        uint8_t nx[32];
+        if ((index >> l) & 1) host_node(sib, cur, nx); else host_node(cur, sib, nx);
+        memcpy(cur, nx, 32);
+    }
+    *ok = memcmp(cur, root32, 32) == 0 ? 1 : 0;
+    return ZK_OK;
+}
+
+}  // extern "C"

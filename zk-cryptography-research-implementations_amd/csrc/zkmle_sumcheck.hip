@@ -89,6 +89,15 @@ template <class F> int absorb_table(Transcript &t, const void *dptr, size_t len)
     return rc;
 }
 
+// The step that binds a basic sumcheck's transcript to its table (prover.rs:38-39, verifier.rs:34-35): the table's bytes, as the reference
+// does, or -- root32 given -- the 32-byte Merkle root of the table (the committed provers of include/zkmle.h), which is written there too.
+template <class F> int bind_table(Transcript &t, const zk_table *table, uint8_t *root32) {
+    if (!root32) return absorb_table<F>(t, table->dptr, table->len);
+    ZK_TRY(merkle_root_device(table, root32));
+    t.append(root32, 32);
+    return ZK_OK;
+}
+
 template <class F> int download_elems(const void *d, size_t n, Fe<F> *out) {
     ZK_HIP(zk::memcpy_on_stream(out, d, n * 4 * F::N, hipMemcpyDeviceToHost));
     return ZK_OK;
@@ -688,12 +697,13 @@ int fold_pass(const void *in, void *out, size_t n, int k, const void *const *rp,
 }
 
 // ---- basic sumcheck prover: prover.rs:22-71 ----------------------------------------------------------
-template <class F> int basic_prove(const zk_table *table, Transcript &tr, uint64_t *claimed_sum, uint64_t *round_polys, uint64_t *challenges) {
+template <class F> int basic_prove(const zk_table *table, Transcript &tr, uint64_t *claimed_sum, uint64_t *round_polys, uint64_t *challenges,
+                                   uint8_t *root32 = nullptr) {
     const size_t esz = 4 * F::N, L64 = F::N / 2;
     size_t len = table->len;
     unsigned nvars = ilog2(len);
     double t0 = now_ms();
-    ZK_TRY(absorb_table<F>(tr, table->dptr, len));                     // :38-39
+    ZK_TRY(bind_table<F>(tr, table, root32));                          // :38-39
     double t1 = now_ms();
     g_stats = zk_sumcheck_stats{nvars, (float)(t1 - t0), 0.f};
     // working buffers: len/2 and len/4 elements, plus reduction partials
@@ -782,12 +792,14 @@ template <class F> int basic_prove(const zk_table *table, Transcript &tr, uint64
 
 // ---- basic sumcheck verifier: verifier.rs:23-71 -------------------------------------------------------
 template <class F> int basic_verify(const zk_table *table, const uint64_t *claimed_sum, const uint64_t *round_polys,
-                                    size_t nrounds, int *ok) {
+                                    size_t nrounds, int *ok, bool committed = false, const uint8_t *root_given = nullptr) {
     const size_t L64 = F::N / 2;
     *ok = 0;
     if (nrounds != ilog2(table->len)) return ZK_OK;                    // :26-30
     Transcript tr;
-    ZK_TRY(absorb_table<F>(tr, table->dptr, table->len));              // :34-35
+    uint8_t root[32];
+    ZK_TRY(bind_table<F>(tr, table, committed ? root : nullptr));      // :34-35
+    if (committed && root_given && memcmp(root, root_given, 32) != 0) return ZK_OK;   // not the table the prover committed to
     Fe<F> cur = load_el<F>(claimed_sum);
     tr.append_be<F>(cur);                                              // :36-37
     std::vector<uint64_t> chal(nrounds * L64 + L64);
@@ -1463,6 +1475,24 @@ int zk_sumcheck_basic_verify(const zk_table *table, const uint64_t *claimed_sum,
     return ZK_OK;
 }
 
+int zk_sumcheck_basic_prove_committed(const zk_table *table, zk_transcript *transcript, uint8_t root32[32], uint64_t *claimed_sum, uint64_t *round_polys,
+                                      uint64_t *challenges) {
+    if (!table || !root32 || !claimed_sum || !round_polys) return ZK_E_ARG;
+    if (!is_pow2(table->len)) return ZK_E_NOT_POW2;
+    ZK_TRY(require_device());
+    Transcript fresh;
+    Transcript &tr = transcript ? transcript->t : fresh;
+    ZK_DISPATCH_FIELD(table->field, return basic_prove<F>(table, tr, claimed_sum, round_polys, challenges, root32));
+    return ZK_OK;
+}
+int zk_sumcheck_basic_verify_committed(const zk_table *table, const uint8_t *root32, const uint64_t *claimed_sum, const uint64_t *round_polys,
+                                       size_t nrounds, int *ok) {
+    if (!table || !claimed_sum || (!round_polys && nrounds) || !ok) return ZK_E_ARG;
+    if (!is_pow2(table->len)) return ZK_E_NOT_POW2;
+    ZK_TRY(require_device());
+    ZK_DISPATCH_FIELD(table->field, return basic_verify<F>(table, claimed_sum, round_polys, nrounds, ok, true, root32));
+    return ZK_OK;
+}
 int zk_sumpoly_round_evals(const zk_table *const *tables, size_t nprod, size_t nfac, uint64_t *out) {
     ZK_TRY(check_sumpoly(tables, nprod, nfac));
     // the reference reduces with add_polynomials_element_wise (:134), which asserts > 1 (sum_polynomial.rs:58-61)

@@ -270,6 +270,8 @@ def _decl_sparse():
     lib.zk_sparse_circuit_free.restype = C.c_int
     lib.zk_gkr_sparse_prove_compiled.argtypes = [C.c_int, L.vp, u64p, sz] + [u64p] * 8 + [fp]
     lib.zk_gkr_sparse_prove_compiled.restype = C.c_int
+    lib.zk_gkr_sparse_prove_committed.argtypes = [C.c_int, L.vp, u64p, sz] + [u64p] * 8 + [fp, L.u8p]
+    lib.zk_gkr_sparse_prove_committed.restype = C.c_int
     lib._sparse_declared = True
     return lib
 
@@ -307,9 +309,10 @@ class SparseCircuit:
             self._h = None
 
 
-def sparse_prove(field, layer_gate_rows, out_bits, inputs, circuit=None):
+def sparse_prove(field, layer_gate_rows, out_bits, inputs, circuit=None, commit_output=False):
     """layer_gate_rows: list (layer 0 = output layer) of (n_l, 4) arrays of (left, right, out, op);
-    pass a SparseCircuit as `circuit` to reuse a compiled circuit."""
+    pass a SparseCircuit as `circuit` to reuse a compiled circuit.  commit_output: bind the transcript to the output layer's Merkle
+    root (proof.output_root) instead of its bytes (extension, include/zkmle.h)."""
     lib = _decl_sparse()
     Lm = limbs(field)
     x = np.ascontiguousarray(inputs, np.uint64).reshape(-1, Lm)
@@ -329,10 +332,17 @@ def sparse_prove(field, layer_gate_rows, out_bits, inputs, circuit=None):
     wc = np.zeros((max(nl - 1, 1), Lm), np.uint64)
     ra = np.zeros((out_bits[0], Lm), np.uint64)
     ms = (C.c_float * nl)()
-    L.check(lib.zk_gkr_sparse_prove_compiled(field, circuit._h, L.p64(x), x.shape[0], L.p64(out), L.p64(cs), L.p64(claims), L.p64(co),
-                                             L.p64(ch), L.p64(wb), L.p64(wc), L.p64(ra), ms))
+    root = None
+    if commit_output:
+        rbuf = np.zeros(32, np.uint8)
+        L.check(lib.zk_gkr_sparse_prove_committed(field, circuit._h, L.p64(x), x.shape[0], L.p64(out), L.p64(cs), L.p64(claims), L.p64(co),
+                                                  L.p64(ch), L.p64(wb), L.p64(wc), L.p64(ra), ms, L.p8(rbuf)))
+        root = rbuf.tobytes()
+    else:
+        L.check(lib.zk_gkr_sparse_prove_compiled(field, circuit._h, L.p64(x), x.shape[0], L.p64(out), L.p64(cs), L.p64(claims), L.p64(co),
+                                                 L.p64(ch), L.p64(wb), L.p64(wc), L.p64(ra), ms))
     return SparseProof(circuit_output=out, claimed_sum=cs, layer_claims=claims, coeffs=co, challenges=ch, wb_evals=wb[: nl - 1],
-                       wc_evals=wc[: nl - 1], output_challenges=ra, rounds=rounds, in_bits=in_bits, ms_layers=list(ms))
+                       wc_evals=wc[: nl - 1], output_challenges=ra, rounds=rounds, in_bits=in_bits, ms_layers=list(ms), output_root=root)
 
 
 def sparse_wiring_eval(field, gate_rows, out_bits, in_bits, pa, rb, rc, alpha=None, beta=None, pb=None):
@@ -352,9 +362,11 @@ def _fe_to_bytes_be(field, a):
     return out.tobytes()
 
 
-def sparse_verify(field, layer_gate_rows, out_bits, proof, inputs):
+def sparse_verify(field, layer_gate_rows, out_bits, proof, inputs, commit_output=False):
     """The verifier of gkr_protocol.rs:146-236 for the sparse representation (the wiring predicates are
-    evaluated from the gate lists in O(#gates) on the GPU).  Used by tests and the config-4 bench."""
+    evaluated from the gate lists in O(#gates) on the GPU).  Used by tests and the config-4 bench.
+    commit_output: the proof of sparse_prove(commit_output=True) -- the output layer's Merkle root is recomputed from
+    proof.circuit_output, must equal proof.output_root when that is set, and is what the transcript absorbs first."""
     from .mle import MultilinearPolynomial
     from .sumcheck import Transcript, SumcheckProverProof, verify as sumcheck_verify
     from . import sharded as S
@@ -370,7 +382,14 @@ def sparse_verify(field, layer_gate_rows, out_bits, proof, inputs):
     nl = len(layer_gate_rows)
     t = Transcript()
     w0 = MultilinearPolynomial(field, proof.circuit_output)
-    t.append(w0.convert_to_bytes())
+    if commit_output:
+        from .merkle import merkle_root
+        root = merkle_root(w0)
+        if getattr(proof, "output_root", None) is not None and bytes(proof.output_root) != root:
+            return False
+        t.append(root)
+    else:
+        t.append(w0.convert_to_bytes())
     ra = np.stack([t.random_challenge_as_field_element(field) for _ in range(out_bits[0])])
     claim = w0.evaluate(ra)
     alpha = beta = None

@@ -1,0 +1,68 @@
+"""Keccak-256 Merkle commitment of an HBM table (extension: the reference's merkle_tree/ crate is empty; bytes in include/zkmle.h).
+
+  leaf_i = Keccak256(0x00 || convert_to_bytes(e_i)),  node = Keccak256(0x01 || left || right),  root = the node of level log2(len)
+
+`merkle_root(poly)` keeps nothing but the root (what the committed provers bind their transcript to); `MerkleTree.build(poly)` keeps
+every level in HBM and opens any number of entries with one kernel and one download; `MerkleTree.verify` is host code.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from .mle import limbs
+
+
+def merkle_root(poly):
+    """the 32-byte root of a MultilinearPolynomial's table, root-only mode"""
+    out = np.zeros(32, np.uint8)
+    L.check(L.lib().zk_mle_merkle_root(poly._h, L.p8(out)))
+    return out.tobytes()
+
+
+class MerkleTree:
+    def __init__(self, handle, field, length):
+        self._h, self.field, self.length = handle, field, length
+        self.depth = int(L.lib().zk_merkle_depth(handle))
+
+    @classmethod
+    def build(cls, poly):
+        h = C.c_void_p()
+        L.check(L.lib().zk_merkle_build(poly._h, C.byref(h)))
+        return cls(h, poly.field, len(poly))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                L.lib().zk_merkle_free(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+    def root(self):
+        out = np.zeros(32, np.uint8)
+        L.check(L.lib().zk_merkle_root(self._h, L.p8(out)))
+        return out.tobytes()
+
+    def open(self, indices):
+        """-> (len(indices), depth, 32) uint8: for each index its authentication path, the leaf's sibling first"""
+        idx = np.ascontiguousarray(indices, np.uint64).reshape(-1)
+        out = np.zeros((idx.shape[0], self.depth, 32), np.uint8)
+        buf = out if out.size else np.zeros(32, np.uint8)
+        L.check(L.lib().zk_merkle_open(self._h, idx.ctypes.data_as(C.POINTER(C.c_size_t)), idx.shape[0], L.p8(buf)))
+        return out
+
+    @staticmethod
+    def verify(field, root, index, element, path):
+        """host only: does `element` (Montgomery limbs) at `index` hash up `path` ((depth, 32) bytes) to `root`?"""
+        root = np.frombuffer(bytes(root), np.uint8).copy()
+        if root.shape[0] != 32:
+            raise L.ZkError(L.ZK_E_ARG, "a Merkle root is 32 bytes")
+        path = np.ascontiguousarray(path, np.uint8).reshape(-1, 32)
+        el = np.ascontiguousarray(element, np.uint64).reshape(-1)
+        if el.shape[0] != limbs(field):
+            raise L.ZkError(L.ZK_E_ARG, "element has the wrong number of limbs")
+        ok = C.c_int(0)
+        buf = path if path.size else np.zeros(32, np.uint8)
+        L.check(L.lib().zk_merkle_verify(field, L.p8(root), path.shape[0], int(index), L.p64(el), L.p8(buf), C.byref(ok)))
+        return bool(ok.value)

@@ -33,6 +33,8 @@ def _decl():
         "zk_sumcheck_basic_prove": [vp, u64p, u64p, u64p],
         "zk_sumcheck_basic_prove_on": [vp, vp, u64p, u64p, u64p],
         "zk_sumcheck_basic_verify": [vp, u64p, u64p, sz, C.POINTER(C.c_int)],
+        "zk_sumcheck_basic_prove_committed": [vp, vp, u8p, u64p, u64p, u64p],
+        "zk_sumcheck_basic_verify_committed": [vp, u8p, u64p, u64p, sz, C.POINTER(C.c_int)],
         "zk_sumpoly_evaluate": [C.POINTER(vp), sz, sz, u64p, sz, u64p],
         "zk_sumpoly_reduce": [C.POINTER(vp), sz, sz, vp],
         "zk_prodpoly_reduce": [C.POINTER(vp), sz, vp],
@@ -293,10 +295,11 @@ def verify(proof, transcript, field):
 
 # ---- basic sumcheck -------------------------------------------------------------------------------
 class SumcheckProof:                                                    # prover.rs:15-19
-    def __init__(self, initial_polynomial, initial_claimed_sum, round_univariate_polynomials):
+    def __init__(self, initial_polynomial, initial_claimed_sum, round_univariate_polynomials, root=None):
         self.initial_polynomial = initial_polynomial
         self.initial_claimed_sum = initial_claimed_sum
         self.round_univariate_polynomials = round_univariate_polynomials   # (nvars, 2, limbs)
+        self.root = root                                                # prove_committed: the table's Merkle root (32 bytes)
 
 
 class Prover:
@@ -334,6 +337,22 @@ class Prover:
         self.challenges = ch[:n]
         return SumcheckProof(self.initial_polynomial, cs, rp[:n])
 
+    def prove_committed(self):
+        """prove() with one change (extension, include/zkmle.h): the transcript's first append is the table's Merkle root, not its bytes"""
+        if not self.is_initialized:
+            raise L.ReferencePanic(L.ZK_E_NOT_INIT, "Can't prove without init")
+        n = self.initial_polynomial.number_of_variables()
+        Lm = limbs(self.field)
+        cs = np.zeros(Lm, np.uint64)
+        rp = np.zeros((max(n, 1), 2, Lm), np.uint64)
+        ch = np.zeros((max(n, 1), Lm), np.uint64)
+        root = np.zeros(32, np.uint8)
+        L.check(_decl().zk_sumcheck_basic_prove_committed(self.initial_polynomial._h, self.transcript._h, L.p8(root), L.p64(cs), L.p64(rp), L.p64(ch)))
+        assert np.array_equal(cs, self.initial_claimed_sum)
+        self.round_univariate_polynomials = rp[:n]
+        self.challenges = ch[:n]
+        return SumcheckProof(self.initial_polynomial, cs, rp[:n], root=root.tobytes())
+
 
 class Verifier:
     """basic_sumcheck::verifier::Verifier (verifier.rs:8-71)"""
@@ -356,4 +375,22 @@ class Verifier:
         cs = np.ascontiguousarray(proof.initial_claimed_sum, np.uint64)
         ptr = L.p64(rp) if rp.size else L.p64(cs)
         L.check(_decl().zk_sumcheck_basic_verify(proof.initial_polynomial._h, L.p64(cs), ptr, nr, C.byref(ok)))
+        return bool(ok.value)
+
+    def verify_committed(self, proof, root=None):
+        """verify() of a prove_committed() proof: the root is recomputed from the table; `root` (or proof.root), when given, must equal it"""
+        if not self.is_initialized:
+            raise L.ReferencePanic(L.ZK_E_NOT_INIT, "Can't verify without init")
+        if root is None:
+            root = getattr(proof, "root", None)
+        rp = np.ascontiguousarray(proof.round_univariate_polynomials, np.uint64)
+        nr = rp.shape[0] if rp.size else 0
+        ok = C.c_int(0)
+        cs = np.ascontiguousarray(proof.initial_claimed_sum, np.uint64)
+        ptr = L.p64(rp) if rp.size else L.p64(cs)
+        rbuf = np.frombuffer(bytes(root), np.uint8).copy() if root is not None else None
+        if rbuf is not None and rbuf.shape[0] != 32:
+            raise L.ZkError(L.ZK_E_ARG, "a Merkle root is 32 bytes")
+        L.check(_decl().zk_sumcheck_basic_verify_committed(proof.initial_polynomial._h, L.p8(rbuf) if rbuf is not None else None, L.p64(cs), ptr, nr,
+                                                           C.byref(ok)))
         return bool(ok.value)
