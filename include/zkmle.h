@@ -174,6 +174,28 @@ int zk_merkle_open(const zk_merkle_tree *m, const size_t *indices, size_t nidx, 
 int zk_merkle_verify(int field, const uint8_t root32[32], size_t depth, size_t index, const uint64_t *element,
                      const uint8_t *path, int *ok);
 
+/* ---- number-theoretic transform (extension: the reference's fft/ crate is empty; csrc/ntt.cuh) -------------------------------
+ * The definition is arkworks' Radix2EvaluationDomain.  p - 1 = 2^s t with t odd, g the field's multiplicative generator (7 for
+ * BLS12-381 Fr, s = 32; 5 for BN254 Fr, s = 28): w_{2^s} = g^t and w_n = w_{2^s}^(2^s / n) for n = 2^log_n <= 2^s.  The two Fq
+ * fields have s = 1 (w_2 = -1): lengths 1 and 2 work there.  With the coset shift c (non-zero; NULL = 1):
+ *   forward  out[k] = sum_i in[i] c^i w_n^(i k)      the coefficient table evaluated at c w_n^k   (fft / coset_fft)
+ *   inverse  the exact inverse map, n^-1 and c^-i included                                         (ifft / coset_ifft)
+ * Input and output are in natural order; elements stay in the stored Montgomery form, fully reduced.  Status order: ZK_E_ARG (NULL
+ * argument, bad field, zero coset), ZK_E_NOT_POW2, ZK_E_RANGE (log_n > s), all before ZK_E_NO_DEVICE.  Launches go on the calling
+ * thread's stream, nothing is synchronised; the twiddle tables and, above 2^10 entries, a scratch table of the same length come from the
+ * calling thread's caching pool (zk_release_cached_memory). */
+int zk_ntt_two_adicity(int field, uint32_t *s);                                   /* host */
+int zk_ntt_root_of_unity(int field, uint32_t log_n, uint64_t *omega);             /* host; w_n in the stored form, like zk_fe_* */
+int zk_ntt(zk_table *t, int inverse, const uint64_t *coset);                      /* in place */
+/* upload + zk_ntt + download, like zk_host_partial_evaluate */
+int zk_host_ntt(int field, const uint64_t *in, size_t n, int inverse, const uint64_t *coset, uint64_t *out);
+/* the Reed-Solomon codeword of a coefficient table: its len * 2^log_blowup evaluations at c w^k (a new table).  The zero part of the
+ * padded input is never read from memory. */
+int zk_uni_low_degree_extend(const zk_table *coeffs, uint32_t log_blowup, const uint64_t *coset, zk_table **out);
+/* the product of two coefficient tables of equal length n: a new table of 2 n coefficients (two forward transforms of size 2 n,
+ * zk_prodpoly_reduce, one inverse).  Unequal lengths: ZK_E_LEN_MISMATCH. */
+int zk_uni_mul(const zk_table *a, const zk_table *b, zk_table **out);
+
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */
 int zk_uni_lagrange_interpolate(int field, const uint64_t *xs, const uint64_t *ys, size_t n, uint64_t *out); /* :74 */

@@ -16,6 +16,8 @@ from . import sumcheck  # noqa: F401
 from .sumcheck import Transcript, ProductPolynomial, SumPolynomial, Prover, Verifier  # noqa: F401
 from . import merkle  # noqa: F401
 from .merkle import MerkleTree, merkle_root  # noqa: F401
+from . import ntt  # noqa: F401  (the module, like merkle and kzg: the transform itself is zk.ntt.ntt)
+from .ntt import two_adicity, root_of_unity, ntt_inplace, low_degree_extend, poly_mul  # noqa: F401
 from . import gkr  # noqa: F401
 from .gkr import Circuit, Gate, Layer, Operator  # noqa: F401
 from . import kzg  # noqa: F401
@@ -23,4 +25,5 @@ from .kzg import G1Bases, TrustedSetup, MultilinearKZG, MultilinearKZGProof, Mul
 from . import sharded  # noqa: F401
 
 __all__ = ["MultilinearPolynomial", "FR381", "FQ381", "BN254_FQ", "BN254_FR", "ZkError", "ReferencePanic",
-           "from_ints", "to_ints", "limbs", "lib", "library_path", "MerkleTree", "merkle_root"]
+           "from_ints", "to_ints", "limbs", "lib", "library_path", "MerkleTree", "merkle_root",
+           "ntt", "two_adicity", "root_of_unity", "ntt_inplace", "low_degree_extend", "poly_mul"]

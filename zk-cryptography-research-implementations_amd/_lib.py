@@ -100,6 +100,13 @@ def lib():
         "zk_merkle_root": [vp, u8p],
         "zk_merkle_open": [vp, C.POINTER(sz), sz, u8p],
         "zk_merkle_verify": [C.c_int, u8p, sz, sz, u64p, u8p, C.POINTER(C.c_int)],
+        # number-theoretic transform (extension)
+        "zk_ntt_two_adicity": [C.c_int, C.POINTER(C.c_uint32)],
+        "zk_ntt_root_of_unity": [C.c_int, C.c_uint32, u64p],
+        "zk_ntt": [vp, C.c_int, u64p],
+        "zk_host_ntt": [C.c_int, u64p, sz, C.c_int, u64p, u64p],
+        "zk_uni_low_degree_extend": [vp, C.c_uint32, u64p, C.POINTER(vp)],
+        "zk_uni_mul": [vp, vp, C.POINTER(vp)],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)       # AttributeError = missing export: loud
