@@ -196,6 +196,62 @@ int zk_uni_low_degree_extend(const zk_table *coeffs, uint32_t log_blowup, const 
  * zk_prodpoly_reduce, one inverse).  Unequal lengths: ZK_E_LEN_MISMATCH. */
 int zk_uni_mul(const zk_table *a, const zk_table *b, zk_table **out);
 
+/* ---- FRI low-degree proof (extension: the reference's fri/ crate is empty; csrc/fri.cuh, csrc/zkmle_fri.hip) -------------------
+ * A hash-based commitment to a coefficient table on the NTT and the Merkle tree above: no trusted setup, no MSM.  Fields: ZK_FR381
+ * and ZK_BN254_FR (the two Fq fields cannot hold a domain: every shape returns ZK_E_RANGE there).
+ * Input: a coefficient table of n = 2^d entries; log_blowup = b, 1 <= b <= 8; log_final = f, 0 <= f < d; nqueries = Q,
+ * 1 <= Q <= 4096; the coset shift c, non-zero, NULL = 1.  L = d + b, N = 2^L, R = d - f folds, m = 2^f; w = zk_ntt_root_of_unity(L).
+ * Layer l has N_l = N >> l entries on the domain {c_l w_l^k}, c_l = c^(2^l), w_l = w^(2^l).  Layer 0 is f_0[k] = f(c w^k), the table
+ * zk_uni_low_degree_extend(coeffs, b, c) returns.  The fold, for k < N_l / 2 and the challenge beta_l:
+ *   f_{l+1}[k] = (f_l[k] + f_l[k + N_l/2]) / 2  +  beta_l (f_l[k] - f_l[k + N_l/2]) / (2 c_l w_l^k)
+ * = f_even(x^2) + beta_l f_odd(x^2) on the squared domain: f_{l+1} is the extension, with shift c_{l+1}, of a'[i] = a[2i] + beta_l a[2i+1].
+ * Layers 0 .. R - 1 are each committed by the Merkle tree above of the layer's table in natural order (root_l = zk_mle_merkle_root(f_l)).
+ * Layer R is not committed: it is sent as the m low coefficients h_0 .. h_{m-1} of the polynomial of degree < N_R that interpolates
+ * f_R on {c_R w_R^k} (the higher ones are zero for an honest input).
+ * Transcript (t = NULL: a fresh Transcript::new()), plain appends in this order:
+ *   1. 48 bytes in one append: d, b, f, Q as four big-endian u32, then c as the 32-byte canonical big-endian element;
+ *   2. root_0 (32 bytes);
+ *   3. for l = 0 .. R - 1: beta_l = random_challenge_as_field_element(); then, if l + 1 < R, append root_{l+1};
+ *   4. h_0 .. h_{m-1}, each as the 32-byte canonical big-endian element;
+ *   5. for q < Q: i_q = the little-endian integer of sample_random_challenge() mod N / 2 (duplicates are answered twice).
+ * The answer to i = i_q holds, for each l < R with j_l = i mod N_l / 2, the two elements f_l[j_l] (low) and f_l[j_l + N_l/2] (high) and
+ * their two authentication paths of L - l digests each, in zk_merkle_open's order.
+ * Flat layouts: roots R x 32 bytes; final_coeffs m elements (Montgomery, like every element of this API);
+ * query_values[(q R + l) 2 + side]; query_paths per q, per l, the low path then the high path (zk_fri_proof_sizes gives the counts).
+ * Status order, as for zk_ntt: ZK_E_ARG (NULL, bad field, Q or b out of range, zero coset, and once the length is known to be a
+ * power of two: f >= d, a codeword no longer than its blow-up), ZK_E_NOT_POW2, ZK_E_RANGE (d + b above the field's two-adicity),
+ * all before ZK_E_NO_DEVICE.  The provers have no CPU path; the verifier is host code and never opens a device.
+ * Everything runs on the calling thread's stream.  Tables, trees (one block: 64 bytes x 2 N for the R trees together) and the power
+ * tables come from its caching pool (zk_release_cached_memory); beta_l depends on root_l, so a proof synchronises once per layer. */
+/* one fold of a codeword of len >= 2 on {coset w_len^k} by `beta`: a new table of len / 2 entries */
+int zk_fri_fold(const zk_table *codeword, const uint64_t *beta, const uint64_t *coset, zk_table **out);
+/* host: the counts of the flat outputs; any pointer may be NULL.  ZK_E_ARG / ZK_E_RANGE (d + b > 32) as above */
+int zk_fri_proof_sizes(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots, size_t *nfinal,
+                       size_t *nvalues, size_t *path_bytes);
+/* betas (R elements) and query_indices (Q words) are diagnostic and may be NULL */
+int zk_fri_prove(const zk_table *coeffs, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset,
+                 zk_transcript *t, uint8_t *roots, uint64_t *final_coeffs, uint64_t *betas, uint64_t *query_indices,
+                 uint64_t *query_values, uint8_t *query_paths);
+/* the same from the N evaluations a caller already holds (d = log2 len - log_blowup): zk_fri_prove is zk_uni_low_degree_extend
+ * followed by this.  A codeword that is not of low degree is not an error: its proof does not verify. */
+int zk_fri_prove_codeword(const zk_table *codeword, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
+                          const uint64_t *coset, zk_transcript *t, uint8_t *roots, uint64_t *final_coeffs, uint64_t *betas,
+                          uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths);
+/* HOST only.  Replays the transcript; for every query and layer checks both paths (zk_merkle_verify), folds the pair with beta_l at
+ * x = c_l w_l^(j_l) and compares the result with the opened element of layer l + 1 at position j_l (the low one if j_l < N_{l+1} / 2,
+ * else the high one), for l = R - 1 with sum_j h_j x'^j at x' = c_R w_R^(j_l).  Anything else -- an element that is not reduced
+ * included -- gives *ok = 0.  `t` ends in the prover's state whenever the status is ZK_OK. */
+int zk_fri_verify(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset,
+                  zk_transcript *t, const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values,
+                  const uint8_t *query_paths, int *ok);
+/* HIP-event times of the calling thread's last zk_fri_prove / zk_fri_prove_codeword: the extension (0 for a codeword), the trees
+ * (root downloads included), the folds, and the inverse transform of the last layer with the query gather and its downloads */
+typedef struct {
+    uint32_t layers, queries;
+    float ms_extend, ms_trees, ms_folds, ms_queries, ms_total;
+} zk_fri_stats;
+int zk_fri_last_stats(zk_fri_stats *out);
+
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */
 int zk_uni_lagrange_interpolate(int field, const uint64_t *xs, const uint64_t *ys, size_t n, uint64_t *out); /* :74 */

@@ -107,6 +107,13 @@ def lib():
         "zk_host_ntt": [C.c_int, u64p, sz, C.c_int, u64p, u64p],
         "zk_uni_low_degree_extend": [vp, C.c_uint32, u64p, C.POINTER(vp)],
         "zk_uni_mul": [vp, vp, C.POINTER(vp)],
+        # FRI low-degree proof (extension)
+        "zk_fri_fold": [vp, u64p, u64p, C.POINTER(vp)],
+        "zk_fri_proof_sizes": [C.c_uint32] * 4 + [C.POINTER(sz)] * 4,
+        "zk_fri_prove": [vp] + [C.c_uint32] * 3 + [u64p, vp, u8p, u64p, u64p, u64p, u64p, u8p],
+        "zk_fri_prove_codeword": [vp] + [C.c_uint32] * 3 + [u64p, vp, u8p, u64p, u64p, u64p, u64p, u8p],
+        "zk_fri_verify": [C.c_int] + [C.c_uint32] * 4 + [u64p, vp, u8p, u64p, u64p, u8p, C.POINTER(C.c_int)],
+        "zk_fri_last_stats": [vp],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)       # AttributeError = missing export: loud

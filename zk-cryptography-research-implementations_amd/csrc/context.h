@@ -86,6 +86,11 @@ class Transcript;
 int transcript_absorb_table(Transcript &t, const zk_table *table);
 // the table's Keccak-256 Merkle root, root-only mode (zkmle_merkle.hip): what the committed provers append in place of the table's bytes
 int merkle_root_device(const zk_table *t, uint8_t root32[32]);
+// every level of the table's tree into the caller's device block of 2 len - 1 digests, laid out as zk_merkle_build's; launches only, no
+// checks (the FRI prover: one block for the trees of all its layers)
+int merkle_levels_device(const zk_table *t, uint64_t *levels);
+// zk_uni_low_degree_extend into a table the caller allocated (out->len = coeffs->len << log_blowup); launches only, no checks (zkmle_ntt.hip)
+int ntt_extend_into(const zk_table *coeffs, const uint64_t *coset, zk_table *out);
 // Proof slots shared by a proof made of several sumchecks (zkmle_sumcheck.hip): the sponge, the interpolation basis and every slot
 // (coefficients, challenges, final values, layer links) live in ONE device block; rounds() and link() only enqueue kernels on the
 // current stream, collect() is the single download.  Slot layout of rounds(): round k's nfac + 1 coefficients at s0 + per k, its

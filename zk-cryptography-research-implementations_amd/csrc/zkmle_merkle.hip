@@ -95,6 +95,10 @@ int merkle_root_device(const zk_table *t, uint8_t root32[32]) {
     ZK_DISPATCH_FIELD(t->field, return root_only<F>(t, root32));
     return ZK_OK;
 }
+int merkle_levels_device(const zk_table *t, uint64_t *levels) {
+    ZK_DISPATCH_FIELD(t->field, ZK_TRY(launch_leaves<F>(t, levels)));
+    return hash_up(levels, t->len);
+}
 }  // namespace zk
 
 extern "C" {

@@ -181,6 +181,13 @@ int ntt_check(int field, size_t len, const uint64_t *coset) {
 
 }  // namespace
 
+namespace zk {
+int ntt_extend_into(const zk_table *coeffs, const uint64_t *coset, zk_table *out) {
+    ZK_DISPATCH_FIELD(coeffs->field, return ntt_run<F>(coeffs->dptr, coeffs->len, out->dptr, ilog2(out->len), false, coset));
+    return ZK_OK;
+}
+}  // namespace zk
+
 extern "C" {
 
 int zk_ntt_two_adicity(int field, uint32_t *s) {
