@@ -26,7 +26,7 @@ struct FriUni {
 };
 
 // x / 2 for a canonical x: (x + p) / 2 when x is odd; p < 2^(32 N - 1), so the sum fits the limbs
-template <class F> __device__ __forceinline__ Fe<F> fe_halve(const Fe<F> &x) {
+template <class F> ZK_HD Fe<F> fe_halve(const Fe<F> &x) {
     const uint32_t mask = 0u - (x.l[0] & 1u);
     Fe<F> s;
     unsigned c = 0;
@@ -39,7 +39,7 @@ template <class F> __device__ __forceinline__ Fe<F> fe_halve(const Fe<F> &x) {
 
 // a + r t for the uniform multiplier r: ufold's columns (ufield.cuh) with the digits of t in place of those of a difference.  a, t:
 // normalized limbs of canonical elements.  Output: normalized limbs of a value congruent to a + r t, below a + p (1 + 2^-24).
-template <class F> __device__ __forceinline__ Ufe<F> uni_muladd(const UniMul<F> &m, const Ufe<F> &a, const Ufe<F> &t) {
+template <class F> ZK_HD Ufe<F> uni_muladd(const UniMul<F> &m, const Ufe<F> &a, const Ufe<F> &t) {
     constexpr int L = UParams<F>::L;
     uint64_t T[L];
     T[0] = 0;
