@@ -252,6 +252,73 @@ typedef struct {
 } zk_fri_stats;
 int zk_fri_last_stats(zk_fri_stats *out);
 
+/* ---- FRI polynomial commitment: opening at a point (extension; csrc/fri_pcs.cuh, csrc/zkmle_fri_pcs.hip) ------------------------
+ * What turns the low-degree proof above into a polynomial commitment: commit to a coefficient table, later claim f(z) = y, and let a
+ * verifier who holds only the root check the claim.  Batched from the start: k polynomials opened at ONE point with ONE proof
+ * (zk_kzg_batch_open's counterpart); k = 1 is the plain opening.  Fields and parameters are FRI's: ZK_FR381 and ZK_BN254_FR; d, b, f, Q,
+ * the coset c (NULL = 1), L = d + b, N = 2^L, w = zk_ntt_root_of_unity(L).
+ * Commitment to a table a of n = 2^d coefficients: root = zk_mle_merkle_root(zk_uni_low_degree_extend(a, b, c)) -- byte for byte the
+ * root_0 zk_fri_prove puts out for the same input.  The prover-side zk_fri_commitment owns a device copy of the coefficients, the
+ * codeword and every level of its tree (64 bytes x N), long-lived allocations of their own like zk_merkle_build's.
+ * Opening of f_0 .. f_{k-1}, 1 <= k <= 64, at z.  All commitments share field, d, b and c (else ZK_E_LEN_MISMATCH).  z must be a reduced
+ * element outside the evaluation domain: (z / c)^N = 1 returns ZK_E_ARG, from prover and verifier alike, before the device check.
+ *   1. y_j = f_j(z).
+ *   2. Transcript (t = NULL: a fresh Transcript::new()), plain appends in this order: one append of 4 bytes, k as a big-endian u32; the k
+ *      roots, 32 bytes each; z as its 32-byte canonical big-endian element; y_0 .. y_{k-1} likewise.  Then
+ *      gamma = random_challenge_as_field_element().
+ *   3. The quotient codeword, for i < N and x_i = c w^i:   q[i] = (sum_j gamma^j (f_j[i] - y_j)) / (x_i - z).
+ *      For honest y_j every f_j - y_j vanishes at z, so q is the extension of a polynomial of degree < n - 1.  FRI proves degree < n:
+ *      there is ONE degree of slack, i.e. the proof shows that sum_j gamma^j (f_j - y_j) agrees on the queried positions with (x - z) times
+ *      a polynomial of degree <= n - 1, a product of degree <= n where the honest numerator has degree <= n - 1.  The slack is the usual
+ *      one of a DEEP quotient proved at the committed degree bound; it costs the soundness analysis one unit of degree, not a query.
+ *   4. zk_fri_prove_codeword(q, b, f, Q, c, t, ..) on the SAME transcript, unchanged: it appends its header, roots and final coefficients
+ *      and samples i_0 .. i_{Q-1}.
+ *   5. For every query q, side s in {0, 1} and j < k: the element f_j[i_q + s N/2] and its authentication path of L digests against
+ *      root_j, in zk_merkle_open's order.  Flat layouts: opened_values[(q 2 + s) k + j]; opened_paths in the same order, L x 32 bytes each.
+ * Verifier (HOST only, never opens a device): replays 2, runs the FRI verifier on the same transcript, checks every path of 5 with
+ * zk_merkle_verify, and checks for every (q, s) that  sum_j gamma^j (v_j - y_j) = (x - z) (FRI's layer-0 value at that position),
+ * x = c w^(i_q + s N/2).  Anything else -- an element that is not reduced included -- gives *ok = 0.  `t` ends in the prover's state
+ * whenever the status is ZK_OK.
+ * Status order as for FRI: ZK_E_ARG (NULL, bad field, k, b or Q out of range, zero coset, d < 1, f >= d, z in the domain or not reduced),
+ * ZK_E_NOT_POW2, ZK_E_LEN_MISMATCH, ZK_E_RANGE (a field without a domain, d + b above the two-adicity), all before ZK_E_NO_DEVICE.
+ * Everything runs on the calling thread's stream; the quotient, the power tables and the gather buffers come from its caching pool. */
+typedef struct zk_fri_commitment zk_fri_commitment;
+int zk_fri_commit(const zk_table *coeffs, uint32_t log_blowup, const uint64_t *coset, zk_fri_commitment **out);
+int zk_fri_commitment_free(zk_fri_commitment *cm);
+int zk_fri_commitment_root(const zk_fri_commitment *cm, uint8_t root32[32]);                 /* host copy, no device work */
+/* the N evaluations f(c w^i): a BORROWED table that lives as long as the commitment (do not free it) */
+int zk_fri_commitment_codeword(const zk_fri_commitment *cm, const zk_table **out);
+/* host: zk_fri_proof_sizes' four counts plus nopened = Q 2 k elements and opened_path_bytes = Q 2 k L 32; any pointer may be NULL */
+int zk_fri_pcs_sizes(uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots, size_t *nfinal,
+                     size_t *nvalues, size_t *path_bytes, size_t *nopened, size_t *opened_path_bytes);
+/* y = sum_i coeffs[i] z^i of a device table of 2^d coefficients (d >= 0), on the device: the element zk_uni_evaluate gives on the host.
+ * One lane per run of 8 coefficients, the powers of z from a two-level table, two launches and one 32-byte download. */
+int zk_uni_evaluate_device(const zk_table *coeffs, const uint64_t *z, uint64_t *y);
+/* step 3 on its own (as zk_fri_fold is for the fold): a new table of N entries from the k codewords, ys (k elements) and gamma.  The N
+ * inversions are Montgomery batch inversions of T entries per lane, T = N / 2^16 between 1 and 16;
+ * the environment's ZK_FRI_PCS_BATCH = 1, 2, 4, 8 or 16, read per call, overrides the choice (tests, measurements).  The table does not
+ * depend on T. */
+int zk_fri_pcs_quotient(const zk_fri_commitment *const *cms, size_t k, const uint64_t *z, const uint64_t *ys, const uint64_t *gamma,
+                        zk_table **out);
+/* ys_out: k elements.  roots .. query_paths: the FRI proof of the quotient, as zk_fri_prove_codeword (betas and query_indices may be
+ * NULL).  opened_values: Q 2 k elements; opened_paths: Q 2 k L 32 bytes. */
+int zk_fri_pcs_open(const zk_fri_commitment *const *cms, size_t k, const uint64_t *z, uint32_t log_final, uint32_t nqueries, zk_transcript *t,
+                    uint64_t *ys_out, uint8_t *roots, uint64_t *final_coeffs, uint64_t *betas, uint64_t *query_indices, uint64_t *query_values,
+                    uint8_t *query_paths, uint64_t *opened_values, uint8_t *opened_paths);
+/* HOST only.  roots_of_f: k x 32 bytes, in the prover's order. */
+int zk_fri_pcs_verify(int field, size_t k, const uint8_t *roots_of_f, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
+                      const uint64_t *coset, const uint64_t *z, const uint64_t *ys, zk_transcript *t, const uint8_t *roots,
+                      const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, const uint64_t *opened_values,
+                      const uint8_t *opened_paths, int *ok);
+/* HIP-event times of the calling thread's last zk_fri_pcs_open: the k evaluations (download included), the quotient, the FRI proof of it
+ * (zk_fri_last_stats splits that one further), the gather of the opened values and paths with its downloads; ms_total is the host clock
+ * over the call.  After zk_fri_pcs_quotient: ms_quotient alone.  batch = the T of the quotient's batch inversion. */
+typedef struct {
+    uint32_t polys, batch;
+    float ms_evals, ms_quotient, ms_fri, ms_gather, ms_total;
+} zk_fri_pcs_stats;
+int zk_fri_pcs_last_stats(zk_fri_pcs_stats *out);
+
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */
 int zk_uni_lagrange_interpolate(int field, const uint64_t *xs, const uint64_t *ys, size_t n, uint64_t *out); /* :74 */

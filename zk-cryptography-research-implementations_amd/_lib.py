@@ -114,6 +114,17 @@ def lib():
         "zk_fri_prove_codeword": [vp] + [C.c_uint32] * 3 + [u64p, vp, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_fri_verify": [C.c_int] + [C.c_uint32] * 4 + [u64p, vp, u8p, u64p, u64p, u8p, C.POINTER(C.c_int)],
         "zk_fri_last_stats": [vp],
+        # FRI polynomial commitment: opening at a point (extension)
+        "zk_fri_commit": [vp, C.c_uint32, u64p, C.POINTER(vp)],
+        "zk_fri_commitment_free": [vp],
+        "zk_fri_commitment_root": [vp, u8p],
+        "zk_fri_commitment_codeword": [vp, C.POINTER(vp)],
+        "zk_fri_pcs_sizes": [C.c_uint32] * 5 + [C.POINTER(sz)] * 6,
+        "zk_uni_evaluate_device": [vp, u64p, u64p],
+        "zk_fri_pcs_quotient": [C.POINTER(vp), sz, u64p, u64p, u64p, C.POINTER(vp)],
+        "zk_fri_pcs_open": [C.POINTER(vp), sz, u64p, C.c_uint32, C.c_uint32, vp, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p, u8p],
+        "zk_fri_pcs_verify": [C.c_int, sz, u8p] + [C.c_uint32] * 4 + [u64p, u64p, u64p, vp, u8p, u64p, u64p, u8p, u64p, u8p, C.POINTER(C.c_int)],
+        "zk_fri_pcs_last_stats": [vp],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)       # AttributeError = missing export: loud

@@ -91,6 +91,11 @@ int merkle_root_device(const zk_table *t, uint8_t root32[32]);
 int merkle_levels_device(const zk_table *t, uint64_t *levels);
 // zk_uni_low_degree_extend into a table the caller allocated (out->len = coeffs->len << log_blowup); launches only, no checks (zkmle_ntt.hip)
 int ntt_extend_into(const zk_table *coeffs, const uint64_t *coset, zk_table *out);
+// zk_fri_verify's checks and body on a caller's Transcript; indices_out (nqueries words, may be null) receives the sampled query indices
+// (zkmle_fri.hip; the opening verifier of zkmle_fri_pcs.hip checks the committed polynomials at the same positions)
+int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
+                    const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,
+                    uint64_t *indices_out);
 // Proof slots shared by a proof made of several sumchecks (zkmle_sumcheck.hip): the sponge, the interpolation basis and every slot
 // (coefficients, challenges, final values, layer links) live in ONE device block; rounds() and link() only enqueue kernels on the
 // current stream, collect() is the single download.  Slot layout of rounds(): round k's nfac + 1 coefficients at s0 + per k, its

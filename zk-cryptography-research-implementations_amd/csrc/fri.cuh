@@ -107,7 +107,7 @@ template <class F> __global__ void __launch_bounds__(kFriBlock) fri_query_values
 
 // every authentication path with one launch (merkle_open_kernel over the layers): per query and layer the low entry's path, then the
 // high entry's, log_len0 - l digests each, the leaf's sibling first
-__global__ void __launch_bounds__(kFriBlock) fri_query_paths_kernel(FriLayers a, const uint64_t *__restrict__ indices, size_t nq, uint64_t *__restrict__ paths) {
+static __global__ void __launch_bounds__(kFriBlock) fri_query_paths_kernel(FriLayers a, const uint64_t *__restrict__ indices, size_t nq, uint64_t *__restrict__ paths) {
     const uint32_t per = a.path_off[a.nlayers];
     const size_t total = nq * per, stride = (size_t)gridDim.x * kFriBlock;
     for (size_t t = (size_t)blockIdx.x * kFriBlock + threadIdx.x; t < total; t += stride) {

@@ -299,8 +299,9 @@ int prove_any(const zk_table *in, bool is_codeword, uint32_t b, uint32_t f, uint
 }
 
 // ---- the verifier (host) -------------------------------------------------------------------------------------------------------
+// `indices_out` (Q words, may be null): the sampled i_q, for a caller that checks more at the queried positions (zkmle_fri_pcs.hip)
 template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t Q, const uint64_t *coset, Transcript &tr, const uint8_t *roots,
-                                   const uint64_t *final_coeffs, const uint64_t *values, const uint8_t *paths, int *ok) {
+                                   const uint64_t *final_coeffs, const uint64_t *values, const uint8_t *paths, int *ok, uint64_t *indices_out) {
     constexpr int W = F::N / 2;
     const unsigned L = d + b, R = d - f;
     const size_t m = (size_t)1 << f;
@@ -323,6 +324,7 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
     }
     std::vector<uint64_t> idx(Q);
     for (unsigned q = 0; q < Q; q++) idx[q] = sample_index(tr, L - 1);
+    if (indices_out) memcpy(indices_out, idx.data(), Q * 8);
     *ok = 0;
     for (size_t k = 0; good && k < (size_t)Q * R * 2; k++) good = is_reduced<F>(values + k * W);
     if (!good) return ZK_OK;
@@ -362,6 +364,21 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
 
 }  // namespace
 
+namespace zk {
+int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
+                    const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,
+                    uint64_t *indices_out) {
+    if (!roots || !final_coeffs || !query_values || !query_paths || !ok || field_limbs64(field) < 0) return ZK_E_ARG;
+    ZK_TRY(params_check(log_blowup, nqueries));
+    if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
+    if (d < 1 || log_final >= d) return ZK_E_ARG;
+    if (d > 32) return ZK_E_RANGE;
+    ZK_TRY(shape_check(field, d + log_blowup, log_blowup, log_final));
+    FRI_DISPATCH(field, return verify_host<F>(d, log_blowup, log_final, nqueries, coset, tr, roots, final_coeffs, query_values, query_paths, ok, indices_out));
+    return ZK_OK;
+}
+}  // namespace zk
+
 extern "C" {
 
 int zk_fri_fold(const zk_table *codeword, const uint64_t *beta, const uint64_t *coset, zk_table **out) {
@@ -399,15 +416,8 @@ int zk_fri_prove_codeword(const zk_table *codeword, uint32_t log_blowup, uint32_
 
 int zk_fri_verify(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, zk_transcript *t,
                   const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok) {
-    if (!roots || !final_coeffs || !query_values || !query_paths || !ok || field_limbs64(field) < 0) return ZK_E_ARG;
-    ZK_TRY(params_check(log_blowup, nqueries));
-    if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
-    if (d < 1 || log_final >= d) return ZK_E_ARG;
-    if (d > 32) return ZK_E_RANGE;
-    ZK_TRY(shape_check(field, d + log_blowup, log_blowup, log_final));
     Transcript fresh;
-    FRI_DISPATCH(field, return verify_host<F>(d, log_blowup, log_final, nqueries, coset, t ? t->t : fresh, roots, final_coeffs, query_values, query_paths, ok));
-    return ZK_OK;
+    return fri_verify_core(field, d, log_blowup, log_final, nqueries, coset, t ? t->t : fresh, roots, final_coeffs, query_values, query_paths, ok, nullptr);
 }
 
 int zk_fri_last_stats(zk_fri_stats *out) {

@@ -4,6 +4,10 @@
   transcript's challenge; the last layer is sent as its m = 2^log_final low coefficients; Q queries open a pair of every committed layer.
 
 `prove` / `prove_codeword` run on the GPU (there is no CPU path); `verify` is host code and needs no device.
+
+The evaluation opening on top of it (include/zkmle.h "FRI polynomial commitment"): `commit` keeps the coefficients, the codeword and its tree
+in HBM; `open_at` proves f_j(z) = y_j for k commitments at one point with one proof (the DEEP quotient, proved low-degree, every query tied
+back to the roots); `verify_opening` is host code and needs nothing but the roots.
 """
 import ctypes as C
 
@@ -96,3 +100,120 @@ def last_stats():
     st = _Stats()
     L.check(L.lib().zk_fri_last_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _Stats._fields_}
+
+
+# ---- the evaluation opening ------------------------------------------------------------------------------------------------------------
+class _PcsStats(C.Structure):
+    _fields_ = [("polys", C.c_uint32), ("batch", C.c_uint32), ("ms_evals", C.c_float), ("ms_quotient", C.c_float), ("ms_fri", C.c_float),
+                ("ms_gather", C.c_float), ("ms_total", C.c_float)]
+
+
+def pcs_sizes(k, d, log_blowup, log_final, nqueries):
+    """-> sizes(..) + (nopened, opened_path_bytes) of an opening of k polynomials of 2^d coefficients"""
+    out = [C.c_size_t(0) for _ in range(6)]
+    L.check(L.lib().zk_fri_pcs_sizes(k, d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+class FriCommitment:
+    """The prover's side of a commitment: a device copy of the coefficients, the codeword and every level of its Merkle tree.  `root` is all a
+    verifier needs.  Use as a context manager, or call free()."""
+
+    def __init__(self, field, d, log_blowup, coset, handle):
+        self.field, self.d, self.log_blowup, self._h = field, d, log_blowup, handle
+        self.coset = None if coset is None else _elem(field, coset).copy()
+        root = np.zeros(32, np.uint8)
+        L.check(L.lib().zk_fri_commitment_root(handle, L.p8(root)))
+        self.root = root.tobytes()
+
+    def codeword(self):
+        """a copy of the N evaluations f(c w^i) as a table of its own"""
+        h, out = C.c_void_p(), C.c_void_p()
+        L.check(L.lib().zk_fri_commitment_codeword(self._h, C.byref(h)))
+        L.check(L.lib().zk_table_clone(h, C.byref(out)))
+        return MultilinearPolynomial(self.field, _handle=out)
+
+    def free(self):
+        if self._h is not None:
+            L.lib().zk_fri_commitment_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:      # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+def commit(coeffs, log_blowup, coset=None):
+    """the commitment to the coefficient table `coeffs` (2^d entries): its root is root_0 of `prove` on the same input"""
+    h = C.c_void_p()
+    cs = None if coset is None else L.p64(_elem(coeffs.field, coset))
+    L.check(L.lib().zk_fri_commit(coeffs._h, log_blowup, cs, C.byref(h)))
+    return FriCommitment(coeffs.field, len(coeffs).bit_length() - 1, log_blowup, coset, h)
+
+
+class FriOpening:
+    """ys (k, limbs); proof: the FriProof of the quotient; opened_values (Q, 2, k, limbs); opened_paths (Q 2 k L 32,) bytes"""
+
+    def __init__(self, field, k, d, log_blowup, log_final, nqueries, coset=None):
+        self.field, self.k = field, k
+        self.proof = FriProof(field, d, log_blowup, log_final, nqueries, coset)
+        n = limbs(field)
+        self.ys = np.zeros((k, n), np.uint64)
+        self.opened_values = np.zeros((nqueries, 2, k, n), np.uint64)
+        self.opened_paths = np.zeros(nqueries * 2 * k * (d + log_blowup) * 32, np.uint8)
+
+
+def _handles(commitments):
+    arr = (C.c_void_p * len(commitments))(*[c._h for c in commitments])
+    return arr
+
+
+def quotient(commitments, z, ys, gamma):
+    """the DEEP quotient codeword (sum_j gamma^j (f_j[i] - ys[j])) / (c w^i - z): a new table of N entries"""
+    c0 = commitments[0]
+    h = C.c_void_p()
+    ys = np.ascontiguousarray(ys, np.uint64)
+    L.check(L.lib().zk_fri_pcs_quotient(_handles(commitments), len(commitments), L.p64(_elem(c0.field, z)), L.p64(ys),
+                                        L.p64(_elem(c0.field, gamma)), C.byref(h)))
+    return MultilinearPolynomial(c0.field, _handle=h)
+
+
+def open_at(commitments, z, log_final, nqueries, transcript=None):
+    """one proof that f_j(z) = ys[j] for every commitment (same field, size, blow-up and coset); z outside the evaluation domain"""
+    c0 = commitments[0]
+    op = FriOpening(c0.field, len(commitments), c0.d, c0.log_blowup, log_final, nqueries, c0.coset)
+    pr = op.proof
+    L.check(L.lib().zk_fri_pcs_open(_handles(commitments), len(commitments), L.p64(_elem(c0.field, z)), log_final, nqueries, _handle(transcript),
+                                    L.p64(op.ys), L.p8(pr.roots), L.p64(pr.final_coeffs), L.p64(pr.betas), L.p64(pr.query_indices),
+                                    L.p64(pr.query_values), L.p8(pr.query_paths), L.p64(op.opened_values), L.p8(op.opened_paths)))
+    return op
+
+
+def verify_opening(field, roots, z, opening, d, log_blowup, log_final, nqueries, coset=None, transcript=None):
+    """host only: `roots` = the k commitment roots (32 bytes each) in the prover's order"""
+    ok = C.c_int(0)
+    pr = opening.proof
+    rf = np.frombuffer(b"".join(bytes(r) for r in roots), np.uint8).copy()
+    arrs = [np.ascontiguousarray(a, t) for a, t in ((opening.ys, np.uint64), (pr.roots, np.uint8), (pr.final_coeffs, np.uint64),
+                                                    (pr.query_values, np.uint64), (pr.query_paths, np.uint8),
+                                                    (opening.opened_values, np.uint64), (opening.opened_paths, np.uint8))]
+    ys, fr, fin, vals, paths, ov, opaths = arrs
+    cs = None if coset is None else L.p64(_elem(field, coset))
+    L.check(L.lib().zk_fri_pcs_verify(field, len(roots), L.p8(rf), d, log_blowup, log_final, nqueries, cs, L.p64(_elem(field, z)), L.p64(ys),
+                                      _handle(transcript), L.p8(fr), L.p64(fin), L.p64(vals), L.p8(paths), L.p64(ov), L.p8(opaths), C.byref(ok)))
+    return bool(ok.value)
+
+
+def pcs_last_stats():
+    """milliseconds of the calling thread's last open_at: the evaluations, the quotient, the FRI proof, the opening gather"""
+    st = _PcsStats()
+    L.check(L.lib().zk_fri_pcs_last_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _PcsStats._fields_}

@@ -52,3 +52,10 @@ def poly_mul(a, b):
     h = C.c_void_p()
     L.check(L.lib().zk_uni_mul(a._h, b._h, C.byref(h)))
     return MultilinearPolynomial(a.field, _handle=h)
+
+
+def evaluate_at(poly, z):
+    """sum_i poly[i] z^i of the coefficient table `poly`, on the device: one element (Montgomery limbs)"""
+    out = np.zeros(limbs(poly.field), np.uint64)
+    L.check(L.lib().zk_uni_evaluate_device(poly._h, L.p64(_elem(poly.field, z)), L.p64(out)))
+    return out
