@@ -319,6 +319,81 @@ typedef struct {
 } zk_fri_pcs_stats;
 int zk_fri_pcs_last_stats(zk_fri_pcs_stats *out);
 
+/* ---- FRI commitment opened as a multilinear polynomial (extension; csrc/fri_ml.cuh, csrc/zkmle_fri_ml.hip) -----------------------
+ * The same zk_fri_commitment, read the other way: the n = 2^d entries of an EVALUATION table T are committed as the coefficient table of
+ * zk_fri_commit(T, b, c), and the claim opened is y = zk_mle_evaluate(T, z) at z = (z_0 .. z_{d-1}) in zk_mle_evaluate's order (variable 0 is
+ * the most significant index bit).  This is the Basefold opening: a codeword folded with  f'(x^2) = (1 - r) f_even(x^2) + r f_odd(x^2)
+ * instead of f_even + beta f_odd is the extension of a'[i] = (1 - r) a[2i] + r a[2i+1], the MLE fold of the coefficient table by r in its
+ * LAST variable; a sumcheck of  sum_x T[x] eq(x, z) = y  that binds the variables last to first on the same challenges ends in the very
+ * table the folded codeword ends in.  No basis change, no second tree of T: one commitment opens as a univariate (above) or as a multilinear.
+ * Fields and parameters are FRI's: ZK_FR381 and ZK_BN254_FR; d, b, f, Q, c (NULL = 1), L = d + b, N = 2^L, R = d - f >= 1, m = 2^f.  Any
+ * reduced elements are allowed in z; nothing is refused for lying in a domain.
+ * Rounds.  T_0 = T; round l < R binds variable v = d - 1 - l, the lowest index bit of T_l.  E_l = the eq table of (z_0 .. z_{v-1}) over the
+ * remaining v variables; A_l = prod_{l' < l} eq1(r_l', z_{d-1-l'}), eq1(a, b) = a b + (1 - a)(1 - b).  The round polynomial
+ *   g_l(X) = A_l eq1(X, z_v) (S_0 + X (S_1 - S_0)),   S_X = sum_x' E_l[x'] T_l[2x' + X],
+ * is sent as the three elements g_l(0), g_l(1), g_l(2).  Then T_{l+1} = zk_mle_fold(T_l, var = last, r_l) and
+ *   f_{l+1}[k] = (1 - r_l) (f_l[k] + f_l[k + N_l/2]) / 2  +  r_l (f_l[k] - f_l[k + N_l/2]) / (2 c_l w_l^k)
+ * = zk_uni_low_degree_extend(T_{l+1}, b, c_{l+1}), byte for byte.
+ * Transcript (t = NULL: a fresh Transcript::new()), plain appends in this order:
+ *   1. FRI's 48-byte header, unchanged;
+ *   2. root_0, the commitment's root;
+ *   3. z_0 .. z_{d-1}, then y, each as the 32-byte canonical big-endian element;
+ *   4. for l = 0 .. R - 1: g_l(0), g_l(1), g_l(2) (96 bytes); r_l = random_challenge_as_field_element(); if l + 1 < R, root_{l+1} =
+ *      zk_mle_merkle_root(f_{l+1});
+ *   5. the m entries of T_R, 32 bytes each: at once the final table of the sumcheck and the final coefficients of the FRI layer;
+ *   6. Q indices, exactly as FRI's step 5.
+ * Answers: layout and counts are FRI's (zk_fri_proof_sizes; query_values[(q R + l) 2 + side], the paths in the same order); roots[0] is the
+ * commitment's root.  Layer 0's values and paths are read from the commitment's own codeword and tree: nothing of T's codeword is hashed again.
+ * Verifier (HOST only, never opens a device): replays the transcript; claim = y; per round the three elements must be reduced and
+ * g_l(0) + g_l(1) = claim, then claim = g_l(r_l) by quadratic interpolation; at the end A_R (the MLE of T_R at (z_0 .. z_{f-1})) = claim.  For
+ * every query and layer it checks both paths, folds the pair with r_l by the formula above and compares with the next layer's opened
+ * element, for l = R - 1 with sum_j T_R[j] x'^j at x' = c_R w_R^(j_l).  It is FRI's verifier with the fold mode switched, not a copy.
+ * Anything else -- an element that is not reduced included, z and y among them -- gives *ok = 0.  `t` ends in the prover's state whenever
+ * the status is ZK_OK.
+ * Status order is FRI's: ZK_E_ARG (NULL, bad field, Q, b or f out of range, zero coset; from the prover also a z_i that is not reduced), then
+ * ZK_E_NOT_POW2, then ZK_E_RANGE, all before ZK_E_NO_DEVICE.  Everything runs on the calling thread's stream.  T_l, E_l, the layers
+ * f_1 .. f_{R-1} and their R - 1 trees are ONE block of the caching pool (32 bytes x (2 n + 3 N) and a little); layer R is never built, since
+ * T_R comes out of the sumcheck's side.  One host synchronisation per round: r_l depends on g_l, and root_{l+1} on r_l -- the fold of the
+ * codeword, its tree and the next round's pass over T_l and E_l are enqueued behind one another and waited for once.  y needs no pass of
+ * its own: y = g_0(0) + g_0(1). */
+/* one Lagrange-form fold of a codeword of len >= 2 on {coset w_len^k} by r (as zk_fri_fold is for the monomial form): a new table of len / 2
+ * entries = zk_uni_low_degree_extend(zk_mle_fold(T, last, r), b, coset^2) when the codeword is zk_uni_low_degree_extend(T, b, coset) */
+int zk_fri_ml_fold(const zk_table *codeword, const uint64_t *r, const uint64_t *coset, zk_table **out);
+/* host: zk_fri_proof_sizes' four counts plus nround = 3 R elements of round polynomials; any pointer may be NULL */
+int zk_fri_ml_sizes(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots, size_t *nfinal, size_t *nvalues,
+                    size_t *path_bytes, size_t *nround);
+/* z: d elements.  y_out: one element; round_polys: 3 R; roots: R x 32 bytes; final_table: m; challenges (R) and query_indices (Q) are
+ * diagnostic and may be NULL.  The commitment's tables are only read. */
+int zk_fri_ml_open(const zk_fri_commitment *cm, const uint64_t *z, uint32_t log_final, uint32_t nqueries, zk_transcript *t, uint64_t *y_out,
+                   uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices,
+                   uint64_t *query_values, uint8_t *query_paths);
+/* HOST only.  root32: the commitment's root as the verifier holds it; roots[0] must be the same bytes. */
+int zk_fri_ml_verify(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
+                     const uint64_t *coset, const uint64_t *z, const uint64_t *y, zk_transcript *t, const uint64_t *round_polys,
+                     const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, int *ok);
+/* HIP-event times of the calling thread's last zk_fri_ml_open: the sumcheck's passes (E_0, the round kernels, their downloads and the last
+ * fold of T), the folds of the codeword, the trees, the query gather with its downloads; ms_total is the host clock over the call */
+typedef struct {
+    uint32_t rounds, queries;
+    float ms_sumcheck, ms_folds, ms_trees, ms_queries, ms_total;
+} zk_fri_ml_stats;
+int zk_fri_ml_last_stats(zk_fri_ml_stats *out);
+/* The basic sumcheck finished by a verifier who holds 32 bytes.  Prover::prove (prover.rs:35-71) with one change, as
+ * zk_sumcheck_basic_prove_committed: the first append (:38-39) is the COMMITMENT's root (zk_fri_commitment_root: the root of the codeword of
+ * the table, not zk_mle_merkle_root of the table).  The rounds run on the commitment's device table, which is only read; then
+ * zk_fri_ml_open runs at z = the sumcheck's d challenges on the same transcript.  claimed_sum: one element; round_polys: d x 2; challenges:
+ * d elements (required: they are the point); the rest as zk_fri_ml_open.  t = NULL: a fresh Transcript::new(). */
+int zk_sumcheck_basic_prove_succinct(const zk_fri_commitment *cm, uint32_t log_final, uint32_t nqueries, zk_transcript *t,
+                                     uint64_t *claimed_sum, uint64_t *round_polys, uint64_t *challenges, uint64_t *y_out,
+                                     uint64_t *open_round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *open_challenges,
+                                     uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths);
+/* HOST only: no table, no device.  The checks of Verifier::verify (verifier.rs:23-71) on the root, with the final `evaluate` (:67) replaced by
+ * y and the verified opening of y at the challenges.  Statuses as zk_fri_ml_verify, all before the transcript is touched. */
+int zk_sumcheck_basic_verify_succinct(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final,
+                                      uint32_t nqueries, const uint64_t *coset, zk_transcript *t, const uint64_t *claimed_sum,
+                                      const uint64_t *round_polys, const uint64_t *y, const uint64_t *open_round_polys, const uint8_t *roots,
+                                      const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, int *ok);
+
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */
 int zk_uni_lagrange_interpolate(int field, const uint64_t *xs, const uint64_t *ys, size_t n, uint64_t *out); /* :74 */

@@ -19,7 +19,7 @@ from .merkle import MerkleTree, merkle_root  # noqa: F401
 from . import ntt  # noqa: F401  (the module, like merkle and kzg: the transform itself is zk.ntt.ntt)
 from .ntt import two_adicity, root_of_unity, ntt_inplace, low_degree_extend, poly_mul, evaluate_at  # noqa: F401
 from . import fri  # noqa: F401  (the module: zk.fri.prove, zk.fri.verify, ...)
-from .fri import FriProof, FriCommitment, FriOpening  # noqa: F401
+from .fri import FriProof, FriCommitment, FriOpening, FriMlOpening  # noqa: F401
 from . import gkr  # noqa: F401
 from .gkr import Circuit, Gate, Layer, Operator  # noqa: F401
 from . import kzg  # noqa: F401
@@ -29,4 +29,4 @@ from . import sharded  # noqa: F401
 __all__ = ["MultilinearPolynomial", "FR381", "FQ381", "BN254_FQ", "BN254_FR", "ZkError", "ReferencePanic",
            "from_ints", "to_ints", "limbs", "lib", "library_path", "MerkleTree", "merkle_root",
            "ntt", "two_adicity", "root_of_unity", "ntt_inplace", "low_degree_extend", "poly_mul", "evaluate_at", "fri", "FriProof",
-           "FriCommitment", "FriOpening"]
+           "FriCommitment", "FriOpening", "FriMlOpening"]

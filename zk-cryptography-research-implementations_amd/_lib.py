@@ -125,6 +125,15 @@ def lib():
         "zk_fri_pcs_open": [C.POINTER(vp), sz, u64p, C.c_uint32, C.c_uint32, vp, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p, u8p],
         "zk_fri_pcs_verify": [C.c_int, sz, u8p] + [C.c_uint32] * 4 + [u64p, u64p, u64p, vp, u8p, u64p, u64p, u8p, u64p, u8p, C.POINTER(C.c_int)],
         "zk_fri_pcs_last_stats": [vp],
+        # FRI commitment opened as a multilinear polynomial (extension)
+        "zk_fri_ml_fold": [vp, u64p, u64p, C.POINTER(vp)],
+        "zk_fri_ml_sizes": [C.c_uint32] * 4 + [C.POINTER(sz)] * 5,
+        "zk_fri_ml_open": [vp, u64p, C.c_uint32, C.c_uint32, vp, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
+        "zk_fri_ml_verify": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, u64p, u64p, vp, u64p, u8p, u64p, u64p, u8p, C.POINTER(C.c_int)],
+        "zk_fri_ml_last_stats": [vp],
+        "zk_sumcheck_basic_prove_succinct": [vp, C.c_uint32, C.c_uint32, vp, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
+        "zk_sumcheck_basic_verify_succinct": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, vp, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u8p,
+                                                                                 C.POINTER(C.c_int)],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)       # AttributeError = missing export: loud

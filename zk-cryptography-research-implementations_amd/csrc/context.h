@@ -78,6 +78,16 @@ struct zk_table {
     void *dptr;
     int owned;      // 0 = view of caller memory (zk_table_wrap), 1 = hipMalloc, 2 = block of the scratch pool
 };
+// the prover's side of a FRI commitment (zkmle_fri_pcs.hip makes and frees it; zkmle_fri_ml.hip opens it as a multilinear polynomial)
+struct zk_fri_commitment {
+    int field;
+    unsigned d, b;
+    bool has_coset;
+    uint64_t coset[4];
+    zk_table *coeffs, *codeword;     // long-lived tables of their own (zk_table_clone, zk_table_alloc)
+    uint64_t *levels;                // 2 N - 1 digests (hipMalloc), zk_merkle_build's layout
+    uint8_t root[32];
+};
 
 namespace zk {
 class Transcript;
@@ -93,9 +103,19 @@ int merkle_levels_device(const zk_table *t, uint64_t *levels);
 int ntt_extend_into(const zk_table *coeffs, const uint64_t *coset, zk_table *out);
 // zk_fri_verify's checks and body on a caller's Transcript; indices_out (nqueries words, may be null) receives the sampled query indices
 // (zkmle_fri.hip; the opening verifier of zkmle_fri_pcs.hip checks the committed polynomials at the same positions)
+// `ml` (may be null) switches the fold mode: the proof is the multilinear opening of include/zkmle.h (zkmle_fri_ml.hip) -- z and y are appended
+// after root_0, every round's three evaluations before its challenge, the layers fold in Lagrange form, `final_coeffs` is the final table T_R
+// and the sumcheck's checks are made beside FRI's.  roots[0] is then the verifier's own copy of the commitment's root.
+struct FriMlClaim {
+    const uint64_t *z, *y, *round_polys;                     // d elements, one element, R x 3 elements
+};
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,
-                    uint64_t *indices_out);
+                    uint64_t *indices_out, const FriMlClaim *ml = nullptr);
+// Prover::prove (prover.rs:35-71) on a caller's Transcript whose binding append (:38-39) is the 32 bytes `bound` -- a commitment the caller
+// holds -- instead of the table's bytes; no checks (zkmle_sumcheck.hip; the succinct sumcheck of zkmle_fri_ml.hip)
+int sumcheck_basic_prove_bound(const zk_table *table, Transcript &tr, const uint8_t bound[32], uint64_t *claimed_sum, uint64_t *round_polys,
+                               uint64_t *challenges);
 // Proof slots shared by a proof made of several sumchecks (zkmle_sumcheck.hip): the sponge, the interpolation basis and every slot
 // (coefficients, challenges, final values, layer links) live in ONE device block; rounds() and link() only enqueue kernels on the
 // current stream, collect() is the single download.  Slot layout of rounds(): round k's nfac + 1 coefficients at s0 + per k, its

@@ -300,8 +300,10 @@ int prove_any(const zk_table *in, bool is_codeword, uint32_t b, uint32_t f, uint
 
 // ---- the verifier (host) -------------------------------------------------------------------------------------------------------
 // `indices_out` (Q words, may be null): the sampled i_q, for a caller that checks more at the queried positions (zkmle_fri_pcs.hip)
+// `ml`: the fold mode of the multilinear opening (context.h FriMlClaim); null = the monomial fold of zk_fri_verify, byte for byte as before
 template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t Q, const uint64_t *coset, Transcript &tr, const uint8_t *roots,
-                                   const uint64_t *final_coeffs, const uint64_t *values, const uint8_t *paths, int *ok, uint64_t *indices_out) {
+                                   const uint64_t *final_coeffs, const uint64_t *values, const uint8_t *paths, int *ok, uint64_t *indices_out,
+                                   const FriMlClaim *ml) {
     constexpr int W = F::N / 2;
     const unsigned L = d + b, R = d - f;
     const size_t m = (size_t)1 << f;
@@ -311,8 +313,20 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
     host_to_bytes_be<F>(c, cbe);
     transcript_header(tr, d, b, f, Q, cbe);
     tr.append(roots, 32);
+    if (ml) {
+        for (unsigned i = 0; i <= d; i++) {                  // z_0 .. z_{d-1}, then y
+            const uint64_t *el = i < d ? ml->z + (size_t)i * W : ml->y;
+            good = good && is_reduced<F>(el);
+            tr.append_be<F>(load_host<F>(el));
+        }
+    }
     std::vector<Fe<F>> beta(R);
     for (unsigned l = 0; l < R; l++) {
+        for (unsigned k = 0; ml && k < 3; k++) {             // g_l(0), g_l(1), g_l(2)
+            const uint64_t *el = ml->round_polys + ((size_t)l * 3 + k) * W;
+            good = good && is_reduced<F>(el);
+            tr.append_be<F>(load_host<F>(el));
+        }
         beta[l] = tr.random_challenge_as_field_element<F>();
         if (l + 1 < R) tr.append(roots + 32 * (l + 1), 32);
     }
@@ -330,6 +344,28 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
     if (!good) return ZK_OK;
 
     const Fe<F> w = root_of_unity<F>(L), winv = fe_inv<F>(w), inv2 = fe_inv<F>(fe_from_u64<F>(2));
+    if (ml) {                                                // the sumcheck of sum_x T[x] eq(x, z) = y beside the folds, on the same challenges
+        const Fe<F> one = fe_one<F>(), two = fe_from_u64<F>(2);
+        Fe<F> claim = load_host<F>(ml->y), A = one;
+        for (unsigned l = 0; l < R; l++) {
+            const uint64_t *g = ml->round_polys + (size_t)l * 3 * W;
+            const Fe<F> g0 = load_host<F>(g), g1 = load_host<F>(g + W), g2 = load_host<F>(g + 2 * W), r = beta[l];
+            if (!fe_eq<F>(fe_add<F>(g0, g1), claim)) return ZK_OK;
+            // g_l(r) from its values at 0, 1, 2:  g0 (r - 1)(r - 2) / 2 - g1 r (r - 2) + g2 r (r - 1) / 2
+            const Fe<F> r1 = fe_sub<F>(r, one), r2 = fe_sub<F>(r, two);
+            const Fe<F> outer = fe_mul<F>(inv2, fe_add<F>(fe_mul<F>(g0, fe_mul<F>(r1, r2)), fe_mul<F>(g2, fe_mul<F>(r, r1))));
+            claim = fe_sub<F>(outer, fe_mul<F>(g1, fe_mul<F>(r, r2)));
+            const Fe<F> zv = load_host<F>(ml->z + (size_t)(d - 1 - l) * W);   // eq1(r_l, z_v) = 1 - r - z + 2 r z
+            A = fe_mul<F>(A, fe_add<F>(fe_sub<F>(fe_sub<F>(one, r), zv), fe_mul<F>(two, fe_mul<F>(r, zv))));
+        }
+        std::vector<Fe<F>> t(h);                             // the MLE of T_R at (z_0 .. z_{f-1}): f folds of variable 0
+        for (unsigned i = 0; i < f; i++) {
+            const size_t half = m >> (i + 1);
+            const Fe<F> zi = load_host<F>(ml->z + (size_t)i * W);
+            for (size_t j = 0; j < half; j++) t[j] = fe_add<F>(t[j], fe_mul<F>(zi, fe_sub<F>(t[j + half], t[j])));
+        }
+        if (!fe_eq<F>(fe_mul<F>(A, t[0]), claim)) return ZK_OK;
+    }
     std::vector<Fe<F>> cinv(R);                               // c_l^-1
     Fe<F> cl = c, ci = fe_inv<F>(c);
     for (unsigned l = 0; l < R; l++) {
@@ -351,7 +387,11 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
             if (!ok_lo || !ok_hi) return ZK_OK;
             const Fe<F> a = load_host<F>(lo), bb = load_host<F>(hi);
             const Fe<F> xinv = fe_mul<F>(cinv[l], fe_pow<F>(winv, (uint64_t)j << l));
-            const Fe<F> v = fe_mul<F>(inv2, fe_add<F>(fe_add<F>(a, bb), fe_mul<F>(fe_mul<F>(beta[l], xinv), fe_sub<F>(a, bb))));
+            Fe<F> v;
+            if (ml) {                                         // (1 - r) (a + b) / 2 + r (a - b) / (2 x)
+                const Fe<F> even = fe_mul<F>(fe_sub<F>(fe_one<F>(), beta[l]), fe_add<F>(a, bb));
+                v = fe_mul<F>(inv2, fe_add<F>(even, fe_mul<F>(fe_mul<F>(beta[l], xinv), fe_sub<F>(a, bb))));
+            } else v = fe_mul<F>(inv2, fe_add<F>(fe_add<F>(a, bb), fe_mul<F>(fe_mul<F>(beta[l], xinv), fe_sub<F>(a, bb))));
             Fe<F> want;
             if (l + 1 < R) want = load_host<F>(values + (((size_t)q * R + l + 1) * 2 + (j >= half / 2 ? 1 : 0)) * W);
             else want = uni_evaluate<F>(h, fe_mul<F>(cR, fe_pow<F>(w, (uint64_t)j << R)));
@@ -367,14 +407,15 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
 namespace zk {
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,
-                    uint64_t *indices_out) {
+                    uint64_t *indices_out, const FriMlClaim *ml) {
+    if (ml && (!ml->z || !ml->y || !ml->round_polys)) return ZK_E_ARG;
     if (!roots || !final_coeffs || !query_values || !query_paths || !ok || field_limbs64(field) < 0) return ZK_E_ARG;
     ZK_TRY(params_check(log_blowup, nqueries));
     if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
     if (d < 1 || log_final >= d) return ZK_E_ARG;
     if (d > 32) return ZK_E_RANGE;
     ZK_TRY(shape_check(field, d + log_blowup, log_blowup, log_final));
-    FRI_DISPATCH(field, return verify_host<F>(d, log_blowup, log_final, nqueries, coset, tr, roots, final_coeffs, query_values, query_paths, ok, indices_out));
+    FRI_DISPATCH(field, return verify_host<F>(d, log_blowup, log_final, nqueries, coset, tr, roots, final_coeffs, query_values, query_paths, ok, indices_out, ml));
     return ZK_OK;
 }
 }  // namespace zk

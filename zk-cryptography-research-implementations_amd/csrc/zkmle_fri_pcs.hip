@@ -14,16 +14,6 @@
 
 using namespace zk;
 
-struct zk_fri_commitment {
-    int field;
-    unsigned d, b;
-    bool has_coset;
-    uint64_t coset[4];
-    zk_table *coeffs, *codeword;     // long-lived tables of their own (zk_table_clone, zk_table_alloc)
-    uint64_t *levels;                // 2 N - 1 digests (hipMalloc), zk_merkle_build's layout
-    uint8_t root[32];
-};
-
 namespace {
 
 struct DevBuf {   // RAII block of the caching pool

@@ -697,13 +697,15 @@ int fold_pass(const void *in, void *out, size_t n, int k, const void *const *rp,
 }
 
 // ---- basic sumcheck prover: prover.rs:22-71 ----------------------------------------------------------
+// `bound` (with root32 null): the caller's 32 bytes are the binding append (sumcheck_basic_prove_bound)
 template <class F> int basic_prove(const zk_table *table, Transcript &tr, uint64_t *claimed_sum, uint64_t *round_polys, uint64_t *challenges,
-                                   uint8_t *root32 = nullptr) {
+                                   uint8_t *root32 = nullptr, const uint8_t *bound = nullptr) {
     const size_t esz = 4 * F::N, L64 = F::N / 2;
     size_t len = table->len;
     unsigned nvars = ilog2(len);
     double t0 = now_ms();
-    ZK_TRY(bind_table<F>(tr, table, root32));                          // :38-39
+    if (bound) tr.append(bound, 32);
+    else ZK_TRY(bind_table<F>(tr, table, root32));                     // :38-39
     double t1 = now_ms();
     g_stats = zk_sumcheck_stats{nvars, (float)(t1 - t0), 0.f};
     // working buffers: len/2 and len/4 elements, plus reduction partials
@@ -1373,6 +1375,11 @@ int transcript_absorb_table(Transcript &t, const zk_table *table) {
     if (!table) return ZK_E_ARG;
     ZK_TRY(require_device());
     ZK_DISPATCH_FIELD(table->field, return absorb_table<F>(t, table->dptr, table->len));
+    return ZK_OK;
+}
+int sumcheck_basic_prove_bound(const zk_table *table, Transcript &tr, const uint8_t bound[32], uint64_t *claimed_sum, uint64_t *round_polys,
+                               uint64_t *challenges) {
+    ZK_DISPATCH_FIELD(table->field, return basic_prove<F>(table, tr, claimed_sum, round_polys, challenges, nullptr, bound));
     return ZK_OK;
 }
 }  // namespace zk

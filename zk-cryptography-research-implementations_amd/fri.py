@@ -8,6 +8,10 @@
 The evaluation opening on top of it (include/zkmle.h "FRI polynomial commitment"): `commit` keeps the coefficients, the codeword and its tree
 in HBM; `open_at` proves f_j(z) = y_j for k commitments at one point with one proof (the DEEP quotient, proved low-degree, every query tied
 back to the roots); `verify_opening` is host code and needs nothing but the roots.
+
+The same commitment opened as a MULTILINEAR polynomial (include/zkmle.h "FRI commitment opened as a multilinear polynomial"): the committed
+table read as evaluations over the cube, `open_multilinear` proves y = evaluate(table, z) by a sumcheck interleaved with Lagrange-form folds of
+the codeword; `verify_multilinear` is host code and needs nothing but the root.
 """
 import ctypes as C
 
@@ -217,3 +221,90 @@ def pcs_last_stats():
     st = _PcsStats()
     L.check(L.lib().zk_fri_pcs_last_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _PcsStats._fields_}
+
+
+# ---- the multilinear opening ------------------------------------------------------------------------------------------------------------
+class _MlStats(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("queries", C.c_uint32), ("ms_sumcheck", C.c_float), ("ms_folds", C.c_float), ("ms_trees", C.c_float),
+                ("ms_queries", C.c_float), ("ms_total", C.c_float)]
+
+
+def ml_sizes(d, log_blowup, log_final, nqueries):
+    """-> sizes(..) + (nround,): the 3 R elements of round polynomials of a multilinear opening of a table of 2^d entries"""
+    out = [C.c_size_t(0) for _ in range(5)]
+    L.check(L.lib().zk_fri_ml_sizes(d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+def ml_fold(codeword, r, coset=None):
+    """one Lagrange-form fold of a codeword on {coset w_len^k}: (1 - r) f_even + r f_odd on the squared domain, a new table of half the length"""
+    h = C.c_void_p()
+    cs = None if coset is None else L.p64(_elem(codeword.field, coset))
+    L.check(L.lib().zk_fri_ml_fold(codeword._h, L.p64(_elem(codeword.field, r)), cs, C.byref(h)))
+    return MultilinearPolynomial(codeword.field, _handle=h)
+
+
+class FriMlOpening:
+    """y (limbs,); round_polys (R, 3, limbs); roots (R, 32) bytes, roots[0] = the commitment's; final_table (m, limbs); query_values
+    (Q, R, 2, limbs); query_paths (path_bytes,) bytes; challenges (R, limbs) and query_indices (Q,) are what the prover's transcript gave
+    (diagnostic: the verifier derives its own)."""
+
+    def __init__(self, field, d, log_blowup, log_final, nqueries, coset=None):
+        self.field, self.d, self.log_blowup, self.log_final, self.nqueries = field, d, log_blowup, log_final, nqueries
+        self.coset = None if coset is None else _elem(field, coset).copy()
+        nroots, nfinal, nvalues, path_bytes, nround = ml_sizes(d, log_blowup, log_final, nqueries)
+        n = limbs(field)
+        self.y = np.zeros(n, np.uint64)
+        self.round_polys = np.zeros((nround // 3, 3, n), np.uint64)
+        self.roots = np.zeros((nroots, 32), np.uint8)
+        self.final_table = np.zeros((nfinal, n), np.uint64)
+        self.challenges = np.zeros((nroots, n), np.uint64)
+        self.query_indices = np.zeros(nqueries, np.uint64)
+        self.query_values = np.zeros((nqueries, nroots, 2, n), np.uint64)
+        self.query_paths = np.zeros(path_bytes, np.uint8)
+
+    def _coset(self):
+        return None if self.coset is None else L.p64(self.coset)
+
+
+def _point(field, z):
+    z = np.ascontiguousarray(z, np.uint64)
+    if z.ndim != 2 or z.shape[1] != limbs(field):
+        raise L.ZkError(L.ZK_E_ARG, "the point is a (d, limbs) array of elements")
+    return z
+
+
+def open_multilinear(commitment, z, log_final, nqueries, transcript=None):
+    """the proof that the committed table, read as evaluations over the cube, has the multilinear extension value `.y` at z (d elements, variable 0
+    the most significant index bit, as MultilinearPolynomial.evaluate)"""
+    z = _point(commitment.field, z)
+    if z.shape[0] != commitment.d:
+        raise L.ZkError(L.ZK_E_ARG, "the point needs one element per variable")
+    op = FriMlOpening(commitment.field, commitment.d, commitment.log_blowup, log_final, nqueries, commitment.coset)
+    L.check(L.lib().zk_fri_ml_open(commitment._h, L.p64(z), log_final, nqueries, _handle(transcript), L.p64(op.y), L.p64(op.round_polys), L.p8(op.roots),
+                                   L.p64(op.final_table), L.p64(op.challenges), L.p64(op.query_indices), L.p64(op.query_values), L.p8(op.query_paths)))
+    return op
+
+
+def verify_multilinear(root, z, opening, transcript=None):
+    """host only: `root` = the commitment's 32 bytes; the claim checked is evaluate(table, z) = opening.y"""
+    ok = C.c_int(0)
+    op = opening
+    rbuf = np.frombuffer(bytes(root), np.uint8).copy()
+    if rbuf.shape[0] != 32:
+        raise L.ZkError(L.ZK_E_ARG, "a Merkle root is 32 bytes")
+    z = _point(op.field, z)
+    if z.shape[0] != op.d:
+        raise L.ZkError(L.ZK_E_ARG, "the point needs one element per variable")
+    y, rp, fin, vals = (np.ascontiguousarray(a, np.uint64) for a in (op.y, op.round_polys, op.final_table, op.query_values))
+    roots, paths = np.ascontiguousarray(op.roots, np.uint8), np.ascontiguousarray(op.query_paths, np.uint8)
+    L.check(L.lib().zk_fri_ml_verify(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, op._coset(), L.p64(z), L.p64(y),
+                                     _handle(transcript), L.p64(rp), L.p8(roots), L.p64(fin), L.p64(vals), L.p8(paths), C.byref(ok)))
+    return bool(ok.value)
+
+
+def ml_last_stats():
+    """milliseconds of the calling thread's last open_multilinear: the sumcheck's passes, the codeword folds, the trees, the query gather"""
+    st = _MlStats()
+    L.check(L.lib().zk_fri_ml_last_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _MlStats._fields_}

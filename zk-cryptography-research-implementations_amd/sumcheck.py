@@ -354,6 +354,51 @@ class Prover:
         return SumcheckProof(self.initial_polynomial, cs, rp[:n], root=root.tobytes())
 
 
+class SuccinctSumcheckProof:
+    """prove_succinct's proof: what a verifier who holds the commitment's 32 bytes needs, and no table.  `opening` is a fri.FriMlOpening at
+    z = the sumcheck's challenges (its .y = the table's multilinear extension there)."""
+
+    def __init__(self, root, initial_claimed_sum, round_univariate_polynomials, opening):
+        self.root = root
+        self.initial_claimed_sum = initial_claimed_sum
+        self.round_univariate_polynomials = round_univariate_polynomials   # (nvars, 2, limbs)
+        self.opening = opening
+
+
+def prove_succinct(commitment, log_final, nqueries, transcript=None):
+    """Prover.prove_committed bound to a fri.FriCommitment of the table (extension, include/zkmle.h): the transcript's first append is the
+    commitment's root, the rounds run on the commitment's device table, and the table's value at the challenges is opened against the root
+    on the same transcript.  -> (SuccinctSumcheckProof, challenges)"""
+    from . import fri
+    field, n = commitment.field, commitment.d
+    Lm = limbs(field)
+    cs = np.zeros(Lm, np.uint64)
+    rp = np.zeros((n, 2, Lm), np.uint64)
+    ch = np.zeros((n, Lm), np.uint64)
+    op = fri.FriMlOpening(field, n, commitment.log_blowup, log_final, nqueries, commitment.coset)
+    L.check(L.lib().zk_sumcheck_basic_prove_succinct(commitment._h, log_final, nqueries, None if transcript is None else transcript._h, L.p64(cs), L.p64(rp),
+                                                     L.p64(ch), L.p64(op.y), L.p64(op.round_polys), L.p8(op.roots), L.p64(op.final_table),
+                                                     L.p64(op.challenges), L.p64(op.query_indices), L.p64(op.query_values), L.p8(op.query_paths)))
+    return SuccinctSumcheckProof(commitment.root, cs, rp, op), ch
+
+
+def verify_succinct(proof, root=None, transcript=None):
+    """host only, no table and no device: Verifier.verify with the final evaluate replaced by the opened value and its verified opening.
+    `root` (default: proof.root) is the commitment the verifier holds."""
+    op = proof.opening
+    rbuf = np.frombuffer(bytes(proof.root if root is None else root), np.uint8).copy()
+    if rbuf.shape[0] != 32:
+        raise L.ZkError(L.ZK_E_ARG, "a Merkle root is 32 bytes")
+    cs, rp, y, orp, fin, vals = (np.ascontiguousarray(a, np.uint64) for a in (proof.initial_claimed_sum, proof.round_univariate_polynomials, op.y,
+                                                                            op.round_polys, op.final_table, op.query_values))
+    roots, paths = np.ascontiguousarray(op.roots, np.uint8), np.ascontiguousarray(op.query_paths, np.uint8)
+    ok = C.c_int(0)
+    L.check(L.lib().zk_sumcheck_basic_verify_succinct(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, op._coset(),
+                                                      None if transcript is None else transcript._h, L.p64(cs), L.p64(rp), L.p64(y), L.p64(orp),
+                                                      L.p8(roots), L.p64(fin), L.p64(vals), L.p8(paths), C.byref(ok)))
+    return bool(ok.value)
+
+
 class Verifier:
     """basic_sumcheck::verifier::Verifier (verifier.rs:8-71)"""
 
