@@ -378,6 +378,52 @@ typedef struct {
     float ms_sumcheck, ms_folds, ms_trees, ms_queries, ms_total;
 } zk_fri_ml_stats;
 int zk_fri_ml_last_stats(zk_fri_ml_stats *out);
+/* ---- FRI commitment opened at several points (extension; csrc/fri_ml.cuh fri_ml_round_w_kernel, csrc/zkmle_fri_ml.hip) -----------------
+ * ONE proof that y_p = zk_mle_evaluate(T, z^p) for P points z^0 .. z^{P-1} of the same commitment: the folded layers and their trees, the
+ * larger part of an opening, are built once instead of P times.  Everything is as in "FRI commitment opened as a multilinear polynomial"
+ * above: fields, d, b, f, Q, c, R = d - f >= 1, m = 2^f; a round binds the LAST variable; the codeword fold is zk_fri_ml_fold.
+ * Points: 1 <= P <= 8, each of d reduced elements in zk_mle_evaluate's order; equal points are allowed.
+ * Transcript (t = NULL: a fresh Transcript::new()), plain appends in this order:
+ *   1. FRI's 48-byte header, unchanged;
+ *   2. root_0;
+ *   3. P as a 4-byte big-endian u32;
+ *   4. the points, point-major: z^0_0 .. z^0_{d-1}, z^1_0 ..;
+ *   5. y_0 .. y_{P-1} (points and claims each as the 32-byte canonical big-endian element);
+ *   6. gamma = random_challenge_as_field_element();
+ *   7. (nothing is appended) claim_0 = sum_p gamma^p y_p;
+ *   8. for l = 0 .. R - 1: g_l(0), g_l(1), g_l(2); r_l = random_challenge_as_field_element(); root_{l+1} if l + 1 < R;
+ *   9. the m entries of T_R;
+ *  10. the Q indices.  Steps 8 to 10 are exactly steps 4 to 6 of the single-point protocol.
+ * Round polynomial.  W_0[x] = sum_p gamma^p eq(x, z^p) and W_{l+1} = zk_mle_fold(W_l, last, r_l), as T_{l+1} from T_l:
+ *   g_l(X) = sum_x' (W_l[2x'] + X (W_l[2x'+1] - W_l[2x'])) (T_l[2x'] + X (T_l[2x'+1] - T_l[2x'])).
+ * Since W_l[2x' + X'] = sum_p gamma^p A^p_l E^p_l[x'] eq1(X', z^p_v) (v = d - 1 - l, A^p_l and E^p_l the single-point protocol's A_l and
+ * E_l at z^p), this is the SAME polynomial as the per-point form  sum_p gamma^p A^p_l eq1(X, z^p_v) (S^p_0 + X (S^p_1 - S^p_0)),
+ * S^p_X = sum_x' E^p_l[x'] T_l[2x' + X]; at P = 1 it is the single-point protocol's g_l.  The prover computes the first form -- one pass
+ * over T_l and W_l whose cost does not depend on P -- and the verifier checks the second, which needs no table.
+ * Answers: layouts and counts are zk_fri_ml_sizes'; they do not depend on P.  Layer 0 is answered from the commitment's own codeword and tree.
+ * Verifier (HOST only): fri_verify_core with the FriMlClaim switch extended to P points and gamma, not a copy.  claim = claim_0; per round
+ * g_l(0) + g_l(1) = claim, then claim = g_l(r_l); at the end  sum_{j<m} T_R[j] W_R[j] = claim  with
+ * W_R[j] = sum_p gamma^p A^p_R eq(j; z^p_0 .. z^p_{f-1}),  A^p_R = prod_l eq1(r_l, z^p_{d-1-l}); then FRI's query checks with the Lagrange fold.
+ * Anything unreduced -- a point's entry, a claim, any proof element -- gives *ok = 0.  Status order, and "t ends in the prover's state
+ * whenever the status is ZK_OK", are zk_fri_ml_verify's; P outside 1 .. 8 is ZK_E_ARG (from the prover also an unreduced point entry).
+ * Prover: y_p by zk_mle_evaluate (P passes, before gamma exists); W_0 from P eq tables combined in one pass (P = 1: built in place); then
+ * one pass per round (fri_ml_round_w_kernel) that folds T_{l-1} and W_{l-1} by r_{l-1} and accumulates g_l at the nodes 0, 1 and infinity
+ * (g_l(2) = 2 g_l(1) - g_l(0) + 2 g_l(inf) on the host).  One host synchronisation per round, as in the single-point opening.  T_l, W_l,
+ * the layers, their trees and the P eq tables are ONE block of the caching pool (32 bytes x (3 n + 3 N + P n) and a little; no P n for P = 1). */
+/* one round pass on its own (as zk_fri_ml_fold is for the fold).  r = NULL: round 0's form, nothing is folded or allocated, g3 = g(0), g(1),
+ * g(2) of (T, W), len >= 2.  r != NULL: *T_out = zk_mle_fold(T, last, r), *W_out the same of W (new tables, len / 2), g3 of the folded pair;
+ * len >= 4.  ZK_E_ARG (NULL, mixed or unsupported field, too short, r not reduced), ZK_E_LEN_MISMATCH, ZK_E_NOT_POW2, then ZK_E_NO_DEVICE. */
+int zk_fri_ml_round(const zk_table *T, const zk_table *W, const uint64_t *r, zk_table **T_out, zk_table **W_out, uint64_t *g3);
+/* points: npoints x d elements, point-major.  ys_out: npoints elements; gamma_out (one element) is diagnostic and may be NULL; the rest as
+ * zk_fri_ml_open.  zk_fri_ml_last_stats reports this call too: the y_p and W_0 passes count in ms_sumcheck. */
+int zk_fri_ml_open_points(const zk_fri_commitment *cm, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                          zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table,
+                          uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths);
+/* HOST only. */
+int zk_fri_ml_verify_points(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
+                            const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys, zk_transcript *t,
+                            const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
+                            const uint8_t *query_paths, int *ok);
 /* The basic sumcheck finished by a verifier who holds 32 bytes.  Prover::prove (prover.rs:35-71) with one change, as
  * zk_sumcheck_basic_prove_committed: the first append (:38-39) is the COMMITMENT's root (zk_fri_commitment_root: the root of the codeword of
  * the table, not zk_mle_merkle_root of the table).  The rounds run on the commitment's device table, which is only read; then
@@ -706,6 +752,21 @@ int zk_gkr_sparse_prove_committed(int field, const zk_sparse_circuit *c, const u
                                   uint64_t *circuit_output, uint64_t *claimed_sum, uint64_t *layer_claims,
                                   uint64_t *coeffs, uint64_t *challenges, uint64_t *wb_evals, uint64_t *wc_evals,
                                   uint64_t *output_challenges, float *ms_layers, uint8_t output_root32[32]);
+/* Succinct sparse GKR without a trusted setup, for ZK_FR381 and ZK_BN254_FR (extension): the inputs are the table `cm` commits to
+ * (zk_fri_commit; 2^in_bits(last layer) entries, else ZK_E_LEN_MISMATCH; no host copy is passed), and the verifier holds the gate lists, the
+ * output layer and the commitment's 32-byte root.  The GKR transcript's FIRST append is that root (returned in input_root32); every append
+ * of zk_gkr_sparse_prove_compiled follows unchanged, so the last layer's challenges rb and rc depend on the commitment.  Then
+ * zk_fri_ml_open_points opens the commitment at z^0 = rb, z^1 = rc (P = 2; the last layer's first and second k = in_bits challenges) on a
+ * FRESH Transcript::new(): the opening absorbs its whole statement -- header, root, points, values -- itself, and the GKR sponge lives in
+ * device slots, so nothing is gained by continuing it.  input_evals (2 elements) = the opening's y_0, y_1: they take the place of the last
+ * layer's W(rb), W(rc) in the verifier's final check.  The proof outputs are zk_gkr_sparse_prove_compiled's, the opening outputs
+ * zk_fri_ml_open's (sizes: zk_fri_ml_sizes(in_bits, cm's b, log_final, nqueries)). */
+int zk_gkr_sparse_prove_succinct(int field, const zk_sparse_circuit *c, const zk_fri_commitment *cm, uint32_t log_final, uint32_t nqueries,
+                                 uint64_t *circuit_output, uint64_t *claimed_sum, uint64_t *layer_claims, uint64_t *coeffs,
+                                 uint64_t *challenges, uint64_t *wb_evals, uint64_t *wc_evals, uint64_t *output_challenges, float *ms_layers,
+                                 uint8_t input_root32[32], uint64_t *input_evals, uint64_t *open_round_polys, uint8_t *roots,
+                                 uint64_t *final_table, uint64_t *open_challenges, uint64_t *query_indices, uint64_t *query_values,
+                                 uint8_t *query_paths);
 /* independent evaluation of the wiring predicates at a point (the verifier's O(#gates) work):
  * add_r = sum_{add gates} w_g eq(rb, left_g) eq(rc, right_g), same for mul, with
  * w_g = alpha eq(pa, out_g) + beta eq(pb, out_g)  (layer 0: alpha = 1, beta = 0, pa = output challenges). */

@@ -1,0 +1,273 @@
+"""CPU: the host side of the multilinear opening of a FRI commitment at SEVERAL points (include/zkmle.h "FRI commitment opened at several
+points").  The Python model of tests/_fri_ml_points_model.py is checked against itself (its openings pass its verifier, a false y_p does not,
+for each p) and against the single-point model: at P = 1, on the same challenges, its round polynomials -- sums over a weight table -- are
+the per-point form A_l eq1(X, z_v) (S_0 + X (S_1 - S_0)) of tests/_fri_ml_model.py.  The library's HOST verifier zk_fri_ml_verify_points
+accepts the model's openings over both fields, the shapes (d, b, f) = (1,1,0), (4,2,1), (6,1,0), (5,2,4), with and without a coset, P in
+{1, 2, 3, 8}, at random points, at z^0 = z^1 and at points with entries in {0, 1, p - 1}; it leaves a caller's transcript in the model's
+state; it rejects a single-bit change in every byte class, another P, the two points swapped, every differing parameter and every element
+that is not reduced.  The verifier is fri_verify_core with its claim switch extended: tests/test_fri_ml_cpu.py, test_fri_cpu.py and
+test_fri_pcs_cpu.py run the other three verifiers through the same core, unchanged.
+
+A zk_fri_commitment cannot exist without a device: the prover, the round pass and the succinct GKR run in tests/test_gpu_fri_ml_points.py."""
+import ctypes as C
+import functools
+import random
+
+import numpy as np
+import pytest
+
+import __graft_entry__ as G
+import _fri_ml_model as ML
+import _fri_ml_points_model as PT
+import _fri_pcs_model as PM
+import _merkle_model as MM
+import _ntt_model as NM
+from oracle import pymodel as M
+
+zk = G.import_package()
+P64, P8 = C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
+p64 = lambda a: a.ctypes.data_as(P64) if a is not None else None
+p8 = lambda a: a.ctypes.data_as(P8) if a is not None else None
+NEW_NAMES = ("zk_fri_ml_round", "zk_fri_ml_open_points", "zk_fri_ml_verify_points", "zk_gkr_sparse_prove_succinct")
+SHAPES = [(1, 1, 0), (4, 2, 1), (6, 1, 0), (5, 2, 4)]        # (d, b, f)
+
+
+@functools.lru_cache(maxsize=None)
+def hasher():
+    return MM.check_host_keccak(zk)
+
+
+@functools.lru_cache(maxsize=None)
+def commitment(field, d, b, with_coset, seed=0):
+    coset = random.Random(41 * d + b + field).randrange(2, NM.MODULUS[field]) if with_coset else 1
+    return PM.commit(field, NM.random_ints(field, 1 << d, 6300 + 13 * d + field + seed), b, coset, hasher())
+
+
+def point_sets(field, d, P):
+    """P random points; P points of which the first two are equal; P points with entries in {0, 1, p - 1}"""
+    p, rng = NM.MODULUS[field], random.Random(97 * d + 7 * P + field)
+    rand = [[rng.randrange(p) for _ in range(d)] for _ in range(P)]
+    equal = [list(z) for z in rand]
+    if P > 1:
+        equal[1] = list(equal[0])
+    edge = [[rng.choice((0, 1, p - 1)) for _ in range(d)] for _ in range(P)]
+    return [rand, equal, edge]
+
+
+def lib_verify(op, fl=None, tr=None, **over):
+    """zk_fri_ml_verify_points on the model's opening `op` (flat arrays `fl`), parameters overridable -> (status, ok)"""
+    fl = PT.flat(zk, op) if fl is None else fl
+    a = {n: op[n] for n in ("d", "b", "f", "Q")}
+    a["P"] = len(op["points"])
+    a.update({n: v for n, v in over.items() if n in a})
+    coset = over.get("coset", op["coset"])
+    cm = None if coset is None else zk.from_ints(op["field"], [coset])[0]
+    ok = C.c_int(-1)
+    rc = zk.lib().zk_fri_ml_verify_points(op["field"], p8(fl["root"]), a["d"], a["b"], a["f"], a["Q"], p64(cm), p64(fl["points"]), a["P"], p64(fl["ys"]),
+                                          None if tr is None else tr._h, p64(fl["polys"]), p8(fl["roots"]), p64(fl["final"]), p64(fl["values"]),
+                                          p8(fl["paths"]), C.byref(ok))
+    return rc, ok.value
+
+
+def test_new_exports_are_present():
+    lib = zk.lib()
+    header = open(G.ROOT + "/include/zkmle.h").read()
+    for name in NEW_NAMES:
+        assert hasattr(lib, name), name
+        assert name + "(" in header, name
+    assert "FRI commitment opened at several points" in header
+    for name in ("open_multilinear_points", "verify_multilinear_points", "ml_round", "FriMlPointsOpening"):
+        assert callable(getattr(zk.fri, name)), name
+    assert callable(zk.gkr.sparse_prove_succinct) and callable(zk.gkr.sparse_verify_succinct)
+
+
+@pytest.mark.parametrize("with_coset", (False, True))
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("field", (0, 3))
+def test_model_openings_pass_the_model_verifier_and_the_library_verifier(field, shape, with_coset):
+    d, b, f = shape
+    cm = commitment(field, d, b, with_coset)
+    for P in (1, 2, 3, 8):
+        for pts in point_sets(field, d, P):
+            op = PT.open_points(cm, pts, f, 3, hasher=hasher())
+            assert op["ys"] == [ML.mle_evaluate(field, cm["coeffs"], z) for z in pts]
+            assert PT.verify(op, hasher=hasher()), (P, pts)
+            fl = PT.flat(zk, op)
+            assert lib_verify(op, fl) == (0, 1), (field, shape, with_coset, P)
+            if not with_coset:
+                assert lib_verify(op, fl, coset=None) == (0, 1)
+            assert ML.sizes(d, b, f, 3) == (fl["roots"].shape[0], fl["final"].shape[0], fl["values"].size // 4, fl["paths"].size, fl["polys"].size // 4)
+    # the Python wrapper on the last opening
+    cs = zk.from_ints(field, [cm["coset"]])[0]
+    o = zk.fri.FriMlPointsOpening(field, 8, d, b, f, 3, coset=cs)
+    o.ys, o.round_polys, o.roots, o.final_table, o.query_values, o.query_paths = fl["ys"], fl["polys"], fl["roots"], fl["final"], fl["values"], fl["paths"]
+    assert zk.fri.verify_multilinear_points(cm["root"], fl["points"], o)
+    assert not zk.fri.verify_multilinear_points(cm["root"][::-1], fl["points"], o)
+
+
+def test_a_false_y_is_rejected_for_each_p_by_the_model_and_by_the_library():
+    """round 0 is shifted so that it sums to the false claim_0 and passes its own check; a later check fails"""
+    for field, d, b, f, P in ((0, 6, 1, 0, 3), (3, 5, 2, 2, 2)):
+        cm = commitment(field, d, b, field == 3, seed=3)
+        pts = point_sets(field, d, P)[0]
+        honest = PT.open_points(cm, pts, f, 8, hasher=hasher())
+        assert PT.verify(honest, hasher=hasher()) and lib_verify(honest) == (0, 1)
+        for k in range(P):
+            op = PT.open_points(cm, pts, f, 8, false_y=(k, honest["ys"][k] + 1), hasher=hasher())
+            assert op["ys"][k] != honest["ys"][k] and op["ys"][:k] + op["ys"][k + 1:] == honest["ys"][:k] + honest["ys"][k + 1:]
+            assert not PT.verify(op, hasher=hasher()), k
+            assert lib_verify(op) == (0, 0), k
+
+
+@pytest.mark.parametrize("field", (0, 3))
+def test_at_one_point_the_rounds_are_the_single_point_protocols(field):
+    """the weight-table sums equal A_l eq1(X, z_v) (S_0 + X (S_1 - S_0)) of tests/_fri_ml_model.py when both run on the same challenges"""
+    p = NM.MODULUS[field]
+    for d, b, f in ((1, 1, 0), (4, 2, 1), (6, 1, 0)):
+        cm = commitment(field, d, b, True)
+        for z in point_sets(field, d, 1):
+            single = ML.open_at(cm, z[0], f, 2, hasher=hasher())
+            polys, final = PT.round_polys(field, cm["coeffs"], z, gamma=12345, rs=single["challenges"])
+            assert polys == single["polys"] and final == single["final"], (d, b, f)
+    # and at several points the sum of the per-point forms, gamma-weighted
+    d, gamma = 5, 0xABCDEF
+    cm = commitment(field, d, 1, False)
+    rng = random.Random(5 + field)
+    pts = [[rng.randrange(p) for _ in range(d)] for _ in range(3)]
+    rs = [rng.randrange(p) for _ in range(d)]
+    polys, _ = PT.round_polys(field, cm["coeffs"], pts, gamma, rs)
+    T, A = list(cm["coeffs"]), [pow(gamma, k, p) for k in range(3)]
+    for l in range(d):
+        v = d - 1 - l
+        want = [0, 0, 0]
+        for k, z in enumerate(pts):
+            E = ML.eq_table(z[:v], p)
+            S = [sum(E[x] * T[2 * x + X] for x in range(len(E))) % p for X in (0, 1)]
+            for X in (0, 1, 2):
+                want[X] += A[k] * ML.eq1(X, z[v], p) * (S[0] + X * (S[1] - S[0]))
+            A[k] = A[k] * ML.eq1(rs[l], z[v], p) % p
+        assert polys[l] == [w % p for w in want], l
+        T = ML.mle_fold_last(field, T, rs[l])
+
+
+def small_opening(tr=None, P=2):
+    cm = commitment(0, 3, 1, True, seed=9)
+    return PT.open_points(cm, point_sets(0, 3, P)[0], 0, 4, tr, hasher=hasher())
+
+
+def test_every_single_bit_change_is_rejected():
+    """every byte class: a point, a y, a round element, a root, the final table, a query value, a path, and the verifier's own root"""
+    op = small_opening()
+    d, L, R, Q, P = 3, 4, 3, 4, 2
+    base = PT.flat(zk, op)
+    assert lib_verify(op, base) == (0, 1)
+    rng = random.Random(7413)
+    spots = [("polys", (l, k, rng.randrange(4))) for l in range(R) for k in range(3)]
+    spots += [("roots", (l, rng.randrange(32))) for l in range(R)]
+    spots += [("final", (0, rng.randrange(4)))]
+    spots += [("ys", (k, w)) for k in range(P) for w in range(4)]
+    spots += [("points", (k, i, rng.randrange(4))) for k in range(P) for i in range(d)]
+    spots += [("root", (rng.randrange(32),)) for _ in range(3)]
+    for q in (0, 3):
+        for l in range(R):
+            spots += [("values", (q, l, s, rng.randrange(4))) for s in range(2)]
+    per_query = base["paths"].size // Q
+    off = 0
+    for l in range(R):                                                               # query 1: first and last digest of both paths of every layer
+        for side in range(2):
+            spots.append(("paths", (per_query + off + rng.randrange(32),)))
+            spots.append(("paths", (per_query + off + 32 * (L - l - 1) + rng.randrange(32),)))
+            off += 32 * (L - l)
+    assert off == per_query
+    for name, at in spots:
+        fl = {n: v.copy() for n, v in base.items()}
+        bits = 8 if fl[name].dtype == np.uint8 else 64
+        fl[name][at] ^= fl[name].dtype.type(1 << rng.randrange(bits))
+        assert lib_verify(op, fl) == (0, 0), (name, at)
+    p = NM.MODULUS[0]
+    for name, at in (("ys", (0,)), ("ys", (1,)), ("points", (0, 1)), ("points", (1, 2)), ("polys", (1, 2)), ("polys", (0, 0)), ("final", (0,)),
+                     ("values", (2, 1, 0))):
+        fl = {n: v.copy() for n, v in base.items()}                                  # the same residue, not reduced: x + p < 2^256
+        fl[name][at] = np.frombuffer((int.from_bytes(fl[name][at].tobytes(), "little") + p).to_bytes(32, "little"), np.uint64)
+        assert lib_verify(op, fl) == (0, 0), (name, at)
+
+
+def test_a_verifier_with_other_parameters_rejects():
+    from zkmle_amd import _lib as L
+    op = small_opening()
+    fl = PT.flat(zk, op)
+    big = {n: np.concatenate([v.reshape(-1), np.zeros(4 * v.size + 4096, v.dtype)]) for n, v in fl.items()}   # room for any shape below
+    assert lib_verify(op, big) == (0, 1)
+    for over in ({"Q": 3}, {"Q": 5}, {"f": 1}, {"coset": 1}, {"coset": None}, {"coset": op["coset"] + 1}, {"b": 2}, {"d": 4}, {"d": 2}, {"P": 1}, {"P": 3}):
+        assert lib_verify(op, big, **over) == (0, 0), over
+    for P in (0, 9, 1 << 31):
+        assert lib_verify(op, big, P=P) == (L.ZK_E_ARG, -1), P
+    swapped = dict(fl, points=np.ascontiguousarray(fl["points"][::-1]))                  # the two points swapped, the claims in place
+    assert lib_verify(op, swapped) == (0, 0)
+    both = dict(swapped, ys=np.ascontiguousarray(fl["ys"][::-1]))                        # ... and with their claims: another statement, another gamma
+    assert lib_verify(op, both) == (0, 0)
+    three = small_opening(P=3)                                                           # a proof for three points shown as one for the first two
+    assert lib_verify(three) == (0, 1) and lib_verify(three, P=2) == (0, 0)
+
+
+def test_a_callers_transcript_ends_in_the_models_state():
+    prior = b"what the caller had absorbed before"
+    mt = M.Transcript()
+    mt.append(prior)
+    op = small_opening(mt)
+    vt = M.Transcript()
+    vt.append(prior)
+    assert PT.verify(op, vt, hasher()) and vt.buf == mt.buf
+    t = zk.Transcript()
+    t.append(prior)
+    assert lib_verify(op, tr=t) == (0, 1)
+    want = zk.Transcript()
+    want.append(bytes(mt.buf))
+    assert np.array_equal(t.export_state(), want.export_state())
+    assert lib_verify(op) == (0, 0)                                   # the opening is bound to the prior content
+
+
+def test_precondition_codes():
+    import torch
+    from zkmle_amd import _lib as L
+    lib = zk.lib()
+    roots, fin, vals, paths = np.zeros(64 * 32, np.uint8), np.zeros(4 << 10, np.uint64), np.zeros(1 << 16, np.uint64), np.zeros(1 << 20, np.uint8)
+    root, pts, ys, polys = np.zeros(32, np.uint8), np.zeros(8 * 64 * 4, np.uint64), np.zeros(8 * 4, np.uint64), np.zeros(64 * 12, np.uint64)
+    ok = C.c_int(-1)
+    for field in (0, 1, 2, 3):
+        ver = lambda d, b, f, Q, P=2, zz=pts, okp=C.byref(ok): lib.zk_fri_ml_verify_points(
+            field, p8(root), d, b, f, Q, None, p64(zz), P, p64(ys), None, p64(polys), p8(roots), p64(fin), p64(vals), p8(paths), okp)
+        assert ver(3, 1, 0, 4, okp=None) == L.ZK_E_ARG and ver(3, 1, 0, 4, zz=None) == L.ZK_E_ARG
+        for d, b, f, Q in ((3, 0, 0, 4), (3, 9, 0, 4), (3, 1, 0, 0), (3, 1, 0, 4097), (3, 1, 3, 4), (0, 1, 0, 4), (40, 1, 40, 4)):
+            assert ver(d, b, f, Q) == L.ZK_E_ARG, (d, b, f, Q)
+        assert ver(3, 1, 0, 4, P=0) == L.ZK_E_ARG and ver(3, 1, 0, 4, P=9) == L.ZK_E_ARG and ver(40, 1, 0, 4, P=9) == L.ZK_E_ARG
+        if field in (1, 2):
+            assert ver(3, 1, 0, 4) == L.ZK_E_RANGE
+        else:
+            assert ver(NM.two_adicity(field), 1, 0, 4) == L.ZK_E_RANGE and ver(40, 1, 0, 4) == L.ZK_E_RANGE
+            assert ver(3, 1, 0, 4) == 0 and ok.value == 0                                  # zeros are no proof
+    # the device entries, as far as they go without a table or a commitment
+    g3 = np.zeros(12, np.uint64)
+    assert lib.zk_fri_ml_round(None, None, None, None, None, p64(g3)) == L.ZK_E_ARG
+    assert lib.zk_fri_ml_open_points(None, p64(pts), 2, 0, 4, None, p64(ys), None, p64(polys), p8(roots), p64(fin), None, None, p64(vals),
+                                     p8(paths)) == L.ZK_E_ARG
+    h = {}
+    for n in (1, 2, 4, 6, 8):
+        h[n] = C.c_void_p()
+        L.check(lib.zk_table_wrap(0, C.c_void_p(0x1000), n, C.byref(h[n])))
+    other = C.c_void_p()
+    L.check(lib.zk_table_wrap(1, C.c_void_p(0x1000), 8, C.byref(other)))
+    one = zk.from_ints(0, [1])[0]
+    to, wo = C.c_void_p(), C.c_void_p()
+    rnd = lambda T, W, r: lib.zk_fri_ml_round(T, W, p64(r), C.byref(to), C.byref(wo), p64(g3))
+    assert rnd(h[8], other, None) == L.ZK_E_ARG and rnd(other, other, None) == L.ZK_E_ARG
+    assert rnd(h[8], h[4], None) == L.ZK_E_LEN_MISMATCH and rnd(h[6], h[6], None) == L.ZK_E_NOT_POW2
+    assert rnd(h[1], h[1], None) == L.ZK_E_ARG and rnd(h[2], h[2], one) == L.ZK_E_ARG
+    assert lib.zk_fri_ml_round(h[8], h[8], p64(one), None, None, p64(g3)) == L.ZK_E_ARG
+    p = NM.MODULUS[0]
+    unreduced = np.frombuffer((int.from_bytes(one.tobytes(), "little") + p).to_bytes(32, "little"), np.uint64).copy()
+    assert rnd(h[8], h[8], unreduced) == L.ZK_E_ARG
+    if not torch.cuda.is_available():
+        assert rnd(h[8], h[8], one) == L.ZK_E_NO_DEVICE and rnd(h[2], h[2], None) == L.ZK_E_NO_DEVICE
+    for t in list(h.values()) + [other]:
+        lib.zk_table_free(t)

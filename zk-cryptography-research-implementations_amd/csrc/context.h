@@ -106,8 +106,12 @@ int ntt_extend_into(const zk_table *coeffs, const uint64_t *coset, zk_table *out
 // `ml` (may be null) switches the fold mode: the proof is the multilinear opening of include/zkmle.h (zkmle_fri_ml.hip) -- z and y are appended
 // after root_0, every round's three evaluations before its challenge, the layers fold in Lagrange form, `final_coeffs` is the final table T_R
 // and the sumcheck's checks are made beside FRI's.  roots[0] is then the verifier's own copy of the commitment's root.
+// npoints > 0: the opening at SEVERAL points ("... opened at several points"): z holds npoints x d elements (point-major), y npoints elements;
+// after root_0 the transcript takes npoints (4 bytes), the points, the claims, then gamma is drawn; the sumcheck's first claim is
+// sum_p gamma^p y_p and its last check is sum_p gamma^p A^p_R MLE(T_R)(z^p_0 .. z^p_{f-1}) = claim.  npoints = 0: the single-point form, as before.
 struct FriMlClaim {
     const uint64_t *z, *y, *round_polys;                     // d elements, one element, R x 3 elements
+    uint32_t npoints = 0;
 };
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,

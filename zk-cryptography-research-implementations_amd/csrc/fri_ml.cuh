@@ -1,6 +1,7 @@
 // fri_ml.cuh -- kernels of the multilinear opening of a FRI commitment (include/zkmle.h "FRI commitment opened as a multilinear
-// polynomial"): the Lagrange-form fold of a codeword and the round pass of the sumcheck that runs beside it.  The gather of the queries is
-// fri.cuh's, the trees are merkle.cuh's.
+// polynomial"): the Lagrange-form fold of a codeword and the round pass of the sumcheck that runs beside it, in its single-point form (an
+// eq table summed out) and its several-point form (a weight table folded beside T: fri_ml_round_w_kernel, at the end).  The gather of the
+// queries is fri.cuh's, the trees are merkle.cuh's.
 //
 //   fold    g[k] = (1 - r) (f[k] + f[k + h]) / 2 + r (f[k] - f[k + h]) / (2 c w^k),  k < h = len / 2, on the domain {c w^k}
 //                = u + (r / 2c) ((f[k] - f[k + h]) w^-k - c (f[k] + f[k + h])),       u = (f[k] + f[k + h]) / 2
@@ -79,6 +80,53 @@ template <class F, bool FOLD> __global__ void __launch_bounds__(kBlock) fri_ml_r
     }
     Fe<F> tot;
     if (block_reduce_wide<F, 2>(sum, sh, tot)) fe_store<F>(partials, (size_t)threadIdx.x * gridDim.x + blockIdx.x, tot);
+}
+
+// The round pass of the opening at SEVERAL points (include/zkmle.h "... opened at several points"): the weights are a table W_l of their
+// own, the gamma-combination of the points' eq tables, folded by the same challenge as T_l -- the pass does not know how many points
+// there are.  Lane i < q (FOLD):
+//     T_l[2i + X] = T_{l-1}[4i + 2X] + r (T_{l-1}[4i + 2X + 1] - T_{l-1}[4i + 2X]),   W_l[2i + X] the same from W_{l-1}
+//     s_0 += W_l[2i] T_l[2i],   s_1 += W_l[2i+1] T_l[2i+1],   s_inf += (W_l[2i+1] - W_l[2i]) (T_l[2i+1] - T_l[2i])
+// g_l at the nodes 0, 1 and infinity (the X^2 coefficient), as sumcheck_kernels.cuh; the host forms g_l(2) = 2 g_l(1) - g_l(0) + 2 s_inf.
+// Eight contiguous reads and four writes per lane.  T is folded and stored before W is loaded, so at most four loaded elements are live at
+// a time beside the three lazy sums.  !FOLD: tin and win have 2 q entries each and are only read; tout, wout and r are not used.
+// partials[X * gridDim.x + block], X < 3.
+template <class F, bool FOLD> __global__ void __launch_bounds__(kBlock) fri_ml_round_w_kernel(const void *__restrict__ tin, const void *__restrict__ win,
+                                                                                            void *__restrict__ tout, void *__restrict__ wout, size_t q, Fe<F> r,
+                                                                                            void *__restrict__ partials) {
+    __shared__ Wide<F> sh[3 * kBlock / 64];
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    Wide<F> sum[3] = {wide_zero<F>(), wide_zero<F>(), wide_zero<F>()};
+    const Multiplier<F> mr(r);
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < q; i += stride) {
+        Fe<F> t0, t1, w0, w1;
+        if (FOLD) {
+            {
+                const Fe<F> a0 = fe_load<F>(tin, 4 * i), a1 = fe_load<F>(tin, 4 * i + 1), b0 = fe_load<F>(tin, 4 * i + 2), b1 = fe_load<F>(tin, 4 * i + 3);
+                t0 = fe_add<F>(a0, mr.times(fe_sub<F>(a1, a0)));
+                t1 = fe_add<F>(b0, mr.times(fe_sub<F>(b1, b0)));
+                fe_store<F>(tout, 2 * i, t0);
+                fe_store<F>(tout, 2 * i + 1, t1);
+            }
+            {
+                const Fe<F> a0 = fe_load<F>(win, 4 * i), a1 = fe_load<F>(win, 4 * i + 1), b0 = fe_load<F>(win, 4 * i + 2), b1 = fe_load<F>(win, 4 * i + 3);
+                w0 = fe_add<F>(a0, mr.times(fe_sub<F>(a1, a0)));
+                w1 = fe_add<F>(b0, mr.times(fe_sub<F>(b1, b0)));
+                fe_store<F>(wout, 2 * i, w0);
+                fe_store<F>(wout, 2 * i + 1, w1);
+            }
+        } else {
+            t0 = fe_load<F>(tin, 2 * i);
+            t1 = fe_load<F>(tin, 2 * i + 1);
+            w0 = fe_load<F>(win, 2 * i);
+            w1 = fe_load<F>(win, 2 * i + 1);
+        }
+        wide_add_fe<F>(sum[0], fe_mul<F>(w0, t0));
+        wide_add_fe<F>(sum[1], fe_mul<F>(w1, t1));
+        wide_add_fe<F>(sum[2], fe_mul<F>(fe_sub<F>(w1, w0), fe_sub<F>(t1, t0)));
+    }
+    Fe<F> tot;
+    if (block_reduce_wide<F, 3>(sum, sh, tot)) fe_store<F>(partials, (size_t)threadIdx.x * gridDim.x + blockIdx.x, tot);
 }
 
 }  // namespace zk

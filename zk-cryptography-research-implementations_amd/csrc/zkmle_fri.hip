@@ -313,12 +313,24 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
     host_to_bytes_be<F>(c, cbe);
     transcript_header(tr, d, b, f, Q, cbe);
     tr.append(roots, 32);
-    if (ml) {
+    const unsigned P = ml ? ml->npoints : 0;                 // 0: the single-point form
+    Fe<F> gamma = fe_one<F>();
+    if (ml && P == 0) {
         for (unsigned i = 0; i <= d; i++) {                  // z_0 .. z_{d-1}, then y
             const uint64_t *el = i < d ? ml->z + (size_t)i * W : ml->y;
             good = good && is_reduced<F>(el);
             tr.append_be<F>(load_host<F>(el));
         }
+    } else if (ml) {                                         // P, the points (point-major), the claims, then gamma
+        uint8_t pbe[4];
+        for (int k = 0; k < 4; k++) pbe[k] = (uint8_t)(P >> (24 - 8 * k));
+        tr.append(pbe, 4);
+        for (size_t i = 0; i < (size_t)P * d + P; i++) {
+            const uint64_t *el = i < (size_t)P * d ? ml->z + i * W : ml->y + (i - (size_t)P * d) * W;
+            good = good && is_reduced<F>(el);
+            tr.append_be<F>(load_host<F>(el));
+        }
+        gamma = tr.random_challenge_as_field_element<F>();
     }
     std::vector<Fe<F>> beta(R);
     for (unsigned l = 0; l < R; l++) {
@@ -346,7 +358,13 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
     const Fe<F> w = root_of_unity<F>(L), winv = fe_inv<F>(w), inv2 = fe_inv<F>(fe_from_u64<F>(2));
     if (ml) {                                                // the sumcheck of sum_x T[x] eq(x, z) = y beside the folds, on the same challenges
         const Fe<F> one = fe_one<F>(), two = fe_from_u64<F>(2);
-        Fe<F> claim = load_host<F>(ml->y), A = one;
+        const unsigned np = P ? P : 1;                        // per point p: gamma^p A^p_l; the single-point form is np = 1 with gamma^0
+        std::vector<Fe<F>> A(np, one);
+        Fe<F> claim = fe_zero<F>();
+        for (unsigned p = 0; p < np; p++) {
+            if (p) A[p] = fe_mul<F>(A[p - 1], gamma);
+            claim = fe_add<F>(claim, fe_mul<F>(A[p], load_host<F>(ml->y + (size_t)p * W)));
+        }
         for (unsigned l = 0; l < R; l++) {
             const uint64_t *g = ml->round_polys + (size_t)l * 3 * W;
             const Fe<F> g0 = load_host<F>(g), g1 = load_host<F>(g + W), g2 = load_host<F>(g + 2 * W), r = beta[l];
@@ -355,16 +373,23 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
             const Fe<F> r1 = fe_sub<F>(r, one), r2 = fe_sub<F>(r, two);
             const Fe<F> outer = fe_mul<F>(inv2, fe_add<F>(fe_mul<F>(g0, fe_mul<F>(r1, r2)), fe_mul<F>(g2, fe_mul<F>(r, r1))));
             claim = fe_sub<F>(outer, fe_mul<F>(g1, fe_mul<F>(r, r2)));
-            const Fe<F> zv = load_host<F>(ml->z + (size_t)(d - 1 - l) * W);   // eq1(r_l, z_v) = 1 - r - z + 2 r z
-            A = fe_mul<F>(A, fe_add<F>(fe_sub<F>(fe_sub<F>(one, r), zv), fe_mul<F>(two, fe_mul<F>(r, zv))));
+            for (unsigned p = 0; p < np; p++) {
+                const Fe<F> zv = load_host<F>(ml->z + ((size_t)p * d + d - 1 - l) * W);   // eq1(r_l, z_v) = 1 - r - z + 2 r z
+                A[p] = fe_mul<F>(A[p], fe_add<F>(fe_sub<F>(fe_sub<F>(one, r), zv), fe_mul<F>(two, fe_mul<F>(r, zv))));
+            }
         }
-        std::vector<Fe<F>> t(h);                             // the MLE of T_R at (z_0 .. z_{f-1}): f folds of variable 0
-        for (unsigned i = 0; i < f; i++) {
-            const size_t half = m >> (i + 1);
-            const Fe<F> zi = load_host<F>(ml->z + (size_t)i * W);
-            for (size_t j = 0; j < half; j++) t[j] = fe_add<F>(t[j], fe_mul<F>(zi, fe_sub<F>(t[j + half], t[j])));
+        // sum_j T_R[j] W_R[j] = sum_p gamma^p A^p_R (the MLE of T_R at (z^p_0 .. z^p_{f-1})): f folds of variable 0 per point
+        Fe<F> end = fe_zero<F>();
+        for (unsigned p = 0; p < np; p++) {
+            std::vector<Fe<F>> t(h);
+            for (unsigned i = 0; i < f; i++) {
+                const size_t half = m >> (i + 1);
+                const Fe<F> zi = load_host<F>(ml->z + ((size_t)p * d + i) * W);
+                for (size_t j = 0; j < half; j++) t[j] = fe_add<F>(t[j], fe_mul<F>(zi, fe_sub<F>(t[j + half], t[j])));
+            }
+            end = fe_add<F>(end, fe_mul<F>(A[p], t[0]));
         }
-        if (!fe_eq<F>(fe_mul<F>(A, t[0]), claim)) return ZK_OK;
+        if (!fe_eq<F>(end, claim)) return ZK_OK;
     }
     std::vector<Fe<F>> cinv(R);                               // c_l^-1
     Fe<F> cl = c, ci = fe_inv<F>(c);
@@ -408,7 +433,7 @@ namespace zk {
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,
                     uint64_t *indices_out, const FriMlClaim *ml) {
-    if (ml && (!ml->z || !ml->y || !ml->round_polys)) return ZK_E_ARG;
+    if (ml && (!ml->z || !ml->y || !ml->round_polys || ml->npoints > 8)) return ZK_E_ARG;
     if (!roots || !final_coeffs || !query_values || !query_paths || !ok || field_limbs64(field) < 0) return ZK_E_ARG;
     ZK_TRY(params_check(log_blowup, nqueries));
     if (coset && is_zero_element(field, coset)) return ZK_E_ARG;

@@ -1,7 +1,8 @@
 // zkmle_fri_ml.hip -- C ABI of the multilinear opening of a FRI commitment (fri_ml.cuh): one Lagrange-form fold, the opening (a sumcheck
 // of sum_x T[x] eq(x, z) interleaved with the folds of the codeword, on the same challenges), its host verifier, and the basic sumcheck
-// that ends in such an opening.  Extension: the reference leaves `fri/` empty; the protocol is defined in include/zkmle.h "FRI commitment
-// opened as a multilinear polynomial".
+// that ends in such an opening; and the opening at several points with one proof (a sumcheck against the gamma-combination of the points'
+// eq tables: "FRI commitment opened at several points").  Extension: the reference leaves `fri/` empty; the protocol is defined in
+// include/zkmle.h "FRI commitment opened as a multilinear polynomial".
 #include <string.h>
 
 #include <chrono>
@@ -159,6 +160,39 @@ template <class F> int launch_round(bool fold, const void *tin, const void *ein,
     return ZK_OK;
 }
 
+// the queries: FRI's step 5 and FRI's gather over the layers of `fl` (layer 0 = the commitment's codeword and tree); *ms = the gather with
+// its downloads.  Ends with the stream drained.
+template <class F> int answer_queries(Transcript &tr, const FriLayers &fl, unsigned L, unsigned R, uint32_t Q, const OpenOut &o, Events &ev, float *ms) {
+    constexpr size_t ESZ = sizeof(Fe<F>);
+    std::vector<uint64_t> idx(Q);
+    for (unsigned q = 0; q < Q; q++) {
+        uint8_t dg[32];
+        tr.sample_random_challenge(dg);
+        uint64_t v = 0;
+        for (int k = 0; k < 8; k++) v |= (uint64_t)dg[k] << (8 * k);
+        idx[q] = v & (((uint64_t)1 << (L - 1)) - 1);
+    }
+    if (o.query_indices) memcpy(o.query_indices, idx.data(), Q * 8);
+    const size_t nval = (size_t)Q * R * 2, ndig = (size_t)Q * fl.path_off[R];
+    DevBuf didx, dval, dpath;
+    ZK_TRY(didx.alloc(Q * 8));
+    ZK_TRY(dval.alloc(nval * ESZ));
+    ZK_TRY(dpath.alloc(ndig * 32));
+    size_t q0, q1;
+    ZK_TRY(ev.mark(&q0));
+    ZK_HIP(hipMemcpyAsync(didx.p, idx.data(), Q * 8, hipMemcpyHostToDevice, cur_stream()));
+    fri_query_values_kernel<F><<<(unsigned)((nval + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(fl, (const uint64_t *)didx.p, Q, dval.p);
+    ZK_HIP(hipGetLastError());
+    fri_query_paths_kernel<<<(unsigned)((ndig + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(fl, (const uint64_t *)didx.p, Q, (uint64_t *)dpath.p);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpyAsync(o.query_values, dval.p, nval * ESZ, hipMemcpyDeviceToHost, cur_stream()));   // one download each, one wait for both
+    ZK_HIP(zk::memcpy_on_stream(o.query_paths, dpath.p, ndig * 32, hipMemcpyDeviceToHost));
+    ZK_TRY(ev.mark(&q1));
+    ZK_HIP(hipEventSynchronize(ev.ev[q1]));
+    *ms = ev.ms(q0, q1);
+    return ZK_OK;
+}
+
 template <class F> int open_any(const zk_fri_commitment *cm, const uint64_t *z, uint32_t f, uint32_t Q, Transcript &tr, const OpenOut &o) {
     constexpr size_t ESZ = sizeof(Fe<F>);
     constexpr int W = F::N / 2;
@@ -268,32 +302,8 @@ template <class F> int open_any(const zk_fri_commitment *cm, const uint64_t *z, 
     }
     for (size_t j = 0; j < m; j++) tr.append_be<F>(load_host<F>(o.final_table + j * W));
 
-    // the queries: FRI's step 5 and FRI's gather, layer 0 read from the commitment's codeword and tree
-    std::vector<uint64_t> idx(Q);
-    for (unsigned q = 0; q < Q; q++) {
-        uint8_t dg[32];
-        tr.sample_random_challenge(dg);
-        uint64_t v = 0;
-        for (int k = 0; k < 8; k++) v |= (uint64_t)dg[k] << (8 * k);
-        idx[q] = v & (((uint64_t)1 << (L - 1)) - 1);
-    }
-    if (o.query_indices) memcpy(o.query_indices, idx.data(), Q * 8);
-    const size_t nval = (size_t)Q * R * 2, ndig = (size_t)Q * fl.path_off[R];
-    DevBuf didx, dval, dpath;
-    ZK_TRY(didx.alloc(Q * 8));
-    ZK_TRY(dval.alloc(nval * ESZ));
-    ZK_TRY(dpath.alloc(ndig * 32));
-    size_t q0, q1;
-    ZK_TRY(ev.mark(&q0));
-    ZK_HIP(hipMemcpyAsync(didx.p, idx.data(), Q * 8, hipMemcpyHostToDevice, cur_stream()));
-    fri_query_values_kernel<F><<<(unsigned)((nval + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(fl, (const uint64_t *)didx.p, Q, dval.p);
-    ZK_HIP(hipGetLastError());
-    fri_query_paths_kernel<<<(unsigned)((ndig + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(fl, (const uint64_t *)didx.p, Q, (uint64_t *)dpath.p);
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(o.query_values, dval.p, nval * ESZ, hipMemcpyDeviceToHost, cur_stream()));   // one download each, one wait for both
-    ZK_HIP(zk::memcpy_on_stream(o.query_paths, dpath.p, ndig * 32, hipMemcpyDeviceToHost));
-    ZK_TRY(ev.mark(&q1));
-    ZK_HIP(hipEventSynchronize(ev.ev[q1]));
+    float ms_queries = 0.f;
+    ZK_TRY((answer_queries<F>(tr, fl, L, R, Q, o, ev, &ms_queries)));
 
     zk_fri_ml_stats st{};
     st.rounds = R;
@@ -304,7 +314,7 @@ template <class F> int open_any(const zk_fri_commitment *cm, const uint64_t *z, 
         st.ms_trees += ev.ms(tb_[l], tc[l]);
         st.ms_sumcheck += ev.ms(tc[l], td[l]);
     }
-    st.ms_queries = ev.ms(q0, q1);
+    st.ms_queries = ms_queries;
     st.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     g_ml_stats = st;
     return ZK_OK;
@@ -314,6 +324,190 @@ template <class F> int open_any(const zk_fri_commitment *cm, const uint64_t *z, 
 int open_check(const zk_fri_commitment *cm, const uint64_t *z, uint32_t f, uint32_t Q) {
     if (Q < 1 || Q > 4096 || f >= cm->d) return ZK_E_ARG;
     if (z && !all_reduced(cm->field, z, cm->d)) return ZK_E_ARG;
+    return ZK_OK;
+}
+
+// ---- the opening at several points ----------------------------------------------------------------------------------------------------
+// sums (device, 3 elements) = the pass's sums at the nodes 0, 1, infinity (fri_ml_round_w_kernel).  Launches only.
+template <class F> int launch_round_w(bool fold, const void *tin, const void *win, void *tout, void *wout, size_t q, const Fe<F> &r, void *partials, void *sums) {
+    const int grid = reduce_grid_for(q);
+    if (fold) fri_ml_round_w_kernel<F, true><<<grid, kBlock, 0, cur_stream()>>>(tin, win, tout, wout, q, r, partials);
+    else fri_ml_round_w_kernel<F, false><<<grid, kBlock, 0, cur_stream()>>>(tin, win, tout, wout, q, r, partials);
+    ZK_HIP(hipGetLastError());
+    finish_sums_kernel<F><<<1, kBlock, 0, cur_stream()>>>(partials, (size_t)grid, 3, sums);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+// g(0), g(1), g(2) from the sums at 0, 1, infinity: g(2) = 2 g(1) - g(0) + 2 g(inf)
+template <class F> void nodes_to_g3(const Fe<F> S[3], Fe<F> g[3]) {
+    g[0] = S[0];
+    g[1] = S[1];
+    const Fe<F> t = fe_add<F>(S[1], S[2]);
+    g[2] = fe_sub<F>(fe_add<F>(t, t), S[0]);
+}
+
+template <class F> int round_once(const zk_table *T, const zk_table *Wt, const uint64_t *r, zk_table **T_out, zk_table **W_out, uint64_t *g3) {
+    constexpr size_t ESZ = sizeof(Fe<F>);
+    constexpr int W = F::N / 2;
+    const bool fold = r != nullptr;
+    const size_t q = fold ? T->len / 4 : T->len / 2;
+    DevBuf scr;
+    const size_t cap = (size_t)reduce_block_cap();
+    ZK_TRY(scr.alloc((3 * cap + 3) * ESZ));
+    void *sums = (char *)scr.p + 3 * cap * ESZ;
+    zk_table *to = nullptr, *wo = nullptr;
+    if (fold) {
+        ZK_TRY(zk_table_alloc(T->field, T->len / 2, &to));
+        const int rc = zk_table_alloc(T->field, T->len / 2, &wo);
+        if (rc != ZK_OK) { zk_table_free(to); return rc; }
+    }
+    Fe<F> S[3], g[3];
+    int rc = launch_round_w<F>(fold, T->dptr, Wt->dptr, fold ? to->dptr : nullptr, fold ? wo->dptr : nullptr, q, fold ? load_host<F>(r) : fe_one<F>(), scr.p, sums);
+    if (rc == ZK_OK && zk::memcpy_on_stream(S, sums, 3 * ESZ, hipMemcpyDeviceToHost) != hipSuccess) rc = ZK_E_HIP;
+    if (rc != ZK_OK) { zk_table_free(to); zk_table_free(wo); return rc; }
+    nodes_to_g3<F>(S, g);
+    for (int k = 0; k < 3; k++) store_host<F>(g3 + (size_t)k * W, g[k]);
+    if (fold) { *T_out = to; *W_out = wo; }
+    return ZK_OK;
+}
+
+template <class F> int open_points_any(const zk_fri_commitment *cm, const uint64_t *pts, uint32_t P, uint32_t f, uint32_t Q, Transcript &tr, uint64_t *ys_out,
+                                       uint64_t *gamma_out, const OpenOut &o) {
+    constexpr size_t ESZ = sizeof(Fe<F>);
+    constexpr int W = F::N / 2;
+    const auto t0 = std::chrono::steady_clock::now();
+    const unsigned d = cm->d, b = cm->b, L = d + b, R = d - f;
+    const size_t n = (size_t)1 << d, N = (size_t)1 << L, m = (size_t)1 << f;
+    const Fe<F> one = fe_one<F>(), c = cm->has_coset ? load_host<F>(cm->coset) : one;
+
+    // steps 1 to 4: the header, root_0, P, the points
+    uint8_t hdr[48], pbe[4];
+    put_be32(hdr, d);
+    put_be32(hdr + 4, b);
+    put_be32(hdr + 8, f);
+    put_be32(hdr + 12, Q);
+    host_to_bytes_be<F>(c, hdr + 16);
+    tr.append(hdr, sizeof hdr);
+    memcpy(o.roots, cm->root, 32);
+    tr.append(cm->root, 32);
+    put_be32(pbe, P);
+    tr.append(pbe, 4);
+    for (size_t i = 0; i < (size_t)P * d; i++) tr.append_be<F>(load_host<F>(pts + i * W));
+
+    // one block: T_1 .. T_R (below n elements), W_0 .. W_{R-1} (below 2 n), f_1 .. f_{R-1} (below N), their trees (below 2 N digests), the
+    // workgroups' partial sums and the three sums, and -- for P > 1 -- the P eq tables W_0 is combined from
+    const size_t cap = (size_t)reduce_block_cap();
+    const size_t off_w = n, off_f = 3 * n, off_tree = off_f + N, off_part = off_tree + 2 * N, off_eq = off_part + 3 * cap + 3;
+    const size_t total = off_eq + (P > 1 ? (size_t)P * n : 0);   // in elements (a digest is 32 bytes too)
+    static_assert(ESZ == 32, "the block is laid out in 32-byte units");
+    DevBuf blk;
+    ZK_TRY(blk.alloc(total * ESZ));
+    char *base = (char *)blk.p;
+    auto T_at = [&](unsigned l) -> void * { return l == 0 ? cm->coeffs->dptr : base + (n - (n >> (l - 1))) * ESZ; };          // n >> l entries
+    auto W_at = [&](unsigned l) -> void * { return base + (off_w + 2 * n - ((2 * n) >> l)) * ESZ; };                         // n >> l entries
+    auto f_at = [&](unsigned l) -> void * { return l == 0 ? cm->codeword->dptr : base + (off_f + N - (N >> (l - 1))) * ESZ; };   // N >> l entries
+    auto tree_at = [&](unsigned l) -> uint64_t * { return l == 0 ? cm->levels : (uint64_t *)(base + (off_tree + 2 * N - ((4 * N) >> l)) * ESZ); };
+    void *partials = base + off_part * ESZ, *sums = base + (off_part + 3 * cap) * ESZ;
+
+    Events ev;
+    std::vector<size_t> ta(R), tb_(R), tc(R), td(R);
+    size_t e0, e1;
+    FoldTables<F> pw;
+    ZK_TRY(pw.build(L));
+    FriLayers fl{};
+    fl.log_len0 = L;
+    fl.nlayers = R;
+
+    // step 5: y_p = zk_mle_evaluate(T, z^p), a pass each; they are absorbed before gamma exists
+    ZK_TRY(ev.mark(&e0));
+    for (unsigned p = 0; p < P; p++) {
+        ZK_TRY(zk_mle_evaluate(cm->coeffs, pts + (size_t)p * d * W, d, ys_out + (size_t)p * W));
+        tr.append_be<F>(load_host<F>(ys_out + (size_t)p * W));
+    }
+    const Fe<F> gamma = tr.random_challenge_as_field_element<F>();
+    if (gamma_out) store_host<F>(gamma_out, gamma);
+    // W_0 = sum_p gamma^p eq(., z^p): one point's table is built in place, several are combined in one pass
+    std::vector<EqBuilder<F>> eqb(P);
+    if (P == 1) {
+        ZK_TRY(eqb[0].build(pts, d, W_at(0)));
+    } else {
+        const void *tabs[8];
+        uint64_t coef[8 * W];
+        Fe<F> gp = one;
+        for (unsigned p = 0; p < P; p++) {
+            tabs[p] = base + (off_eq + (size_t)p * n) * ESZ;
+            ZK_TRY(eqb[p].build(pts + (size_t)p * d * W, d, (void *)tabs[p]));
+            store_host<F>(coef + (size_t)p * W, gp);
+            gp = fe_mul<F>(gp, gamma);
+        }
+        ZK_HIP((lincomb_launch<F, false>(tabs, P, coef, W_at(0), n, fe_zero<F>(), fe_zero<F>(), nullptr, cur_stream())));
+    }
+    // round 0's pass reads the commitment's own coefficient table and W_0 and writes neither
+    ZK_TRY((launch_round_w<F>(false, T_at(0), W_at(0), nullptr, nullptr, n / 2, one, partials, sums)));
+    Fe<F> S[3];
+    ZK_HIP(zk::memcpy_on_stream(S, sums, 3 * ESZ, hipMemcpyDeviceToHost));      // round 0's synchronisation
+    for (auto &e : eqb) e.release();
+    ZK_TRY(ev.mark(&e1));
+
+    Fe<F> cl = c, gscale = fe_inv<F>(fe_mul<F>(fe_from_u64<F>(2), c)), cinv = fe_inv<F>(c);   // c_l, 1 / (2 c_l), c_l^-1
+    for (unsigned l = 0; l < R; l++) {
+        Fe<F> g[3];
+        nodes_to_g3<F>(S, g);
+        for (int k = 0; k < 3; k++) {
+            store_host<F>(o.round_polys + ((size_t)l * 3 + k) * W, g[k]);
+            tr.append_be<F>(g[k]);
+        }
+        const Fe<F> r = tr.random_challenge_as_field_element<F>();
+        if (o.challenges) store_host<F>(o.challenges + (size_t)l * W, r);
+
+        fl.table[l] = f_at(l);
+        fl.tree[l] = tree_at(l);
+        fl.path_off[l + 1] = fl.path_off[l] + 2 * (L - l);
+        ZK_TRY(ev.mark(&ta[l]));
+        if (l + 1 < R) {
+            // f_{l+1}, its tree, and round l + 1's pass (which folds T_l and W_l by r_l) behind one another; one wait for the root and the sums
+            ZK_TRY((launch_fold<F>(f_at(l), f_at(l + 1), N >> l, l, pw, fe_mul<F>(r, gscale), cm->has_coset ? &cl : nullptr)));
+            ZK_TRY(ev.mark(&tb_[l]));
+            const zk_table layer{cm->field, N >> (l + 1), f_at(l + 1), 0};
+            uint64_t *tree = tree_at(l + 1);
+            ZK_TRY(merkle_levels_device(&layer, tree));
+            ZK_TRY(ev.mark(&tc[l]));
+            ZK_TRY((launch_round_w<F>(true, T_at(l), W_at(l), T_at(l + 1), W_at(l + 1), n >> (l + 2), r, partials, sums)));
+            uint8_t *root = o.roots + 32 * (l + 1);
+            ZK_HIP(hipMemcpyAsync(root, tree + 4 * (2 * layer.len - 2), 32, hipMemcpyDeviceToHost, cur_stream()));
+            ZK_HIP(zk::memcpy_on_stream(S, sums, 3 * ESZ, hipMemcpyDeviceToHost));   // the round's synchronisation
+            tr.append(root, 32);
+        } else {
+            // the last challenge: T_R alone is needed (W_R is the verifier's to compute); layer R is never built
+            ZK_TRY(ev.mark(&tb_[l]));
+            ZK_TRY(ev.mark(&tc[l]));
+            uint64_t r64[W];
+            store_host<F>(r64, r);
+            ZK_TRY(zk_mle_fold_ptr(cm->field, T_at(l), n >> l, d - l - 1, r64, T_at(R), cur_stream()));
+            ZK_HIP(zk::memcpy_on_stream(o.final_table, T_at(R), m * ESZ, hipMemcpyDeviceToHost));
+        }
+        ZK_TRY(ev.mark(&td[l]));
+        gscale = fe_mul<F>(gscale, cinv);                     // 1 / (2 c_{l+1}) = (1 / (2 c_l)) c_l^-1
+        cinv = fe_sqr<F>(cinv);
+        cl = fe_sqr<F>(cl);
+    }
+    for (size_t j = 0; j < m; j++) tr.append_be<F>(load_host<F>(o.final_table + j * W));
+
+    float ms_queries = 0.f;
+    ZK_TRY((answer_queries<F>(tr, fl, L, R, Q, o, ev, &ms_queries)));
+
+    zk_fri_ml_stats st{};
+    st.rounds = R;
+    st.queries = Q;
+    st.ms_sumcheck = ev.ms(e0, e1);                           // the y_p passes, W_0 and round 0's pass
+    for (unsigned l = 0; l < R; l++) {
+        st.ms_folds += ev.ms(ta[l], tb_[l]);
+        st.ms_trees += ev.ms(tb_[l], tc[l]);
+        st.ms_sumcheck += ev.ms(tc[l], td[l]);
+    }
+    st.ms_queries = ms_queries;
+    st.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    g_ml_stats = st;
     return ZK_OK;
 }
 
@@ -385,6 +579,50 @@ int zk_fri_ml_verify(int field, const uint8_t *root32, uint32_t d, uint32_t log_
     memcpy(rs.data(), root32, 32);
     Transcript fresh;
     const FriMlClaim ml{z, y, round_polys};
+    int good = 0;
+    ZK_TRY(fri_verify_core(field, d, log_blowup, log_final, nqueries, coset, t ? t->t : fresh, rs.data(), final_table, query_values, query_paths, &good, nullptr, &ml));
+    *ok = good && same_root ? 1 : 0;
+    return ZK_OK;
+}
+
+int zk_fri_ml_round(const zk_table *T, const zk_table *W, const uint64_t *r, zk_table **T_out, zk_table **W_out, uint64_t *g3) {
+    if (!T || !W || !g3 || (r && (!T_out || !W_out)) || T->field != W->field || (T->field != ZK_FR381 && T->field != ZK_BN254_FR)) return ZK_E_ARG;
+    if (T->len != W->len) return ZK_E_LEN_MISMATCH;
+    if (!is_pow2(T->len)) return ZK_E_NOT_POW2;
+    if (T->len < (r ? 4u : 2u) || (r && !all_reduced(T->field, r, 1))) return ZK_E_ARG;
+    ZK_TRY(require_device());
+    ML_DISPATCH(T->field, return round_once<F>(T, W, r, T_out, W_out, g3));
+    return ZK_OK;
+}
+
+int zk_fri_ml_open_points(const zk_fri_commitment *cm, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries, zk_transcript *t,
+                          uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *challenges,
+                          uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths) {
+    if (!cm || !points || !ys_out || !round_polys || !roots || !final_table || !query_values || !query_paths) return ZK_E_ARG;
+    if (npoints < 1 || npoints > 8) return ZK_E_ARG;
+    ZK_TRY(open_check(cm, nullptr, log_final, nqueries));
+    if (!all_reduced(cm->field, points, (size_t)npoints * cm->d)) return ZK_E_ARG;
+    ZK_TRY(require_device());
+    Transcript fresh;
+    const OpenOut o{nullptr, round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
+    ML_DISPATCH(cm->field, return open_points_any<F>(cm, points, npoints, log_final, nqueries, t ? t->t : fresh, ys_out, gamma_out, o));
+    return ZK_OK;
+}
+
+int zk_fri_ml_verify_points(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset,
+                            const uint64_t *points, uint32_t npoints, const uint64_t *ys, zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots,
+                            const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, int *ok) {
+    if (!root32 || !points || !ys || !round_polys || !roots || !final_table || !query_values || !query_paths || !ok) return ZK_E_ARG;
+    if (npoints < 1 || npoints > 8) return ZK_E_ARG;
+    if (field_limbs64(field) < 0 || log_blowup < 1 || log_blowup > 8 || nqueries < 1 || nqueries > 4096 || d < 1 || log_final >= d) return ZK_E_ARG;
+    if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
+    if (d > 32) return ZK_E_RANGE;                           // what sizes the copy below; fri_verify_core repeats these and checks the rest
+    std::vector<uint8_t> rs(roots, roots + (size_t)32 * (d - log_final));
+    const bool same_root = memcmp(roots, root32, 32) == 0;
+    memcpy(rs.data(), root32, 32);
+    Transcript fresh;
+    FriMlClaim ml{points, ys, round_polys};
+    ml.npoints = npoints;
     int good = 0;
     ZK_TRY(fri_verify_core(field, d, log_blowup, log_final, nqueries, coset, t ? t->t : fresh, rs.data(), final_table, query_values, query_paths, &good, nullptr, &ml));
     *ok = good && same_root ? 1 : 0;

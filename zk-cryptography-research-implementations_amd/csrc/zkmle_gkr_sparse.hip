@@ -443,11 +443,14 @@ template <class F> int eq_table(const uint64_t *point, uint32_t nbits, TablePtr 
     return eb.build(point, nbits, out->dptr, scale);
 }
 
-template <class F> int evaluate_layers(std::vector<LayerDev> &layers, const uint64_t *inputs, size_t ninputs, std::vector<TablePtr> &W) {
+// `input_dev` (may be null): the inputs are that device table (copied; `inputs` is not read)
+template <class F> int evaluate_layers(std::vector<LayerDev> &layers, const uint64_t *inputs, size_t ninputs, std::vector<TablePtr> &W,
+                                       const zk_table *input_dev = nullptr) {
     size_t nl = layers.size();
     W.resize(nl + 1);
     zk_table *t = nullptr;
-    ZK_TRY(zk_table_upload(F::ID, inputs, ninputs, &t));
+    if (input_dev) ZK_TRY(zk_table_clone(input_dev, &t));
+    else ZK_TRY(zk_table_upload(F::ID, inputs, ninputs, &t));
     W[nl].reset(t);
     for (size_t l = nl; l-- > 0;) {
         size_t nout = (size_t)1 << layers[l].out_bits;
@@ -474,9 +477,16 @@ int build_layers(const zk_gate *gates, const size_t *gate_counts, size_t nlayers
     return ZK_OK;
 }
 
+// the hook of the succinct prover (zk_gkr_sparse_prove_succinct): the transcript's FIRST append is `root32`, the root of a commitment to
+// the inputs, and the inputs are that commitment's device table.  Null everywhere else: nothing is appended, `inputs` is uploaded.
+struct InputBinding {
+    const uint8_t *root32;
+    const zk_table *table;
+};
 template <class F> int sparse_prove(std::vector<LayerDev> &layers, const uint64_t *inputs, size_t ninputs, uint64_t *circuit_output,
                                     uint64_t *claimed_sum, uint64_t *layer_claims, uint64_t *coeffs, uint64_t *challenges,
-                                    uint64_t *wb_evals, uint64_t *wc_evals, uint64_t *output_challenges, float *ms_layers, uint8_t *output_root32) {
+                                    uint64_t *wb_evals, uint64_t *wc_evals, uint64_t *output_challenges, float *ms_layers, uint8_t *output_root32,
+                                    const InputBinding *bound = nullptr) {
     const size_t L64 = F::N / 2, esz = 4 * F::N;
     const size_t nlayers = layers.size();
     std::vector<uint32_t> out_bits_v(nlayers);
@@ -484,9 +494,10 @@ template <class F> int sparse_prove(std::vector<LayerDev> &layers, const uint64_
     const uint32_t *out_bits = out_bits_v.data();
     if (ninputs != ((size_t)1 << layers[nlayers - 1].in_bits)) return ZK_E_LEN_MISMATCH;
     std::vector<TablePtr> W;
-    ZK_TRY((evaluate_layers<F>(layers, inputs, ninputs, W)));                        // Circuit::evaluate (arithmetic_circuit.rs:65-109)
+    ZK_TRY((evaluate_layers<F>(layers, inputs, ninputs, W, bound ? bound->table : nullptr)));   // Circuit::evaluate (arithmetic_circuit.rs:65-109)
     ZK_TRY(zk_table_download(W[0].get(), circuit_output));
     zk_transcript tr;
+    if (bound) tr.t.append(bound->root32, 32);
     // transcript.append(w0 bytes) gkr_protocol.rs:49 (an output layer of one wire is one gate plus a zero pad, :43-47)
     // -- or, committed (zk_gkr_sparse_prove_committed), the output layer's Merkle root in place of its bytes
     if (output_root32) {
@@ -767,6 +778,33 @@ int zk_gkr_sparse_prove_committed(int field, const zk_sparse_circuit *c, const u
     ZK_DISPATCH_FIELD(field, return sparse_prove<F>(layers, inputs, ninputs, circuit_output, claimed_sum, layer_claims, coeffs, challenges,
                                                     wb_evals, wc_evals, output_challenges, ms_layers, output_root32));
     return ZK_OK;
+}
+int zk_gkr_sparse_prove_succinct(int field, const zk_sparse_circuit *c, const zk_fri_commitment *cm, uint32_t log_final, uint32_t nqueries,
+                                 uint64_t *circuit_output, uint64_t *claimed_sum, uint64_t *layer_claims, uint64_t *coeffs, uint64_t *challenges,
+                                 uint64_t *wb_evals, uint64_t *wc_evals, uint64_t *output_challenges, float *ms_layers, uint8_t input_root32[32],
+                                 uint64_t *input_evals, uint64_t *open_round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *open_challenges,
+                                 uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths) {
+    if (!c || !cm || !circuit_output || !claimed_sum || !layer_claims || !coeffs || !challenges || !output_challenges || !input_root32 || !input_evals ||
+        !open_round_polys || !roots || !final_table || !query_values || !query_paths || c->layers.empty())
+        return ZK_E_ARG;
+    if (c->layers.size() > 1 && (!wb_evals || !wc_evals)) return ZK_E_ARG;
+    if (cm->field != field || nqueries < 1 || nqueries > 4096 || log_final >= cm->d) return ZK_E_ARG;
+    const uint32_t k = c->layers.back().in_bits;
+    if (cm->d != k) return ZK_E_LEN_MISMATCH;
+    ZK_TRY(require_device());
+    std::vector<LayerDev> &layers = const_cast<zk_sparse_circuit *>(c)->layers;   // read-only use of device buffers
+    const InputBinding bound{cm->root, cm->coeffs};
+    int rc = ZK_OK;
+    ZK_DISPATCH_FIELD(field, rc = sparse_prove<F>(layers, nullptr, cm->coeffs->len, circuit_output, claimed_sum, layer_claims, coeffs, challenges, wb_evals,
+                                                  wc_evals, output_challenges, ms_layers, nullptr, &bound));
+    ZK_TRY(rc);
+    memcpy(input_root32, cm->root, 32);
+    // z^0 = rb, z^1 = rc: the last layer's first and second k challenges are adjacent in `challenges`, point-major as the opening reads them
+    size_t tot = 0;
+    for (const LayerDev &ly : layers) tot += (size_t)2 * ly.in_bits;
+    const uint64_t *points = challenges + (tot - (size_t)2 * k) * field_limbs64(field);
+    return zk_fri_ml_open_points(cm, points, 2, log_final, nqueries, nullptr, input_evals, nullptr, open_round_polys, roots, final_table, open_challenges,
+                                 query_indices, query_values, query_paths);
 }
 int zk_gkr_sparse_wiring_eval(int field, const zk_gate *layer_gates, size_t ngates, uint32_t out_bits, uint32_t in_bits, const uint64_t *alpha,
                               const uint64_t *pa, const uint64_t *beta, const uint64_t *pb, const uint64_t *rb, const uint64_t *rc,

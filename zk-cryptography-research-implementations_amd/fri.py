@@ -11,7 +11,8 @@ back to the roots); `verify_opening` is host code and needs nothing but the root
 
 The same commitment opened as a MULTILINEAR polynomial (include/zkmle.h "FRI commitment opened as a multilinear polynomial"): the committed
 table read as evaluations over the cube, `open_multilinear` proves y = evaluate(table, z) by a sumcheck interleaved with Lagrange-form folds of
-the codeword; `verify_multilinear` is host code and needs nothing but the root.
+the codeword; `verify_multilinear` is host code and needs nothing but the root.  `open_multilinear_points` opens ONE commitment at up to
+eight points with one proof (include/zkmle.h "FRI commitment opened at several points"): the layers and trees are built once.
 """
 import ctypes as C
 
@@ -303,8 +304,67 @@ def verify_multilinear(root, z, opening, transcript=None):
     return bool(ok.value)
 
 
+# ---- the multilinear opening at several points ------------------------------------------------------------------------------------------
+class FriMlPointsOpening(FriMlOpening):
+    """FriMlOpening with ys (P, limbs) in place of y, and gamma (limbs,), the batching challenge the prover's transcript gave (diagnostic)."""
+
+    def __init__(self, field, npoints, d, log_blowup, log_final, nqueries, coset=None):
+        super().__init__(field, d, log_blowup, log_final, nqueries, coset)
+        del self.y
+        self.npoints = npoints
+        self.ys = np.zeros((npoints, limbs(field)), np.uint64)
+        self.gamma = np.zeros(limbs(field), np.uint64)
+
+
+def _points(field, d, points):
+    pts = np.ascontiguousarray(points, np.uint64)
+    if pts.ndim != 3 or pts.shape[1] != d or pts.shape[2] != limbs(field):
+        raise L.ZkError(L.ZK_E_ARG, "the points are a (P, d, limbs) array of elements")
+    return pts
+
+
+def ml_round(T, W, r=None):
+    """one round pass of the several-point opening on its own.  r = None: -> g3 (3, limbs) = g(0), g(1), g(2) of (T, W), nothing folded.
+    Otherwise -> (T', W', g3): both tables folded by r in their last variable, g3 of the folded pair."""
+    g3 = np.zeros((3, limbs(T.field)), np.uint64)
+    if r is None:
+        L.check(L.lib().zk_fri_ml_round(T._h, W._h, None, None, None, L.p64(g3)))
+        return g3
+    to, wo = C.c_void_p(), C.c_void_p()
+    L.check(L.lib().zk_fri_ml_round(T._h, W._h, L.p64(_elem(T.field, r)), C.byref(to), C.byref(wo), L.p64(g3)))
+    return MultilinearPolynomial(T.field, _handle=to), MultilinearPolynomial(T.field, _handle=wo), g3
+
+
+def open_multilinear_points(commitment, points, log_final, nqueries, transcript=None):
+    """one proof that the committed table's multilinear extension has the values `.ys` at the P <= 8 points (P, d, limbs)"""
+    pts = _points(commitment.field, commitment.d, points)
+    op = FriMlPointsOpening(commitment.field, pts.shape[0], commitment.d, commitment.log_blowup, log_final, nqueries, commitment.coset)
+    L.check(L.lib().zk_fri_ml_open_points(commitment._h, L.p64(pts), pts.shape[0], log_final, nqueries, _handle(transcript), L.p64(op.ys),
+                                          L.p64(op.gamma), L.p64(op.round_polys), L.p8(op.roots), L.p64(op.final_table), L.p64(op.challenges),
+                                          L.p64(op.query_indices), L.p64(op.query_values), L.p8(op.query_paths)))
+    return op
+
+
+def verify_multilinear_points(root, points, opening, transcript=None):
+    """host only: `root` = the commitment's 32 bytes; the claims checked are evaluate(table, points[p]) = opening.ys[p]"""
+    ok = C.c_int(0)
+    op = opening
+    rbuf = np.frombuffer(bytes(root), np.uint8).copy()
+    if rbuf.shape[0] != 32:
+        raise L.ZkError(L.ZK_E_ARG, "a Merkle root is 32 bytes")
+    pts = _points(op.field, op.d, points)
+    ys, rp, fin, vals = (np.ascontiguousarray(a, np.uint64) for a in (op.ys, op.round_polys, op.final_table, op.query_values))
+    if ys.shape != (pts.shape[0], limbs(op.field)):
+        raise L.ZkError(L.ZK_E_ARG, "one claim per point")
+    roots, paths = np.ascontiguousarray(op.roots, np.uint8), np.ascontiguousarray(op.query_paths, np.uint8)
+    L.check(L.lib().zk_fri_ml_verify_points(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, op._coset(), L.p64(pts),
+                                            pts.shape[0], L.p64(ys), _handle(transcript), L.p64(rp), L.p8(roots), L.p64(fin), L.p64(vals),
+                                            L.p8(paths), C.byref(ok)))
+    return bool(ok.value)
+
+
 def ml_last_stats():
-    """milliseconds of the calling thread's last open_multilinear: the sumcheck's passes, the codeword folds, the trees, the query gather"""
+    """milliseconds of the calling thread's last open_multilinear / open_multilinear_points: the sumcheck's passes, the codeword folds, the trees, the query gather"""
     st = _MlStats()
     L.check(L.lib().zk_fri_ml_last_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _MlStats._fields_}

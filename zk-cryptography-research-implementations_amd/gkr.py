@@ -1,4 +1,5 @@
 """Host mirror of circuit/src/arithmetic_circuit.rs and gkr/src/gkr_protocol.rs over the C ABI."""
+import copy
 import ctypes as C
 
 import numpy as np
@@ -362,11 +363,9 @@ def _fe_to_bytes_be(field, a):
     return out.tobytes()
 
 
-def sparse_verify(field, layer_gate_rows, out_bits, proof, inputs, commit_output=False):
-    """The verifier of gkr_protocol.rs:146-236 for the sparse representation (the wiring predicates are
-    evaluated from the gate lists in O(#gates) on the GPU).  Used by tests and the config-4 bench.
-    commit_output: the proof of sparse_prove(commit_output=True) -- the output layer's Merkle root is recomputed from
-    proof.circuit_output, must equal proof.output_root when that is set, and is what the transcript absorbs first."""
+def _sparse_verify_layers(field, layer_gate_rows, out_bits, proof, first_append, last_values, commit_output=False):
+    """The body of the sparse verifier.  first_append: bytes the transcript absorbs before anything else (None: nothing);
+    last_values(rb, rc) -> (W(rb), W(rc)) of the input layer, or None to reject."""
     from .mle import MultilinearPolynomial
     from .sumcheck import Transcript, SumcheckProverProof, verify as sumcheck_verify
     from . import sharded as S
@@ -381,6 +380,8 @@ def sparse_verify(field, layer_gate_rows, out_bits, proof, inputs, commit_output
 
     nl = len(layer_gate_rows)
     t = Transcript()
+    if first_append is not None:
+        t.append(first_append)
     w0 = MultilinearPolynomial(field, proof.circuit_output)
     if commit_output:
         from .merkle import merkle_root
@@ -395,7 +396,6 @@ def sparse_verify(field, layer_gate_rows, out_bits, proof, inputs, commit_output
     alpha = beta = None
     pa, pb = ra, None
     off = 0
-    x = MultilinearPolynomial(field, inputs)
     for l in range(nl):
         if not np.array_equal(claim, proof.layer_claims[l]):
             return False
@@ -408,7 +408,10 @@ def sparse_verify(field, layer_gate_rows, out_bits, proof, inputs, commit_output
         if l + 1 < nl:
             wb, wc = proof.wb_evals[l], proof.wc_evals[l]
         else:
-            wb, wc = x.evaluate(ch[:k]), x.evaluate(ch[k:])
+            last = last_values(ch[:k], ch[k:])
+            if last is None:
+                return False
+            wb, wc = last
         add_r, mul_r = sparse_wiring_eval(field, layer_gate_rows[l], out_bits[l], k, pa, ch[:k], ch[k:], alpha, beta, pb)
         expect = S.fe_add(field, mul(add_r, S.fe_add(field, wb, wc)), mul(mul_r, mul(wb, wc)))
         if not np.array_equal(expect, res.last_claimed_sum):
@@ -421,3 +424,71 @@ def sparse_verify(field, layer_gate_rows, out_bits, proof, inputs, commit_output
         pa, pb = ch[:k], ch[k:]
         off += r
     return True
+
+
+def sparse_verify(field, layer_gate_rows, out_bits, proof, inputs, commit_output=False):
+    """The verifier of gkr_protocol.rs:146-236 for the sparse representation (the wiring predicates are
+    evaluated from the gate lists in O(#gates) on the GPU).  Used by tests and the config-4 bench.
+    commit_output: the proof of sparse_prove(commit_output=True) -- the output layer's Merkle root is recomputed from
+    proof.circuit_output, must equal proof.output_root when that is set, and is what the transcript absorbs first."""
+    x = MultilinearPolynomial(field, inputs)
+    return _sparse_verify_layers(field, layer_gate_rows, out_bits, proof, None, lambda rb, rc: (x.evaluate(rb), x.evaluate(rc)), commit_output)
+
+
+# ---- succinct sparse GKR on a FRI commitment of the inputs (extension, include/zkmle.h zk_gkr_sparse_prove_succinct) ----------------
+def sparse_prove_succinct(field, layer_gate_rows, out_bits, commitment, log_final, nqueries, circuit=None):
+    """The sparse proof for the inputs `commitment` (fri.commit of the input table) commits to, bound to its root, ending in the opening
+    of that commitment at the last layer's rb and rc.  -> SparseProof with input_root (32 bytes), input_evals (2, limbs) and opening
+    (fri.FriMlPointsOpening)."""
+    from . import fri
+    lib = _decl_sparse()
+    if not getattr(lib, "_sparse_succinct_declared", False):
+        u64p, u8p = L.u64p, L.u8p
+        lib.zk_gkr_sparse_prove_succinct.argtypes = [C.c_int, L.vp, L.vp, C.c_uint32, C.c_uint32] + [u64p] * 8 + [C.POINTER(C.c_float), u8p, u64p, u64p,
+                                                                                                              u8p, u64p, u64p, u64p, u64p, u8p]
+        lib.zk_gkr_sparse_prove_succinct.restype = C.c_int
+        lib._sparse_succinct_declared = True
+    Lm = limbs(field)
+    ninputs = 1 << commitment.d
+    if circuit is None:
+        circuit = SparseCircuit(layer_gate_rows, out_bits, ninputs)
+    out_bits = circuit.out_bits
+    nl = circuit.nlayers
+    in_bits = [out_bits[i + 1] if i + 1 < nl else commitment.d for i in range(nl)]
+    rounds = [2 * k for k in in_bits]
+    tot = sum(rounds)
+    out = np.zeros((1 << out_bits[0], Lm), np.uint64)
+    cs = np.zeros(Lm, np.uint64)
+    claims = np.zeros((nl, Lm), np.uint64)
+    co = np.zeros((tot, 3, Lm), np.uint64)
+    ch = np.zeros((tot, Lm), np.uint64)
+    wb = np.zeros((max(nl - 1, 1), Lm), np.uint64)
+    wc = np.zeros((max(nl - 1, 1), Lm), np.uint64)
+    ra = np.zeros((out_bits[0], Lm), np.uint64)
+    ms = (C.c_float * nl)()
+    root = np.zeros(32, np.uint8)
+    op = fri.FriMlPointsOpening(field, 2, commitment.d, commitment.log_blowup, log_final, nqueries, commitment.coset)
+    L.check(lib.zk_gkr_sparse_prove_succinct(field, circuit._h, commitment._h, log_final, nqueries, L.p64(out), L.p64(cs), L.p64(claims), L.p64(co),
+                                             L.p64(ch), L.p64(wb), L.p64(wc), L.p64(ra), ms, L.p8(root), L.p64(op.ys), L.p64(op.round_polys),
+                                             L.p8(op.roots), L.p64(op.final_table), L.p64(op.challenges), L.p64(op.query_indices),
+                                             L.p64(op.query_values), L.p8(op.query_paths)))
+    return SparseProof(circuit_output=out, claimed_sum=cs, layer_claims=claims, coeffs=co, challenges=ch, wb_evals=wb[: nl - 1],
+                       wc_evals=wc[: nl - 1], output_challenges=ra, rounds=rounds, in_bits=in_bits, ms_layers=list(ms), output_root=None,
+                       input_root=root.tobytes(), input_evals=op.ys, opening=op)
+
+
+def sparse_verify_succinct(field, layer_gate_rows, out_bits, proof):
+    """The sparse verifier without the inputs: it holds the gate lists, the output layer (proof.circuit_output) and proof.input_root.  The
+    transcript absorbs the root first; the last layer's two values are proof.input_evals, checked by the opening of the root at (rb, rc)."""
+    from . import fri
+    op = proof.opening
+    evals = np.ascontiguousarray(proof.input_evals, np.uint64)
+
+    def last_values(rb, rc):
+        opened = copy.copy(op)                                # the claims checked are the proof's input_evals, whatever the opening carries
+        opened.ys = evals
+        if not fri.verify_multilinear_points(proof.input_root, np.stack([rb, rc]), opened):
+            return None
+        return evals[0], evals[1]
+
+    return _sparse_verify_layers(field, layer_gate_rows, out_bits, proof, bytes(proof.input_root), last_values)
