@@ -424,6 +424,57 @@ int zk_fri_ml_verify_points(int field, const uint8_t *root32, uint32_t d, uint32
                             const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys, zk_transcript *t,
                             const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
                             const uint8_t *query_paths, int *ok);
+/* ---- FRI commitment opened with a fold arity (extension; csrc/fri_ml.cuh fri_ml_fold4_kernel, csrc/zkmle_fri_ml.hip) -----------------------
+ * The opening at several points with every SECOND folded layer committed: half as many trees over a third of the leaves, and the codeword
+ * read once per two folds.  Everything is as in "FRI commitment opened at several points" above; the additions hang on log_arity = a in {1, 2}.
+ * a = 1 is that protocol byte for byte: same transcript, same layouts.  a = 2 requires R = d - f >= 2 (otherwise ZK_E_ARG).
+ * Layers.  The committed layers are the even l < R: R' = ceil(R / 2) roots, roots[0] the commitment's, roots[s] the root of f_{2s}.  A STEP
+ * starts at an even layer l: it folds by 4 to f_{l+2} if l + 2 <= R; otherwise (R odd, l = R - 1) it is the fold by 2 to the final layer.
+ * Layer R is never built, and neither is any odd layer.
+ * Transcript, plain appends in this order:
+ *   1. FRI's 48-byte header, unchanged;
+ *   2. ONLY when a = 2: a as a 4-byte big-endian u32 (domain separation from the a = 1 protocol);
+ *   3. root_0, P, the points, y_0 .. y_{P-1}, gamma, as steps 2 to 6 above;
+ *   4. for l = 0 .. R - 1: g_l(0), g_l(1), g_l(2); r_l = random_challenge_as_field_element(); and, only if l + 1 is even and l + 1 < R,
+ *      root_{l+1} = zk_mle_merkle_root(f_{l+1});
+ *   5. the m entries of T_R;
+ *   6. Q indices i_q = the sample mod N / 4 (mod N / 2 for a = 1).
+ * The sumcheck is unchanged: R rounds, one challenge each, the same round polynomials.
+ * Fold by 4, k < N_l / 4, with x = c_l w_l^k, i = w_l^(N_l / 4) (the primitive fourth root of unity) and
+ *   fold(a, b; r, x) = (1 - r) (a + b) / 2 + r (a - b) / (2 x):
+ *   u0 = fold(f_l[k], f_l[k + N_l/2]; r_l, x),  u1 = fold(f_l[k + N_l/4], f_l[k + 3 N_l/4]; r_l, i x),  f_{l+2}[k] = fold(u0, u1; r_{l+1}, x^2)
+ * -- canonical, and byte for byte what two zk_fri_ml_fold calls give (u0 = f_{l+1}[k], u1 = f_{l+1}[k + N_l/4]).
+ * Answers.  For query i and a fold-4 step at layer l: j = i mod N_l / 4 and the four elements f_l[j + s N_l / 4], s = 0 .. 3, with their
+ * four paths of L - l digests; for a final fold-2 step j = i mod N_l / 2, two elements and two paths.  Flat layout: per query, per step in
+ * order, per s; the paths in the same order.  Counts (zk_fri_ml_sizes_arity): nroots = ceil(R / 2), nvalues = Q (4 floor(R / 2) + 2 (R mod 2)),
+ * path_bytes = 32 Q sum over the steps of sides (L - l); nfinal and nround are unchanged.  The proof does NOT get smaller: four paths for half
+ * as many layers.
+ * Verifier (HOST only, never opens a device): fri_verify_core with FriMlClaim extended by the arity, not a copy; the sumcheck's checks are
+ * unchanged.  Per fold-4 step it checks four paths, computes u0, u1 and the fold by r_{l+1} and compares with the NEXT step's opened
+ * element at position j -- side j div (N_{l+2} / A'), A' the next step's number of sides -- and for the last step with sum_j T_R[j] x'^j,
+ * x' = c_R w_R^j.  Unreduced elements give *ok = 0.  Status order is zk_fri_ml_verify_points'; a outside {1, 2}, or a = 2 with R < 2, is
+ * ZK_E_ARG.  `t` ends in the prover's state whenever the status is ZK_OK.
+ * Prover.  After r_l with l even and l + 1 < R only round l + 1's pass is enqueued and waited for; after r_{l+1} the fold by 4 f_l -> f_{l+2}
+ * with (r_l, r_{l+1}), the tree of f_{l+2} and round l + 2's pass behind one another, and one wait for the root and the sums: still one host
+ * synchronisation per round.  The pool block is 32 bytes x (3 n + 3 C + P n) and a little, C = the entries of the committed layers
+ * f_a, f_2a, .. below R together: below N for a = 1, below N / 3 for a = 2. */
+/* two Lagrange-form folds of a codeword of len >= 4 on {coset w_len^k} in one pass: a new table of len / 4 entries, byte for byte
+ * zk_fri_ml_fold(zk_fri_ml_fold(codeword, r0, coset), r1, coset^2).  Statuses as zk_fri_ml_fold; len < 4 is ZK_E_ARG. */
+int zk_fri_ml_fold4(const zk_table *codeword, const uint64_t *r0, const uint64_t *r1, const uint64_t *coset, zk_table **out);
+/* host: zk_fri_ml_sizes' five counts for the arity; log_arity outside {1, 2}, or 2 with d - log_final < 2, is ZK_E_ARG */
+int zk_fri_ml_sizes_arity(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, size_t *nroots,
+                          size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround);
+/* zk_fri_ml_open_points with log_arity after nqueries; the outputs are sized by zk_fri_ml_sizes_arity (challenges: R elements as before).
+ * zk_fri_ml_last_stats reports this call too. */
+int zk_fri_ml_open_points_arity(const zk_fri_commitment *cm, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                                uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots,
+                                uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values,
+                                uint8_t *query_paths);
+/* HOST only: zk_fri_ml_verify_points with log_arity after nqueries. */
+int zk_fri_ml_verify_points_arity(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
+                                  uint32_t log_arity, const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys,
+                                  zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table,
+                                  const uint64_t *query_values, const uint8_t *query_paths, int *ok);
 /* The basic sumcheck finished by a verifier who holds 32 bytes.  Prover::prove (prover.rs:35-71) with one change, as
  * zk_sumcheck_basic_prove_committed: the first append (:38-39) is the COMMITMENT's root (zk_fri_commitment_root: the root of the codeword of
  * the table, not zk_mle_merkle_root of the table).  The rounds run on the commitment's device table, which is only read; then

@@ -112,6 +112,7 @@ int ntt_extend_into(const zk_table *coeffs, const uint64_t *coset, zk_table *out
 struct FriMlClaim {
     const uint64_t *z, *y, *round_polys;                     // d elements, one element, R x 3 elements
     uint32_t npoints = 0;
+    uint32_t log_arity = 1;                                  // 2: the opening folded by 4 (include/zkmle.h "... opened with a fold arity"); needs npoints >= 1
 };
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,

@@ -87,26 +87,41 @@ template <class F> __global__ void __launch_bounds__(kFriBlock) fri_fold_kernel(
 
 // The committed layers of one proof: layer l has len0 >> l entries; its tree holds every level as zk_merkle_build lays them out (level
 // v at digest offset 2 len - (2 len >> v)).  path_off[l] = digests of one query's answer before layer l (2 (log_len0 - l') for each l' < l).
+// `wide` != 0 (the multilinear opening folded by 4, fri_ml.cuh): the nlayers entries are STEPS; step s opens 2^log_sides[s] entries of a
+// layer of 2^log_len[s] entries, a part = len >> log_sides apart; val_off[s] = values of one query's answer before step s, path_off[s] its
+// digests (2^log_sides paths of log_len digests per step).  wide == 0: step s is layer s with two sides and the three arrays are not read.
 struct FriLayers {
     const void *table[kFriMaxLayers];
     const uint64_t *tree[kFriMaxLayers];
     uint32_t path_off[kFriMaxLayers + 1];
     uint32_t log_len0, nlayers;
+    uint32_t wide;
+    uint32_t val_off[kFriMaxLayers + 1];
+    uint8_t log_len[kFriMaxLayers], log_sides[kFriMaxLayers];
 };
 
-// every opened value with one launch: out[(q R + l) 2 + side] = f_l[(i_q mod len_l / 2) + side len_l / 2]
+// every opened value with one launch: out[(q R + l) 2 + side] = f_l[(i_q mod len_l / 2) + side len_l / 2]; wide: out[q per + val_off[s] + side]
 template <class F> __global__ void __launch_bounds__(kFriBlock) fri_query_values_kernel(FriLayers a, const uint64_t *__restrict__ indices, size_t nq,
                                                                                        void *__restrict__ out) {
-    const size_t total = nq * a.nlayers * 2, stride = (size_t)gridDim.x * kFriBlock;
+    const size_t per = a.wide ? a.val_off[a.nlayers] : 2 * (size_t)a.nlayers, total = nq * per, stride = (size_t)gridDim.x * kFriBlock;
     for (size_t t = (size_t)blockIdx.x * kFriBlock + threadIdx.x; t < total; t += stride) {
-        const unsigned side = (unsigned)(t & 1), l = (unsigned)((t >> 1) % a.nlayers);
-        const size_t q = (t >> 1) / a.nlayers, half = ((size_t)1 << (a.log_len0 - l)) >> 1;
-        fe_store<F>(out, t, fe_load<F>(a.table[l], (indices[q] & (half - 1)) + side * half));
+        const size_t q = t / per;
+        const uint32_t r = (uint32_t)(t % per);
+        unsigned l = r >> 1, side = r & 1, depth = a.log_len0 - l, ls = 1;
+        if (a.wide) {
+            l = 0;
+            while (l + 1 < a.nlayers && a.val_off[l + 1] <= r) l++;
+            side = r - a.val_off[l];
+            depth = a.log_len[l];
+            ls = a.log_sides[l];
+        }
+        const size_t part = ((size_t)1 << depth) >> ls;
+        fe_store<F>(out, t, fe_load<F>(a.table[l], (indices[q] & (part - 1)) + side * part));
     }
 }
 
 // every authentication path with one launch (merkle_open_kernel over the layers): per query and layer the low entry's path, then the
-// high entry's, log_len0 - l digests each, the leaf's sibling first
+// high entry's, log_len0 - l digests each, the leaf's sibling first; wide: per step the 2^log_sides paths in the order of the sides
 static __global__ void __launch_bounds__(kFriBlock) fri_query_paths_kernel(FriLayers a, const uint64_t *__restrict__ indices, size_t nq, uint64_t *__restrict__ paths) {
     const uint32_t per = a.path_off[a.nlayers];
     const size_t total = nq * per, stride = (size_t)gridDim.x * kFriBlock;
@@ -115,9 +130,9 @@ static __global__ void __launch_bounds__(kFriBlock) fri_query_paths_kernel(FriLa
         const uint32_t r = (uint32_t)(t % per);
         unsigned l = 0;
         while (l + 1 < a.nlayers && a.path_off[l + 1] <= r) l++;
-        const unsigned depth = a.log_len0 - l, side = (r - a.path_off[l]) / depth, v = (r - a.path_off[l]) % depth;
-        const size_t len = (size_t)1 << depth, half = len >> 1;
-        const size_t pos = (indices[q] & (half - 1)) + side * half;
+        const unsigned depth = a.wide ? a.log_len[l] : a.log_len0 - l, side = (r - a.path_off[l]) / depth, v = (r - a.path_off[l]) % depth;
+        const size_t len = (size_t)1 << depth, part = len >> (a.wide ? a.log_sides[l] : 1);
+        const size_t pos = (indices[q] & (part - 1)) + side * part;
         const uint4 *src = reinterpret_cast<const uint4 *>(a.tree[l]) + 2 * (2 * len - ((2 * len) >> v) + ((pos >> v) ^ 1));   // a digest: 32 bytes
         uint4 *dst = reinterpret_cast<uint4 *>(paths) + 2 * t;
         const uint4 d0 = src[0], d1 = src[1];

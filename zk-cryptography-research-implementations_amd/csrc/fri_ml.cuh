@@ -9,6 +9,13 @@
 //           multiplier (r / 2c, the 81 argument words of fri.cuh's FriUni) as before.  c s is one product more by a lane-uniform value;
 //           c travels as a plain element (8 argument words, a Multiplier in registers), not as a second set of 81 rows, and with c = 1
 //           (no coset: COSET = false) the product is not there at all.  Every result is canonical.
+//   fold4   two folds in one pass (the opening folded by 4: include/zkmle.h "FRI commitment opened with a fold arity"), lane k < q = len / 4:
+//             u0 = fold(f[k], f[k + 2q]; r0, x),  u1 = fold(f[k + q], f[k + 3q]; r0, i x),  g[k] = fold(u0, u1; r1, x^2),  x = c w^k, i = w^q
+//           four coalesced reads at the quarter strides and one write where two fold launches read four, write three and read two of
+//           them again.  Stage 1 is the fold above twice with the ONE uniform multiplier r0 / 2c (w^-(k+q) = (i x / c)^-1 is the table's
+//           entry k + q); stage 2 multiplies by r1 / 2c^2 as a Multiplier in registers (8 argument words): a second set of 81 rows
+//           does not fit the scalar registers.  (w^-k)^2 is the table's entry 2k.  Every result is canonical, so g is the table two
+//           fri_ml_fold_kernel launches leave, byte for byte.
 //   round   one pass per sumcheck round over the table T_{l-1} of 4 q entries and the eq table E_{l-1} of 2 q entries (FOLD), lane i < q:
 //             T_l[2i + X] = T_{l-1}[4i + 2X] + r (T_{l-1}[4i + 2X + 1] - T_{l-1}[4i + 2X])     the MLE fold of the LAST variable
 //             E_l[i]      = E_{l-1}[2i] + E_{l-1}[2i + 1]                                       the eq table with its last variable summed out
@@ -48,6 +55,47 @@ template <class F, bool COSET> __global__ void __launch_bounds__(kFriBlock) fri_
     if constexpr (COSET) t = fe_sub<F>(t, Multiplier<F>(c.c).times(s));
     else t = fe_sub<F>(t, s);
     fe_store<F>(out, k, fe_from_u_below_2p<F>(uni_muladd<F>(m, u_from_limbs32<F>(fe_halve<F>(s)), u_from_limbs32<F>(t))));
+}
+
+// the shifts of a fold by 4: c_l and c_{l+1} = c_l^2 with a coset, nothing without one
+template <class F, bool COSET> struct FriMlShift2 {
+    Fe<F> c, c2;
+};
+template <class F> struct FriMlShift2<F, false> {};
+
+// one stage-1 fold: s / 2 + g (w (a - b) - c s), s = a + b; g = the rows of r0 / (2 c)
+template <class F, bool COSET> __device__ __forceinline__ Fe<F> fri_ml_fold4_stage1(const UniMul<F> &m, const Ufe<F> &w, const Fe<F> &a, const Fe<F> &b,
+                                                                                   const FriMlShift2<F, COSET> &c) {
+    const Fe<F> s = fe_add<F>(a, b);
+    Fe<F> t = fe_mul_u_pre<F>(w, fe_sub<F>(a, b));
+    if constexpr (COSET) t = fe_sub<F>(t, Multiplier<F>(c.c).times(s));
+    else t = fe_sub<F>(t, s);
+    return fe_from_u_below_2p<F>(uni_muladd<F>(m, u_from_limbs32<F>(fe_halve<F>(s)), u_from_limbs32<F>(t)));
+}
+
+// pw_lo / pw_hi, shift: as fri_ml_fold_kernel (the layer's w^-k is entry k << shift; 2 quarter entries of it exist).  g0 = the rows of
+// r0 / (2 c_l); g1 = r1 / (2 c_l^2); c = c_l and c_l^2.  in: 4 quarter entries, out: quarter.
+template <class F, bool COSET> __global__ void __launch_bounds__(kFriBlock) fri_ml_fold4_kernel(const void *__restrict__ in, void *__restrict__ out, size_t quarter,
+                                                                                               const void *__restrict__ pw_lo, const void *__restrict__ pw_hi,
+                                                                                               unsigned shift, FriMlShift2<F, COSET> c, Fe<F> g1, FriUni g0) {
+    constexpr int L = UParams<F>::L;
+    static_assert(L * L == 81, "FriUni holds the rows of a nine-limb field");
+    const size_t k = (size_t)blockIdx.x * kFriBlock + threadIdx.x;
+    if (k >= quarter) return;
+    UniMul<F> m;
+#pragma unroll
+    for (int i = 0; i < L; i++) {
+#pragma unroll
+        for (int j = 0; j < L; j++) m.t[i][j] = g0.t[i * L + j];
+    }
+    const Fe<F> u0 = fri_ml_fold4_stage1<F, COSET>(m, ntt_pow2t<F>(pw_lo, pw_hi, (uint64_t)k << shift), fe_load<F>(in, k), fe_load<F>(in, k + 2 * quarter), c);
+    const Fe<F> u1 = fri_ml_fold4_stage1<F, COSET>(m, ntt_pow2t<F>(pw_lo, pw_hi, (uint64_t)(k + quarter) << shift), fe_load<F>(in, k + quarter),
+                                                   fe_load<F>(in, k + 3 * quarter), c);
+    const Fe<F> s = fe_add<F>(u0, u1);
+    Fe<F> t = fe_mul_u_pre<F>(ntt_pow2t<F>(pw_lo, pw_hi, (uint64_t)k << (shift + 1)), fe_sub<F>(u0, u1));
+    if constexpr (COSET) t = fe_sub<F>(t, Multiplier<F>(c.c2).times(s));
+    else t = fe_sub<F>(t, s);
+    fe_store<F>(out, k, fe_add<F>(fe_halve<F>(s), Multiplier<F>(g1).times(t)));
 }
 
 // q = the number of (T_l pair, E_l entry) a launch covers; partials[X * gridDim.x + block] = the block's share of S_X.

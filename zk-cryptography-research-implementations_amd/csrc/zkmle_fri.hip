@@ -312,6 +312,12 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
     uint8_t cbe[32];
     host_to_bytes_be<F>(c, cbe);
     transcript_header(tr, d, b, f, Q, cbe);
+    const unsigned la = ml ? ml->log_arity : 1;              // 2: every second layer is committed and a query opens four entries of it
+    if (la == 2) {
+        uint8_t abe[4];
+        put_be32(abe, la);
+        tr.append(abe, 4);
+    }
     tr.append(roots, 32);
     const unsigned P = ml ? ml->npoints : 0;                 // 0: the single-point form
     Fe<F> gamma = fe_one<F>();
@@ -340,7 +346,9 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
             tr.append_be<F>(load_host<F>(el));
         }
         beta[l] = tr.random_challenge_as_field_element<F>();
-        if (l + 1 < R) tr.append(roots + 32 * (l + 1), 32);
+        if (la == 2) {
+            if (l + 1 < R && (l + 1) % 2 == 0) tr.append(roots + 32 * ((l + 1) / 2), 32);
+        } else if (l + 1 < R) tr.append(roots + 32 * (l + 1), 32);
     }
     std::vector<Fe<F>> h(m);
     for (size_t j = 0; j < m; j++) {
@@ -349,10 +357,11 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
         tr.append_be<F>(h[j]);
     }
     std::vector<uint64_t> idx(Q);
-    for (unsigned q = 0; q < Q; q++) idx[q] = sample_index(tr, L - 1);
+    for (unsigned q = 0; q < Q; q++) idx[q] = sample_index(tr, L - la);
     if (indices_out) memcpy(indices_out, idx.data(), Q * 8);
     *ok = 0;
-    for (size_t k = 0; good && k < (size_t)Q * R * 2; k++) good = is_reduced<F>(values + k * W);
+    const size_t vper = la == 2 ? 4 * (size_t)(R / 2) + 2 * (R % 2) : (size_t)R * 2;   // opened values of one query
+    for (size_t k = 0; good && k < (size_t)Q * vper; k++) good = is_reduced<F>(values + k * W);
     if (!good) return ZK_OK;
 
     const Fe<F> w = root_of_unity<F>(L), winv = fe_inv<F>(w), inv2 = fe_inv<F>(fe_from_u64<F>(2));
@@ -399,6 +408,44 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
         cl = fe_sqr<F>(cl);
     }
     const Fe<F> cR = cl;
+    if (la == 2) {
+        // steps start at the even layers: a fold by 4 to layer l + 2 <= R, or (R odd, l = R - 1) the fold by 2 to layer R
+        const auto fold = [&](const Fe<F> &a, const Fe<F> &bb, const Fe<F> &r, const Fe<F> &xinv) {   // (1 - r) (a + b) / 2 + r (a - b) / (2 x)
+            const Fe<F> even = fe_mul<F>(fe_sub<F>(fe_one<F>(), r), fe_add<F>(a, bb));
+            return fe_mul<F>(inv2, fe_add<F>(even, fe_mul<F>(fe_mul<F>(r, xinv), fe_sub<F>(a, bb))));
+        };
+        const Fe<F> iinv = fe_pow<F>(winv, (uint64_t)1 << (L - 2));   // i^-1, i = w_l^(N_l / 4) = the primitive fourth root w^(N / 4) at every layer
+        const uint8_t *pp = paths;
+        for (unsigned q = 0; q < Q; q++) {
+            const uint64_t *vq = values + (size_t)q * vper * W;
+            for (unsigned l = 0; l < R; l += 2) {
+                const unsigned sides = l + 2 <= R ? 4 : 2, depth = L - l;
+                const size_t part = ((size_t)1 << depth) / sides, j = idx[q] & (part - 1);
+                const uint64_t *v = vq + (size_t)(l / 2) * 4 * W;
+                Fe<F> e[4];
+                for (unsigned s = 0; s < sides; s++) {
+                    int ok_s = 0;
+                    ZK_TRY(zk_merkle_verify(F::ID, roots + 32 * (l / 2), depth, j + s * part, v + (size_t)s * W, pp, &ok_s));
+                    pp += 32 * (size_t)depth;
+                    if (!ok_s) return ZK_OK;
+                    e[s] = load_host<F>(v + (size_t)s * W);
+                }
+                const Fe<F> xinv = fe_mul<F>(cinv[l], fe_pow<F>(winv, (uint64_t)j << l));
+                Fe<F> got;
+                if (sides == 4) got = fold(fold(e[0], e[2], beta[l], xinv), fold(e[1], e[3], beta[l], fe_mul<F>(xinv, iinv)), beta[l + 1], fe_sqr<F>(xinv));
+                else got = fold(e[0], e[1], beta[l], xinv);
+                const unsigned ln = l + (sides == 4 ? 2 : 1);  // the layer the step lands in: j is a position of it
+                Fe<F> want;
+                if (ln < R) {
+                    const size_t npart = ((size_t)1 << (L - ln)) / (ln + 2 <= R ? 4 : 2);
+                    want = load_host<F>(vq + ((size_t)(ln / 2) * 4 + j / npart) * W);
+                } else want = uni_evaluate<F>(h, fe_mul<F>(cR, fe_pow<F>(w, (uint64_t)j << R)));
+                if (!fe_eq<F>(got, want)) return ZK_OK;
+            }
+        }
+        *ok = 1;
+        return ZK_OK;
+    }
     const size_t per = path_digests(L, R);
     for (unsigned q = 0; q < Q; q++) {
         const uint8_t *pp = paths + (size_t)q * per * 32;
@@ -434,6 +481,7 @@ int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_fin
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,
                     uint64_t *indices_out, const FriMlClaim *ml) {
     if (ml && (!ml->z || !ml->y || !ml->round_polys || ml->npoints > 8)) return ZK_E_ARG;
+    if (ml && (ml->log_arity < 1 || ml->log_arity > 2 || (ml->log_arity == 2 && (ml->npoints < 1 || log_final >= d || d - log_final < 2)))) return ZK_E_ARG;
     if (!roots || !final_coeffs || !query_values || !query_paths || !ok || field_limbs64(field) < 0) return ZK_E_ARG;
     ZK_TRY(params_check(log_blowup, nqueries));
     if (coset && is_zero_element(field, coset)) return ZK_E_ARG;

@@ -141,6 +141,33 @@ template <class F> int fold_once(const zk_table *cw, const uint64_t *r, const ui
     return ZK_OK;
 }
 
+// out[k], k < len / 4, from in[0 .. len): two folds in one pass.  g0 = r0 / (2 c_l), g1 = r1 / (2 c_l^2), `shift` = the layer's number, c = c_l (null: 1)
+template <class F> int launch_fold4(const void *in, void *out, size_t len, unsigned shift, const FoldTables<F> &tb, const Fe<F> &g0, const Fe<F> &g1, const Fe<F> *c) {
+    UniMul<F> um;
+    unimul_from<F>(um, g0);
+    FriUni g;
+    memcpy(g.t, um.t, sizeof g.t);
+    const size_t quarter = len / 4;
+    const unsigned blocks = (unsigned)((quarter + kFriBlock - 1) / kFriBlock);
+    if (c) fri_ml_fold4_kernel<F, true><<<blocks, kFriBlock, 0, cur_stream()>>>(in, out, quarter, tb.lo, tb.hi, shift, FriMlShift2<F, true>{*c, fe_sqr<F>(*c)}, g1, g);
+    else fri_ml_fold4_kernel<F, false><<<blocks, kFriBlock, 0, cur_stream()>>>(in, out, quarter, tb.lo, tb.hi, shift, FriMlShift2<F, false>{}, g1, g);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+
+template <class F> int fold4_once(const zk_table *cw, const uint64_t *r0, const uint64_t *r1, const uint64_t *coset, zk_table **out) {
+    FoldTables<F> tb;
+    ZK_TRY(tb.build(ilog2(cw->len)));
+    const Fe<F> two = fe_from_u64<F>(2), c = coset ? load_host<F>(coset) : fe_one<F>();
+    const Fe<F> g0 = fe_mul<F>(load_host<F>(r0), fe_inv<F>(fe_mul<F>(two, c))), g1 = fe_mul<F>(load_host<F>(r1), fe_inv<F>(fe_mul<F>(two, fe_sqr<F>(c))));
+    zk_table *o = nullptr;
+    ZK_TRY(zk_table_alloc(cw->field, cw->len / 4, &o));
+    const int rc = launch_fold4<F>(cw->dptr, o->dptr, cw->len, 0, tb, g0, g1, coset ? &c : nullptr);
+    if (rc != ZK_OK) { zk_table_free(o); return rc; }
+    *out = o;
+    return ZK_OK;
+}
+
 // ---- the prover ----------------------------------------------------------------------------------------------------------------
 struct OpenOut {
     uint64_t *y, *round_polys;
@@ -161,7 +188,8 @@ template <class F> int launch_round(bool fold, const void *tin, const void *ein,
 }
 
 // the queries: FRI's step 5 and FRI's gather over the layers of `fl` (layer 0 = the commitment's codeword and tree); *ms = the gather with
-// its downloads.  Ends with the stream drained.
+// its downloads.  Ends with the stream drained.  fl.wide (the opening folded by 4): the layers are steps of four or two sides and the
+// indices are taken mod N / 4.
 template <class F> int answer_queries(Transcript &tr, const FriLayers &fl, unsigned L, unsigned R, uint32_t Q, const OpenOut &o, Events &ev, float *ms) {
     constexpr size_t ESZ = sizeof(Fe<F>);
     std::vector<uint64_t> idx(Q);
@@ -170,10 +198,10 @@ template <class F> int answer_queries(Transcript &tr, const FriLayers &fl, unsig
         tr.sample_random_challenge(dg);
         uint64_t v = 0;
         for (int k = 0; k < 8; k++) v |= (uint64_t)dg[k] << (8 * k);
-        idx[q] = v & (((uint64_t)1 << (L - 1)) - 1);
+        idx[q] = v & (((uint64_t)1 << (L - (fl.wide ? 2 : 1))) - 1);
     }
     if (o.query_indices) memcpy(o.query_indices, idx.data(), Q * 8);
-    const size_t nval = (size_t)Q * R * 2, ndig = (size_t)Q * fl.path_off[R];
+    const size_t nval = (size_t)Q * (fl.wide ? fl.val_off[fl.nlayers] : R * 2), ndig = (size_t)Q * fl.path_off[fl.nlayers];
     DevBuf didx, dval, dpath;
     ZK_TRY(didx.alloc(Q * 8));
     ZK_TRY(dval.alloc(nval * ESZ));
@@ -371,8 +399,10 @@ template <class F> int round_once(const zk_table *T, const zk_table *Wt, const u
     return ZK_OK;
 }
 
-template <class F> int open_points_any(const zk_fri_commitment *cm, const uint64_t *pts, uint32_t P, uint32_t f, uint32_t Q, Transcript &tr, uint64_t *ys_out,
-                                       uint64_t *gamma_out, const OpenOut &o) {
+// la = log_arity.  1: every layer f_1 .. f_{R-1} is committed.  2 (R >= 2): the even ones are; after r_l with l even only round l + 1's pass
+// runs, after r_{l+1} the fold by 4 f_l -> f_{l+2}, its tree and round l + 2's pass.  One host synchronisation per round either way.
+template <class F> int open_points_any(const zk_fri_commitment *cm, const uint64_t *pts, uint32_t P, uint32_t f, uint32_t Q, unsigned la, Transcript &tr,
+                                       uint64_t *ys_out, uint64_t *gamma_out, const OpenOut &o) {
     constexpr size_t ESZ = sizeof(Fe<F>);
     constexpr int W = F::N / 2;
     const auto t0 = std::chrono::steady_clock::now();
@@ -380,7 +410,7 @@ template <class F> int open_points_any(const zk_fri_commitment *cm, const uint64
     const size_t n = (size_t)1 << d, N = (size_t)1 << L, m = (size_t)1 << f;
     const Fe<F> one = fe_one<F>(), c = cm->has_coset ? load_host<F>(cm->coset) : one;
 
-    // steps 1 to 4: the header, root_0, P, the points
+    // steps 1 to 4: the header, (the arity when it is not 1,) root_0, P, the points
     uint8_t hdr[48], pbe[4];
     put_be32(hdr, d);
     put_be32(hdr + 4, b);
@@ -388,16 +418,28 @@ template <class F> int open_points_any(const zk_fri_commitment *cm, const uint64
     put_be32(hdr + 12, Q);
     host_to_bytes_be<F>(c, hdr + 16);
     tr.append(hdr, sizeof hdr);
+    if (la == 2) {
+        put_be32(pbe, la);
+        tr.append(pbe, 4);
+    }
     memcpy(o.roots, cm->root, 32);
     tr.append(cm->root, 32);
     put_be32(pbe, P);
     tr.append(pbe, 4);
     for (size_t i = 0; i < (size_t)P * d; i++) tr.append_be<F>(load_host<F>(pts + i * W));
 
-    // one block: T_1 .. T_R (below n elements), W_0 .. W_{R-1} (below 2 n), f_1 .. f_{R-1} (below N), their trees (below 2 N digests), the
-    // workgroups' partial sums and the three sums, and -- for P > 1 -- the P eq tables W_0 is combined from
+    // one block: T_1 .. T_R (below n elements), W_0 .. W_{R-1} (below 2 n), the committed layers f_la, f_2la, .. below R (C = their N >> l
+    // entries together: below N for la = 1, below N / 3 for la = 2), their trees (2 C digests), the workgroups' partial sums and the three sums,
+    // and -- for P > 1 -- the P eq tables W_0 is combined from: 32 bytes x (3 n + 3 C + P n) and a little.  A layer that is not committed is
+    // never built.
     const size_t cap = (size_t)reduce_block_cap();
-    const size_t off_w = n, off_f = 3 * n, off_tree = off_f + N, off_part = off_tree + 2 * N, off_eq = off_part + 3 * cap + 3;
+    std::vector<size_t> f_off(R + 1, 0);                      // of the committed layer l, in entries from off_f; its tree at twice that from off_tree
+    size_t C = 0;
+    for (unsigned l = la; l < R; l += la) {
+        f_off[l] = C;
+        C += N >> l;
+    }
+    const size_t off_w = n, off_f = 3 * n, off_tree = off_f + C, off_part = off_tree + 2 * C, off_eq = off_part + 3 * cap + 3;
     const size_t total = off_eq + (P > 1 ? (size_t)P * n : 0);   // in elements (a digest is 32 bytes too)
     static_assert(ESZ == 32, "the block is laid out in 32-byte units");
     DevBuf blk;
@@ -405,8 +447,8 @@ template <class F> int open_points_any(const zk_fri_commitment *cm, const uint64
     char *base = (char *)blk.p;
     auto T_at = [&](unsigned l) -> void * { return l == 0 ? cm->coeffs->dptr : base + (n - (n >> (l - 1))) * ESZ; };          // n >> l entries
     auto W_at = [&](unsigned l) -> void * { return base + (off_w + 2 * n - ((2 * n) >> l)) * ESZ; };                         // n >> l entries
-    auto f_at = [&](unsigned l) -> void * { return l == 0 ? cm->codeword->dptr : base + (off_f + N - (N >> (l - 1))) * ESZ; };   // N >> l entries
-    auto tree_at = [&](unsigned l) -> uint64_t * { return l == 0 ? cm->levels : (uint64_t *)(base + (off_tree + 2 * N - ((4 * N) >> l)) * ESZ); };
+    auto f_at = [&](unsigned l) -> void * { return l == 0 ? cm->codeword->dptr : base + (off_f + f_off[l]) * ESZ; };          // N >> l entries, l committed
+    auto tree_at = [&](unsigned l) -> uint64_t * { return l == 0 ? cm->levels : (uint64_t *)(base + (off_tree + 2 * f_off[l]) * ESZ); };   // 2 N >> l digests of room
     void *partials = base + off_part * ESZ, *sums = base + (off_part + 3 * cap) * ESZ;
 
     Events ev;
@@ -416,7 +458,8 @@ template <class F> int open_points_any(const zk_fri_commitment *cm, const uint64
     ZK_TRY(pw.build(L));
     FriLayers fl{};
     fl.log_len0 = L;
-    fl.nlayers = R;
+    fl.nlayers = la == 2 ? (R + 1) / 2 : R;
+    fl.wide = la == 2;
 
     // step 5: y_p = zk_mle_evaluate(T, z^p), a pass each; they are absorbed before gamma exists
     ZK_TRY(ev.mark(&e0));
@@ -450,6 +493,7 @@ template <class F> int open_points_any(const zk_fri_commitment *cm, const uint64
     ZK_TRY(ev.mark(&e1));
 
     Fe<F> cl = c, gscale = fe_inv<F>(fe_mul<F>(fe_from_u64<F>(2), c)), cinv = fe_inv<F>(c);   // c_l, 1 / (2 c_l), c_l^-1
+    Fe<F> r_prev = one, cl_prev = c, gscale_prev = gscale;    // la = 2, l odd: r_{l-1}, c_{l-1}, 1 / (2 c_{l-1})
     for (unsigned l = 0; l < R; l++) {
         Fe<F> g[3];
         nodes_to_g3<F>(S, g);
@@ -460,11 +504,44 @@ template <class F> int open_points_any(const zk_fri_commitment *cm, const uint64
         const Fe<F> r = tr.random_challenge_as_field_element<F>();
         if (o.challenges) store_host<F>(o.challenges + (size_t)l * W, r);
 
-        fl.table[l] = f_at(l);
-        fl.tree[l] = tree_at(l);
-        fl.path_off[l + 1] = fl.path_off[l] + 2 * (L - l);
+        if (la == 1) {
+            fl.table[l] = f_at(l);
+            fl.tree[l] = tree_at(l);
+            fl.path_off[l + 1] = fl.path_off[l] + 2 * (L - l);
+        } else if (l % 2 == 0) {                              // a step starts here: four sides if layer l + 2 exists, else the fold by 2 to layer R
+            const unsigned s = l / 2, ls = l + 2 <= R ? 2 : 1;
+            fl.table[s] = f_at(l);
+            fl.tree[s] = tree_at(l);
+            fl.log_len[s] = (uint8_t)(L - l);
+            fl.log_sides[s] = (uint8_t)ls;
+            fl.val_off[s + 1] = fl.val_off[s] + (1u << ls);
+            fl.path_off[s + 1] = fl.path_off[s] + (L - l) * (1u << ls);
+        }
         ZK_TRY(ev.mark(&ta[l]));
-        if (l + 1 < R) {
+        if (la == 2 && l + 1 < R && l % 2 == 0) {
+            // the first challenge of a step: nothing is committed for it; round l + 1's pass alone, and the wait for its sums
+            ZK_TRY(ev.mark(&tb_[l]));
+            ZK_TRY(ev.mark(&tc[l]));
+            ZK_TRY((launch_round_w<F>(true, T_at(l), W_at(l), T_at(l + 1), W_at(l + 1), n >> (l + 2), r, partials, sums)));
+            ZK_HIP(zk::memcpy_on_stream(S, sums, 3 * ESZ, hipMemcpyDeviceToHost));   // the round's synchronisation
+            r_prev = r;
+            cl_prev = cl;
+            gscale_prev = gscale;
+        } else if (la == 2 && l + 1 < R) {
+            // the second: f_{l+1} = the fold by 4 of f_{l-1} by (r_{l-1}, r_l), its tree, and round l + 1's pass behind one another; one wait
+            ZK_TRY((launch_fold4<F>(f_at(l - 1), f_at(l + 1), N >> (l - 1), l - 1, pw, fe_mul<F>(r_prev, gscale_prev), fe_mul<F>(r, gscale),
+                                    cm->has_coset ? &cl_prev : nullptr)));
+            ZK_TRY(ev.mark(&tb_[l]));
+            const zk_table layer{cm->field, N >> (l + 1), f_at(l + 1), 0};
+            uint64_t *tree = tree_at(l + 1);
+            ZK_TRY(merkle_levels_device(&layer, tree));
+            ZK_TRY(ev.mark(&tc[l]));
+            ZK_TRY((launch_round_w<F>(true, T_at(l), W_at(l), T_at(l + 1), W_at(l + 1), n >> (l + 2), r, partials, sums)));
+            uint8_t *root = o.roots + 32 * ((l + 1) / 2);
+            ZK_HIP(hipMemcpyAsync(root, tree + 4 * (2 * layer.len - 2), 32, hipMemcpyDeviceToHost, cur_stream()));
+            ZK_HIP(zk::memcpy_on_stream(S, sums, 3 * ESZ, hipMemcpyDeviceToHost));   // the round's synchronisation
+            tr.append(root, 32);
+        } else if (l + 1 < R) {
             // f_{l+1}, its tree, and round l + 1's pass (which folds T_l and W_l by r_l) behind one another; one wait for the root and the sums
             ZK_TRY((launch_fold<F>(f_at(l), f_at(l + 1), N >> l, l, pw, fe_mul<F>(r, gscale), cm->has_coset ? &cl : nullptr)));
             ZK_TRY(ev.mark(&tb_[l]));
@@ -605,7 +682,71 @@ int zk_fri_ml_open_points(const zk_fri_commitment *cm, const uint64_t *points, u
     ZK_TRY(require_device());
     Transcript fresh;
     const OpenOut o{nullptr, round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
-    ML_DISPATCH(cm->field, return open_points_any<F>(cm, points, npoints, log_final, nqueries, t ? t->t : fresh, ys_out, gamma_out, o));
+    ML_DISPATCH(cm->field, return open_points_any<F>(cm, points, npoints, log_final, nqueries, 1, t ? t->t : fresh, ys_out, gamma_out, o));
+    return ZK_OK;
+}
+
+int zk_fri_ml_open_points_arity(const zk_fri_commitment *cm, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                                zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table,
+                                uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths) {
+    if (!cm || !points || !ys_out || !round_polys || !roots || !final_table || !query_values || !query_paths) return ZK_E_ARG;
+    if (npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2) return ZK_E_ARG;
+    ZK_TRY(open_check(cm, nullptr, log_final, nqueries));
+    if (log_arity == 2 && cm->d - log_final < 2) return ZK_E_ARG;
+    if (!all_reduced(cm->field, points, (size_t)npoints * cm->d)) return ZK_E_ARG;
+    ZK_TRY(require_device());
+    Transcript fresh;
+    const OpenOut o{nullptr, round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
+    ML_DISPATCH(cm->field, return open_points_any<F>(cm, points, npoints, log_final, nqueries, log_arity, t ? t->t : fresh, ys_out, gamma_out, o));
+    return ZK_OK;
+}
+
+int zk_fri_ml_verify_points_arity(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                                  const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys, zk_transcript *t,
+                                  const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
+                                  const uint8_t *query_paths, int *ok) {
+    if (!root32 || !points || !ys || !round_polys || !roots || !final_table || !query_values || !query_paths || !ok) return ZK_E_ARG;
+    if (npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2) return ZK_E_ARG;
+    if (field_limbs64(field) < 0 || log_blowup < 1 || log_blowup > 8 || nqueries < 1 || nqueries > 4096 || d < 1 || log_final >= d) return ZK_E_ARG;
+    if (log_arity == 2 && d - log_final < 2) return ZK_E_ARG;
+    if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
+    if (d > 32) return ZK_E_RANGE;                           // what sizes the copy below; fri_verify_core repeats these and checks the rest
+    const unsigned R = d - log_final;
+    std::vector<uint8_t> rs(roots, roots + (size_t)32 * (log_arity == 2 ? (R + 1) / 2 : R));
+    const bool same_root = memcmp(roots, root32, 32) == 0;
+    memcpy(rs.data(), root32, 32);
+    Transcript fresh;
+    FriMlClaim ml{points, ys, round_polys};
+    ml.npoints = npoints;
+    ml.log_arity = log_arity;
+    int good = 0;
+    ZK_TRY(fri_verify_core(field, d, log_blowup, log_final, nqueries, coset, t ? t->t : fresh, rs.data(), final_table, query_values, query_paths, &good, nullptr, &ml));
+    *ok = good && same_root ? 1 : 0;
+    return ZK_OK;
+}
+
+int zk_fri_ml_fold4(const zk_table *codeword, const uint64_t *r0, const uint64_t *r1, const uint64_t *coset, zk_table **out) {
+    if (!codeword || !r0 || !r1 || !out || field_limbs64(codeword->field) < 0 || codeword->len == 1 || codeword->len == 2) return ZK_E_ARG;
+    if (coset && is_zero_element(codeword->field, coset)) return ZK_E_ARG;
+    if (!is_pow2(codeword->len)) return ZK_E_NOT_POW2;
+    if ((codeword->field != ZK_FR381 && codeword->field != ZK_BN254_FR) || ilog2(codeword->len) > two_adicity(codeword->field)) return ZK_E_RANGE;
+    ZK_TRY(require_device());
+    ML_DISPATCH(codeword->field, return fold4_once<F>(codeword, r0, r1, coset, out));
+    return ZK_OK;
+}
+
+int zk_fri_ml_sizes_arity(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, size_t *nroots, size_t *nfinal,
+                          size_t *nvalues, size_t *path_bytes, size_t *nround) {
+    if (log_arity < 1 || log_arity > 2) return ZK_E_ARG;
+    ZK_TRY(zk_fri_ml_sizes(d, log_blowup, log_final, nqueries, nroots, nfinal, nvalues, path_bytes, nround));
+    if (log_arity == 1) return ZK_OK;
+    const unsigned R = d - log_final, L = d + log_blowup;
+    if (R < 2) return ZK_E_ARG;
+    size_t digests = 0;
+    for (unsigned l = 0; l < R; l += 2) digests += (size_t)(l + 2 <= R ? 4 : 2) * (L - l);
+    if (nroots) *nroots = (R + 1) / 2;
+    if (nvalues) *nvalues = (size_t)nqueries * (4 * (size_t)(R / 2) + 2 * (R % 2));
+    if (path_bytes) *path_bytes = (size_t)nqueries * digests * 32;
     return ZK_OK;
 }
 

@@ -12,7 +12,8 @@ back to the roots); `verify_opening` is host code and needs nothing but the root
 The same commitment opened as a MULTILINEAR polynomial (include/zkmle.h "FRI commitment opened as a multilinear polynomial"): the committed
 table read as evaluations over the cube, `open_multilinear` proves y = evaluate(table, z) by a sumcheck interleaved with Lagrange-form folds of
 the codeword; `verify_multilinear` is host code and needs nothing but the root.  `open_multilinear_points` opens ONE commitment at up to
-eight points with one proof (include/zkmle.h "FRI commitment opened at several points"): the layers and trees are built once.
+eight points with one proof (include/zkmle.h "FRI commitment opened at several points"): the layers and trees are built once.  With
+`log_arity=2` it commits every second folded layer only (include/zkmle.h "FRI commitment opened with a fold arity"): a third of the leaves hashed.
 """
 import ctypes as C
 
@@ -230,10 +231,14 @@ class _MlStats(C.Structure):
                 ("ms_queries", C.c_float), ("ms_total", C.c_float)]
 
 
-def ml_sizes(d, log_blowup, log_final, nqueries):
-    """-> sizes(..) + (nround,): the 3 R elements of round polynomials of a multilinear opening of a table of 2^d entries"""
+def ml_sizes(d, log_blowup, log_final, nqueries, log_arity=1):
+    """-> sizes(..) + (nround,): the 3 R elements of round polynomials of a multilinear opening of a table of 2^d entries; log_arity = 2: the
+    counts of the opening folded by 4 (nroots = ceil(R / 2), four values and paths per fold-4 step)"""
     out = [C.c_size_t(0) for _ in range(5)]
-    L.check(L.lib().zk_fri_ml_sizes(d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
+    if log_arity == 1:
+        L.check(L.lib().zk_fri_ml_sizes(d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
+    else:
+        L.check(L.lib().zk_fri_ml_sizes_arity(d, log_blowup, log_final, nqueries, log_arity, *[C.byref(o) for o in out]))
     return tuple(int(o.value) for o in out)
 
 
@@ -245,23 +250,32 @@ def ml_fold(codeword, r, coset=None):
     return MultilinearPolynomial(codeword.field, _handle=h)
 
 
+def ml_fold4(codeword, r0, r1, coset=None):
+    """two Lagrange-form folds in one pass: ml_fold(ml_fold(codeword, r0, coset), r1, coset^2) byte for byte, a new table of a quarter the length"""
+    h = C.c_void_p()
+    cs = None if coset is None else L.p64(_elem(codeword.field, coset))
+    L.check(L.lib().zk_fri_ml_fold4(codeword._h, L.p64(_elem(codeword.field, r0)), L.p64(_elem(codeword.field, r1)), cs, C.byref(h)))
+    return MultilinearPolynomial(codeword.field, _handle=h)
+
+
 class FriMlOpening:
     """y (limbs,); round_polys (R, 3, limbs); roots (R, 32) bytes, roots[0] = the commitment's; final_table (m, limbs); query_values
     (Q, R, 2, limbs); query_paths (path_bytes,) bytes; challenges (R, limbs) and query_indices (Q,) are what the prover's transcript gave
     (diagnostic: the verifier derives its own)."""
 
-    def __init__(self, field, d, log_blowup, log_final, nqueries, coset=None):
+    def __init__(self, field, d, log_blowup, log_final, nqueries, coset=None, log_arity=1):
         self.field, self.d, self.log_blowup, self.log_final, self.nqueries = field, d, log_blowup, log_final, nqueries
         self.coset = None if coset is None else _elem(field, coset).copy()
-        nroots, nfinal, nvalues, path_bytes, nround = ml_sizes(d, log_blowup, log_final, nqueries)
+        nroots, nfinal, nvalues, path_bytes, nround = ml_sizes(d, log_blowup, log_final, nqueries, log_arity)
         n = limbs(field)
         self.y = np.zeros(n, np.uint64)
         self.round_polys = np.zeros((nround // 3, 3, n), np.uint64)
         self.roots = np.zeros((nroots, 32), np.uint8)
         self.final_table = np.zeros((nfinal, n), np.uint64)
-        self.challenges = np.zeros((nroots, n), np.uint64)
+        self.challenges = np.zeros((nround // 3, n), np.uint64)
         self.query_indices = np.zeros(nqueries, np.uint64)
-        self.query_values = np.zeros((nqueries, nroots, 2, n), np.uint64)
+        # log_arity = 2: per query the steps' values one after the other, four per fold-4 step and two for a final fold-2 step
+        self.query_values = np.zeros((nqueries, nroots, 2, n) if log_arity == 1 else (nqueries, nvalues // nqueries, n), np.uint64)
         self.query_paths = np.zeros(path_bytes, np.uint8)
 
     def _coset(self):
@@ -306,12 +320,13 @@ def verify_multilinear(root, z, opening, transcript=None):
 
 # ---- the multilinear opening at several points ------------------------------------------------------------------------------------------
 class FriMlPointsOpening(FriMlOpening):
-    """FriMlOpening with ys (P, limbs) in place of y, and gamma (limbs,), the batching challenge the prover's transcript gave (diagnostic)."""
+    """FriMlOpening with ys (P, limbs) in place of y, and gamma (limbs,), the batching challenge the prover's transcript gave (diagnostic).
+    log_arity = 2: roots (ceil(R / 2), 32), query_values (Q, 4 floor(R / 2) + 2 (R mod 2), limbs)."""
 
-    def __init__(self, field, npoints, d, log_blowup, log_final, nqueries, coset=None):
-        super().__init__(field, d, log_blowup, log_final, nqueries, coset)
+    def __init__(self, field, npoints, d, log_blowup, log_final, nqueries, coset=None, log_arity=1):
+        super().__init__(field, d, log_blowup, log_final, nqueries, coset, log_arity)
         del self.y
-        self.npoints = npoints
+        self.npoints, self.log_arity = npoints, log_arity
         self.ys = np.zeros((npoints, limbs(field)), np.uint64)
         self.gamma = np.zeros(limbs(field), np.uint64)
 
@@ -335,20 +350,26 @@ def ml_round(T, W, r=None):
     return MultilinearPolynomial(T.field, _handle=to), MultilinearPolynomial(T.field, _handle=wo), g3
 
 
-def open_multilinear_points(commitment, points, log_final, nqueries, transcript=None):
-    """one proof that the committed table's multilinear extension has the values `.ys` at the P <= 8 points (P, d, limbs)"""
+def open_multilinear_points(commitment, points, log_final, nqueries, transcript=None, log_arity=1):
+    """one proof that the committed table's multilinear extension has the values `.ys` at the P <= 8 points (P, d, limbs); log_arity = 2 folds
+    by 4 and commits every second layer"""
     pts = _points(commitment.field, commitment.d, points)
-    op = FriMlPointsOpening(commitment.field, pts.shape[0], commitment.d, commitment.log_blowup, log_final, nqueries, commitment.coset)
-    L.check(L.lib().zk_fri_ml_open_points(commitment._h, L.p64(pts), pts.shape[0], log_final, nqueries, _handle(transcript), L.p64(op.ys),
-                                          L.p64(op.gamma), L.p64(op.round_polys), L.p8(op.roots), L.p64(op.final_table), L.p64(op.challenges),
-                                          L.p64(op.query_indices), L.p64(op.query_values), L.p8(op.query_paths)))
+    op = FriMlPointsOpening(commitment.field, pts.shape[0], commitment.d, commitment.log_blowup, log_final, nqueries, commitment.coset, log_arity)
+    out = (L.p64(op.ys), L.p64(op.gamma), L.p64(op.round_polys), L.p8(op.roots), L.p64(op.final_table), L.p64(op.challenges),
+           L.p64(op.query_indices), L.p64(op.query_values), L.p8(op.query_paths))
+    if log_arity == 1:
+        L.check(L.lib().zk_fri_ml_open_points(commitment._h, L.p64(pts), pts.shape[0], log_final, nqueries, _handle(transcript), *out))
+    else:
+        L.check(L.lib().zk_fri_ml_open_points_arity(commitment._h, L.p64(pts), pts.shape[0], log_final, nqueries, log_arity, _handle(transcript), *out))
     return op
 
 
-def verify_multilinear_points(root, points, opening, transcript=None):
-    """host only: `root` = the commitment's 32 bytes; the claims checked are evaluate(table, points[p]) = opening.ys[p]"""
+def verify_multilinear_points(root, points, opening, transcript=None, log_arity=None):
+    """host only: `root` = the commitment's 32 bytes; the claims checked are evaluate(table, points[p]) = opening.ys[p].  log_arity: the
+    opening's own unless given"""
     ok = C.c_int(0)
     op = opening
+    log_arity = getattr(op, "log_arity", 1) if log_arity is None else log_arity
     rbuf = np.frombuffer(bytes(root), np.uint8).copy()
     if rbuf.shape[0] != 32:
         raise L.ZkError(L.ZK_E_ARG, "a Merkle root is 32 bytes")
@@ -357,9 +378,16 @@ def verify_multilinear_points(root, points, opening, transcript=None):
     if ys.shape != (pts.shape[0], limbs(op.field)):
         raise L.ZkError(L.ZK_E_ARG, "one claim per point")
     roots, paths = np.ascontiguousarray(op.roots, np.uint8), np.ascontiguousarray(op.query_paths, np.uint8)
-    L.check(L.lib().zk_fri_ml_verify_points(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, op._coset(), L.p64(pts),
-                                            pts.shape[0], L.p64(ys), _handle(transcript), L.p64(rp), L.p8(roots), L.p64(fin), L.p64(vals),
-                                            L.p8(paths), C.byref(ok)))
+    if log_arity != 1:                                        # the counts differ from the opening's own when the arity is overridden
+        nroots, nfinal, nvalues, path_bytes, nround = ml_sizes(op.d, op.log_blowup, op.log_final, op.nqueries, log_arity)
+        n = limbs(op.field)
+        if roots.size < 32 * nroots or fin.size < nfinal * n or vals.size < nvalues * n or paths.size < path_bytes or rp.size < nround * n:
+            raise L.ZkError(L.ZK_E_ARG, "the opening's arrays are shorter than this arity's proof")
+    rest = (op._coset(), L.p64(pts), pts.shape[0], L.p64(ys), _handle(transcript), L.p64(rp), L.p8(roots), L.p64(fin), L.p64(vals), L.p8(paths), C.byref(ok))
+    if log_arity == 1:
+        L.check(L.lib().zk_fri_ml_verify_points(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, *rest))
+    else:
+        L.check(L.lib().zk_fri_ml_verify_points_arity(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, log_arity, *rest))
     return bool(ok.value)
 
 
