@@ -5,132 +5,24 @@
 #include <chrono>
 #include <vector>
 
-#include "context.h"
-#include "fri.cuh"
-#include "transcript.h"
+#include "fri_host.h"
 #include "univariate.h"
 
 using namespace zk;
+using namespace zk::host;
 
 namespace {
 
-struct DevBuf {   // RAII block of the caching pool
-    void *p = nullptr;
-    ~DevBuf() { pool_free(p); }
-    int alloc(size_t bytes) { return pool_alloc(bytes, &p); }
-};
-struct TableHolder {   // tables of the pool, freed with the proof
-    std::vector<zk_table *> v;
-    ~TableHolder() { for (zk_table *t : v) zk_table_free(t); }
-};
-// HIP events along the calling thread's stream; elapsed times are read after the proof's last synchronisation
-struct Events {
-    std::vector<hipEvent_t> ev;
-    ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    int mark(size_t *id) {
-        hipEvent_t e;
-        ZK_HIP(hipEventCreate(&e));
-        ev.push_back(e);
-        ZK_HIP(hipEventRecord(e, cur_stream()));
-        *id = ev.size() - 1;
-        return ZK_OK;
-    }
-    float ms(size_t a, size_t b) const {
-        float v = 0.f;
-        return hipEventElapsedTime(&v, ev[a], ev[b]) == hipSuccess ? v : 0.f;
-    }
-};
-
 thread_local zk_fri_stats g_fri_stats{};
 
-// the two scalar fields: the only ones with a domain (every shape of the Fq fields is out of range)
-#define FRI_DISPATCH(field_id, ...)                                        \
-    switch (field_id) {                                                    \
-        case ZK_FR381: { using F = ::zk::Fr381; __VA_ARGS__; } break;      \
-        case ZK_BN254_FR: { using F = ::zk::Bn254Fr; __VA_ARGS__; } break; \
-        default: return ZK_E_RANGE;                                        \
-    }
-
-template <class F> Fe<F> load_host(const uint64_t *src) {
-    Fe<F> e;
-    memcpy(e.l, src, sizeof(uint32_t) * F::N);
-    return e;
-}
-template <class F> Fe<F> fe_pow(Fe<F> b, uint64_t e) {
-    Fe<F> acc = fe_one<F>();
-    for (; e; e >>= 1) {
-        if (e & 1) acc = fe_mul<F>(acc, b);
-        b = fe_sqr<F>(b);
-    }
-    return acc;
-}
-template <class F> bool is_reduced(const uint64_t *el) {
-    const Fe<F> x = load_host<F>(el);
-    for (int i = F::N - 1; i >= 0; i--)
-        if (x.l[i] != F::p(i)) return x.l[i] < F::p(i);
-    return false;
-}
-bool is_zero_element(int field, const uint64_t *x) {
-    uint64_t v = 0;
-    for (int k = 0; k < field_limbs64(field); k++) v |= x[k];
-    return v == 0;
-}
-unsigned two_adicity(int field) {
-    uint32_t s = 0;
-    return zk_ntt_two_adicity(field, &s) == ZK_OK ? s : 0;
-}
-// w_{2^log_n}; log_n within the field's two-adicity
-template <class F> Fe<F> root_of_unity(unsigned log_n) {
-    uint64_t w[F::N / 2];
-    (void)zk_ntt_root_of_unity(F::ID, log_n, w);
-    return load_host<F>(w);
-}
-void put_be32(uint8_t *out, uint32_t v) {
-    for (int k = 0; k < 4; k++) out[k] = (uint8_t)(v >> (24 - 8 * k));
-}
 // the checks on (b, f, Q) that need no length, then those that need d = the coefficient table's log2 length
 int params_check(uint32_t b, uint32_t Q) { return b >= 1 && b <= 8 && Q >= 1 && Q <= 4096 ? ZK_OK : ZK_E_ARG; }
-size_t path_digests(unsigned L, unsigned R) {             // of one query's answer
-    size_t n = 0;
-    for (unsigned l = 0; l < R; l++) n += 2 * (size_t)(L - l);
-    return n;
-}
 
 // ---- the fold ------------------------------------------------------------------------------------------------------------------
-// the powers of w_N^-1 below N / 2, N = 2^log_n, as ntt_pow2t reads them: built once per proof, layer l indexes them with k << l
-template <class F> struct FoldTables {
-    DevBuf buf;
-    const void *lo = nullptr, *hi = nullptr;
-    int build(unsigned log_n) {
-        const size_t half = (size_t)1 << (log_n - 1);
-        const bool two = half > ((size_t)1 << kNttLoBits);
-        const size_t lo_count = two ? (size_t)1 << kNttLoBits : half, hi_count = two ? half >> kNttLoBits : 0;
-        const size_t off_hi = (lo_count * sizeof(Ufe<F>) + 63) / 64 * 64;
-        ZK_TRY(buf.alloc(off_hi + (hi_count + 1) * sizeof(Fe<F>)));
-        const Fe<F> winv = fe_inv<F>(root_of_unity<F>(log_n)), one = fe_one<F>();
-        const size_t blocks = (lo_count + kNttBlock - 1) / kNttBlock;
-        ntt_pow_table_kernel<F, true><<<(unsigned)blocks, kNttBlock, 0, cur_stream()>>>(winv, one, (uint32_t)lo_count, buf.p);
-        ZK_HIP(hipGetLastError());
-        lo = buf.p;
-        if (two) {
-            Fe<F> step = winv;
-            for (unsigned k = 0; k < kNttLoBits; k++) step = fe_sqr<F>(step);
-            const size_t hb = (hi_count + kNttBlock - 1) / kNttBlock;
-            ntt_pow_table_kernel<F, false><<<(unsigned)(hb < 1024 ? hb : 1024), kNttBlock, 0, cur_stream()>>>(step, one, (uint32_t)hi_count, (char *)buf.p + off_hi);
-            ZK_HIP(hipGetLastError());
-            hi = (char *)buf.p + off_hi;
-        }
-        return ZK_OK;
-    }
-};
 // out[k], k < len / 2, from in[0 .. len): gamma = beta / (2 c) of this layer, `shift` = the layer's number
 template <class F> int launch_fold(const void *in, void *out, size_t len, unsigned shift, const FoldTables<F> &tb, const Fe<F> &gamma) {
-    UniMul<F> um;
-    unimul_from<F>(um, gamma);
-    FriUni g;
-    memcpy(g.t, um.t, sizeof g.t);
     const size_t half = len / 2;
-    fri_fold_kernel<F><<<(unsigned)((half + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(in, out, half, tb.lo, tb.hi, shift, g);
+    fri_fold_kernel<F><<<(unsigned)((half + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(in, out, half, tb.lo, tb.hi, shift, fri_uni<F>(gamma));
     ZK_HIP(hipGetLastError());
     return ZK_OK;
 }
@@ -155,24 +47,6 @@ struct ProofOut {
     uint8_t *query_paths;
 };
 
-void transcript_header(Transcript &tr, uint32_t d, uint32_t b, uint32_t f, uint32_t Q, const uint8_t coset_be[32]) {
-    uint8_t hdr[48];
-    put_be32(hdr, d);
-    put_be32(hdr + 4, b);
-    put_be32(hdr + 8, f);
-    put_be32(hdr + 12, Q);
-    memcpy(hdr + 16, coset_be, 32);
-    tr.append(hdr, sizeof hdr);
-}
-// i_q = the little-endian integer of a sampled digest mod 2^bits, bits <= 31
-uint64_t sample_index(Transcript &tr, unsigned bits) {
-    uint8_t dg[32];
-    tr.sample_random_challenge(dg);
-    uint64_t v = 0;
-    for (int k = 0; k < 8; k++) v |= (uint64_t)dg[k] << (8 * k);
-    return v & (((uint64_t)1 << bits) - 1);
-}
-
 // `cw` = layer 0 (N = 2^L entries, L = d + b); events: `ev0` was recorded before the extension (or is the proof's first event)
 template <class F> int prove_layers(const zk_table *cw, unsigned b, unsigned f, unsigned Q, const uint64_t *coset, Transcript &tr, const ProofOut &o,
                                     Events &ev, float *ms_trees, float *ms_folds, float *ms_queries) {
@@ -189,9 +63,8 @@ template <class F> int prove_layers(const zk_table *cw, unsigned b, unsigned f, 
     DevBuf trees;                                             // layer l's levels at digest offset 4 N - (4 N >> l): 2 N_l digests of room each
     ZK_TRY(trees.alloc(4 * N * 32));
     TableHolder layers;
-    FriLayers fl{};
-    fl.log_len0 = L;
-    fl.nlayers = R;
+    const FriSchedule sc(L, R, 1);
+    FriLayers fl = sc.layers();
 
     std::vector<size_t> ta(R + 1), tf(R);
     const zk_table *cur = cw;
@@ -200,7 +73,6 @@ template <class F> int prove_layers(const zk_table *cw, unsigned b, unsigned f, 
         uint64_t *tree = (uint64_t *)trees.p + 4 * (4 * N - ((4 * N) >> l));
         fl.table[l] = cur->dptr;
         fl.tree[l] = tree;
-        fl.path_off[l + 1] = fl.path_off[l] + 2 * (L - l);
         ZK_TRY(ev.mark(&ta[l]));
         ZK_TRY(merkle_levels_device(cur, tree));
         uint8_t *root = o.roots + 32 * l;
@@ -209,8 +81,7 @@ template <class F> int prove_layers(const zk_table *cw, unsigned b, unsigned f, 
         const Fe<F> beta = tr.random_challenge_as_field_element<F>();
         if (o.betas) memcpy(o.betas + l * (F::N / 2), beta.l, ESZ);
         zk_table *next = nullptr;
-        ZK_TRY(table_alloc_pooled(cw->field, cur->len / 2, &next));
-        layers.v.push_back(next);
+        ZK_TRY(layers.alloc(cw->field, cur->len / 2, &next));
         ZK_TRY(ev.mark(&tf[l]));
         ZK_TRY((launch_fold<F>(cur->dptr, next->dptr, cur->len, l, tb, fe_mul<F>(beta, gscale))));
         gscale = fe_mul<F>(gscale, cinv_sq);
@@ -229,30 +100,13 @@ template <class F> int prove_layers(const zk_table *cw, unsigned b, unsigned f, 
     ZK_HIP(zk::memcpy_on_stream(o.final_coeffs, last->dptr, m * ESZ, hipMemcpyDeviceToHost));
     for (size_t j = 0; j < m; j++) tr.append_be<F>(load_host<F>(o.final_coeffs + j * (F::N / 2)));
 
-    std::vector<uint64_t> idx(Q);
-    for (unsigned q = 0; q < Q; q++) idx[q] = sample_index(tr, L - 1);
-    if (o.query_indices) memcpy(o.query_indices, idx.data(), Q * 8);
-    const size_t nval = (size_t)Q * R * 2, ndig = (size_t)Q * fl.path_off[R];
-    DevBuf didx, dval, dpath;
-    ZK_TRY(didx.alloc(Q * 8));
-    ZK_TRY(dval.alloc(nval * ESZ));
-    ZK_TRY(dpath.alloc(ndig * 32));
-    ZK_HIP(hipMemcpyAsync(didx.p, idx.data(), Q * 8, hipMemcpyHostToDevice, cur_stream()));
-    fri_query_values_kernel<F><<<(unsigned)((nval + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(fl, (const uint64_t *)didx.p, Q, dval.p);
-    ZK_HIP(hipGetLastError());
-    fri_query_paths_kernel<<<(unsigned)((ndig + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(fl, (const uint64_t *)didx.p, Q, (uint64_t *)dpath.p);
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(o.query_values, dval.p, nval * ESZ, hipMemcpyDeviceToHost, cur_stream()));   // one download each, one wait for both
-    ZK_HIP(zk::memcpy_on_stream(o.query_paths, dpath.p, ndig * 32, hipMemcpyDeviceToHost));
-    size_t end;
-    ZK_TRY(ev.mark(&end));
-    ZK_HIP(hipEventSynchronize(ev.ev[end]));
+    ZK_TRY((answer_queries<F>(tr, fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, nullptr)));
     *ms_trees = *ms_folds = 0.f;
     for (unsigned l = 0; l < R; l++) {
         *ms_trees += ev.ms(ta[l], tf[l]);
         *ms_folds += ev.ms(tf[l], ta[l + 1]);
     }
-    *ms_queries = ev.ms(ta[R], end);
+    *ms_queries = ev.since(ta[R]);                            // the last layer's transform and download, then the gather
     return ZK_OK;
 }
 
@@ -280,8 +134,7 @@ int prove_any(const zk_table *in, bool is_codeword, uint32_t b, uint32_t f, uint
     ZK_TRY(ev.mark(&e0));
     if (!is_codeword) {
         zk_table *x = nullptr;
-        ZK_TRY(table_alloc_pooled(in->field, in->len << b, &x));
-        ext.v.push_back(x);
+        ZK_TRY(ext.alloc(in->field, in->len << b, &x));
         ZK_TRY(ntt_extend_into(in, coset, x));
         cw = x;
     }
@@ -299,179 +152,159 @@ int prove_any(const zk_table *in, bool is_codeword, uint32_t b, uint32_t f, uint
 }
 
 // ---- the verifier (host) -------------------------------------------------------------------------------------------------------
-// `indices_out` (Q words, may be null): the sampled i_q, for a caller that checks more at the queried positions (zkmle_fri_pcs.hip)
-// `ml`: the fold mode of the multilinear opening (context.h FriMlClaim); null = the monomial fold of zk_fri_verify, byte for byte as before
-template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t Q, const uint64_t *coset, Transcript &tr, const uint8_t *roots,
-                                   const uint64_t *final_coeffs, const uint64_t *values, const uint8_t *paths, int *ok, uint64_t *indices_out,
-                                   const FriMlClaim *ml) {
+// what the transcript gives back: `good` = every element absorbed so far was a reduced one
+template <class F> struct Replayed {
+    bool good;
+    Fe<F> gamma = fe_one<F>();                                // the several-point form's batching challenge
+    std::vector<Fe<F>> beta, h;                               // the R fold challenges; the final coefficients (or table)
+    std::vector<uint64_t> idx;                                // the Q query indices
+};
+
+// the prover's transcript over again.  `ml`: the claim and round polynomials of the multilinear forms (context.h FriMlClaim), null = zk_fri_verify
+template <class F> Replayed<F> replay(uint32_t d, uint32_t b, uint32_t f, uint32_t Q, const uint64_t *coset, Transcript &tr, const FriSchedule &sc,
+                                      const uint8_t *roots, const uint64_t *final_coeffs, const FriMlClaim *ml) {
     constexpr int W = F::N / 2;
-    const unsigned L = d + b, R = d - f;
-    const size_t m = (size_t)1 << f;
-    const Fe<F> c = coset ? load_host<F>(coset) : fe_one<F>();
-    bool good = !coset || is_reduced<F>(coset);
-    uint8_t cbe[32];
-    host_to_bytes_be<F>(c, cbe);
+    const unsigned R = d - f;
+    Replayed<F> rp;
+    rp.good = !coset || is_reduced<F>(coset);
+    const auto absorb = [&](const uint64_t *el) {
+        rp.good = rp.good && is_reduced<F>(el);
+        const Fe<F> e = load_host<F>(el);
+        tr.append_be<F>(e);
+        return e;
+    };
+    uint8_t cbe[32], be[4];
+    host_to_bytes_be<F>(coset ? load_host<F>(coset) : fe_one<F>(), cbe);
     transcript_header(tr, d, b, f, Q, cbe);
-    const unsigned la = ml ? ml->log_arity : 1;              // 2: every second layer is committed and a query opens four entries of it
-    if (la == 2) {
-        uint8_t abe[4];
-        put_be32(abe, la);
-        tr.append(abe, 4);
+    if (sc.log_arity == 2) {
+        put_be32(be, sc.log_arity);
+        tr.append(be, 4);
     }
     tr.append(roots, 32);
-    const unsigned P = ml ? ml->npoints : 0;                 // 0: the single-point form
-    Fe<F> gamma = fe_one<F>();
-    if (ml && P == 0) {
-        for (unsigned i = 0; i <= d; i++) {                  // z_0 .. z_{d-1}, then y
-            const uint64_t *el = i < d ? ml->z + (size_t)i * W : ml->y;
-            good = good && is_reduced<F>(el);
-            tr.append_be<F>(load_host<F>(el));
-        }
+    if (ml && ml->npoints == 0) {                            // z_0 .. z_{d-1}, then y
+        for (unsigned i = 0; i < d; i++) absorb(ml->z + (size_t)i * W);
+        absorb(ml->y);
     } else if (ml) {                                         // P, the points (point-major), the claims, then gamma
-        uint8_t pbe[4];
-        for (int k = 0; k < 4; k++) pbe[k] = (uint8_t)(P >> (24 - 8 * k));
-        tr.append(pbe, 4);
-        for (size_t i = 0; i < (size_t)P * d + P; i++) {
-            const uint64_t *el = i < (size_t)P * d ? ml->z + i * W : ml->y + (i - (size_t)P * d) * W;
-            good = good && is_reduced<F>(el);
-            tr.append_be<F>(load_host<F>(el));
-        }
-        gamma = tr.random_challenge_as_field_element<F>();
+        const size_t P = ml->npoints;
+        put_be32(be, ml->npoints);
+        tr.append(be, 4);
+        for (size_t i = 0; i < P * d; i++) absorb(ml->z + i * W);
+        for (size_t p = 0; p < P; p++) absorb(ml->y + p * W);
+        rp.gamma = tr.random_challenge_as_field_element<F>();
     }
-    std::vector<Fe<F>> beta(R);
-    for (unsigned l = 0; l < R; l++) {
-        for (unsigned k = 0; ml && k < 3; k++) {             // g_l(0), g_l(1), g_l(2)
-            const uint64_t *el = ml->round_polys + ((size_t)l * 3 + k) * W;
-            good = good && is_reduced<F>(el);
-            tr.append_be<F>(load_host<F>(el));
-        }
-        beta[l] = tr.random_challenge_as_field_element<F>();
-        if (la == 2) {
-            if (l + 1 < R && (l + 1) % 2 == 0) tr.append(roots + 32 * ((l + 1) / 2), 32);
-        } else if (l + 1 < R) tr.append(roots + 32 * (l + 1), 32);
+    rp.beta.resize(R);
+    for (unsigned l = 0, s = 0; l < R; l++) {
+        for (unsigned k = 0; ml && k < 3; k++) absorb(ml->round_polys + ((size_t)l * 3 + k) * W);   // g_l(0), g_l(1), g_l(2)
+        rp.beta[l] = tr.random_challenge_as_field_element<F>();
+        if (s + 1 < sc.nsteps && sc.step[s + 1].layer == l + 1) tr.append(roots + 32 * sc.step[++s].root, 32);   // layer l + 1 is committed
     }
-    std::vector<Fe<F>> h(m);
-    for (size_t j = 0; j < m; j++) {
-        good = good && is_reduced<F>(final_coeffs + j * W);
-        h[j] = load_host<F>(final_coeffs + j * W);
-        tr.append_be<F>(h[j]);
-    }
-    std::vector<uint64_t> idx(Q);
-    for (unsigned q = 0; q < Q; q++) idx[q] = sample_index(tr, L - la);
-    if (indices_out) memcpy(indices_out, idx.data(), Q * 8);
-    *ok = 0;
-    const size_t vper = la == 2 ? 4 * (size_t)(R / 2) + 2 * (R % 2) : (size_t)R * 2;   // opened values of one query
-    for (size_t k = 0; good && k < (size_t)Q * vper; k++) good = is_reduced<F>(values + k * W);
-    if (!good) return ZK_OK;
+    for (size_t j = 0; j < (size_t)1 << f; j++) rp.h.push_back(absorb(final_coeffs + j * W));
+    for (unsigned q = 0; q < Q; q++) rp.idx.push_back(sample_index(tr, sc.index_bits()));
+    return rp;
+}
 
-    const Fe<F> w = root_of_unity<F>(L), winv = fe_inv<F>(w), inv2 = fe_inv<F>(fe_from_u64<F>(2));
-    if (ml) {                                                // the sumcheck of sum_x T[x] eq(x, z) = y beside the folds, on the same challenges
-        const Fe<F> one = fe_one<F>(), two = fe_from_u64<F>(2);
-        const unsigned np = P ? P : 1;                        // per point p: gamma^p A^p_l; the single-point form is np = 1 with gamma^0
-        std::vector<Fe<F>> A(np, one);
-        Fe<F> claim = fe_zero<F>();
-        for (unsigned p = 0; p < np; p++) {
-            if (p) A[p] = fe_mul<F>(A[p - 1], gamma);
-            claim = fe_add<F>(claim, fe_mul<F>(A[p], load_host<F>(ml->y + (size_t)p * W)));
-        }
-        for (unsigned l = 0; l < R; l++) {
-            const uint64_t *g = ml->round_polys + (size_t)l * 3 * W;
-            const Fe<F> g0 = load_host<F>(g), g1 = load_host<F>(g + W), g2 = load_host<F>(g + 2 * W), r = beta[l];
-            if (!fe_eq<F>(fe_add<F>(g0, g1), claim)) return ZK_OK;
-            // g_l(r) from its values at 0, 1, 2:  g0 (r - 1)(r - 2) / 2 - g1 r (r - 2) + g2 r (r - 1) / 2
-            const Fe<F> r1 = fe_sub<F>(r, one), r2 = fe_sub<F>(r, two);
-            const Fe<F> outer = fe_mul<F>(inv2, fe_add<F>(fe_mul<F>(g0, fe_mul<F>(r1, r2)), fe_mul<F>(g2, fe_mul<F>(r, r1))));
-            claim = fe_sub<F>(outer, fe_mul<F>(g1, fe_mul<F>(r, r2)));
-            for (unsigned p = 0; p < np; p++) {
-                const Fe<F> zv = load_host<F>(ml->z + ((size_t)p * d + d - 1 - l) * W);   // eq1(r_l, z_v) = 1 - r - z + 2 r z
-                A[p] = fe_mul<F>(A[p], fe_add<F>(fe_sub<F>(fe_sub<F>(one, r), zv), fe_mul<F>(two, fe_mul<F>(r, zv))));
-            }
-        }
-        // sum_j T_R[j] W_R[j] = sum_p gamma^p A^p_R (the MLE of T_R at (z^p_0 .. z^p_{f-1})): f folds of variable 0 per point
-        Fe<F> end = fe_zero<F>();
-        for (unsigned p = 0; p < np; p++) {
-            std::vector<Fe<F>> t(h);
-            for (unsigned i = 0; i < f; i++) {
-                const size_t half = m >> (i + 1);
-                const Fe<F> zi = load_host<F>(ml->z + ((size_t)p * d + i) * W);
-                for (size_t j = 0; j < half; j++) t[j] = fe_add<F>(t[j], fe_mul<F>(zi, fe_sub<F>(t[j + half], t[j])));
-            }
-            end = fe_add<F>(end, fe_mul<F>(A[p], t[0]));
-        }
-        if (!fe_eq<F>(end, claim)) return ZK_OK;
+// the sumcheck of sum_x T[x] W[x] = sum_p gamma^p y_p beside the folds, on the same challenges; the single-point form is one point with gamma^0
+template <class F> bool sumcheck_holds(uint32_t d, uint32_t f, const FriMlClaim &ml, const Replayed<F> &rp) {
+    constexpr int W = F::N / 2;
+    const unsigned R = d - f, np = ml.npoints ? ml.npoints : 1;
+    const size_t m = (size_t)1 << f;
+    const Fe<F> one = fe_one<F>(), two = fe_from_u64<F>(2), inv2 = fe_inv<F>(two);
+    std::vector<Fe<F>> A(np, one);                            // per point p: gamma^p A^p_l
+    Fe<F> claim = fe_zero<F>();
+    for (unsigned p = 0; p < np; p++) {
+        if (p) A[p] = fe_mul<F>(A[p - 1], rp.gamma);
+        claim = fe_add<F>(claim, fe_mul<F>(A[p], load_host<F>(ml.y + (size_t)p * W)));
     }
+    for (unsigned l = 0; l < R; l++) {
+        const uint64_t *g = ml.round_polys + (size_t)l * 3 * W;
+        const Fe<F> g0 = load_host<F>(g), g1 = load_host<F>(g + W), g2 = load_host<F>(g + 2 * W), r = rp.beta[l];
+        if (!fe_eq<F>(fe_add<F>(g0, g1), claim)) return false;
+        // g_l(r) from its values at 0, 1, 2:  g0 (r - 1)(r - 2) / 2 - g1 r (r - 2) + g2 r (r - 1) / 2
+        const Fe<F> r1 = fe_sub<F>(r, one), r2 = fe_sub<F>(r, two);
+        const Fe<F> outer = fe_mul<F>(inv2, fe_add<F>(fe_mul<F>(g0, fe_mul<F>(r1, r2)), fe_mul<F>(g2, fe_mul<F>(r, r1))));
+        claim = fe_sub<F>(outer, fe_mul<F>(g1, fe_mul<F>(r, r2)));
+        for (unsigned p = 0; p < np; p++) {
+            const Fe<F> zv = load_host<F>(ml.z + ((size_t)p * d + d - 1 - l) * W);   // eq1(r_l, z_v) = 1 - r - z + 2 r z
+            A[p] = fe_mul<F>(A[p], fe_add<F>(fe_sub<F>(fe_sub<F>(one, r), zv), fe_mul<F>(two, fe_mul<F>(r, zv))));
+        }
+    }
+    // sum_j T_R[j] W_R[j] = sum_p gamma^p A^p_R (the MLE of T_R at (z^p_0 .. z^p_{f-1})): f folds of variable 0 per point
+    Fe<F> end = fe_zero<F>();
+    for (unsigned p = 0; p < np; p++) {
+        std::vector<Fe<F>> t(rp.h);
+        for (unsigned i = 0; i < f; i++) {
+            const size_t half = m >> (i + 1);
+            const Fe<F> zi = load_host<F>(ml.z + ((size_t)p * d + i) * W);
+            for (size_t j = 0; j < half; j++) t[j] = fe_add<F>(t[j], fe_mul<F>(zi, fe_sub<F>(t[j + half], t[j])));
+        }
+        end = fe_add<F>(end, fe_mul<F>(A[p], t[0]));
+    }
+    return fe_eq<F>(end, claim);
+}
+
+// every query: its steps' paths, and each step's fold against the next step's value (the last against the final polynomial).  `lagrange`: the
+// fold of the multilinear forms, (1 - r) (a + b) / 2 + r (a - b) / (2 x); else the monomial (a + b) / 2 + r (a - b) / (2 x)
+template <class F> int queries_hold(const FriSchedule &sc, unsigned R, bool lagrange, const Fe<F> &c, const Replayed<F> &rp, const uint8_t *roots,
+                                    const uint64_t *values, const uint8_t *paths, int *ok) {
+    constexpr int W = F::N / 2;
+    const unsigned L = sc.step[0].log_len;
+    const Fe<F> w = root_of_unity<F>(L), winv = fe_inv<F>(w), inv2 = fe_inv<F>(fe_from_u64<F>(2));
+    const Fe<F> iinv = fe_pow<F>(winv, (uint64_t)1 << (L - 2));   // i^-1, i = w_l^(N_l / 4) = the primitive fourth root w^(N / 4) at every layer
     std::vector<Fe<F>> cinv(R);                               // c_l^-1
-    Fe<F> cl = c, ci = fe_inv<F>(c);
+    Fe<F> cR = c, ci = fe_inv<F>(c);
     for (unsigned l = 0; l < R; l++) {
         cinv[l] = ci;
         ci = fe_sqr<F>(ci);
-        cl = fe_sqr<F>(cl);
+        cR = fe_sqr<F>(cR);
     }
-    const Fe<F> cR = cl;
-    if (la == 2) {
-        // steps start at the even layers: a fold by 4 to layer l + 2 <= R, or (R odd, l = R - 1) the fold by 2 to layer R
-        const auto fold = [&](const Fe<F> &a, const Fe<F> &bb, const Fe<F> &r, const Fe<F> &xinv) {   // (1 - r) (a + b) / 2 + r (a - b) / (2 x)
-            const Fe<F> even = fe_mul<F>(fe_sub<F>(fe_one<F>(), r), fe_add<F>(a, bb));
-            return fe_mul<F>(inv2, fe_add<F>(even, fe_mul<F>(fe_mul<F>(r, xinv), fe_sub<F>(a, bb))));
-        };
-        const Fe<F> iinv = fe_pow<F>(winv, (uint64_t)1 << (L - 2));   // i^-1, i = w_l^(N_l / 4) = the primitive fourth root w^(N / 4) at every layer
-        const uint8_t *pp = paths;
-        for (unsigned q = 0; q < Q; q++) {
-            const uint64_t *vq = values + (size_t)q * vper * W;
-            for (unsigned l = 0; l < R; l += 2) {
-                const unsigned sides = l + 2 <= R ? 4 : 2, depth = L - l;
-                const size_t part = ((size_t)1 << depth) / sides, j = idx[q] & (part - 1);
-                const uint64_t *v = vq + (size_t)(l / 2) * 4 * W;
-                Fe<F> e[4];
-                for (unsigned s = 0; s < sides; s++) {
-                    int ok_s = 0;
-                    ZK_TRY(zk_merkle_verify(F::ID, roots + 32 * (l / 2), depth, j + s * part, v + (size_t)s * W, pp, &ok_s));
-                    pp += 32 * (size_t)depth;
-                    if (!ok_s) return ZK_OK;
-                    e[s] = load_host<F>(v + (size_t)s * W);
-                }
-                const Fe<F> xinv = fe_mul<F>(cinv[l], fe_pow<F>(winv, (uint64_t)j << l));
-                Fe<F> got;
-                if (sides == 4) got = fold(fold(e[0], e[2], beta[l], xinv), fold(e[1], e[3], beta[l], fe_mul<F>(xinv, iinv)), beta[l + 1], fe_sqr<F>(xinv));
-                else got = fold(e[0], e[1], beta[l], xinv);
-                const unsigned ln = l + (sides == 4 ? 2 : 1);  // the layer the step lands in: j is a position of it
-                Fe<F> want;
-                if (ln < R) {
-                    const size_t npart = ((size_t)1 << (L - ln)) / (ln + 2 <= R ? 4 : 2);
-                    want = load_host<F>(vq + ((size_t)(ln / 2) * 4 + j / npart) * W);
-                } else want = uni_evaluate<F>(h, fe_mul<F>(cR, fe_pow<F>(w, (uint64_t)j << R)));
-                if (!fe_eq<F>(got, want)) return ZK_OK;
+    const auto fold = [&](const Fe<F> &a, const Fe<F> &bb, const Fe<F> &r, const Fe<F> &xinv) {
+        Fe<F> even = fe_add<F>(a, bb);
+        if (lagrange) even = fe_mul<F>(fe_sub<F>(fe_one<F>(), r), even);
+        return fe_mul<F>(inv2, fe_add<F>(even, fe_mul<F>(fe_mul<F>(r, xinv), fe_sub<F>(a, bb))));
+    };
+    for (size_t q = 0; q < rp.idx.size(); q++) {
+        const uint64_t *vq = values + q * sc.nvalues * W;
+        const uint8_t *pq = paths + q * sc.ndigests * 32;
+        for (unsigned s = 0; s < sc.nsteps; s++) {
+            const FriStep &st = sc.step[s];
+            const unsigned l = st.layer, sides = 1u << st.log_sides;
+            const size_t part = ((size_t)1 << st.log_len) >> st.log_sides, j = rp.idx[q] & (part - 1);
+            const uint64_t *v = vq + st.val_off * W;
+            Fe<F> e[4];
+            for (unsigned side = 0; side < sides; side++) {
+                int ok_s = 0;
+                ZK_TRY(zk_merkle_verify(F::ID, roots + 32 * st.root, st.log_len, j + side * part, v + (size_t)side * W,
+                                        pq + 32 * (st.path_off + (size_t)side * st.log_len), &ok_s));
+                if (!ok_s) return ZK_OK;
+                e[side] = load_host<F>(v + (size_t)side * W);
             }
-        }
-        *ok = 1;
-        return ZK_OK;
-    }
-    const size_t per = path_digests(L, R);
-    for (unsigned q = 0; q < Q; q++) {
-        const uint8_t *pp = paths + (size_t)q * per * 32;
-        for (unsigned l = 0; l < R; l++) {
-            const size_t half = ((size_t)1 << (L - l)) >> 1, j = idx[q] & (half - 1);
-            const uint64_t *lo = values + ((size_t)q * R + l) * 2 * W, *hi = lo + W;
-            int ok_lo = 0, ok_hi = 0;
-            ZK_TRY(zk_merkle_verify(F::ID, roots + 32 * l, L - l, j, lo, pp, &ok_lo));
-            ZK_TRY(zk_merkle_verify(F::ID, roots + 32 * l, L - l, j + half, hi, pp + 32 * (L - l), &ok_hi));
-            pp += 64 * (size_t)(L - l);
-            if (!ok_lo || !ok_hi) return ZK_OK;
-            const Fe<F> a = load_host<F>(lo), bb = load_host<F>(hi);
             const Fe<F> xinv = fe_mul<F>(cinv[l], fe_pow<F>(winv, (uint64_t)j << l));
-            Fe<F> v;
-            if (ml) {                                         // (1 - r) (a + b) / 2 + r (a - b) / (2 x)
-                const Fe<F> even = fe_mul<F>(fe_sub<F>(fe_one<F>(), beta[l]), fe_add<F>(a, bb));
-                v = fe_mul<F>(inv2, fe_add<F>(even, fe_mul<F>(fe_mul<F>(beta[l], xinv), fe_sub<F>(a, bb))));
-            } else v = fe_mul<F>(inv2, fe_add<F>(fe_add<F>(a, bb), fe_mul<F>(fe_mul<F>(beta[l], xinv), fe_sub<F>(a, bb))));
-            Fe<F> want;
-            if (l + 1 < R) want = load_host<F>(values + (((size_t)q * R + l + 1) * 2 + (j >= half / 2 ? 1 : 0)) * W);
-            else want = uni_evaluate<F>(h, fe_mul<F>(cR, fe_pow<F>(w, (uint64_t)j << R)));
-            if (!fe_eq<F>(v, want)) return ZK_OK;
+            Fe<F> got;
+            if (sides == 4) got = fold(fold(e[0], e[2], rp.beta[l], xinv), fold(e[1], e[3], rp.beta[l], fe_mul<F>(xinv, iinv)), rp.beta[l + 1], fe_sqr<F>(xinv));
+            else got = fold(e[0], e[1], rp.beta[l], xinv);
+            Fe<F> want;                                       // the step lands in layer l + log_sides: j is a position of it
+            if (s + 1 < sc.nsteps) {
+                const FriStep &nx = sc.step[s + 1];
+                want = load_host<F>(vq + (nx.val_off + j / (((size_t)1 << nx.log_len) >> nx.log_sides)) * W);
+            } else want = uni_evaluate<F>(rp.h, fe_mul<F>(cR, fe_pow<F>(w, (uint64_t)j << R)));
+            if (!fe_eq<F>(got, want)) return ZK_OK;
         }
     }
     *ok = 1;
     return ZK_OK;
+}
+
+// `indices_out` (Q words, may be null): the sampled i_q, for a caller that checks more at the queried positions (zkmle_fri_pcs.hip)
+template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t Q, const uint64_t *coset, Transcript &tr, const uint8_t *roots,
+                                   const uint64_t *final_coeffs, const uint64_t *values, const uint8_t *paths, int *ok, uint64_t *indices_out,
+                                   const FriMlClaim *ml) {
+    const FriSchedule sc(d + b, d - f, ml ? ml->log_arity : 1);
+    Replayed<F> rp = replay<F>(d, b, f, Q, coset, tr, sc, roots, final_coeffs, ml);
+    if (indices_out) memcpy(indices_out, rp.idx.data(), Q * 8);
+    *ok = 0;
+    for (size_t k = 0; rp.good && k < (size_t)Q * sc.nvalues; k++) rp.good = is_reduced<F>(values + k * (F::N / 2));
+    if (!rp.good || (ml && !sumcheck_holds<F>(d, f, *ml, rp))) return ZK_OK;
+    return queries_hold<F>(sc, d - f, ml != nullptr, coset ? load_host<F>(coset) : fe_one<F>(), rp, roots, values, paths, ok);
 }
 
 }  // namespace
@@ -496,11 +329,7 @@ int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_fin
 extern "C" {
 
 int zk_fri_fold(const zk_table *codeword, const uint64_t *beta, const uint64_t *coset, zk_table **out) {
-    if (!codeword || !beta || !out || field_limbs64(codeword->field) < 0 || codeword->len == 1) return ZK_E_ARG;
-    if (coset && is_zero_element(codeword->field, coset)) return ZK_E_ARG;
-    if (!is_pow2(codeword->len)) return ZK_E_NOT_POW2;
-    if ((codeword->field != ZK_FR381 && codeword->field != ZK_BN254_FR) || ilog2(codeword->len) > two_adicity(codeword->field)) return ZK_E_RANGE;
-    ZK_TRY(require_device());
+    ZK_TRY(fold_check(codeword, beta && out, coset, 1));
     FRI_DISPATCH(codeword->field, return fold_once<F>(codeword, beta, coset, out));
     return ZK_OK;
 }
@@ -510,11 +339,11 @@ int zk_fri_proof_sizes(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint
     ZK_TRY(params_check(log_blowup, nqueries));
     if (d < 1 || log_final >= d) return ZK_E_ARG;
     if (d > 32 || d + log_blowup > 32) return ZK_E_RANGE;
-    const unsigned R = d - log_final;
-    if (nroots) *nroots = R;
+    const FriSchedule sc(d + log_blowup, d - log_final, 1);
+    if (nroots) *nroots = sc.nsteps;
     if (nfinal) *nfinal = (size_t)1 << log_final;
-    if (nvalues) *nvalues = (size_t)nqueries * R * 2;
-    if (path_bytes) *path_bytes = (size_t)nqueries * path_digests(d + log_blowup, R) * 32;
+    if (nvalues) *nvalues = (size_t)nqueries * sc.nvalues;
+    if (path_bytes) *path_bytes = (size_t)nqueries * sc.ndigests * 32;
     return ZK_OK;
 }
 

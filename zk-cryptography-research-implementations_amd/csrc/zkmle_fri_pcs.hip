@@ -8,87 +8,21 @@
 #include <chrono>
 #include <vector>
 
-#include "context.h"
+#include "fri_host.h"
 #include "fri_pcs.cuh"
-#include "transcript.h"
 
 using namespace zk;
+using namespace zk::host;
 
 namespace {
 
-struct DevBuf {   // RAII block of the caching pool
-    void *p = nullptr;
-    ~DevBuf() { pool_free(p); }
-    int alloc(size_t bytes) { return pool_alloc(bytes, &p); }
-};
-struct TableGuard {
-    zk_table *t = nullptr;
-    ~TableGuard() { zk_table_free(t); }
-};
-struct Events {
-    std::vector<hipEvent_t> ev;
-    ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    int mark(size_t *id) {
-        hipEvent_t e;
-        ZK_HIP(hipEventCreate(&e));
-        ev.push_back(e);
-        ZK_HIP(hipEventRecord(e, cur_stream()));
-        *id = ev.size() - 1;
-        return ZK_OK;
-    }
-    float ms(size_t a, size_t b) const {
-        float v = 0.f;
-        return hipEventElapsedTime(&v, ev[a], ev[b]) == hipSuccess ? v : 0.f;
-    }
-};
-
 thread_local zk_fri_pcs_stats g_pcs_stats{};
 
-#define PCS_DISPATCH(field_id, ...)                                        \
-    switch (field_id) {                                                    \
-        case ZK_FR381: { using F = ::zk::Fr381; __VA_ARGS__; } break;      \
-        case ZK_BN254_FR: { using F = ::zk::Bn254Fr; __VA_ARGS__; } break; \
-        default: return ZK_E_RANGE;                                        \
-    }
-
-template <class F> Fe<F> load_host(const uint64_t *src) {
-    Fe<F> e;
-    memcpy(e.l, src, sizeof(uint32_t) * F::N);
-    return e;
-}
-template <class F> bool is_reduced(const uint64_t *el) {
-    const Fe<F> x = load_host<F>(el);
-    for (int i = F::N - 1; i >= 0; i--)
-        if (x.l[i] != F::p(i)) return x.l[i] < F::p(i);
-    return false;
-}
-template <class F> Fe<F> fe_pow(Fe<F> b, uint64_t e) {
-    Fe<F> acc = fe_one<F>();
-    for (; e; e >>= 1) {
-        if (e & 1) acc = fe_mul<F>(acc, b);
-        b = fe_sqr<F>(b);
-    }
-    return acc;
-}
 template <class F> Fe<F> sqr_times(Fe<F> x, unsigned k) {
     while (k--) x = fe_sqr<F>(x);
     return x;
 }
 bool scalar_field(int field) { return field == ZK_FR381 || field == ZK_BN254_FR; }
-bool is_zero_element(int field, const uint64_t *x) {
-    uint64_t v = 0;
-    for (int k = 0; k < field_limbs64(field); k++) v |= x[k];
-    return v == 0;
-}
-unsigned two_adicity(int field) {
-    uint32_t s = 0;
-    return zk_ntt_two_adicity(field, &s) == ZK_OK ? s : 0;
-}
-template <class F> Fe<F> root_of_unity(unsigned log_n) {
-    uint64_t w[F::N / 2];
-    (void)zk_ntt_root_of_unity(F::ID, log_n, w);
-    return load_host<F>(w);
-}
 // 1: z (reduced) lies in {c w^i}: (z / c)^N = 1
 template <class F> bool in_domain(const uint64_t *z, const uint64_t *coset, unsigned L) {
     Fe<F> r = load_host<F>(z);
@@ -97,7 +31,7 @@ template <class F> bool in_domain(const uint64_t *z, const uint64_t *coset, unsi
 }
 // ZK_E_ARG for a point that is not a reduced element or lies in the evaluation domain of 2^L entries (scalar field, L within its two-adicity)
 int point_check(int field, const uint64_t *z, const uint64_t *coset, unsigned L) {
-    PCS_DISPATCH(field, return is_reduced<F>(z) && !in_domain<F>(z, coset, L) ? ZK_OK : ZK_E_ARG);
+    FRI_DISPATCH(field, return is_reduced<F>(z) && !in_domain<F>(z, coset, L) ? ZK_OK : ZK_E_ARG);
     return ZK_OK;
 }
 // the statuses of (field, d, b) that a commitment, and every proof on it, need before the device check
@@ -106,10 +40,6 @@ int shape_check(int field, uint64_t d, uint32_t b) {
     if (!scalar_field(field) || d + b > two_adicity(field)) return ZK_E_RANGE;
     return ZK_OK;
 }
-void put_be32(uint8_t *out, uint32_t v) {
-    for (int k = 0; k < 4; k++) out[k] = (uint8_t)(v >> (24 - 8 * k));
-}
-
 // base^e, e < n, as ntt_pow2t reads them (pre times base^lo as 29-bit limbs, base^(4096 hi)): hi stays null when n <= 4096
 template <class F> struct PowTables {
     DevBuf buf;
@@ -193,10 +123,7 @@ template <class F> int launch_quotient(const zk_fri_commitment *const *cms, size
         gp = fe_mul<F>(gp, gamma);
         tb.cw[j] = cms[j]->codeword->dptr;
     }
-    UniMul<F> um;
-    unimul_from<F>(um, gamma);
-    FriUni g;
-    memcpy(g.t, um.t, sizeof g.t);
+    const FriUni g = fri_uni<F>(gamma);
     const Fe<F> z = load_host<F>(z64);
     const unsigned T = pick_batch(n);
     *batch = T;
@@ -265,15 +192,16 @@ template <class F> int open_any(const zk_fri_commitment *const *cms, size_t k, c
     zk_transcript fresh;
     zk_transcript *tt = t ? t : &fresh;
     const Fe<F> gamma = opening_challenge<F>(tt->t, k, roots.data(), z, o.ys);
-    TableGuard q;
-    ZK_TRY(table_alloc_pooled(c0->field, n, &q.t));
-    ZK_TRY((launch_quotient<F>(cms, k, z, o.ys, gamma, q.t, &st.batch)));
+    TableHolder hold;
+    zk_table *quot = nullptr;
+    ZK_TRY(hold.alloc(c0->field, n, &quot));
+    ZK_TRY((launch_quotient<F>(cms, k, z, o.ys, gamma, quot, &st.batch)));
     ZK_TRY(ev.mark(&e2));
 
     std::vector<uint64_t> idx_own;
     uint64_t *idx = o.query_indices;
     if (!idx) { idx_own.resize(Q); idx = idx_own.data(); }
-    ZK_TRY(zk_fri_prove_codeword(q.t, c0->b, f, Q, c0->has_coset ? c0->coset : nullptr, tt, o.roots, o.final_coeffs, o.betas, idx, o.query_values, o.query_paths));
+    ZK_TRY(zk_fri_prove_codeword(quot, c0->b, f, Q, c0->has_coset ? c0->coset : nullptr, tt, o.roots, o.final_coeffs, o.betas, idx, o.query_values, o.query_paths));
     ZK_TRY(ev.mark(&e3));
 
     PcsTrees tr{};
@@ -410,7 +338,7 @@ int zk_uni_evaluate_device(const zk_table *coeffs, const uint64_t *z, uint64_t *
     if (!is_pow2(coeffs->len)) return ZK_E_NOT_POW2;
     if (!scalar_field(coeffs->field) || ilog2(coeffs->len) > 32) return ZK_E_RANGE;
     ZK_TRY(require_device());
-    PCS_DISPATCH(coeffs->field, return evaluate_many<F>(&coeffs, 1, z, y));
+    FRI_DISPATCH(coeffs->field, return evaluate_many<F>(&coeffs, 1, z, y));
     return ZK_OK;
 }
 
@@ -425,7 +353,7 @@ int zk_fri_pcs_quotient(const zk_fri_commitment *const *cms, size_t k, const uin
     zk_fri_pcs_stats st{};
     st.polys = (uint32_t)k;
     int rc = ev.mark(&e0);
-    if (rc == ZK_OK) PCS_DISPATCH(cms[0]->field, rc = launch_quotient<F>(cms, k, z, ys, load_host<F>(gamma), o, &st.batch));
+    if (rc == ZK_OK) FRI_DISPATCH(cms[0]->field, rc = launch_quotient<F>(cms, k, z, ys, load_host<F>(gamma), o, &st.batch));
     if (rc == ZK_OK) rc = ev.mark(&e1);
     if (rc == ZK_OK && hipEventSynchronize(ev.ev[e1]) != hipSuccess) { set_last_error("zk_fri_pcs_quotient: the kernel failed"); rc = ZK_E_HIP; }
     if (rc != ZK_OK) { zk_table_free(o); return rc; }
@@ -444,7 +372,7 @@ int zk_fri_pcs_open(const zk_fri_commitment *const *cms, size_t k, const uint64_
     if (log_final >= cms[0]->d) return ZK_E_ARG;
     ZK_TRY(require_device());
     const OpenOut o{ys_out, roots, final_coeffs, betas, query_indices, query_values, query_paths, opened_values, opened_paths};
-    PCS_DISPATCH(cms[0]->field, return open_any<F>(cms, k, z, log_final, nqueries, t, o));
+    FRI_DISPATCH(cms[0]->field, return open_any<F>(cms, k, z, log_final, nqueries, t, o));
     return ZK_OK;
 }
 
@@ -458,11 +386,11 @@ int zk_fri_pcs_verify(int field, size_t k, const uint8_t *roots_of_f, uint32_t d
     ZK_TRY(shape_check(field, d, log_blowup));
     {                                                        // a point in the domain is refused; one that is not reduced is just no proof
         bool reduced = false;
-        PCS_DISPATCH(field, reduced = is_reduced<F>(z) && (!coset || is_reduced<F>(coset)));
+        FRI_DISPATCH(field, reduced = is_reduced<F>(z) && (!coset || is_reduced<F>(coset)));
         if (reduced) ZK_TRY(point_check(field, z, coset, d + log_blowup));
     }
     Transcript fresh;
-    PCS_DISPATCH(field, return verify_host<F>(k, roots_of_f, d, log_blowup, log_final, nqueries, coset, z, ys, t ? t->t : fresh, roots, final_coeffs,
+    FRI_DISPATCH(field, return verify_host<F>(k, roots_of_f, d, log_blowup, log_final, nqueries, coset, z, ys, t ? t->t : fresh, roots, final_coeffs,
                                                query_values, query_paths, opened_values, opened_paths, ok));
     return ZK_OK;
 }

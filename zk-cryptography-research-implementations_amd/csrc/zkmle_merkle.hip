@@ -5,11 +5,12 @@
 
 #include <vector>
 
-#include "context.h"
+#include "host_util.h"
 #include "merkle.cuh"
 #include "transcript.h"
 
 using namespace zk;
+using host::DevBuf;
 
 struct zk_merkle_tree {
     int field;
@@ -19,12 +20,6 @@ struct zk_merkle_tree {
 };
 
 namespace {
-
-struct DevBuf {   // RAII block of the caching pool
-    void *p = nullptr;
-    ~DevBuf() { pool_free(p); }
-    int alloc(size_t bytes) { return pool_alloc(bytes, &p); }
-};
 
 inline unsigned merkle_grid(size_t work) {
     size_t b = (work + kMerkleBlock - 1) / kMerkleBlock;

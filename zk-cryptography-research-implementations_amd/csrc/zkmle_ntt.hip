@@ -4,24 +4,14 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "context.h"
+#include "host_util.h"
 #include "ntt.cuh"
 
 using namespace zk;
+using host::DevBuf;
+using host::load_host;
 
 namespace {
-
-struct DevBuf {   // RAII block of the caching pool
-    void *p = nullptr;
-    ~DevBuf() { pool_free(p); }
-    int alloc(size_t bytes) { return pool_alloc(bytes, &p); }
-};
-
-template <class F> Fe<F> load_host(const uint64_t *src) {
-    Fe<F> e;
-    memcpy(e.l, src, sizeof(uint32_t) * F::N);
-    return e;
-}
 
 // w_{2^S} = g^t, t = (p - 1) >> S; -1 where S = 1
 template <class F> Fe<F> top_root() {
@@ -37,7 +27,7 @@ template <class F> Fe<F> top_root() {
     }
     return acc;
 }
-template <class F> Fe<F> root_of_unity(unsigned log_n) {                // log_n <= S
+template <class F> Fe<F> domain_root(unsigned log_n) {                  // w_{2^log_n}, log_n <= S
     static const Fe<F> top = top_root<F>();
     if (log_n == 0) return fe_one<F>();
     Fe<F> w = top;
@@ -90,7 +80,7 @@ template <class F> int ntt_run(const void *src, size_t src_len, void *dst, unsig
     const Plan pl = make_plan(log_n);
     unsigned tw_log = 0;
     for (unsigned d = 0; d < pl.ndig; d++) tw_log = pl.dig[d] > tw_log ? pl.dig[d] : tw_log;
-    Fe<F> wn = root_of_unity<F>(log_n);
+    Fe<F> wn = domain_root<F>(log_n);
     if (inverse) wn = fe_inv<F>(wn);
     const bool two = log_n > kNttLoBits;                                  // the powers need their second table
     const size_t lo_count = two ? (size_t)1 << kNttLoBits : n, hi_count = two ? n >> kNttLoBits : 0;
@@ -198,7 +188,7 @@ int zk_ntt_two_adicity(int field, uint32_t *s) {
 int zk_ntt_root_of_unity(int field, uint32_t log_n, uint64_t *omega) {
     if (!omega || field_limbs64(field) < 0) return ZK_E_ARG;
     if (log_n > two_adicity(field)) return ZK_E_RANGE;
-    ZK_DISPATCH_FIELD(field, { const Fe<F> w = root_of_unity<F>(log_n); memcpy(omega, w.l, 4 * F::N); });
+    ZK_DISPATCH_FIELD(field, { const Fe<F> w = domain_root<F>(log_n); memcpy(omega, w.l, 4 * F::N); });
     return ZK_OK;
 }
 int zk_ntt(zk_table *t, int inverse, const uint64_t *coset) {
