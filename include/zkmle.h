@@ -173,6 +173,21 @@ int zk_merkle_open(const zk_merkle_tree *m, const size_t *indices, size_t nidx, 
  * index >= 2^depth returns ZK_E_RANGE. */
 int zk_merkle_verify(int field, const uint8_t root32[32], size_t depth, size_t index, const uint64_t *element,
                      const uint8_t *path, int *ok);
+/* Merkle commitment with grouped leaves (csrc/merkle.cuh merkle_leaf_group_kernel).  For a table of len = 2^d elements of 32 bytes (the 48-byte
+ * field is ZK_E_ARG) and log_group = g in {1, 2}, with part = len >> g:
+ *   leaf_j = Keccak256(0x00 || bytes(e_j) || bytes(e_{j + part}) || .. || bytes(e_{j + (2^g - 1) part})),  j < part
+ * -- the 2^g entries a FRI fold of arity 2^g reads together -- 65 bytes for g = 1, 129 bytes for g = 2: with the pad's two bytes still inside
+ * the 136-byte rate, so a leaf over the group is the ONE permutation a leaf over one element is.  The pair leaf has a node's length but a
+ * leaf's tag.  Nodes and root are as above over `part` leaves: the tree has 2 part - 1 digests and depth d - g, and zk_merkle_open (indices
+ * below part), zk_merkle_root, zk_merkle_depth and zk_merkle_free work on it as they are.  log_group = 0 is zk_merkle_build /
+ * zk_mle_merkle_root.  ZK_E_ARG for NULL, log_group > 2, a field whose elements are not 32 bytes or len < 2^log_group, then ZK_E_NOT_POW2,
+ * all before the device is touched. */
+int zk_merkle_build_grouped(const zk_table *t, uint32_t log_group, zk_merkle_tree **out);
+int zk_mle_merkle_root_grouped(const zk_table *t, uint32_t log_group, uint8_t root32[32]);   /* root-only mode: scratch of 64 bytes x part */
+/* HOST only: *ok = 1 when the 2^log_group `elements` (Montgomery limbs, in the leaf's order) of leaf `index` hash up `path` (depth digests)
+ * to root32; an element that is not reduced gives *ok = 0.  log_group > 2 or a 48-byte field: ZK_E_ARG; index >= 2^depth: ZK_E_RANGE. */
+int zk_merkle_verify_grouped(int field, const uint8_t root32[32], size_t depth, size_t index, uint32_t log_group, const uint64_t *elements,
+                             const uint8_t *path, int *ok);
 
 /* ---- number-theoretic transform (extension: the reference's fft/ crate is empty; csrc/ntt.cuh) -------------------------------
  * The definition is arkworks' Radix2EvaluationDomain.  p - 1 = 2^s t with t odd, g the field's multiplicative generator (7 for
@@ -288,6 +303,14 @@ int zk_fri_commitment_free(zk_fri_commitment *cm);
 int zk_fri_commitment_root(const zk_fri_commitment *cm, uint8_t root32[32]);                 /* host copy, no device work */
 /* the N evaluations f(c w^i): a BORROWED table that lives as long as the commitment (do not free it) */
 int zk_fri_commitment_codeword(const zk_fri_commitment *cm, const zk_table **out);
+/* The same commitment with its tree over grouped leaves.  log_group = 2: root = zk_mle_merkle_root_grouped(codeword, 2), a leaf per coset
+ * {f[j], f[j + N/4], f[j + N/2], f[j + 3N/4]} of the first fold by 4, 2 (N / 4) - 1 digests (16 bytes x N); coefficients and codeword are
+ * zk_fri_commit's.  log_group = 0 is zk_fri_commit byte for byte; anything else is ZK_E_ARG.  Such a commitment is opened by
+ * zk_fri_ml_open_points_grouped only: zk_fri_pcs_open, zk_fri_ml_open, zk_fri_ml_open_points, zk_fri_ml_open_points_arity,
+ * zk_sumcheck_basic_prove_succinct and zk_gkr_sparse_prove_succinct return ZK_E_ARG for it before any device work; zk_fri_pcs_quotient and
+ * the root and codeword accessors do not read the tree and work as before. */
+int zk_fri_commit_grouped(const zk_table *coeffs, uint32_t log_blowup, const uint64_t *coset, uint32_t log_group, zk_fri_commitment **out);
+uint32_t zk_fri_commitment_log_group(const zk_fri_commitment *cm);                            /* 0 for NULL */
 /* host: zk_fri_proof_sizes' four counts plus nopened = Q 2 k elements and opened_path_bytes = Q 2 k L 32; any pointer may be NULL */
 int zk_fri_pcs_sizes(uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots, size_t *nfinal,
                      size_t *nvalues, size_t *path_bytes, size_t *nopened, size_t *opened_path_bytes);
@@ -475,6 +498,35 @@ int zk_fri_ml_verify_points_arity(int field, const uint8_t *root32, uint32_t d, 
                                   uint32_t log_arity, const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys,
                                   zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table,
                                   const uint64_t *query_values, const uint8_t *query_paths, int *ok);
+/* ---- FRI commitment opened with grouped leaves (extension; csrc/merkle.cuh merkle_leaf_group_kernel, csrc/zkmle_fri_ml.hip) ---------------------
+ * The opening with a fold arity at a = 2 in which every tree has ONE leaf per fold coset: a layer of n entries costs 2 (n / 4) - 1 permutations
+ * instead of 2 n - 1, and a query one path of log n - 2 digests per step instead of four of log n.  It is "FRI commitment opened with a fold
+ * arity" at a = 2 with these differences and no others:
+ *   Commitment.  zk_fri_commit_grouped(.., log_group = 2); any other commitment is ZK_E_ARG.
+ *   Transcript.  Step 2 appends 8 bytes: a = 2 as a big-endian u32, then the u32 1 (domain separation from the ungrouped protocol).  The header,
+ *     root_0, P, the points, the claims, gamma, the rounds, the roots' positions, T_R and the Q indices mod N / 4 are unchanged.
+ *   Leaves.  Every committed layer f_l is hashed with leaves grouped by the sides of the step that starts there: root_l =
+ *     zk_mle_merkle_root_grouped(f_l, 2) for a fold-4 step and (f_l, 1) for the final fold-2 step at l = R - 1 when R is odd -- a pair leaf.
+ *     Layer 0 always starts a fold-4 step (R >= 2).
+ *   Answers.  The values as before: per query, per step, per side.  The paths: per query and step ONE path of L - l - log_sides digests, that
+ *     of leaf j = i_q mod (N_l >> log_sides), the leaf's sibling first.
+ *   Counts (zk_fri_ml_sizes_grouped).  nroots, nfinal, nvalues and nround are the arity's; path_bytes = 32 Q sum over the steps of
+ *     (L - l - log_sides).  d = 24, b = 2, f = 6: 144 digests a query, where a = 1 has 630 and a = 2 ungrouped 648.
+ *   Verifier (HOST only).  fri_verify_core with FriMlClaim extended by a flag, not a copy: per step it hashes the 2^log_sides opened values
+ *     into the leaf (zk_merkle_verify_grouped), climbs the one path and compares with the step's root; the fold and sumcheck checks are unchanged.
+ *   Prover.  The pool block is 32 bytes x (3 n + C + 2 G + P n) and a little: C as before (below N / 3), G = the leaves of the committed layers
+ *     below R together, below C / 4 + 1 -- where the ungrouped block has 3 C.
+ * Statuses are zk_fri_ml_open_points_arity's and zk_fri_ml_verify_points_arity's at log_arity = 2.  zk_fri_ml_last_stats reports this call too. */
+int zk_fri_ml_sizes_grouped(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots, size_t *nfinal, size_t *nvalues,
+                            size_t *path_bytes, size_t *nround);
+int zk_fri_ml_open_points_grouped(const zk_fri_commitment *cm, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                                  zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots,
+                                  uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values,
+                                  uint8_t *query_paths);
+int zk_fri_ml_verify_points_grouped(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
+                                    const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys, zk_transcript *t,
+                                    const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
+                                    const uint8_t *query_paths, int *ok);
 /* The basic sumcheck finished by a verifier who holds 32 bytes.  Prover::prove (prover.rs:35-71) with one change, as
  * zk_sumcheck_basic_prove_committed: the first append (:38-39) is the COMMITMENT's root (zk_fri_commitment_root: the root of the codeword of
  * the table, not zk_mle_merkle_root of the table).  The rounds run on the commitment's device table, which is only read; then

@@ -139,6 +139,22 @@ pub mod ffi {
         pub fn zk_merkle_root(m: *const c_void, root32: *mut u8) -> c_int;
         pub fn zk_merkle_open(m: *const c_void, indices: *const usize, nidx: usize, paths: *mut u8) -> c_int;
         pub fn zk_merkle_verify(field: c_int, root32: *const u8, depth: usize, index: usize, element: *const u64, path: *const u8, ok: *mut c_int) -> c_int;
+        // grouped leaves: a leaf per fold coset (include/zkmle.h "Merkle commitment with grouped leaves", "FRI commitment opened with grouped leaves")
+        pub fn zk_merkle_build_grouped(t: *const zk_table, log_group: u32, out: *mut *mut c_void) -> c_int;
+        pub fn zk_mle_merkle_root_grouped(t: *const zk_table, log_group: u32, root32: *mut u8) -> c_int;
+        pub fn zk_merkle_verify_grouped(field: c_int, root32: *const u8, depth: usize, index: usize, log_group: u32, elements: *const u64, path: *const u8,
+                                        ok: *mut c_int) -> c_int;
+        pub fn zk_fri_commit_grouped(coeffs: *const zk_table, log_blowup: u32, coset: *const u64, log_group: u32, out: *mut *mut c_void) -> c_int;
+        pub fn zk_fri_commitment_log_group(cm: *const c_void) -> u32;
+        pub fn zk_fri_ml_sizes_grouped(d: u32, log_blowup: u32, log_final: u32, nqueries: u32, nroots: *mut usize, nfinal: *mut usize, nvalues: *mut usize,
+                                       path_bytes: *mut usize, nround: *mut usize) -> c_int;
+        pub fn zk_fri_ml_open_points_grouped(cm: *const c_void, points: *const u64, npoints: u32, log_final: u32, nqueries: u32, t: *mut zk_transcript,
+                                             ys_out: *mut u64, gamma_out: *mut u64, round_polys: *mut u64, roots: *mut u8, final_table: *mut u64,
+                                             challenges: *mut u64, query_indices: *mut u64, query_values: *mut u64, query_paths: *mut u8) -> c_int;
+        pub fn zk_fri_ml_verify_points_grouped(field: c_int, root32: *const u8, d: u32, log_blowup: u32, log_final: u32, nqueries: u32, coset: *const u64,
+                                               points: *const u64, npoints: u32, ys: *const u64, t: *mut zk_transcript, round_polys: *const u64,
+                                               roots: *const u8, final_table: *const u64, query_values: *const u64, query_paths: *const u8,
+                                               ok: *mut c_int) -> c_int;
         pub fn zk_sumcheck_basic_prove_committed(t: *const zk_table, transcript: *mut zk_transcript, root32: *mut u8, claimed: *mut u64, rounds: *mut u64,
                                                  challenges: *mut u64) -> c_int;
         pub fn zk_sumcheck_basic_verify_committed(t: *const zk_table, root32: *const u8, claimed: *const u64, rounds: *const u64, nrounds: usize,

@@ -54,6 +54,7 @@ def lib():
     L.zk_table_len.restype = sz
     L.zk_table_device_ptr.restype = vp
     L.zk_merkle_depth.restype = sz
+    L.zk_fri_commitment_log_group.restype = C.c_uint32
     sigs = {
         "zk_device_count": [C.POINTER(C.c_int)],
         "zk_init": [C.c_int],
@@ -100,6 +101,9 @@ def lib():
         "zk_merkle_root": [vp, u8p],
         "zk_merkle_open": [vp, C.POINTER(sz), sz, u8p],
         "zk_merkle_verify": [C.c_int, u8p, sz, sz, u64p, u8p, C.POINTER(C.c_int)],
+        "zk_merkle_build_grouped": [vp, C.c_uint32, C.POINTER(vp)],
+        "zk_mle_merkle_root_grouped": [vp, C.c_uint32, u8p],
+        "zk_merkle_verify_grouped": [C.c_int, u8p, sz, sz, C.c_uint32, u64p, u8p, C.POINTER(C.c_int)],
         # number-theoretic transform (extension)
         "zk_ntt_two_adicity": [C.c_int, C.POINTER(C.c_uint32)],
         "zk_ntt_root_of_unity": [C.c_int, C.c_uint32, u64p],
@@ -116,6 +120,8 @@ def lib():
         "zk_fri_last_stats": [vp],
         # FRI polynomial commitment: opening at a point (extension)
         "zk_fri_commit": [vp, C.c_uint32, u64p, C.POINTER(vp)],
+        "zk_fri_commit_grouped": [vp, C.c_uint32, u64p, C.c_uint32, C.POINTER(vp)],
+        "zk_fri_commitment_log_group": [vp],
         "zk_fri_commitment_free": [vp],
         "zk_fri_commitment_root": [vp, u8p],
         "zk_fri_commitment_codeword": [vp, C.POINTER(vp)],
@@ -140,6 +146,11 @@ def lib():
         "zk_fri_ml_open_points_arity": [vp, u64p] + [C.c_uint32] * 4 + [vp, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_fri_ml_verify_points_arity": [C.c_int, u8p] + [C.c_uint32] * 5 + [u64p, u64p, C.c_uint32, u64p, vp, u64p, u8p, u64p, u64p, u8p,
                                                                              C.POINTER(C.c_int)],
+        # ... with grouped leaves
+        "zk_fri_ml_sizes_grouped": [C.c_uint32] * 4 + [C.POINTER(sz)] * 5,
+        "zk_fri_ml_open_points_grouped": [vp, u64p] + [C.c_uint32] * 3 + [vp, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
+        "zk_fri_ml_verify_points_grouped": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, u64p, C.c_uint32, u64p, vp, u64p, u8p, u64p, u64p, u8p,
+                                                                               C.POINTER(C.c_int)],
         "zk_sumcheck_basic_prove_succinct": [vp, C.c_uint32, C.c_uint32, vp, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_sumcheck_basic_verify_succinct": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, vp, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u8p,
                                                                                  C.POINTER(C.c_int)],
@@ -147,7 +158,7 @@ def lib():
     for name, args in sigs.items():
         fn = getattr(L, name)       # AttributeError = missing export: loud
         fn.argtypes = args
-        if name not in ("zk_table_len", "zk_table_device_ptr", "zk_merkle_depth"):
+        if name not in ("zk_table_len", "zk_table_device_ptr", "zk_merkle_depth", "zk_fri_commitment_log_group"):
             fn.restype = C.c_int
     _lib = L
     return L

@@ -85,8 +85,9 @@ struct zk_fri_commitment {
     bool has_coset;
     uint64_t coset[4];
     zk_table *coeffs, *codeword;     // long-lived tables of their own (zk_table_clone, zk_table_alloc)
-    uint64_t *levels;                // 2 N - 1 digests (hipMalloc), zk_merkle_build's layout
+    uint64_t *levels;                // 2 N - 1 digests (hipMalloc), zk_merkle_build's layout; log_group != 0: 2 (N >> log_group) - 1, zk_merkle_build_grouped's
     uint8_t root[32];
+    unsigned log_group;              // 0, or 2: a leaf per coset of the first fold by 4 (zk_fri_commit_grouped).  Who walks `levels` as 2 N - 1 digests refuses the latter
 };
 
 namespace zk {
@@ -99,6 +100,9 @@ int merkle_root_device(const zk_table *t, uint8_t root32[32]);
 // every level of the table's tree into the caller's device block of 2 len - 1 digests, laid out as zk_merkle_build's; launches only, no
 // checks (the FRI prover: one block for the trees of all its layers)
 int merkle_levels_device(const zk_table *t, uint64_t *levels);
+// the same with grouped leaves (merkle.cuh; log_group <= 2, 32-byte elements, len >= 2^log_group): 2 (len >> log_group) - 1 digests, zk_merkle_build_grouped's
+// layout; launches only, no checks.  log_group = 0 is merkle_levels_device
+int merkle_levels_grouped_device(const zk_table *t, unsigned log_group, uint64_t *levels);
 // zk_uni_low_degree_extend into a table the caller allocated (out->len = coeffs->len << log_blowup); launches only, no checks (zkmle_ntt.hip)
 int ntt_extend_into(const zk_table *coeffs, const uint64_t *coset, zk_table *out);
 // zk_fri_verify's checks and body on a caller's Transcript; indices_out (nqueries words, may be null) receives the sampled query indices
@@ -113,6 +117,7 @@ struct FriMlClaim {
     const uint64_t *z, *y, *round_polys;                     // d elements, one element, R x 3 elements
     uint32_t npoints = 0;
     uint32_t log_arity = 1;                                  // 2: the opening folded by 4 (include/zkmle.h "... opened with a fold arity"); needs npoints >= 1
+    uint32_t grouped = 0;                                    // 1: every layer's leaves hold a step's sides ("... with grouped leaves"); needs log_arity = 2
 };
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,

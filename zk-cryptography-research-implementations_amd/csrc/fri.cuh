@@ -90,12 +90,14 @@ template <class F> __global__ void __launch_bounds__(kFriBlock) fri_fold_kernel(
 // `wide` != 0 (the multilinear opening folded by 4, fri_ml.cuh): the nlayers entries are STEPS; step s opens 2^log_sides[s] entries of a
 // layer of 2^log_len[s] entries, a part = len >> log_sides apart; val_off[s] = values of one query's answer before step s, path_off[s] its
 // digests (2^log_sides paths of log_len digests per step).  wide == 0: step s is layer s with two sides and the three arrays are not read.
+// `grouped` != 0 (needs wide): step s's tree has len >> log_sides leaves, leaf j over the step's sides (merkle_leaf_group_kernel), and the
+// answer holds ONE path of log_len - log_sides digests per step.
 struct FriLayers {
     const void *table[kFriMaxLayers];
     const uint64_t *tree[kFriMaxLayers];
     uint32_t path_off[kFriMaxLayers + 1];
     uint32_t log_len0, nlayers;
-    uint32_t wide;
+    uint32_t wide, grouped;
     uint32_t val_off[kFriMaxLayers + 1];
     uint8_t log_len[kFriMaxLayers], log_sides[kFriMaxLayers];
 };
@@ -121,7 +123,8 @@ template <class F> __global__ void __launch_bounds__(kFriBlock) fri_query_values
 }
 
 // every authentication path with one launch (merkle_open_kernel over the layers): per query and layer the low entry's path, then the
-// high entry's, log_len0 - l digests each, the leaf's sibling first; wide: per step the 2^log_sides paths in the order of the sides
+// high entry's, log_len0 - l digests each, the leaf's sibling first; wide: per step the 2^log_sides paths in the order of the sides;
+// grouped: per step the one path of leaf j = i_q mod part in the tree of `part` leaves
 static __global__ void __launch_bounds__(kFriBlock) fri_query_paths_kernel(FriLayers a, const uint64_t *__restrict__ indices, size_t nq, uint64_t *__restrict__ paths) {
     const uint32_t per = a.path_off[a.nlayers];
     const size_t total = nq * per, stride = (size_t)gridDim.x * kFriBlock;
@@ -130,6 +133,16 @@ static __global__ void __launch_bounds__(kFriBlock) fri_query_paths_kernel(FriLa
         const uint32_t r = (uint32_t)(t % per);
         unsigned l = 0;
         while (l + 1 < a.nlayers && a.path_off[l + 1] <= r) l++;
+        if (a.grouped) {
+            const size_t part = ((size_t)1 << a.log_len[l]) >> a.log_sides[l];
+            const unsigned v = r - a.path_off[l];
+            const uint4 *src = reinterpret_cast<const uint4 *>(a.tree[l]) + 2 * (2 * part - ((2 * part) >> v) + (((indices[q] & (part - 1)) >> v) ^ 1));
+            uint4 *dst = reinterpret_cast<uint4 *>(paths) + 2 * t;
+            const uint4 d0 = src[0], d1 = src[1];
+            dst[0] = d0;
+            dst[1] = d1;
+            continue;
+        }
         const unsigned depth = a.wide ? a.log_len[l] : a.log_len0 - l, side = (r - a.path_off[l]) / depth, v = (r - a.path_off[l]) % depth;
         const size_t len = (size_t)1 << depth, part = len >> (a.wide ? a.log_sides[l] : 1);
         const size_t pos = (indices[q] & (part - 1)) + side * part;

@@ -94,23 +94,27 @@ inline uint64_t sample_index(Transcript &tr, unsigned bits) {
 // verifier.  log_arity 1: a step per layer l < R, two sides.  2 (R >= 2): a step per even layer, four sides where layer l + 2 <= R exists
 // (a fold by 4), else (R odd, l = R - 1) two (the fold by 2 to layer R).  A step's sides are its layer's entries j + side (len >> log_sides),
 // j = i_q mod (len >> log_sides); one query's answer holds the steps' values, and their paths of log_len digests, one after the other.
+// `grouped` (log_arity 2 only): every layer's tree has a leaf per j over the step's sides (merkle.cuh), so a step has ONE path, of
+// log_len - log_sides digests.
 struct FriStep {
     unsigned layer, log_len, log_sides, root;                 // the layer opened, its log2 length, of its sides, the index of its root
     size_t val_off, path_off;                                 // values and digests of one query's answer before this step
 };
 struct FriSchedule {
     unsigned log_arity, nsteps = 0;
+    bool grouped;
     size_t nvalues = 0, ndigests = 0;                         // of one query's answer
     FriStep step[kFriMaxLayers];
-    FriSchedule(unsigned L, unsigned R, unsigned log_arity_) : log_arity(log_arity_) {
+    FriSchedule(unsigned L, unsigned R, unsigned log_arity_, bool grouped_ = false) : log_arity(log_arity_), grouped(grouped_) {
         for (unsigned l = 0; l < R; l += log_arity) {
             const unsigned ls = l + log_arity <= R ? log_arity : 1;
             step[nsteps] = FriStep{l, L - l, ls, nsteps, nvalues, ndigests};
             nvalues += (size_t)1 << ls;
-            ndigests += ((size_t)L - l) << ls;
+            ndigests += grouped ? (size_t)L - l - ls : ((size_t)L - l) << ls;
             nsteps++;
         }
     }
+    unsigned leaf_group(unsigned s) const { return grouped ? step[s].log_sides : 0; }   // the log_group of step s's tree
     unsigned index_bits() const { return step[0].log_len - log_arity; }   // every i_q is a position of the first step's part
     // the gather kernels' view; the caller adds each step's table and tree.  wide stays 0 at arity 1: its three arrays are not read then
     FriLayers layers() const {
@@ -118,6 +122,7 @@ struct FriSchedule {
         fl.log_len0 = step[0].log_len;
         fl.nlayers = nsteps;
         fl.wide = log_arity == 2;
+        fl.grouped = grouped;
         for (unsigned s = 0; s < nsteps; s++) {
             fl.path_off[s] = (uint32_t)step[s].path_off;
             if (!fl.wide) continue;

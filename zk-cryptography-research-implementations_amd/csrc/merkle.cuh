@@ -4,7 +4,12 @@
 //   node   = Keccak256(0x01 || left || right)      node j of level l + 1 hashes nodes 2j, 2j + 1 of level l; level 0 = the leaves
 //   root   = the single node of level log2(len); a one-entry table's root is leaf_0
 //
-// Keccak-256 is the transcript's (transcript.h): rate 136, original pad 0x01 .. 0x80.  Every input is 33, 49 or 65 bytes: one block, one
+// GROUPED leaves (include/zkmle.h "Merkle commitment with grouped leaves"; 32-byte elements only): with part = len >> LG, LG = 1 or 2,
+//   leaf_j = Keccak256(0x00 || bytes(e_j) || bytes(e_{j+part}) || .. )    the 2^LG entries a FRI fold of arity 2^LG reads together, j < part
+// and the nodes above are the same over `part` leaves.  The pair leaf (LG = 1, 65 bytes) has a NODE's length but a LEAF's tag: the tag byte
+// alone tells it from a node.  The quad leaf is 129 bytes, 131 with the pad's two bytes: still inside the 136-byte rate.
+//
+// Keccak-256 is the transcript's (transcript.h): rate 136, original pad 0x01 .. 0x80.  Every input is 33, 49, 65 or 129 bytes: one block, one
 // permutation per hash.  The permutation here keeps the 25 lanes of ONE sponge in the VGPRs of ONE GPU lane, all 24 rounds unrolled
 // (round constants and rotation counts become immediates): 64 independent hashes per wave, no LDS, no cross-lane traffic.  The
 // wave-per-sponge permutation of dev_transcript.cuh is the other shape -- one sequential sponge, as fast as it can go -- and stays.
@@ -57,8 +62,10 @@ __device__ __forceinline__ void keccak_f1600_lane(uint64_t (&a)[25]) {
 }
 
 // The padded block of a message of 1 + 8 NW bytes: the tag byte, then the NW words of `s` as they lie in memory (NW = 4 or 6: a leaf's
-// big-endian element; NW = 8: two digests).  Everything after the pad is zero but the rate's last byte.
+// big-endian element; NW = 8: two digests or a pair leaf; NW = 16: a quad leaf, whose pad starts in the rate's last word).  Everything after
+// the pad is zero but the rate's last byte.
 template <int NW> __device__ __forceinline__ void merkle_block(uint64_t (&a)[25], uint64_t tag, const uint64_t (&s)[NW]) {
+    static_assert(NW <= 16, "the message and its first pad byte must fit the rate of 17 words");
     a[0] = tag | (s[0] << 8);
 #pragma unroll
     for (int j = 1; j < NW; j++) a[j] = (s[j - 1] >> 56) | (s[j] << 8);
@@ -68,14 +75,18 @@ template <int NW> __device__ __forceinline__ void merkle_block(uint64_t (&a)[25]
     a[16] ^= (uint64_t)0x80 << 56;
 }
 
-// element (Montgomery) -> canonical big-endian bytes, as OP_TO_CANONICAL_BE (mle_kernels.cuh) does, into the leaf's block
+// element (Montgomery) -> canonical big-endian bytes, as OP_TO_CANONICAL_BE (mle_kernels.cuh) does: F::N / 2 words at s
+template <class F> __device__ __forceinline__ void merkle_be_words(uint64_t *s, const Fe<F> &x) {
+    const Fe<F> c = fe_to_canonical<F>(x);                                          // into_bigint()
+#pragma unroll
+    for (int t = 0; t < F::N / 2; t++)                                              // to_bytes_be(): word t = bytes 8 t .. 8 t + 7
+        s[t] = (uint64_t)__builtin_bswap32(c.l[F::N - 1 - 2 * t]) | ((uint64_t)__builtin_bswap32(c.l[F::N - 2 - 2 * t]) << 32);
+}
+// ... into the leaf's block
 template <class F> __device__ __forceinline__ void merkle_leaf_block(uint64_t (&a)[25], const Fe<F> &x) {
     constexpr int NW = F::N / 2;
-    const Fe<F> c = fe_to_canonical<F>(x);                                          // into_bigint()
     uint64_t s[NW];
-#pragma unroll
-    for (int t = 0; t < NW; t++)                                                    // to_bytes_be(): word t = bytes 8 t .. 8 t + 7
-        s[t] = (uint64_t)__builtin_bswap32(c.l[F::N - 1 - 2 * t]) | ((uint64_t)__builtin_bswap32(c.l[F::N - 2 - 2 * t]) << 32);
+    merkle_be_words<F>(s, x);
     merkle_block<NW>(a, 0x00, s);
 }
 __device__ __forceinline__ void merkle_node_block(uint64_t (&a)[25], const Digest &l, const Digest &r) {
@@ -104,6 +115,23 @@ template <class F> __global__ void __launch_bounds__(kMerkleBlock) merkle_leaf_k
         merkle_leaf_block<F>(a, fe_load<F>(table, i));
         keccak_f1600_lane(a);
         digest_store(out, i, merkle_digest_of(a));
+    }
+}
+
+// level 0 with grouped leaves: one lane per leaf j < part = len >> LG, which reads e[j + s part], s < 2^LG -- across a wave each of the 2^LG
+// strided streams is coalesced -- and hashes them as ONE block: the permutation a single-element leaf costs
+template <class F, int LG> __global__ void __launch_bounds__(kMerkleBlock) merkle_leaf_group_kernel(const void *__restrict__ table, size_t part,
+                                                                                                   uint64_t *__restrict__ out) {
+    static_assert(F::N == 8 && (LG == 1 || LG == 2), "32-byte elements, two or four to a leaf");
+    constexpr int G = 1 << LG;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < part; j += stride) {
+        uint64_t s[4 * G], a[25];
+#pragma unroll
+        for (int g = 0; g < G; g++) merkle_be_words<F>(s + 4 * g, fe_load<F>(table, j + (size_t)g * part));
+        merkle_block<4 * G>(a, 0x00, s);
+        keccak_f1600_lane(a);
+        digest_store(out, j, merkle_digest_of(a));
     }
 }
 

@@ -173,12 +173,13 @@ template <class F> Replayed<F> replay(uint32_t d, uint32_t b, uint32_t f, uint32
         tr.append_be<F>(e);
         return e;
     };
-    uint8_t cbe[32], be[4];
+    uint8_t cbe[32], be[8];
     host_to_bytes_be<F>(coset ? load_host<F>(coset) : fe_one<F>(), cbe);
     transcript_header(tr, d, b, f, Q, cbe);
-    if (sc.log_arity == 2) {
+    if (sc.log_arity == 2) {                                 // the arity, and behind it a 1 when the leaves are grouped
         put_be32(be, sc.log_arity);
-        tr.append(be, 4);
+        put_be32(be + 4, 1);
+        tr.append(be, sc.grouped ? 8 : 4);
     }
     tr.append(roots, 32);
     if (ml && ml->npoints == 0) {                            // z_0 .. z_{d-1}, then y
@@ -242,7 +243,7 @@ template <class F> bool sumcheck_holds(uint32_t d, uint32_t f, const FriMlClaim 
     return fe_eq<F>(end, claim);
 }
 
-// every query: its steps' paths, and each step's fold against the next step's value (the last against the final polynomial).  `lagrange`: the
+// every query: its steps' paths (grouped: each step's one path from the leaf over its sides), and each step's fold against the next step's value (the last against the final polynomial).  `lagrange`: the
 // fold of the multilinear forms, (1 - r) (a + b) / 2 + r (a - b) / (2 x); else the monomial (a + b) / 2 + r (a - b) / (2 x)
 template <class F> int queries_hold(const FriSchedule &sc, unsigned R, bool lagrange, const Fe<F> &c, const Replayed<F> &rp, const uint8_t *roots,
                                     const uint64_t *values, const uint8_t *paths, int *ok) {
@@ -271,10 +272,17 @@ template <class F> int queries_hold(const FriSchedule &sc, unsigned R, bool lagr
             const size_t part = ((size_t)1 << st.log_len) >> st.log_sides, j = rp.idx[q] & (part - 1);
             const uint64_t *v = vq + st.val_off * W;
             Fe<F> e[4];
-            for (unsigned side = 0; side < sides; side++) {
+            if (sc.grouped) {                                 // one leaf over the step's sides, one path
                 int ok_s = 0;
-                ZK_TRY(zk_merkle_verify(F::ID, roots + 32 * st.root, st.log_len, j + side * part, v + (size_t)side * W,
-                                        pq + 32 * (st.path_off + (size_t)side * st.log_len), &ok_s));
+                ZK_TRY(zk_merkle_verify_grouped(F::ID, roots + 32 * st.root, st.log_len - st.log_sides, j, st.log_sides, v, pq + 32 * st.path_off, &ok_s));
+                if (!ok_s) return ZK_OK;
+            }
+            for (unsigned side = 0; side < sides; side++) {
+                int ok_s = sc.grouped;
+                if (!sc.grouped) {
+                    ZK_TRY(zk_merkle_verify(F::ID, roots + 32 * st.root, st.log_len, j + side * part, v + (size_t)side * W,
+                                            pq + 32 * (st.path_off + (size_t)side * st.log_len), &ok_s));
+                }
                 if (!ok_s) return ZK_OK;
                 e[side] = load_host<F>(v + (size_t)side * W);
             }
@@ -298,7 +306,7 @@ template <class F> int queries_hold(const FriSchedule &sc, unsigned R, bool lagr
 template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t Q, const uint64_t *coset, Transcript &tr, const uint8_t *roots,
                                    const uint64_t *final_coeffs, const uint64_t *values, const uint8_t *paths, int *ok, uint64_t *indices_out,
                                    const FriMlClaim *ml) {
-    const FriSchedule sc(d + b, d - f, ml ? ml->log_arity : 1);
+    const FriSchedule sc(d + b, d - f, ml ? ml->log_arity : 1, ml && ml->grouped);
     Replayed<F> rp = replay<F>(d, b, f, Q, coset, tr, sc, roots, final_coeffs, ml);
     if (indices_out) memcpy(indices_out, rp.idx.data(), Q * 8);
     *ok = 0;
@@ -315,6 +323,7 @@ int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_fin
                     uint64_t *indices_out, const FriMlClaim *ml) {
     if (ml && (!ml->z || !ml->y || !ml->round_polys || ml->npoints > 8)) return ZK_E_ARG;
     if (ml && (ml->log_arity < 1 || ml->log_arity > 2 || (ml->log_arity == 2 && (ml->npoints < 1 || log_final >= d || d - log_final < 2)))) return ZK_E_ARG;
+    if (ml && ml->grouped && ml->log_arity != 2) return ZK_E_ARG;
     if (!roots || !final_coeffs || !query_values || !query_paths || !ok || field_limbs64(field) < 0) return ZK_E_ARG;
     ZK_TRY(params_check(log_blowup, nqueries));
     if (coset && is_zero_element(field, coset)) return ZK_E_ARG;

@@ -248,7 +248,9 @@ template <class F> struct ManyPoints {
 // The opening: the sumcheck's rounds interleaved with the folds of the codeword, on the same challenges.  la = log_arity.  1: every layer
 // f_1 .. f_{R-1} is committed.  2 (R >= 2): the even ones are; after r_l with l even only round l + 1's pass runs, after r_{l+1} the fold by 4
 // f_l -> f_{l+2}, its tree and round l + 2's pass.  One host synchronisation per round either way.  A layer that is not committed is never built.
-template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &form, uint32_t f, uint32_t Q, unsigned la, Transcript &tr, const OpenOut &o) {
+// `grouped` (la = 2, a commitment with log_group = 2): every layer's leaves hold the sides of the step that starts there, so its tree is a quarter
+// (the final fold-2 step's: half) as large and a step opens one path.
+template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &form, uint32_t f, uint32_t Q, unsigned la, bool grouped, Transcript &tr, const OpenOut &o) {
     constexpr size_t ESZ = sizeof(Fe<F>);
     constexpr int W = F::N / 2;
     constexpr unsigned K = Form::kSums;
@@ -256,29 +258,33 @@ template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &
     const unsigned d = cm->d, b = cm->b, L = d + b, R = d - f;
     const size_t n = (size_t)1 << d, N = (size_t)1 << L, m = (size_t)1 << f;
     const Fe<F> one = fe_one<F>(), c = cm->has_coset ? load_host<F>(cm->coset) : one;
-    const FriSchedule sc(L, R, la);
+    const FriSchedule sc(L, R, la, grouped);
 
     // the header, (the arity when it is not 1,) root_0, the form's claim
-    uint8_t cbe[32], abe[4];
+    uint8_t cbe[32], abe[8];
     host_to_bytes_be<F>(c, cbe);
     transcript_header(tr, d, b, f, Q, cbe);
     if (la == 2) {
         put_be32(abe, la);
-        tr.append(abe, 4);
+        put_be32(abe + 4, 1);
+        tr.append(abe, grouped ? 8 : 4);
     }
     memcpy(o.roots, cm->root, 32);
     tr.append(cm->root, 32);
     form.absorb(tr);
 
     // one block: T_1 .. T_R (below n elements), the form's weights, the committed layers below R (C = their N >> l entries together: below N
-    // for la = 1, below N / 3 for la = 2), their trees (2 C digests), the workgroups' partial sums and the K sums
+    // for la = 1, below N / 3 for la = 2), their trees (2 G digests: G = C, or grouped the layers' leaves together, below C / 4 + 1), the
+    // workgroups' partial sums and the K sums
     const size_t cap = (size_t)reduce_block_cap();
-    size_t f_off[kFriMaxLayers] = {0}, C = 0;                 // of step s's layer, in entries from off_f; its tree at twice that from off_tree
+    size_t f_off[kFriMaxLayers] = {0}, t_off[kFriMaxLayers] = {0}, C = 0, G = 0;   // of step s's layer, in entries from off_f; of its tree, in digests from off_tree
     for (unsigned s = 1; s < sc.nsteps; s++) {
         f_off[s] = C;
+        t_off[s] = 2 * G;
         C += N >> sc.step[s].layer;
+        G += (N >> sc.step[s].layer) >> sc.leaf_group(s);
     }
-    const size_t off_w = n, off_f = off_w + form.weight_room(n), off_tree = off_f + C, off_part = off_tree + 2 * C, total = off_part + K * cap + K;   // in elements (a digest is 32 bytes too)
+    const size_t off_w = n, off_f = off_w + form.weight_room(n), off_tree = off_f + C, off_part = off_tree + 2 * G, total = off_part + K * cap + K;   // in elements (a digest is 32 bytes too)
     static_assert(ESZ == 32, "the block is laid out in 32-byte units");
     DevBuf blk;
     ZK_TRY(blk.alloc(total * ESZ));
@@ -286,7 +292,7 @@ template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &
     auto T_at = [&](unsigned l) -> void * { return l == 0 ? cm->coeffs->dptr : base + (n - (n >> (l - 1))) * ESZ; };          // n >> l entries
     auto w_at = [&](unsigned l) -> void * { return base + (off_w + form.weight_off(n, l)) * ESZ; };
     auto f_at = [&](unsigned s) -> void * { return s == 0 ? cm->codeword->dptr : base + (off_f + f_off[s]) * ESZ; };          // step s's layer
-    auto tree_at = [&](unsigned s) -> uint64_t * { return s == 0 ? cm->levels : (uint64_t *)(base + (off_tree + 2 * f_off[s]) * ESZ); };   // twice its length in digests of room
+    auto tree_at = [&](unsigned s) -> uint64_t * { return s == 0 ? cm->levels : (uint64_t *)(base + (off_tree + t_off[s]) * ESZ); };   // twice its leaves in digests of room
     const PassMem mem{cm->coeffs->dptr, base + off_w * ESZ, base + off_part * ESZ, base + (off_part + K * cap) * ESZ};
 
     Events ev;
@@ -344,11 +350,11 @@ template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &
             ZK_TRY(ev.mark(&tb_[l]));
             if (commit) {
                 const zk_table layer{cm->field, len, f_at(s + 1), 0};
-                ZK_TRY(merkle_levels_device(&layer, tree));
+                ZK_TRY(merkle_levels_grouped_device(&layer, sc.leaf_group(s + 1), tree));
             }
             ZK_TRY(ev.mark(&tc[l]));
             ZK_TRY(Form::pass(true, T_at(l), w_at(l), T_at(l + 1), w_at(l + 1), n >> (l + 2), r, mem.partials, mem.sums));
-            if (commit) ZK_HIP(hipMemcpyAsync(root, tree + 4 * (2 * len - 2), 32, hipMemcpyDeviceToHost, cur_stream()));
+            if (commit) ZK_HIP(hipMemcpyAsync(root, tree + 4 * (2 * (len >> sc.leaf_group(s + 1)) - 2), 32, hipMemcpyDeviceToHost, cur_stream()));
             ZK_HIP(zk::memcpy_on_stream(S, mem.sums, K * ESZ, hipMemcpyDeviceToHost));   // the round's synchronisation
             if (commit) {
                 tr.append(root, 32);
@@ -386,9 +392,10 @@ template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &
     return ZK_OK;
 }
 
-// the statuses of an opening of `cm` that need no device: ZK_E_ARG for Q or f out of range or a z_i that is not reduced
-int open_check(const zk_fri_commitment *cm, const uint64_t *z, uint32_t f, uint32_t Q) {
-    if (Q < 1 || Q > 4096 || f >= cm->d) return ZK_E_ARG;
+// the statuses of an opening of `cm` that need no device: ZK_E_ARG for Q or f out of range or a z_i that is not reduced, and for a commitment
+// whose leaves are not grouped by `log_group` (the ungrouped openers walk cm->levels as 2 N - 1 digests)
+int open_check(const zk_fri_commitment *cm, const uint64_t *z, uint32_t f, uint32_t Q, unsigned log_group = 0) {
+    if (Q < 1 || Q > 4096 || f >= cm->d || cm->log_group != log_group) return ZK_E_ARG;
     if (z && !all_reduced(cm->field, z, cm->d)) return ZK_E_ARG;
     return ZK_OK;
 }
@@ -416,7 +423,7 @@ template <class F> void sumcheck_replay(Transcript &tr, const uint8_t *root32, u
 }
 
 int open_one(const zk_fri_commitment *cm, const uint64_t *z, uint32_t f, uint32_t Q, Transcript &tr, uint64_t *y_out, const OpenOut &o) {
-    FRI_DISPATCH(cm->field, OnePoint<F> form{z, y_out, cm->d}; return open_with<F>(cm, form, f, Q, 1, tr, o));
+    FRI_DISPATCH(cm->field, OnePoint<F> form{z, y_out, cm->d}; return open_with<F>(cm, form, f, Q, 1, false, tr, o));
     return ZK_OK;
 }
 
@@ -501,7 +508,7 @@ int zk_fri_ml_open_points_arity(const zk_fri_commitment *cm, const uint64_t *poi
     ZK_TRY(require_device());
     Transcript fresh;
     const OpenOut o{round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
-    FRI_DISPATCH(cm->field, ManyPoints<F> form{points, npoints, ys_out, gamma_out, cm->d}; return open_with<F>(cm, form, log_final, nqueries, log_arity, t ? t->t : fresh, o));
+    FRI_DISPATCH(cm->field, ManyPoints<F> form{points, npoints, ys_out, gamma_out, cm->d}; return open_with<F>(cm, form, log_final, nqueries, log_arity, false, t ? t->t : fresh, o));
     return ZK_OK;
 }
 
@@ -533,6 +540,39 @@ int zk_fri_ml_sizes_arity(uint32_t d, uint32_t log_blowup, uint32_t log_final, u
     if (nvalues) *nvalues = (size_t)nqueries * sc.nvalues;
     if (path_bytes) *path_bytes = (size_t)nqueries * sc.ndigests * 32;
     return ZK_OK;
+}
+
+int zk_fri_ml_sizes_grouped(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots, size_t *nfinal, size_t *nvalues,
+                            size_t *path_bytes, size_t *nround) {
+    ZK_TRY(zk_fri_ml_sizes_arity(d, log_blowup, log_final, nqueries, 2, nroots, nfinal, nvalues, path_bytes, nround));
+    if (path_bytes) *path_bytes = (size_t)nqueries * FriSchedule(d + log_blowup, d - log_final, 2, true).ndigests * 32;
+    return ZK_OK;
+}
+
+int zk_fri_ml_open_points_grouped(const zk_fri_commitment *cm, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries, zk_transcript *t,
+                                  uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *challenges,
+                                  uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths) {
+    if (!cm || !points || !ys_out || !round_polys || !roots || !final_table || !query_values || !query_paths) return ZK_E_ARG;
+    if (npoints < 1 || npoints > 8) return ZK_E_ARG;
+    ZK_TRY(open_check(cm, nullptr, log_final, nqueries, 2));
+    if (cm->d - log_final < 2) return ZK_E_ARG;
+    if (!all_reduced(cm->field, points, (size_t)npoints * cm->d)) return ZK_E_ARG;
+    ZK_TRY(require_device());
+    Transcript fresh;
+    const OpenOut o{round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
+    FRI_DISPATCH(cm->field, ManyPoints<F> form{points, npoints, ys_out, gamma_out, cm->d}; return open_with<F>(cm, form, log_final, nqueries, 2, true, t ? t->t : fresh, o));
+    return ZK_OK;
+}
+
+int zk_fri_ml_verify_points_grouped(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset,
+                                    const uint64_t *points, uint32_t npoints, const uint64_t *ys, zk_transcript *t, const uint64_t *round_polys,
+                                    const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, int *ok) {
+    if (npoints < 1 || npoints > 8) return ZK_E_ARG;
+    FriMlClaim ml{points, ys, round_polys};
+    ml.npoints = npoints;
+    ml.log_arity = 2;
+    ml.grouped = 1;
+    return verify_opening(field, root32, d, log_blowup, log_final, nqueries, coset, ml, t, roots, final_table, query_values, query_paths, ok);
 }
 
 int zk_fri_ml_verify_points(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset,

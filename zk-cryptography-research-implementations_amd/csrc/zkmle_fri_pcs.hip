@@ -270,11 +270,8 @@ template <class F> int verify_host(size_t k, const uint8_t *roots_f, uint32_t d,
     return ZK_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int zk_fri_commit(const zk_table *coeffs, uint32_t log_blowup, const uint64_t *coset, zk_fri_commitment **out) {
+// zk_fri_commit (lg = 0) and zk_fri_commit_grouped (lg = 2): the tree has N >> lg leaves
+int commit_any(const zk_table *coeffs, uint32_t log_blowup, const uint64_t *coset, unsigned lg, zk_fri_commitment **out) {
     if (!coeffs || !out || field_limbs64(coeffs->field) < 0 || log_blowup < 1 || log_blowup > 8) return ZK_E_ARG;
     if (coset && is_zero_element(coeffs->field, coset)) return ZK_E_ARG;
     if (coeffs->len == 1) return ZK_E_ARG;
@@ -285,19 +282,20 @@ int zk_fri_commit(const zk_table *coeffs, uint32_t log_blowup, const uint64_t *c
     cm->field = coeffs->field;
     cm->d = ilog2(coeffs->len);
     cm->b = log_blowup;
+    cm->log_group = lg;
     cm->has_coset = coset != nullptr;
     if (coset) memcpy(cm->coset, coset, 32);
-    const size_t n = coeffs->len << log_blowup;
+    const size_t n = coeffs->len << log_blowup, leaves = n >> lg;         // N >= 4: d >= 1 and b >= 1
     int rc = zk_table_clone(coeffs, &cm->coeffs);
     if (rc == ZK_OK) rc = zk_table_alloc(coeffs->field, n, &cm->codeword);
     if (rc == ZK_OK) {
         void *lv = nullptr;
-        if (hipMalloc(&lv, (2 * n - 1) * 32) != hipSuccess) { set_last_error("zk_fri_commit: no memory for the tree"); rc = ZK_E_NOMEM; }
+        if (hipMalloc(&lv, (2 * leaves - 1) * 32) != hipSuccess) { set_last_error("zk_fri_commit: no memory for the tree"); rc = ZK_E_NOMEM; }
         cm->levels = (uint64_t *)lv;
     }
     if (rc == ZK_OK) rc = ntt_extend_into(cm->coeffs, coset, cm->codeword);
-    if (rc == ZK_OK) rc = merkle_levels_device(cm->codeword, cm->levels);
-    if (rc == ZK_OK && zk::memcpy_on_stream(cm->root, cm->levels + 4 * (2 * n - 2), 32, hipMemcpyDeviceToHost) != hipSuccess) {
+    if (rc == ZK_OK) rc = merkle_levels_grouped_device(cm->codeword, lg, cm->levels);
+    if (rc == ZK_OK && zk::memcpy_on_stream(cm->root, cm->levels + 4 * (2 * leaves - 2), 32, hipMemcpyDeviceToHost) != hipSuccess) {
         set_last_error("zk_fri_commit: the transform or the hash kernels failed");
         rc = ZK_E_HIP;
     }
@@ -305,6 +303,19 @@ int zk_fri_commit(const zk_table *coeffs, uint32_t log_blowup, const uint64_t *c
     *out = cm;
     return ZK_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int zk_fri_commit(const zk_table *coeffs, uint32_t log_blowup, const uint64_t *coset, zk_fri_commitment **out) {
+    return commit_any(coeffs, log_blowup, coset, 0, out);
+}
+int zk_fri_commit_grouped(const zk_table *coeffs, uint32_t log_blowup, const uint64_t *coset, uint32_t log_group, zk_fri_commitment **out) {
+    if (log_group != 0 && log_group != 2) return ZK_E_ARG;
+    return commit_any(coeffs, log_blowup, coset, log_group, out);
+}
+uint32_t zk_fri_commitment_log_group(const zk_fri_commitment *cm) { return cm ? cm->log_group : 0; }
 int zk_fri_commitment_free(zk_fri_commitment *cm) {
     if (!cm) return ZK_OK;
     zk_table_free(cm->coeffs);
@@ -370,6 +381,8 @@ int zk_fri_pcs_open(const zk_fri_commitment *const *cms, size_t k, const uint64_
     if (nqueries < 1 || nqueries > 4096) return ZK_E_ARG;
     ZK_TRY(set_check(cms, k, z));
     if (log_final >= cms[0]->d) return ZK_E_ARG;
+    for (size_t j = 0; j < k; j++)
+        if (cms[j]->log_group != 0) return ZK_E_ARG;         // the gather walks trees of 2 N - 1 digests
     ZK_TRY(require_device());
     const OpenOut o{ys_out, roots, final_coeffs, betas, query_indices, query_values, query_paths, opened_values, opened_paths};
     FRI_DISPATCH(cms[0]->field, return open_any<F>(cms, k, z, log_final, nqueries, t, o));

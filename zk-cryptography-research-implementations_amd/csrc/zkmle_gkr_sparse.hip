@@ -788,7 +788,7 @@ int zk_gkr_sparse_prove_succinct(int field, const zk_sparse_circuit *c, const zk
         !open_round_polys || !roots || !final_table || !query_values || !query_paths || c->layers.empty())
         return ZK_E_ARG;
     if (c->layers.size() > 1 && (!wb_evals || !wc_evals)) return ZK_E_ARG;
-    if (cm->field != field || nqueries < 1 || nqueries > 4096 || log_final >= cm->d) return ZK_E_ARG;
+    if (cm->field != field || cm->log_group != 0 || nqueries < 1 || nqueries > 4096 || log_final >= cm->d) return ZK_E_ARG;
     const uint32_t k = c->layers.back().in_bits;
     if (cm->d != k) return ZK_E_LEN_MISMATCH;
     ZK_TRY(require_device());

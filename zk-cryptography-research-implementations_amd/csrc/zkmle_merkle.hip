@@ -14,7 +14,7 @@ using host::DevBuf;
 
 struct zk_merkle_tree {
     int field;
-    size_t len;
+    size_t len;             // the LEAVES: the table's length, or that >> log_group of a tree with grouped leaves
     unsigned depth;
     uint64_t *levels;       // 2 len - 1 digests: level l at digest offset 2 len - (2 len >> l), the root last
 };
@@ -46,6 +46,23 @@ template <class F> int launch_leaves(const zk_table *t, uint64_t *out) {
     ZK_HIP(hipGetLastError());
     return ZK_OK;
 }
+// the len >> lg grouped leaves (lg = 1 or 2) of a table of 32-byte elements
+template <class F> int launch_leaves_grouped(const zk_table *t, unsigned lg, uint64_t *out) {
+    if constexpr (F::N == 8) {
+        const size_t part = t->len >> lg;
+        if (lg == 1) merkle_leaf_group_kernel<F, 1><<<merkle_grid(part), kMerkleBlock, 0, cur_stream()>>>(t->dptr, part, out);
+        else merkle_leaf_group_kernel<F, 2><<<merkle_grid(part), kMerkleBlock, 0, cur_stream()>>>(t->dptr, part, out);
+        ZK_HIP(hipGetLastError());
+        return ZK_OK;
+    } else {
+        return ZK_E_ARG;
+    }
+}
+// the statuses of a grouped tree of `t` that need no device
+int grouped_check(const zk_table *t, uint32_t lg) {
+    if (!t || lg > 2 || field_limbs64(t->field) != 4 || t->len < ((size_t)1 << lg)) return ZK_E_ARG;
+    return is_pow2(t->len) ? ZK_OK : ZK_E_NOT_POW2;
+}
 // Root-only mode: build mode on ONE scratch block of the caching pool, 2 len - 1 digests (64 B x len; cached by the calling thread's pool
 // after the call like every per-call scratch).  Nothing but the root leaves the device.
 template <class F> int root_only(const zk_table *t, uint8_t root32[32]) {
@@ -59,6 +76,15 @@ template <class F> int root_only(const zk_table *t, uint8_t root32[32]) {
     return ZK_OK;
 }
 
+int root_only_grouped(const zk_table *t, unsigned lg, uint8_t root32[32]) {
+    const size_t n = t->len >> lg;
+    DevBuf buf;
+    ZK_TRY(buf.alloc((2 * n - 1) * 32));
+    ZK_TRY(merkle_levels_grouped_device(t, lg, (uint64_t *)buf.p));
+    ZK_HIP(zk::memcpy_on_stream(root32, (uint64_t *)buf.p + 4 * (2 * n - 2), 32, hipMemcpyDeviceToHost));   // the call's one synchronisation
+    return ZK_OK;
+}
+
 // leaf and node hashes on the host (zk_merkle_verify; Keccak256 of transcript.h, pinned by the reference KATs)
 template <class F> void host_leaf(const uint64_t *element, uint8_t out[32]) {
     uint8_t msg[1 + 4 * F::N];
@@ -69,6 +95,23 @@ template <class F> void host_leaf(const uint64_t *element, uint8_t out[32]) {
     Keccak256 h;
     h.update(msg, sizeof msg);
     h.finalize_copy(out);
+}
+// the grouped leaf of 2^lg elements of 32 bytes; false: one of them is not reduced
+template <class F> bool host_leaf_grouped(const uint64_t *elements, unsigned lg, uint8_t out[32]) {
+    if constexpr (F::N == 8) {
+        uint8_t msg[1 + 4 * 32];
+        msg[0] = 0x00;
+        for (size_t g = 0; g < (size_t)1 << lg; g++) {
+            if (!host::is_reduced<F>(elements + 4 * g)) return false;
+            host_to_bytes_be<F>(host::load_host<F>(elements + 4 * g), msg + 1 + 32 * g);
+        }
+        Keccak256 h;
+        h.update(msg, 1 + ((size_t)32 << lg));
+        h.finalize_copy(out);
+        return true;
+    } else {
+        return false;
+    }
 }
 void host_node(const uint8_t *l, const uint8_t *r, uint8_t out[32]) {
     uint8_t msg[65];
@@ -94,6 +137,11 @@ int merkle_levels_device(const zk_table *t, uint64_t *levels) {
     ZK_DISPATCH_FIELD(t->field, ZK_TRY(launch_leaves<F>(t, levels)));
     return hash_up(levels, t->len);
 }
+int merkle_levels_grouped_device(const zk_table *t, unsigned log_group, uint64_t *levels) {
+    if (log_group == 0) return merkle_levels_device(t, levels);
+    ZK_DISPATCH_FIELD(t->field, ZK_TRY(launch_leaves_grouped<F>(t, log_group, levels)));
+    return hash_up(levels, t->len >> log_group);
+}
 }  // namespace zk
 
 extern "C" {
@@ -111,6 +159,28 @@ int zk_merkle_build(const zk_table *t, zk_merkle_tree **out) {
     ZK_DISPATCH_FIELD(t->field, rc = launch_leaves<F>(t, m->levels));
     if (rc == ZK_OK) rc = hash_up(m->levels, m->len);
     if (rc == ZK_OK && hipStreamSynchronize(cur_stream()) != hipSuccess) { set_last_error("zk_merkle_build: the hash kernels failed"); rc = ZK_E_HIP; }
+    if (rc != ZK_OK) { zk_merkle_free(m); return rc; }
+    *out = m;
+    return ZK_OK;
+}
+int zk_mle_merkle_root_grouped(const zk_table *t, uint32_t log_group, uint8_t root32[32]) {
+    if (!root32) return ZK_E_ARG;
+    if (log_group == 0) return merkle_root_device(t, root32);
+    ZK_TRY(grouped_check(t, log_group));
+    ZK_TRY(require_device());
+    return root_only_grouped(t, log_group, root32);
+}
+int zk_merkle_build_grouped(const zk_table *t, uint32_t log_group, zk_merkle_tree **out) {
+    if (!out) return ZK_E_ARG;
+    if (log_group == 0) return zk_merkle_build(t, out);
+    ZK_TRY(grouped_check(t, log_group));
+    ZK_TRY(require_device());
+    const size_t n = t->len >> log_group;
+    void *d = nullptr;
+    ZK_HIP(hipMalloc(&d, (2 * n - 1) * 32));
+    zk_merkle_tree *m = new zk_merkle_tree{t->field, n, ilog2(n), (uint64_t *)d};
+    int rc = merkle_levels_grouped_device(t, log_group, m->levels);
+    if (rc == ZK_OK && hipStreamSynchronize(cur_stream()) != hipSuccess) { set_last_error("zk_merkle_build_grouped: the hash kernels failed"); rc = ZK_E_HIP; }
     if (rc != ZK_OK) { zk_merkle_free(m); return rc; }
     *out = m;
     return ZK_OK;
@@ -149,6 +219,25 @@ int zk_merkle_verify(int field, const uint8_t root32[32], size_t depth, size_t i
     if (depth >= 64 || (index >> depth) != 0) return ZK_E_RANGE;
     uint8_t cur[32];
     ZK_DISPATCH_FIELD(field, host_leaf<F>(element, cur));
+    for (size_t l = 0; l < depth; l++) {                       // the leaf's sibling first
+        const uint8_t *sib = path + 32 * l;
+        uint8_t nx[32];
+        if ((index >> l) & 1) host_node(sib, cur, nx); else host_node(cur, sib, nx);
+        memcpy(cur, nx, 32);
+    }
+    *ok = memcmp(cur, root32, 32) == 0 ? 1 : 0;
+    return ZK_OK;
+}
+
+int zk_merkle_verify_grouped(int field, const uint8_t root32[32], size_t depth, size_t index, uint32_t log_group, const uint64_t *elements,
+                             const uint8_t *path, int *ok) {
+    if (!root32 || !elements || (!path && depth) || !ok || log_group > 2 || field_limbs64(field) != 4) return ZK_E_ARG;
+    if (depth >= 64 || (index >> depth) != 0) return ZK_E_RANGE;
+    uint8_t cur[32];
+    bool reduced = false;
+    ZK_DISPATCH_FIELD(field, reduced = host_leaf_grouped<F>(elements, log_group, cur));
+    *ok = 0;
+    if (!reduced) return ZK_OK;
     for (size_t l = 0; l < depth; l++) {                       // the leaf's sibling first
         const uint8_t *sib = path + 32 * l;
         uint8_t nx[32];

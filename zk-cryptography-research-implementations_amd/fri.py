@@ -14,6 +14,8 @@ table read as evaluations over the cube, `open_multilinear` proves y = evaluate(
 the codeword; `verify_multilinear` is host code and needs nothing but the root.  `open_multilinear_points` opens ONE commitment at up to
 eight points with one proof (include/zkmle.h "FRI commitment opened at several points"): the layers and trees are built once.  With
 `log_arity=2` it commits every second folded layer only (include/zkmle.h "FRI commitment opened with a fold arity"): a third of the leaves hashed.
+On a commitment made with `commit(.., log_group=2)` every tree has one leaf per fold coset (include/zkmle.h "FRI commitment opened with grouped
+leaves"): a quarter of that again, and one path per step instead of four, so the proof shrinks.
 """
 import ctypes as C
 
@@ -127,6 +129,7 @@ class FriCommitment:
 
     def __init__(self, field, d, log_blowup, coset, handle):
         self.field, self.d, self.log_blowup, self._h = field, d, log_blowup, handle
+        self.log_group = int(L.lib().zk_fri_commitment_log_group(handle))
         self.coset = None if coset is None else _elem(field, coset).copy()
         root = np.zeros(32, np.uint8)
         L.check(L.lib().zk_fri_commitment_root(handle, L.p8(root)))
@@ -157,11 +160,15 @@ class FriCommitment:
             pass
 
 
-def commit(coeffs, log_blowup, coset=None):
-    """the commitment to the coefficient table `coeffs` (2^d entries): its root is root_0 of `prove` on the same input"""
+def commit(coeffs, log_blowup, coset=None, log_group=0):
+    """the commitment to the coefficient table `coeffs` (2^d entries): its root is root_0 of `prove` on the same input.  log_group = 2: the
+    tree's leaves are the cosets of the first fold by 4 (a quarter of the hashes); only open_multilinear_points(.., log_arity=2) opens it"""
     h = C.c_void_p()
     cs = None if coset is None else L.p64(_elem(coeffs.field, coset))
-    L.check(L.lib().zk_fri_commit(coeffs._h, log_blowup, cs, C.byref(h)))
+    if log_group == 0:
+        L.check(L.lib().zk_fri_commit(coeffs._h, log_blowup, cs, C.byref(h)))
+    else:
+        L.check(L.lib().zk_fri_commit_grouped(coeffs._h, log_blowup, cs, log_group, C.byref(h)))
     return FriCommitment(coeffs.field, len(coeffs).bit_length() - 1, log_blowup, coset, h)
 
 
@@ -231,11 +238,16 @@ class _MlStats(C.Structure):
                 ("ms_queries", C.c_float), ("ms_total", C.c_float)]
 
 
-def ml_sizes(d, log_blowup, log_final, nqueries, log_arity=1):
+def ml_sizes(d, log_blowup, log_final, nqueries, log_arity=1, grouped=False):
     """-> sizes(..) + (nround,): the 3 R elements of round polynomials of a multilinear opening of a table of 2^d entries; log_arity = 2: the
-    counts of the opening folded by 4 (nroots = ceil(R / 2), four values and paths per fold-4 step)"""
+    counts of the opening folded by 4 (nroots = ceil(R / 2), four values and paths per fold-4 step); grouped (log_arity = 2 only): one path
+    of L - l - log_sides digests per step"""
     out = [C.c_size_t(0) for _ in range(5)]
-    if log_arity == 1:
+    if grouped:
+        if log_arity != 2:
+            raise ValueError("grouped leaves need log_arity=2")
+        L.check(L.lib().zk_fri_ml_sizes_grouped(d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
+    elif log_arity == 1:
         L.check(L.lib().zk_fri_ml_sizes(d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
     else:
         L.check(L.lib().zk_fri_ml_sizes_arity(d, log_blowup, log_final, nqueries, log_arity, *[C.byref(o) for o in out]))
@@ -263,10 +275,10 @@ class FriMlOpening:
     (Q, R, 2, limbs); query_paths (path_bytes,) bytes; challenges (R, limbs) and query_indices (Q,) are what the prover's transcript gave
     (diagnostic: the verifier derives its own)."""
 
-    def __init__(self, field, d, log_blowup, log_final, nqueries, coset=None, log_arity=1):
+    def __init__(self, field, d, log_blowup, log_final, nqueries, coset=None, log_arity=1, grouped=False):
         self.field, self.d, self.log_blowup, self.log_final, self.nqueries = field, d, log_blowup, log_final, nqueries
         self.coset = None if coset is None else _elem(field, coset).copy()
-        nroots, nfinal, nvalues, path_bytes, nround = ml_sizes(d, log_blowup, log_final, nqueries, log_arity)
+        nroots, nfinal, nvalues, path_bytes, nround = ml_sizes(d, log_blowup, log_final, nqueries, log_arity, grouped)
         n = limbs(field)
         self.y = np.zeros(n, np.uint64)
         self.round_polys = np.zeros((nround // 3, 3, n), np.uint64)
@@ -321,12 +333,13 @@ def verify_multilinear(root, z, opening, transcript=None):
 # ---- the multilinear opening at several points ------------------------------------------------------------------------------------------
 class FriMlPointsOpening(FriMlOpening):
     """FriMlOpening with ys (P, limbs) in place of y, and gamma (limbs,), the batching challenge the prover's transcript gave (diagnostic).
-    log_arity = 2: roots (ceil(R / 2), 32), query_values (Q, 4 floor(R / 2) + 2 (R mod 2), limbs)."""
+    log_arity = 2: roots (ceil(R / 2), 32), query_values (Q, 4 floor(R / 2) + 2 (R mod 2), limbs).  grouped: the opening of a commitment with
+    grouped leaves, one path per step."""
 
-    def __init__(self, field, npoints, d, log_blowup, log_final, nqueries, coset=None, log_arity=1):
-        super().__init__(field, d, log_blowup, log_final, nqueries, coset, log_arity)
+    def __init__(self, field, npoints, d, log_blowup, log_final, nqueries, coset=None, log_arity=1, grouped=False):
+        super().__init__(field, d, log_blowup, log_final, nqueries, coset, log_arity, grouped)
         del self.y
-        self.npoints, self.log_arity = npoints, log_arity
+        self.npoints, self.log_arity, self.grouped = npoints, log_arity, grouped
         self.ys = np.zeros((npoints, limbs(field)), np.uint64)
         self.gamma = np.zeros(limbs(field), np.uint64)
 
@@ -352,12 +365,18 @@ def ml_round(T, W, r=None):
 
 def open_multilinear_points(commitment, points, log_final, nqueries, transcript=None, log_arity=1):
     """one proof that the committed table's multilinear extension has the values `.ys` at the P <= 8 points (P, d, limbs); log_arity = 2 folds
-    by 4 and commits every second layer"""
+    by 4 and commits every second layer.  A commitment with grouped leaves (commit(.., log_group=2)) takes the grouped protocol, which
+    exists for log_arity = 2 only"""
+    grouped = getattr(commitment, "log_group", 0) != 0
+    if grouped and log_arity != 2:
+        raise ValueError("a commitment with grouped leaves is opened with log_arity=2")
     pts = _points(commitment.field, commitment.d, points)
-    op = FriMlPointsOpening(commitment.field, pts.shape[0], commitment.d, commitment.log_blowup, log_final, nqueries, commitment.coset, log_arity)
+    op = FriMlPointsOpening(commitment.field, pts.shape[0], commitment.d, commitment.log_blowup, log_final, nqueries, commitment.coset, log_arity, grouped)
     out = (L.p64(op.ys), L.p64(op.gamma), L.p64(op.round_polys), L.p8(op.roots), L.p64(op.final_table), L.p64(op.challenges),
            L.p64(op.query_indices), L.p64(op.query_values), L.p8(op.query_paths))
-    if log_arity == 1:
+    if grouped:
+        L.check(L.lib().zk_fri_ml_open_points_grouped(commitment._h, L.p64(pts), pts.shape[0], log_final, nqueries, _handle(transcript), *out))
+    elif log_arity == 1:
         L.check(L.lib().zk_fri_ml_open_points(commitment._h, L.p64(pts), pts.shape[0], log_final, nqueries, _handle(transcript), *out))
     else:
         L.check(L.lib().zk_fri_ml_open_points_arity(commitment._h, L.p64(pts), pts.shape[0], log_final, nqueries, log_arity, _handle(transcript), *out))
@@ -366,10 +385,13 @@ def open_multilinear_points(commitment, points, log_final, nqueries, transcript=
 
 def verify_multilinear_points(root, points, opening, transcript=None, log_arity=None):
     """host only: `root` = the commitment's 32 bytes; the claims checked are evaluate(table, points[p]) = opening.ys[p].  log_arity: the
-    opening's own unless given"""
+    opening's own unless given; an opening with `.grouped` set is checked by the grouped protocol's verifier"""
     ok = C.c_int(0)
     op = opening
     log_arity = getattr(op, "log_arity", 1) if log_arity is None else log_arity
+    grouped = bool(getattr(op, "grouped", False))
+    if grouped and log_arity != 2:
+        raise ValueError("an opening with grouped leaves has log_arity=2")
     rbuf = np.frombuffer(bytes(root), np.uint8).copy()
     if rbuf.shape[0] != 32:
         raise L.ZkError(L.ZK_E_ARG, "a Merkle root is 32 bytes")
@@ -379,12 +401,14 @@ def verify_multilinear_points(root, points, opening, transcript=None, log_arity=
         raise L.ZkError(L.ZK_E_ARG, "one claim per point")
     roots, paths = np.ascontiguousarray(op.roots, np.uint8), np.ascontiguousarray(op.query_paths, np.uint8)
     if log_arity != 1:                                        # the counts differ from the opening's own when the arity is overridden
-        nroots, nfinal, nvalues, path_bytes, nround = ml_sizes(op.d, op.log_blowup, op.log_final, op.nqueries, log_arity)
+        nroots, nfinal, nvalues, path_bytes, nround = ml_sizes(op.d, op.log_blowup, op.log_final, op.nqueries, log_arity, grouped)
         n = limbs(op.field)
         if roots.size < 32 * nroots or fin.size < nfinal * n or vals.size < nvalues * n or paths.size < path_bytes or rp.size < nround * n:
             raise L.ZkError(L.ZK_E_ARG, "the opening's arrays are shorter than this arity's proof")
     rest = (op._coset(), L.p64(pts), pts.shape[0], L.p64(ys), _handle(transcript), L.p64(rp), L.p8(roots), L.p64(fin), L.p64(vals), L.p8(paths), C.byref(ok))
-    if log_arity == 1:
+    if grouped:
+        L.check(L.lib().zk_fri_ml_verify_points_grouped(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, *rest))
+    elif log_arity == 1:
         L.check(L.lib().zk_fri_ml_verify_points(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, *rest))
     else:
         L.check(L.lib().zk_fri_ml_verify_points_arity(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, log_arity, *rest))
