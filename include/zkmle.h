@@ -527,6 +527,59 @@ int zk_fri_ml_verify_points_grouped(int field, const uint8_t *root32, uint32_t d
                                     const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys, zk_transcript *t,
                                     const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
                                     const uint8_t *query_paths, int *ok);
+/* ---- FRI commitments opened together (extension; csrc/fri_ml.cuh fri_ml_fold_batch_kernel, csrc/zkmle_fri_ml.hip) -------------------------------
+ * k commitments cm_0 .. cm_{k-1}, 1 <= k <= ZK_FRI_ML_BATCH_MAX, opened at the same P <= 8 points with ONE proof: Reed-Solomon encoding is
+ * linear, so the codeword of T = sum_j a_j T_j is sum_j a_j f_j, and one opening of T costs one pass over the k codewords plus k layer-0 answers
+ * per query; every folded layer and every tree of a later layer is built once.  It is "FRI commitment opened at several points" with its arity
+ * (a = log_arity in {1, 2}) and grouped-leaves variants, changed only as follows.
+ *   Inputs.  The commitments share field, d, log_blowup, coset and log_group (0 or 2); anything else is ZK_E_ARG, before any device work.
+ *     log_group = 2 needs a = 2; a = 2 needs R = d - f >= 2.  The claims are y_{j,p} = zk_mle_evaluate(T_j, z^p), laid out table-major.
+ *   Transcript, plain appends in this order:
+ *     1. FRI's 48-byte header;
+ *     2. 16 bytes: the ASCII tag "BTCH", then a, then the grouped flag (0 or 1), then k, each a big-endian u32 -- always present, at a = 1 and
+ *        k = 1 too, so no transcript of an earlier protocol is one of this protocol;
+ *     3. the k roots, in order;
+ *     4. P as a 4-byte big-endian u32, then the points, point-major;
+ *     5. the k P claims, table-major, each 32 bytes canonical big-endian;
+ *     6. ONE challenge gamma.  The coefficient of y_{j,p} is gamma^(j P + p).  With alpha = gamma^P:
+ *          claim_0 = sum_j alpha^j sum_p gamma^p y_{j,p},   T = sum_j alpha^j T_j,   f_0 = sum_j alpha^j f_j,   W_0 = sum_p gamma^p eq(., z^p);
+ *     7. the rounds, the later layers' roots, T_R and the Q indices exactly as in the single-table protocol of the same schedule, on T and f_0.
+ *   Layer 0.  The combined f_0 has no tree and is never stored.  For step 0 a query answers with the step's `sides` values per commitment:
+ *     values j-major, then side; paths j-major, `sides` paths each when ungrouped or one path each when grouped, every path from commitment
+ *     j's own tree.  Steps s >= 1 are laid out as in the single-table protocol.
+ *   Roots.  `roots` holds the k commitment roots first, then the roots of the committed layers of steps 1 and up.
+ *   Counts (zk_fri_ml_sizes_batch).  nroots = k + (the single form's nroots - 1); nvalues and path_bytes = the single form's plus (k - 1) times
+ *     step 0's share (Q sides_0 values; 32 Q sides_0 L bytes ungrouped, 32 Q (L - 2) grouped); nfinal and nround unchanged.
+ *   Verifier (HOST only).  fri_verify_core with FriMlClaim extended by the number of tables, not a copy.  At step 0 it checks each commitment's
+ *     path or paths against root_j, forms u_s = sum_j alpha^j v_{j,s} and carries on with u_s as the step's values; the sumcheck's checks are
+ *     the several-point form's with the new claim_0.  Unreduced elements give *ok = 0; the proof's first k roots must be the verifier's own.
+ *     Status order is zk_fri_ml_verify_points_arity's; k outside 1 .. 16, log_group outside {0, 2} or log_group = 2 with a = 1 is ZK_E_ARG.
+ *   Prover.  k P zk_mle_evaluate passes; W_0 as in the several-point form; T_0 = T by one zk_mle_linear_combination pass into n further
+ *     elements of the pool block; round 0 on (T_0, W_0).  The first step's fold reads the k codewords and forms f_0's entries in registers
+ *     (fri_ml_fold_batch_kernel): k N elements read, N / sides_0 written.  Step 0's answers are gathered from the k commitments by the
+ *     single-table gather kernels, once per commitment.  zk_fri_ml_last_stats reports the call: the evaluations and the combination count in
+ *     ms_sumcheck, the fused first fold in ms_folds. */
+#define ZK_FRI_ML_BATCH_MAX 16
+/* the first step's fold on its own: zk_fri_ml_fold4(sum_j coeffs[j] codewords[j], r0, r1, coset) -- r1 = NULL: zk_fri_ml_fold(.., r0, coset) --
+ * byte for byte, in one pass that never stores the sum.  coeffs: k elements.  ZK_E_ARG (NULL, k outside 1 .. 16, mixed fields),
+ * ZK_E_LEN_MISMATCH (unequal lengths), then zk_fri_ml_fold4's statuses (zk_fri_ml_fold's when r1 = NULL) on codewords[0]. */
+int zk_fri_ml_fold_batch(const zk_table *const *codewords, uint32_t k, const uint64_t *coeffs, const uint64_t *r0, const uint64_t *r1,
+                         const uint64_t *coset, zk_table **out);
+/* host: the five counts of an opening of k commitments; log_group = 2 selects the grouped form (needs log_arity = 2) */
+int zk_fri_ml_sizes_batch(uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
+                          size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround);
+/* ys_out: k x npoints elements, table-major; the other outputs as zk_fri_ml_open_points_arity, sized by zk_fri_ml_sizes_batch with the
+ * commitments' log_group.  Statuses: ZK_E_ARG (NULL, k outside 1 .. 16, commitments that differ in field, d, log_blowup, coset or log_group,
+ * grouped commitments with log_arity = 1, and zk_fri_ml_open_points_arity's), all before ZK_E_NO_DEVICE. */
+int zk_fri_ml_open_batch(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final,
+                         uint32_t nqueries, uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys,
+                         uint8_t *roots, uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values,
+                         uint8_t *query_paths);
+/* HOST only.  roots_of_f: the k commitment roots the verifier holds, 32 bytes each, in the prover's order; ys: k x npoints elements. */
+int zk_fri_ml_verify_batch(int field, const uint8_t *roots_of_f, uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
+                           uint32_t log_arity, uint32_t log_group, const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys,
+                           zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table,
+                           const uint64_t *query_values, const uint8_t *query_paths, int *ok);
 /* The basic sumcheck finished by a verifier who holds 32 bytes.  Prover::prove (prover.rs:35-71) with one change, as
  * zk_sumcheck_basic_prove_committed: the first append (:38-39) is the COMMITMENT's root (zk_fri_commitment_root: the root of the codeword of
  * the table, not zk_mle_merkle_root of the table).  The rounds run on the commitment's device table, which is only read; then

@@ -155,6 +155,17 @@ pub mod ffi {
                                                points: *const u64, npoints: u32, ys: *const u64, t: *mut zk_transcript, round_polys: *const u64,
                                                roots: *const u8, final_table: *const u64, query_values: *const u64, query_paths: *const u8,
                                                ok: *mut c_int) -> c_int;
+        pub fn zk_fri_ml_fold_batch(codewords: *const *const zk_table, k: u32, coeffs: *const u64, r0: *const u64, r1: *const u64, coset: *const u64,
+                                    out: *mut *mut zk_table) -> c_int;
+        pub fn zk_fri_ml_sizes_batch(k: u32, d: u32, log_blowup: u32, log_final: u32, nqueries: u32, log_arity: u32, log_group: u32, nroots: *mut usize,
+                                     nfinal: *mut usize, nvalues: *mut usize, path_bytes: *mut usize, nround: *mut usize) -> c_int;
+        pub fn zk_fri_ml_open_batch(cms: *const *const c_void, k: u32, points: *const u64, npoints: u32, log_final: u32, nqueries: u32, log_arity: u32,
+                                    t: *mut zk_transcript, ys_out: *mut u64, gamma_out: *mut u64, round_polys: *mut u64, roots: *mut u8, final_table: *mut u64,
+                                    challenges: *mut u64, query_indices: *mut u64, query_values: *mut u64, query_paths: *mut u8) -> c_int;
+        pub fn zk_fri_ml_verify_batch(field: c_int, roots_of_f: *const u8, k: u32, d: u32, log_blowup: u32, log_final: u32, nqueries: u32, log_arity: u32,
+                                      log_group: u32, coset: *const u64, points: *const u64, npoints: u32, ys: *const u64, t: *mut zk_transcript,
+                                      round_polys: *const u64, roots: *const u8, final_table: *const u64, query_values: *const u64,
+                                      query_paths: *const u8, ok: *mut c_int) -> c_int;
         pub fn zk_sumcheck_basic_prove_committed(t: *const zk_table, transcript: *mut zk_transcript, root32: *mut u8, claimed: *mut u64, rounds: *mut u64,
                                                  challenges: *mut u64) -> c_int;
         pub fn zk_sumcheck_basic_verify_committed(t: *const zk_table, root32: *const u8, claimed: *const u64, rounds: *const u64, nrounds: usize,

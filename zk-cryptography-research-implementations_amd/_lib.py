@@ -151,6 +151,11 @@ def lib():
         "zk_fri_ml_open_points_grouped": [vp, u64p] + [C.c_uint32] * 3 + [vp, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_fri_ml_verify_points_grouped": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, u64p, C.c_uint32, u64p, vp, u64p, u8p, u64p, u64p, u8p,
                                                                                C.POINTER(C.c_int)],
+        # FRI commitments opened together
+        "zk_fri_ml_fold_batch": [C.POINTER(vp), C.c_uint32, u64p, u64p, u64p, u64p, C.POINTER(vp)],
+        "zk_fri_ml_sizes_batch": [C.c_uint32] * 7 + [C.POINTER(sz)] * 5,
+        "zk_fri_ml_open_batch": [C.POINTER(vp), C.c_uint32, u64p] + [C.c_uint32] * 4 + [vp, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
+        "zk_fri_ml_verify_batch": [C.c_int, u8p] + [C.c_uint32] * 7 + [u64p, u64p, C.c_uint32, u64p, vp, u64p, u8p, u64p, u64p, u8p, C.POINTER(C.c_int)],
         "zk_sumcheck_basic_prove_succinct": [vp, C.c_uint32, C.c_uint32, vp, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_sumcheck_basic_verify_succinct": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, vp, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u8p,
                                                                                  C.POINTER(C.c_int)],

@@ -118,6 +118,10 @@ struct FriMlClaim {
     uint32_t npoints = 0;
     uint32_t log_arity = 1;                                  // 2: the opening folded by 4 (include/zkmle.h "... opened with a fold arity"); needs npoints >= 1
     uint32_t grouped = 0;                                    // 1: every layer's leaves hold a step's sides ("... with grouped leaves"); needs log_arity = 2
+    // k > 0: k commitments opened together ("FRI commitments opened together"; needs npoints >= 1).  y holds k x npoints claims table-major and
+    // `roots` starts with the k commitments' roots (the verifier's own copies), the later layers' behind them; a query's step 0 holds the k
+    // commitments' values and paths, j-major, and the step's values are their alpha-combination, alpha = gamma^npoints.  0: one table, as before
+    uint32_t ntables = 0;
 };
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,

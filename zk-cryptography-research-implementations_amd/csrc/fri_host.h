@@ -116,22 +116,27 @@ struct FriSchedule {
     }
     unsigned leaf_group(unsigned s) const { return grouped ? step[s].log_sides : 0; }   // the log_group of step s's tree
     unsigned index_bits() const { return step[0].log_len - log_arity; }   // every i_q is a position of the first step's part
-    // the gather kernels' view; the caller adds each step's table and tree.  wide stays 0 at arity 1: its three arrays are not read then
-    FriLayers layers() const {
+    // the gather kernels' view of the steps first .. first + count - 1 (all of them by default; first < nsteps), offsets counted from step
+    // `first`; the caller adds each step's table and tree.  wide stays 0 at arity 1: its three arrays are not read then, and step s is layer
+    // s, whose length the kernels take from log_len0
+    FriLayers layers(unsigned first = 0, unsigned count = kFriMaxLayers) const {
+        if (count > nsteps - first) count = nsteps - first;
+        const unsigned end = first + count;
+        const size_t v0 = step[first].val_off, d0 = step[first].path_off;
         FriLayers fl{};
-        fl.log_len0 = step[0].log_len;
-        fl.nlayers = nsteps;
+        fl.log_len0 = step[first].log_len;
+        fl.nlayers = count;
         fl.wide = log_arity == 2;
         fl.grouped = grouped;
-        for (unsigned s = 0; s < nsteps; s++) {
-            fl.path_off[s] = (uint32_t)step[s].path_off;
+        for (unsigned s = 0; s < count; s++) {
+            fl.path_off[s] = (uint32_t)(step[first + s].path_off - d0);
             if (!fl.wide) continue;
-            fl.val_off[s] = (uint32_t)step[s].val_off;
-            fl.log_len[s] = (uint8_t)step[s].log_len;
-            fl.log_sides[s] = (uint8_t)step[s].log_sides;
+            fl.val_off[s] = (uint32_t)(step[first + s].val_off - v0);
+            fl.log_len[s] = (uint8_t)step[first + s].log_len;
+            fl.log_sides[s] = (uint8_t)step[first + s].log_sides;
         }
-        fl.path_off[nsteps] = (uint32_t)ndigests;
-        if (fl.wide) fl.val_off[nsteps] = (uint32_t)nvalues;
+        fl.path_off[count] = (uint32_t)((end < nsteps ? step[end].path_off : ndigests) - d0);
+        if (fl.wide) fl.val_off[count] = (uint32_t)((end < nsteps ? step[end].val_off : nvalues) - v0);
         return fl;
     }
 };

@@ -23,6 +23,8 @@
 //           four contiguous reads of T and two of E, two writes of T and one of E per lane.  Round 0 (FOLD = false) reads T_0 and E_0 and
 //           writes neither.  S_0 and S_1 are mle_kernels.cuh's lazy sums (Wide: a carry chain per term, one reduction per workgroup); the
 //           workgroups' sums are added by finish_sums_kernel, a second launch of one block.
+//   fold_batch  the first step of an opening of k commitments together (include/zkmle.h "FRI commitments opened together"): the fold or
+//           fold4 above on u = sum_j alpha^j f_j, with the combination formed in registers (fri_ml_fold_batch_kernel, at the end).
 #pragma once
 #include "fri.cuh"
 #include "mle_kernels.cuh"
@@ -175,6 +177,59 @@ template <class F, bool FOLD> __global__ void __launch_bounds__(kBlock) fri_ml_r
     }
     Fe<F> tot;
     if (block_reduce_wide<F, 3>(sum, sh, tot)) fe_store<F>(partials, (size_t)threadIdx.x * gridDim.x + blockIdx.x, tot);
+}
+
+// The first step's fold of k codewords opened together, the combination fused in: lane i < part = N / SIDES forms, for each side s,
+//     u_s = sum_j c_j f_j[i + s part]
+// by lincomb_at (mle_kernels.cuh: raw products into 64-bit columns, a normalisation per kRawCarryEvery of them, ONE reduction per side, the
+// coefficients read from the argument block where they are used), one side after the other so that one accumulator is live at a time, and
+// then applies fri_ml_fold_kernel's fold (SIDES = 2: u_0, u_1) or fri_ml_fold4_kernel's (SIDES = 4: u_0, u_2 and u_1, u_3, then the pair)
+// to the canonical u_s.  The k N entries are read once and N / SIDES written; the combined layer never exists in memory.  Layer 0 only:
+// w^-i is the table's entry i.
+// Every fold here is s / 2 + g (w (a - b) - c s) with g as a Multiplier in registers (8 argument words), the form of fri_ml_fold4_kernel's
+// second stage, and NOT the 81 rows of a FriUni: beside the combination's pointers and coefficients the rows do not fit the scalar
+// registers (106 with 50 spilled into lanes and a private segment, profiles/fri_ml_batch).  Each result is the canonical residue of the
+// value the rows give, so the table is byte for byte the one the single-table kernels leave on zk_mle_linear_combination's output.
+// g0 = r0 / (2 c); SIDES = 4: g1 = r1 / (2 c^2) and c.c2 = c^2, not read otherwise.
+constexpr int kFriMlBatchMax = 16;                           // ZK_FRI_ML_BATCH_MAX
+constexpr int kFriMlBatchBlocks = 768;                       // three workgroups a compute unit
+template <class F> struct FriMlBatchArgs {
+    const void *t[kFriMlBatchMax];                           // the k codewords (one may appear more than once)
+    Fe<F> c[kFriMlBatchMax];                                 // lincomb_coeff of the k coefficients
+    int k;
+};
+// one fold: s / 2 + g (w (a - b) - c s), s = a + b
+template <class F, bool COSET> __device__ __forceinline__ Fe<F> fri_ml_fold_by(const Multiplier<F> &g, const Ufe<F> &w, const Fe<F> &a, const Fe<F> &b, const Fe<F> &c) {
+    const Fe<F> s = fe_add<F>(a, b);
+    Fe<F> t = fe_mul_u_pre<F>(w, fe_sub<F>(a, b));
+    if constexpr (COSET) t = fe_sub<F>(t, Multiplier<F>(c).times(s));
+    else t = fe_sub<F>(t, s);
+    return fe_add<F>(fe_halve<F>(s), g.times(t));
+}
+template <class F, int SIDES, bool COSET> __global__ void __launch_bounds__(kFriBlock) fri_ml_fold_batch_kernel(FriMlBatchArgs<F> a, void *__restrict__ out, size_t part,
+                                                                                                          const void *__restrict__ pw_lo,
+                                                                                                          const void *__restrict__ pw_hi,
+                                                                                                          FriMlShift2<F, COSET> c, Fe<F> g0, Fe<F> g1) {
+    static_assert(SIDES == 2 || SIDES == 4, "a fold by 2 or by 4");
+    const size_t stride = (size_t)gridDim.x * kFriBlock;
+    Fe<F> c1 = g0, c2 = g0;                                  // the shifts; not read without a coset
+    if constexpr (COSET) {
+        c1 = c.c;
+        c2 = c.c2;
+    }
+    for (size_t i = (size_t)blockIdx.x * kFriBlock + threadIdx.x; i < part; i += stride) {
+        const Multiplier<F> m0(g0);
+        if constexpr (SIDES == 2) {
+            const Fe<F> u0 = lincomb_at<F>(a, i), u1 = lincomb_at<F>(a, i + part);
+            fe_store<F>(out, i, fri_ml_fold_by<F, COSET>(m0, ntt_pow2t<F>(pw_lo, pw_hi, (uint64_t)i), u0, u1, c1));
+        } else {                                              // each pair is folded as soon as it is there: two sides and one fold live
+            const Fe<F> u0 = lincomb_at<F>(a, i), u2 = lincomb_at<F>(a, i + 2 * part);
+            const Fe<F> v0 = fri_ml_fold_by<F, COSET>(m0, ntt_pow2t<F>(pw_lo, pw_hi, (uint64_t)i), u0, u2, c1);
+            const Fe<F> u1 = lincomb_at<F>(a, i + part), u3 = lincomb_at<F>(a, i + 3 * part);
+            const Fe<F> v1 = fri_ml_fold_by<F, COSET>(m0, ntt_pow2t<F>(pw_lo, pw_hi, (uint64_t)(i + part)), u1, u3, c1);
+            fe_store<F>(out, i, fri_ml_fold_by<F, COSET>(Multiplier<F>(g1), ntt_pow2t<F>(pw_lo, pw_hi, (uint64_t)i << 1), v0, v1, c2));
+        }
+    }
 }
 
 }  // namespace zk

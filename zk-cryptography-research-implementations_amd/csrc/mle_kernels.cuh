@@ -608,7 +608,8 @@ template <class F> struct LinCombArgs {
 };
 // the coefficient in the scan's form: entry (x R_std) times (c R_u), divided by R_u once, is (c x) R_std -- the stored form of the product
 template <class F> ZK_HD Fe<F> lincomb_coeff(const Fe<F> &c_std) { return u_to_limbs32<F>(u_reduce_once<F>(u_from_std<F>(c_std))); }
-template <class F> __device__ __forceinline__ Fe<F> lincomb_at(const LinCombArgs<F> &a, size_t i) {
+// `Args`: LinCombArgs, or another block of the same three members with fewer slots (fri_ml.cuh FriMlBatchArgs)
+template <class F, class Args> __device__ __forceinline__ Fe<F> lincomb_at(const Args &a, size_t i) {
     RawAcc<F> ra;
 #pragma unroll
     for (int c = 0; c < 2 * UParams<F>::L; c++) ra.c[c] = 0;

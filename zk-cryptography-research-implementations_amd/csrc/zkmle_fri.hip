@@ -173,15 +173,24 @@ template <class F> Replayed<F> replay(uint32_t d, uint32_t b, uint32_t f, uint32
         tr.append_be<F>(e);
         return e;
     };
-    uint8_t cbe[32], be[8];
+    uint8_t cbe[32], be[16] = {'B', 'T', 'C', 'H'};
+    const unsigned nt = ml ? ml->ntables : 0;                 // commitments opened together: their roots lead `roots`
     host_to_bytes_be<F>(coset ? load_host<F>(coset) : fe_one<F>(), cbe);
     transcript_header(tr, d, b, f, Q, cbe);
-    if (sc.log_arity == 2) {                                 // the arity, and behind it a 1 when the leaves are grouped
-        put_be32(be, sc.log_arity);
-        put_be32(be + 4, 1);
-        tr.append(be, sc.grouped ? 8 : 4);
+    if (nt) {                                                // the tag, the arity, the grouped flag, k; the k roots
+        put_be32(be + 4, sc.log_arity);
+        put_be32(be + 8, sc.grouped ? 1 : 0);
+        put_be32(be + 12, nt);
+        tr.append(be, 16);
+        tr.append(roots, (size_t)32 * nt);
+    } else {
+        if (sc.log_arity == 2) {                             // the arity, and behind it a 1 when the leaves are grouped
+            put_be32(be, sc.log_arity);
+            put_be32(be + 4, 1);
+            tr.append(be, sc.grouped ? 8 : 4);
+        }
+        tr.append(roots, 32);
     }
-    tr.append(roots, 32);
     if (ml && ml->npoints == 0) {                            // z_0 .. z_{d-1}, then y
         for (unsigned i = 0; i < d; i++) absorb(ml->z + (size_t)i * W);
         absorb(ml->y);
@@ -190,21 +199,22 @@ template <class F> Replayed<F> replay(uint32_t d, uint32_t b, uint32_t f, uint32
         put_be32(be, ml->npoints);
         tr.append(be, 4);
         for (size_t i = 0; i < P * d; i++) absorb(ml->z + i * W);
-        for (size_t p = 0; p < P; p++) absorb(ml->y + p * W);
+        for (size_t p = 0; p < P * (nt ? nt : 1); p++) absorb(ml->y + p * W);   // several tables: table-major
         rp.gamma = tr.random_challenge_as_field_element<F>();
     }
     rp.beta.resize(R);
     for (unsigned l = 0, s = 0; l < R; l++) {
         for (unsigned k = 0; ml && k < 3; k++) absorb(ml->round_polys + ((size_t)l * 3 + k) * W);   // g_l(0), g_l(1), g_l(2)
         rp.beta[l] = tr.random_challenge_as_field_element<F>();
-        if (s + 1 < sc.nsteps && sc.step[s + 1].layer == l + 1) tr.append(roots + 32 * sc.step[++s].root, 32);   // layer l + 1 is committed
+        if (s + 1 < sc.nsteps && sc.step[s + 1].layer == l + 1) tr.append(roots + 32 * (size_t)(sc.step[++s].root + (nt ? nt - 1 : 0)), 32);   // layer l + 1 is committed
     }
     for (size_t j = 0; j < (size_t)1 << f; j++) rp.h.push_back(absorb(final_coeffs + j * W));
     for (unsigned q = 0; q < Q; q++) rp.idx.push_back(sample_index(tr, sc.index_bits()));
     return rp;
 }
 
-// the sumcheck of sum_x T[x] W[x] = sum_p gamma^p y_p beside the folds, on the same challenges; the single-point form is one point with gamma^0
+// the sumcheck of sum_x T[x] W[x] = sum_p gamma^p y_p beside the folds, on the same challenges; the single-point form is one point with gamma^0.
+// k tables together: T = sum_j alpha^j T_j, alpha = gamma^P, so only the first claim differs: sum_j sum_p gamma^(j P + p) y_{j,p}
 template <class F> bool sumcheck_holds(uint32_t d, uint32_t f, const FriMlClaim &ml, const Replayed<F> &rp) {
     constexpr int W = F::N / 2;
     const unsigned R = d - f, np = ml.npoints ? ml.npoints : 1;
@@ -212,9 +222,11 @@ template <class F> bool sumcheck_holds(uint32_t d, uint32_t f, const FriMlClaim 
     const Fe<F> one = fe_one<F>(), two = fe_from_u64<F>(2), inv2 = fe_inv<F>(two);
     std::vector<Fe<F>> A(np, one);                            // per point p: gamma^p A^p_l
     Fe<F> claim = fe_zero<F>();
-    for (unsigned p = 0; p < np; p++) {
-        if (p) A[p] = fe_mul<F>(A[p - 1], rp.gamma);
-        claim = fe_add<F>(claim, fe_mul<F>(A[p], load_host<F>(ml.y + (size_t)p * W)));
+    for (unsigned p = 1; p < np; p++) A[p] = fe_mul<F>(A[p - 1], rp.gamma);
+    Fe<F> gp = one;                                           // gamma^(j P + p)
+    for (size_t t = 0; t < (size_t)np * (ml.ntables ? ml.ntables : 1); t++) {
+        claim = fe_add<F>(claim, fe_mul<F>(gp, load_host<F>(ml.y + t * W)));
+        gp = fe_mul<F>(gp, rp.gamma);
     }
     for (unsigned l = 0; l < R; l++) {
         const uint64_t *g = ml.round_polys + (size_t)l * 3 * W;
@@ -245,8 +257,10 @@ template <class F> bool sumcheck_holds(uint32_t d, uint32_t f, const FriMlClaim 
 
 // every query: its steps' paths (grouped: each step's one path from the leaf over its sides), and each step's fold against the next step's value (the last against the final polynomial).  `lagrange`: the
 // fold of the multilinear forms, (1 - r) (a + b) / 2 + r (a - b) / (2 x); else the monomial (a + b) / 2 + r (a - b) / (2 x)
+// `nt` > 0 (commitments opened together): step 0 of a query holds the nt commitments' values and paths one commitment after the other, each
+// checked against its own root (roots[j]); the step's values are u_side = sum_j alpha^j v_{j,side}; the later steps' roots follow the nt
 template <class F> int queries_hold(const FriSchedule &sc, unsigned R, bool lagrange, const Fe<F> &c, const Replayed<F> &rp, const uint8_t *roots,
-                                    const uint64_t *values, const uint8_t *paths, int *ok) {
+                                    const uint64_t *values, const uint8_t *paths, int *ok, unsigned nt = 0, const Fe<F> &alpha = fe_one<F>()) {
     constexpr int W = F::N / 2;
     const unsigned L = sc.step[0].log_len;
     const Fe<F> w = root_of_unity<F>(L), winv = fe_inv<F>(w), inv2 = fe_inv<F>(fe_from_u64<F>(2));
@@ -263,28 +277,33 @@ template <class F> int queries_hold(const FriSchedule &sc, unsigned R, bool lagr
         if (lagrange) even = fe_mul<F>(fe_sub<F>(fe_one<F>(), r), even);
         return fe_mul<F>(inv2, fe_add<F>(even, fe_mul<F>(fe_mul<F>(r, xinv), fe_sub<F>(a, bb))));
     };
+    // step 0's share of one query's answer, and what the further commitments add in front of the later steps
+    const size_t v0 = sc.nsteps > 1 ? sc.step[1].val_off : sc.nvalues, d0 = sc.nsteps > 1 ? sc.step[1].path_off : sc.ndigests;
+    const size_t more = nt ? nt - 1 : 0, more_v = more * v0, more_d = more * d0;
     for (size_t q = 0; q < rp.idx.size(); q++) {
-        const uint64_t *vq = values + q * sc.nvalues * W;
-        const uint8_t *pq = paths + q * sc.ndigests * 32;
+        const uint64_t *vq = values + q * (sc.nvalues + more_v) * W;
+        const uint8_t *pq = paths + q * (sc.ndigests + more_d) * 32;
         for (unsigned s = 0; s < sc.nsteps; s++) {
             const FriStep &st = sc.step[s];
             const unsigned l = st.layer, sides = 1u << st.log_sides;
             const size_t part = ((size_t)1 << st.log_len) >> st.log_sides, j = rp.idx[q] & (part - 1);
-            const uint64_t *v = vq + st.val_off * W;
-            Fe<F> e[4];
-            if (sc.grouped) {                                 // one leaf over the step's sides, one path
-                int ok_s = 0;
-                ZK_TRY(zk_merkle_verify_grouped(F::ID, roots + 32 * st.root, st.log_len - st.log_sides, j, st.log_sides, v, pq + 32 * st.path_off, &ok_s));
-                if (!ok_s) return ZK_OK;
-            }
-            for (unsigned side = 0; side < sides; side++) {
-                int ok_s = sc.grouped;
-                if (!sc.grouped) {
-                    ZK_TRY(zk_merkle_verify(F::ID, roots + 32 * st.root, st.log_len, j + side * part, v + (size_t)side * W,
-                                            pq + 32 * (st.path_off + (size_t)side * st.log_len), &ok_s));
+            Fe<F> e[4] = {fe_zero<F>(), fe_zero<F>(), fe_zero<F>(), fe_zero<F>()}, aj = fe_one<F>();
+            for (size_t tb = 0; tb < (s == 0 ? more + 1 : 1); tb++) {   // the commitments of step 0; one table otherwise
+                const uint64_t *v = vq + (st.val_off + (s ? more_v : tb * v0)) * W;
+                const uint8_t *pt = pq + 32 * (st.path_off + (s ? more_d : tb * d0)), *root = roots + 32 * (s ? st.root + more : tb);
+                if (sc.grouped) {                             // one leaf over the step's sides, one path
+                    int ok_s = 0;
+                    ZK_TRY(zk_merkle_verify_grouped(F::ID, root, st.log_len - st.log_sides, j, st.log_sides, v, pt, &ok_s));
+                    if (!ok_s) return ZK_OK;
                 }
-                if (!ok_s) return ZK_OK;
-                e[side] = load_host<F>(v + (size_t)side * W);
+                for (unsigned side = 0; side < sides; side++) {
+                    int ok_s = sc.grouped;
+                    if (!sc.grouped) ZK_TRY(zk_merkle_verify(F::ID, root, st.log_len, j + side * part, v + (size_t)side * W, pt + 32 * (size_t)side * st.log_len, &ok_s));
+                    if (!ok_s) return ZK_OK;
+                    const Fe<F> x = load_host<F>(v + (size_t)side * W);
+                    e[side] = nt ? fe_add<F>(e[side], fe_mul<F>(aj, x)) : x;
+                }
+                if (nt) aj = fe_mul<F>(aj, alpha);
             }
             const Fe<F> xinv = fe_mul<F>(cinv[l], fe_pow<F>(winv, (uint64_t)j << l));
             Fe<F> got;
@@ -293,7 +312,7 @@ template <class F> int queries_hold(const FriSchedule &sc, unsigned R, bool lagr
             Fe<F> want;                                       // the step lands in layer l + log_sides: j is a position of it
             if (s + 1 < sc.nsteps) {
                 const FriStep &nx = sc.step[s + 1];
-                want = load_host<F>(vq + (nx.val_off + j / (((size_t)1 << nx.log_len) >> nx.log_sides)) * W);
+                want = load_host<F>(vq + (nx.val_off + more_v + j / (((size_t)1 << nx.log_len) >> nx.log_sides)) * W);
             } else want = uni_evaluate<F>(rp.h, fe_mul<F>(cR, fe_pow<F>(w, (uint64_t)j << R)));
             if (!fe_eq<F>(got, want)) return ZK_OK;
         }
@@ -310,9 +329,13 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
     Replayed<F> rp = replay<F>(d, b, f, Q, coset, tr, sc, roots, final_coeffs, ml);
     if (indices_out) memcpy(indices_out, rp.idx.data(), Q * 8);
     *ok = 0;
-    for (size_t k = 0; rp.good && k < (size_t)Q * sc.nvalues; k++) rp.good = is_reduced<F>(values + k * (F::N / 2));
+    const unsigned nt = ml ? ml->ntables : 0;
+    const size_t per = sc.nvalues + (nt ? nt - 1 : 0) * (sc.nsteps > 1 ? sc.step[1].val_off : sc.nvalues);   // values of one query's answer
+    for (size_t k = 0; rp.good && k < (size_t)Q * per; k++) rp.good = is_reduced<F>(values + k * (F::N / 2));
     if (!rp.good || (ml && !sumcheck_holds<F>(d, f, *ml, rp))) return ZK_OK;
-    return queries_hold<F>(sc, d - f, ml != nullptr, coset ? load_host<F>(coset) : fe_one<F>(), rp, roots, values, paths, ok);
+    Fe<F> alpha = fe_one<F>();                                // gamma^P
+    for (unsigned p = 0; nt && p < ml->npoints; p++) alpha = fe_mul<F>(alpha, rp.gamma);
+    return queries_hold<F>(sc, d - f, ml != nullptr, coset ? load_host<F>(coset) : fe_one<F>(), rp, roots, values, paths, ok, nt, alpha);
 }
 
 }  // namespace
@@ -324,6 +347,7 @@ int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_fin
     if (ml && (!ml->z || !ml->y || !ml->round_polys || ml->npoints > 8)) return ZK_E_ARG;
     if (ml && (ml->log_arity < 1 || ml->log_arity > 2 || (ml->log_arity == 2 && (ml->npoints < 1 || log_final >= d || d - log_final < 2)))) return ZK_E_ARG;
     if (ml && ml->grouped && ml->log_arity != 2) return ZK_E_ARG;
+    if (ml && (ml->ntables > ZK_FRI_ML_BATCH_MAX || (ml->ntables && ml->npoints < 1))) return ZK_E_ARG;
     if (!roots || !final_coeffs || !query_values || !query_paths || !ok || field_limbs64(field) < 0) return ZK_E_ARG;
     ZK_TRY(params_check(log_blowup, nqueries));
     if (coset && is_zero_element(field, coset)) return ZK_E_ARG;

@@ -73,6 +73,55 @@ template <class F> int fold4_once(const zk_table *cw, const uint64_t *r0, const 
     return ZK_OK;
 }
 
+// out[i], i < len / sides, from the k codewords of `len` entries each: the fold (g1 null) or fold4 of sum_j coef_j f_j at layer 0, one pass.
+// coef: k stored-form elements.  g0 = r0 / (2 c), g1 = r1 / (2 c^2), c = the coset's shift (null: 1)
+template <class F> int launch_fold_batch(const void *const *cws, unsigned k, const Fe<F> *coef, void *out, size_t len, const FoldTables<F> &tb, const Fe<F> &g0,
+                                         const Fe<F> *g1, const Fe<F> *c) {
+    FriMlBatchArgs<F> a{};
+    for (unsigned j = 0; j < k; j++) {
+        a.t[j] = cws[j];
+        a.c[j] = lincomb_coeff<F>(coef[j]);
+    }
+    a.k = (int)k;
+    const size_t part = g1 ? len / 4 : len / 2, want = (part + kFriBlock - 1) / kFriBlock;
+    const unsigned blocks = (unsigned)(want < (size_t)kFriMlBatchBlocks ? want : (size_t)kFriMlBatchBlocks);
+    const Fe<F> gg1 = g1 ? *g1 : fe_one<F>();
+    if (c) {
+        const FriMlShift2<F, true> sh{*c, fe_sqr<F>(*c)};
+        if (g1) fri_ml_fold_batch_kernel<F, 4, true><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, sh, g0, gg1);
+        else fri_ml_fold_batch_kernel<F, 2, true><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, sh, g0, gg1);
+    } else {
+        if (g1) fri_ml_fold_batch_kernel<F, 4, false><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, FriMlShift2<F, false>{}, g0, gg1);
+        else fri_ml_fold_batch_kernel<F, 2, false><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, FriMlShift2<F, false>{}, g0, gg1);
+    }
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+
+template <class F> int fold_batch_once(const zk_table *const *cws, unsigned k, const uint64_t *coeffs, const uint64_t *r0, const uint64_t *r1, const uint64_t *coset,
+                                       zk_table **out) {
+    constexpr int W = F::N / 2;
+    const size_t len = cws[0]->len;
+    FoldTables<F> tb;
+    ZK_TRY(tb.build(ilog2(len)));
+    const Fe<F> two = fe_from_u64<F>(2), c = coset ? load_host<F>(coset) : fe_one<F>();
+    const Fe<F> g0 = fe_mul<F>(load_host<F>(r0), fe_inv<F>(fe_mul<F>(two, c)));
+    Fe<F> g1 = fe_one<F>();
+    if (r1) g1 = fe_mul<F>(load_host<F>(r1), fe_inv<F>(fe_mul<F>(two, fe_sqr<F>(c))));
+    const void *ptrs[kFriMlBatchMax];
+    Fe<F> coef[kFriMlBatchMax];
+    for (unsigned j = 0; j < k; j++) {
+        ptrs[j] = cws[j]->dptr;
+        coef[j] = load_host<F>(coeffs + (size_t)j * W);
+    }
+    zk_table *o = nullptr;
+    ZK_TRY(zk_table_alloc(cws[0]->field, r1 ? len / 4 : len / 2, &o));
+    const int rc = launch_fold_batch<F>(ptrs, k, coef, o->dptr, len, tb, g0, r1 ? &g1 : nullptr, coset ? &c : nullptr);
+    if (rc != ZK_OK) { zk_table_free(o); return rc; }
+    *out = o;
+    return ZK_OK;
+}
+
 // ---- the passes ----------------------------------------------------------------------------------------------------------------
 // sums (device, 2 elements) = S_0, S_1 of the pass; FOLD: see fri_ml_round_kernel.  Launches only.
 template <class F> int launch_round(bool fold, const void *tin, const void *ein, void *tout, void *eout, size_t q, const Fe<F> &r, void *partials, void *sums) {
@@ -142,7 +191,7 @@ struct PassMem {
     void *partials, *sums;
 };
 
-// The two forms of the opening.  The driver (open_with) owns everything they share; a form supplies what defines its protocol:
+// The three forms of the opening.  The driver (open_with) owns everything they share; a form supplies what defines its protocol:
 //   kSums                      the sums a pass leaves
 //   weight_room / weight_off   the elements its weight tables take for a table of n entries, and where round l's table starts
 //   absorb                     what enters the transcript between root_0 and round 0
@@ -150,11 +199,15 @@ struct PassMem {
 //   pass                       a round's launches
 //   round_poly                 g_l(0), g_l(1), g_l(2) from the last pass's sums S
 //   bind                       the challenge's effect on the form's own state
+//   kBatch                     ManyTables only, which then also supplies: statement (the tag and the k roots in place of the arity line and
+//                              the single root), ntables, fold0 (the first step's fold, of the k codewords) and layer0 (where a query's
+//                              step-0 answers come from)
 
 // one point z: an eq table of (z_0 .. z_{d-2}) with the last variable summed out, S_0 and S_1, and g_l formed here from A_l, eq1 and the sums
 template <class F> struct OnePoint {
     static constexpr int W = F::N / 2;
     static constexpr unsigned kSums = 2;
+    static constexpr bool kBatch = false;
     const uint64_t *z;
     uint64_t *y_out;
     unsigned d;
@@ -194,6 +247,7 @@ template <class F> struct OnePoint {
 template <class F> struct ManyPoints {
     static constexpr int W = F::N / 2;
     static constexpr unsigned kSums = 3;
+    static constexpr bool kBatch = false;
     const uint64_t *pts;
     uint32_t P;
     uint64_t *ys_out, *gamma_out;
@@ -209,7 +263,6 @@ template <class F> struct ManyPoints {
         for (size_t i = 0; i < (size_t)P * d; i++) tr.append_be<F>(load_host<F>(pts + i * W));
     }
     int start(const zk_fri_commitment *cm, Transcript &tr, const PassMem &m) {
-        constexpr size_t ESZ = sizeof(Fe<F>);
         const size_t n = (size_t)1 << d;
         // y_p = zk_mle_evaluate(T, z^p), a pass each; they are absorbed before gamma exists
         for (unsigned p = 0; p < P; p++) {
@@ -218,7 +271,14 @@ template <class F> struct ManyPoints {
         }
         const Fe<F> gamma = tr.random_challenge_as_field_element<F>();
         if (gamma_out) store_host<F>(gamma_out, gamma);
-        // W_0: one point's table is built in place, several are combined in one pass
+        ZK_TRY(weights(gamma, m));
+        // round 0's pass reads the commitment's own coefficient table and W_0 and writes neither
+        return pass(false, m.T0, m.weights, nullptr, nullptr, n / 2, fe_one<F>(), m.partials, m.sums);
+    }
+    // W_0 = sum_p gamma^p eq(., z^p) into m.weights: one point's table is built in place, several are combined in one pass
+    int weights(const Fe<F> &gamma, const PassMem &m) {
+        constexpr size_t ESZ = sizeof(Fe<F>);
+        const size_t n = (size_t)1 << d;
         eqb.resize(P);
         if (P == 1) {
             ZK_TRY(eqb[0].build(pts, d, m.weights));
@@ -234,8 +294,7 @@ template <class F> struct ManyPoints {
             }
             ZK_HIP((lincomb_launch<F, false>(tabs, P, coef, m.weights, n, fe_zero<F>(), fe_zero<F>(), nullptr, cur_stream())));
         }
-        // round 0's pass reads the commitment's own coefficient table and W_0 and writes neither
-        return pass(false, m.T0, m.weights, nullptr, nullptr, n / 2, fe_one<F>(), m.partials, m.sums);
+        return ZK_OK;
     }
     void release() { for (auto &e : eqb) e.release(); }
     static int pass(bool fold, const void *tin, const void *win, void *tout, void *wout, size_t q, const Fe<F> &r, void *partials, void *sums) {
@@ -244,6 +303,140 @@ template <class F> struct ManyPoints {
     void round_poly(unsigned, const Fe<F> *S, Transcript &, Fe<F> g[3]) const { nodes_to_g3<F>(S, g); }
     void bind(unsigned, const Fe<F> &) {}
 };
+
+// k commitments at the same P points ("FRI commitments opened together"): ManyPoints on T = sum_j alpha^j T_j, alpha = gamma^P.  T_0 is
+// written into n further elements behind the weights (round 1 reads it anyway); f_0 = sum_j alpha^j f_j is never stored: the first step's
+// fold forms it in registers (fri_ml_fold_batch_kernel), and a query's step-0 answers come from the k commitments' own codewords and trees.
+template <class F> struct ManyTables : ManyPoints<F> {
+    using Base = ManyPoints<F>;
+    static constexpr int W = F::N / 2;
+    static constexpr bool kBatch = true;
+    const zk_fri_commitment *const *cms;
+    uint32_t k;
+    Fe<F> coef[kFriMlBatchMax];                              // alpha^j
+    void *table0 = nullptr;                                  // T_0's n elements of the pool block: the driver sets it before start
+
+    ManyTables(const zk_fri_commitment *const *cms_, uint32_t k_, const uint64_t *pts_, uint32_t P_, uint64_t *ys, uint64_t *gamma, unsigned d_)
+        : Base{pts_, P_, ys, gamma, d_, {}}, cms(cms_), k(k_) {}
+    unsigned ntables() const { return k; }
+    size_t weight_room(size_t n) const { return Base::weight_room(n) + n; }   // the base's, then T_0
+    size_t table0_off(size_t n) const { return Base::weight_room(n); }        // in elements from the weights
+    // "BTCH", a, the grouped flag, k; the k roots, which are also the proof's first k
+    void statement(Transcript &tr, unsigned la, bool grouped, uint8_t *roots) const {
+        uint8_t tag[16] = {'B', 'T', 'C', 'H'};
+        put_be32(tag + 4, la);
+        put_be32(tag + 8, grouped ? 1 : 0);
+        put_be32(tag + 12, k);
+        tr.append(tag, sizeof tag);
+        for (uint32_t j = 0; j < k; j++) {
+            memcpy(roots + 32 * (size_t)j, cms[j]->root, 32);
+            tr.append(cms[j]->root, 32);
+        }
+    }
+    // y_{j,p} table-major, a pass each; gamma; W_0; T_0 = sum_j alpha^j T_j in one pass; round 0's pass on T_0 and W_0
+    int start(const zk_fri_commitment *, Transcript &tr, const PassMem &m) {
+        const unsigned P = this->P, d = this->d;
+        const size_t n = (size_t)1 << d;
+        for (uint32_t j = 0; j < k; j++) {
+            for (unsigned p = 0; p < P; p++) {
+                uint64_t *y = this->ys_out + ((size_t)j * P + p) * W;
+                ZK_TRY(zk_mle_evaluate(cms[j]->coeffs, this->pts + (size_t)p * d * W, d, y));
+                tr.append_be<F>(load_host<F>(y));
+            }
+        }
+        const Fe<F> gamma = tr.random_challenge_as_field_element<F>();
+        if (this->gamma_out) store_host<F>(this->gamma_out, gamma);
+        Fe<F> alpha = fe_one<F>();
+        for (unsigned p = 0; p < P; p++) alpha = fe_mul<F>(alpha, gamma);
+        const void *tabs[kFriMlBatchMax];
+        uint64_t cw[kFriMlBatchMax * W];
+        Fe<F> aj = fe_one<F>();
+        for (uint32_t j = 0; j < k; j++) {
+            coef[j] = aj;
+            store_host<F>(cw + (size_t)j * W, aj);
+            tabs[j] = cms[j]->coeffs->dptr;
+            aj = fe_mul<F>(aj, alpha);
+        }
+        ZK_TRY(this->weights(gamma, m));
+        ZK_HIP((lincomb_launch<F, false>(tabs, k, cw, table0, n, fe_zero<F>(), fe_zero<F>(), nullptr, cur_stream())));
+        return Base::pass(false, m.T0, m.weights, nullptr, nullptr, n / 2, fe_one<F>(), m.partials, m.sums);
+    }
+    // layer 0 -> the layer of step 1: out gets len / 2 entries (g1 null) or len / 4
+    int fold0(void *out, size_t len, const FoldTables<F> &tb, const Fe<F> &g0, const Fe<F> *g1, const Fe<F> *shift) const {
+        const void *cws[kFriMlBatchMax];
+        for (uint32_t j = 0; j < k; j++) cws[j] = cms[j]->codeword->dptr;
+        return launch_fold_batch<F>(cws, k, coef, out, len, tb, g0, g1, shift);
+    }
+};
+
+// The queries of an opening of k commitments.  Step 0 has no table and no tree of its own: its answers are the k commitments', gathered by
+// the existing kernels once per commitment over a one-step view of the schedule, and once more over the steps from 1 up; every launch
+// writes its own part of one device block and the host lays a query's answer out as the protocol orders it (j-major for step 0, then the
+// later steps).  The alternative, a table of layer-0 sources inside FriLayers, would add 32 pointers to the argument block of both kernels
+// and a branch to every lane of the single-table provers for the sake of k - 1 small launches here.
+template <class F> int answer_queries_batch(Transcript &tr, const zk_fri_commitment *const *cms, unsigned k, const FriLayers &fl, const FriSchedule &sc, uint32_t Q,
+                                            uint64_t *indices_out, uint64_t *values, uint8_t *paths, Events &ev, float *ms) {
+    constexpr size_t ESZ = sizeof(Fe<F>);
+    std::vector<uint64_t> idx(Q);
+    for (unsigned q = 0; q < Q; q++) idx[q] = sample_index(tr, sc.index_bits());
+    if (indices_out) memcpy(indices_out, idx.data(), Q * 8);
+    // the two views: step 0 alone (its table and tree set per commitment), and the steps from 1 up with their offsets counted from step 1
+    const size_t v0 = sc.nsteps > 1 ? sc.step[1].val_off : sc.nvalues, d0 = sc.nsteps > 1 ? sc.step[1].path_off : sc.ndigests;
+    const size_t v1 = sc.nvalues - v0, d1 = sc.ndigests - d0;
+    FriLayers first = sc.layers(0, 1), rest{};
+    if (sc.nsteps > 1) rest = sc.layers(1);
+    for (unsigned s = 1; s < sc.nsteps; s++) {
+        rest.table[s - 1] = fl.table[s];
+        rest.tree[s - 1] = fl.tree[s];
+    }
+    const size_t nval = (size_t)Q * (k * v0 + v1), ndig = (size_t)Q * (k * d0 + d1);
+    DevBuf didx, dval, dpath;
+    ZK_TRY(didx.alloc(Q * 8));
+    ZK_TRY(dval.alloc(nval * ESZ));
+    ZK_TRY(dpath.alloc(ndig * 32));
+    std::vector<uint64_t> hval(nval * (ESZ / 8));
+    std::vector<uint8_t> hpath(ndig * 32);
+    size_t q0, q1;
+    ZK_TRY(ev.mark(&q0));
+    ZK_HIP(hipMemcpyAsync(didx.p, idx.data(), Q * 8, hipMemcpyHostToDevice, cur_stream()));
+    const auto gather = [&](const FriLayers &view, size_t nv, size_t nd, size_t voff, size_t doff) -> int {
+        fri_query_values_kernel<F><<<(unsigned)((nv + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(view, (const uint64_t *)didx.p, Q, (char *)dval.p + voff * ESZ);
+        ZK_HIP(hipGetLastError());
+        fri_query_paths_kernel<<<(unsigned)((nd + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(view, (const uint64_t *)didx.p, Q, (uint64_t *)((char *)dpath.p + doff * 32));
+        ZK_HIP(hipGetLastError());
+        return ZK_OK;
+    };
+    // the downloads land in this function's own buffers: whatever fails below, the stream is drained before they go
+    const auto run = [&]() -> int {
+        for (unsigned j = 0; j < k; j++) {
+            first.table[0] = cms[j]->codeword->dptr;
+            first.tree[0] = cms[j]->levels;
+            ZK_TRY(gather(first, (size_t)Q * v0, (size_t)Q * d0, (size_t)j * Q * v0, (size_t)j * Q * d0));
+        }
+        if (sc.nsteps > 1) ZK_TRY(gather(rest, (size_t)Q * v1, (size_t)Q * d1, (size_t)k * Q * v0, (size_t)k * Q * d0));
+        ZK_HIP(hipMemcpyAsync(hval.data(), dval.p, nval * ESZ, hipMemcpyDeviceToHost, cur_stream()));
+        ZK_HIP(zk::memcpy_on_stream(hpath.data(), dpath.p, ndig * 32, hipMemcpyDeviceToHost));
+        ZK_TRY(ev.mark(&q1));
+        ZK_HIP(hipEventSynchronize(ev.ev[q1]));
+        return ZK_OK;
+    };
+    const int rc = run();
+    if (rc != ZK_OK) {
+        (void)hipStreamSynchronize(cur_stream());
+        return rc;
+    }
+    if (ms) *ms = ev.ms(q0, q1);
+    const size_t pv = k * v0 + v1, pd = k * d0 + d1;          // of one query's answer
+    for (size_t q = 0; q < Q; q++) {
+        for (unsigned j = 0; j < k; j++) {
+            memcpy((char *)values + (q * pv + j * v0) * ESZ, (const char *)hval.data() + ((size_t)j * Q + q) * v0 * ESZ, v0 * ESZ);
+            memcpy(paths + (q * pd + j * d0) * 32, hpath.data() + ((size_t)j * Q + q) * d0 * 32, d0 * 32);
+        }
+        memcpy((char *)values + (q * pv + k * v0) * ESZ, (const char *)hval.data() + ((size_t)k * Q * v0 + q * v1) * ESZ, v1 * ESZ);
+        memcpy(paths + (q * pd + k * d0) * 32, hpath.data() + ((size_t)k * Q * d0 + q * d1) * 32, d1 * 32);
+    }
+    return ZK_OK;
+}
 
 // The opening: the sumcheck's rounds interleaved with the folds of the codeword, on the same challenges.  la = log_arity.  1: every layer
 // f_1 .. f_{R-1} is committed.  2 (R >= 2): the even ones are; after r_l with l even only round l + 1's pass runs, after r_{l+1} the fold by 4
@@ -260,17 +453,23 @@ template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &
     const Fe<F> one = fe_one<F>(), c = cm->has_coset ? load_host<F>(cm->coset) : one;
     const FriSchedule sc(L, R, la, grouped);
 
-    // the header, (the arity when it is not 1,) root_0, the form's claim
+    // the header, (the arity when it is not 1,) root_0, the form's claim; several tables: the header, the form's tag and roots, its claim
     uint8_t cbe[32], abe[8];
     host_to_bytes_be<F>(c, cbe);
     transcript_header(tr, d, b, f, Q, cbe);
-    if (la == 2) {
-        put_be32(abe, la);
-        put_be32(abe + 4, 1);
-        tr.append(abe, grouped ? 8 : 4);
+    unsigned root_shift = 0;                                  // the roots in front of the later layers' beyond root_0
+    if constexpr (Form::kBatch) {
+        form.statement(tr, la, grouped, o.roots);
+        root_shift = form.ntables() - 1;
+    } else {
+        if (la == 2) {
+            put_be32(abe, la);
+            put_be32(abe + 4, 1);
+            tr.append(abe, grouped ? 8 : 4);
+        }
+        memcpy(o.roots, cm->root, 32);
+        tr.append(cm->root, 32);
     }
-    memcpy(o.roots, cm->root, 32);
-    tr.append(cm->root, 32);
     form.absorb(tr);
 
     // one block: T_1 .. T_R (below n elements), the form's weights, the committed layers below R (C = their N >> l entries together: below N
@@ -289,11 +488,13 @@ template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &
     DevBuf blk;
     ZK_TRY(blk.alloc(total * ESZ));
     char *base = (char *)blk.p;
-    auto T_at = [&](unsigned l) -> void * { return l == 0 ? cm->coeffs->dptr : base + (n - (n >> (l - 1))) * ESZ; };          // n >> l entries
+    void *T0 = cm->coeffs->dptr;                              // several tables: their combination, behind the weights
+    if constexpr (Form::kBatch) T0 = form.table0 = base + (off_w + form.table0_off(n)) * ESZ;
+    auto T_at = [&](unsigned l) -> void * { return l == 0 ? T0 : base + (n - (n >> (l - 1))) * ESZ; };          // n >> l entries
     auto w_at = [&](unsigned l) -> void * { return base + (off_w + form.weight_off(n, l)) * ESZ; };
     auto f_at = [&](unsigned s) -> void * { return s == 0 ? cm->codeword->dptr : base + (off_f + f_off[s]) * ESZ; };          // step s's layer
     auto tree_at = [&](unsigned s) -> uint64_t * { return s == 0 ? cm->levels : (uint64_t *)(base + (off_tree + t_off[s]) * ESZ); };   // twice its leaves in digests of room
-    const PassMem mem{cm->coeffs->dptr, base + off_w * ESZ, base + off_part * ESZ, base + (off_part + K * cap) * ESZ};
+    const PassMem mem{T0, base + off_w * ESZ, base + off_part * ESZ, base + (off_part + K * cap) * ESZ};
 
     Events ev;
     std::vector<size_t> ta(R), tb_(R), tc(R), td(R);
@@ -341,11 +542,21 @@ template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &
             uint8_t *root = nullptr;
             if (commit) {
                 tree = tree_at(s + 1);
-                root = o.roots + 32 * sc.step[s + 1].root;
+                root = o.roots + 32 * (size_t)(sc.step[s + 1].root + root_shift);
                 const Fe<F> *shift = cm->has_coset ? &c_s : nullptr;
                 const Fe<F> g_s = fe_mul<F>(r_s, gscale_s);
-                if (sc.step[s].log_sides == 2) ZK_TRY((launch_fold4<F>(f_at(s), f_at(s + 1), 4 * len, l - 1, pw, g_s, fe_mul<F>(r, gscale), shift)));
-                else ZK_TRY((launch_fold<F>(f_at(s), f_at(s + 1), 2 * len, l, pw, g_s, shift)));
+                const Fe<F> g_1 = fe_mul<F>(r, gscale);         // a fold by 4's second multiplier
+                bool folded = false;
+                if constexpr (Form::kBatch) {                 // layer 0 is the form's: k codewords, combined as they are folded
+                    if (s == 0) {
+                        ZK_TRY(form.fold0(f_at(1), N, pw, g_s, sc.step[0].log_sides == 2 ? &g_1 : nullptr, shift));
+                        folded = true;
+                    }
+                }
+                if (!folded) {
+                    if (sc.step[s].log_sides == 2) ZK_TRY((launch_fold4<F>(f_at(s), f_at(s + 1), 4 * len, l - 1, pw, g_s, g_1, shift)));
+                    else ZK_TRY((launch_fold<F>(f_at(s), f_at(s + 1), 2 * len, l, pw, g_s, shift)));
+                }
             }
             ZK_TRY(ev.mark(&tb_[l]));
             if (commit) {
@@ -378,7 +589,8 @@ template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &
     for (size_t j = 0; j < m; j++) tr.append_be<F>(load_host<F>(o.final_table + j * W));
 
     zk_fri_ml_stats st{};
-    ZK_TRY((answer_queries<F>(tr, fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, &st.ms_queries)));
+    if constexpr (Form::kBatch) ZK_TRY((answer_queries_batch<F>(tr, form.cms, form.ntables(), fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, &st.ms_queries)));
+    else ZK_TRY((answer_queries<F>(tr, fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, &st.ms_queries)));
     st.rounds = R;
     st.queries = Q;
     st.ms_sumcheck = ev.ms(e0, e1);                           // what precedes round 0, and round 0's pass
@@ -437,9 +649,10 @@ int verify_opening(int field, const uint8_t *root32, uint32_t d, uint32_t log_bl
     if (ml.log_arity == 2 && d - log_final < 2) return ZK_E_ARG;
     if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
     if (d > 32) return ZK_E_RANGE;                           // what sizes the copy below; fri_verify_core repeats these and checks the rest
-    std::vector<uint8_t> rs(roots, roots + (size_t)32 * FriSchedule(d + log_blowup, d - log_final, ml.log_arity).nsteps);
-    const bool same_root = memcmp(roots, root32, 32) == 0;
-    memcpy(rs.data(), root32, 32);
+    const size_t own = ml.ntables ? ml.ntables : 1;           // the roots the verifier holds itself: root32 has that many
+    std::vector<uint8_t> rs(roots, roots + (size_t)32 * (own - 1 + FriSchedule(d + log_blowup, d - log_final, ml.log_arity).nsteps));
+    const bool same_root = memcmp(roots, root32, 32 * own) == 0;
+    memcpy(rs.data(), root32, 32 * own);
     Transcript fresh;
     int good = 0;
     ZK_TRY(fri_verify_core(field, d, log_blowup, log_final, nqueries, coset, t ? t->t : fresh, rs.data(), final_table, query_values, query_paths, &good, nullptr, &ml));
@@ -540,6 +753,69 @@ int zk_fri_ml_sizes_arity(uint32_t d, uint32_t log_blowup, uint32_t log_final, u
     if (nvalues) *nvalues = (size_t)nqueries * sc.nvalues;
     if (path_bytes) *path_bytes = (size_t)nqueries * sc.ndigests * 32;
     return ZK_OK;
+}
+
+int zk_fri_ml_fold_batch(const zk_table *const *codewords, uint32_t k, const uint64_t *coeffs, const uint64_t *r0, const uint64_t *r1, const uint64_t *coset,
+                         zk_table **out) {
+    if (!codewords || k < 1 || k > ZK_FRI_ML_BATCH_MAX || !codewords[0]) return ZK_E_ARG;
+    for (uint32_t j = 1; j < k; j++) {
+        if (!codewords[j] || codewords[j]->field != codewords[0]->field) return ZK_E_ARG;
+        if (codewords[j]->len != codewords[0]->len) return ZK_E_LEN_MISMATCH;
+    }
+    ZK_TRY(fold_check(codewords[0], coeffs && r0 && out, coset, r1 ? 2 : 1));
+    FRI_DISPATCH(codewords[0]->field, return fold_batch_once<F>(codewords, k, coeffs, r0, r1, coset, out));
+    return ZK_OK;
+}
+
+int zk_fri_ml_sizes_batch(uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
+                          size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround) {
+    if (k < 1 || k > ZK_FRI_ML_BATCH_MAX || (log_group != 0 && log_group != 2) || (log_group == 2 && log_arity != 2)) return ZK_E_ARG;
+    size_t nr = 0, nv = 0, pb = 0;
+    if (log_group) ZK_TRY(zk_fri_ml_sizes_grouped(d, log_blowup, log_final, nqueries, &nr, nfinal, &nv, &pb, nround));
+    else ZK_TRY(zk_fri_ml_sizes_arity(d, log_blowup, log_final, nqueries, log_arity, &nr, nfinal, &nv, &pb, nround));
+    const FriSchedule sc(d + log_blowup, d - log_final, log_arity, log_group != 0);
+    const size_t v0 = sc.nsteps > 1 ? sc.step[1].val_off : sc.nvalues, d0 = sc.nsteps > 1 ? sc.step[1].path_off : sc.ndigests;   // step 0's share
+    if (nroots) *nroots = k + nr - 1;
+    if (nvalues) *nvalues = nv + (size_t)(k - 1) * nqueries * v0;
+    if (path_bytes) *path_bytes = pb + (size_t)(k - 1) * nqueries * d0 * 32;
+    return ZK_OK;
+}
+
+int zk_fri_ml_open_batch(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                         uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table,
+                         uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths) {
+    if (!cms || !points || !ys_out || !round_polys || !roots || !final_table || !query_values || !query_paths) return ZK_E_ARG;
+    if (k < 1 || k > ZK_FRI_ML_BATCH_MAX || npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2 || !cms[0]) return ZK_E_ARG;
+    const zk_fri_commitment *c0 = cms[0];
+    for (uint32_t j = 1; j < k; j++) {                        // one field, size, blow-up, coset and leaf grouping
+        const zk_fri_commitment *cj = cms[j];
+        if (!cj || cj->field != c0->field || cj->d != c0->d || cj->b != c0->b || cj->log_group != c0->log_group || cj->has_coset != c0->has_coset) return ZK_E_ARG;
+        if (c0->has_coset && memcmp(cj->coset, c0->coset, sizeof c0->coset) != 0) return ZK_E_ARG;
+    }
+    if ((c0->log_group != 0 && c0->log_group != 2) || (c0->log_group == 2 && log_arity != 2)) return ZK_E_ARG;
+    ZK_TRY(open_check(c0, nullptr, log_final, nqueries, c0->log_group));
+    if (log_arity == 2 && c0->d - log_final < 2) return ZK_E_ARG;
+    if (!all_reduced(c0->field, points, (size_t)npoints * c0->d)) return ZK_E_ARG;
+    ZK_TRY(require_device());
+    Transcript fresh;
+    const OpenOut o{round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
+    FRI_DISPATCH(c0->field, ManyTables<F> form(cms, k, points, npoints, ys_out, gamma_out, c0->d);
+                 return open_with<F>(c0, form, log_final, nqueries, log_arity, c0->log_group == 2, t ? t->t : fresh, o));
+    return ZK_OK;
+}
+
+int zk_fri_ml_verify_batch(int field, const uint8_t *roots_of_f, uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
+                           uint32_t log_arity, uint32_t log_group, const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys,
+                           zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
+                           const uint8_t *query_paths, int *ok) {
+    if (k < 1 || k > ZK_FRI_ML_BATCH_MAX || npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2) return ZK_E_ARG;
+    if ((log_group != 0 && log_group != 2) || (log_group == 2 && log_arity != 2)) return ZK_E_ARG;
+    FriMlClaim ml{points, ys, round_polys};
+    ml.npoints = npoints;
+    ml.log_arity = log_arity;
+    ml.grouped = log_group == 2;
+    ml.ntables = k;
+    return verify_opening(field, roots_of_f, d, log_blowup, log_final, nqueries, coset, ml, t, roots, final_table, query_values, query_paths, ok);
 }
 
 int zk_fri_ml_sizes_grouped(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots, size_t *nfinal, size_t *nvalues,

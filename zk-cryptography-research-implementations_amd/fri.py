@@ -238,14 +238,16 @@ class _MlStats(C.Structure):
                 ("ms_queries", C.c_float), ("ms_total", C.c_float)]
 
 
-def ml_sizes(d, log_blowup, log_final, nqueries, log_arity=1, grouped=False):
+def ml_sizes(d, log_blowup, log_final, nqueries, log_arity=1, grouped=False, k=None):
     """-> sizes(..) + (nround,): the 3 R elements of round polynomials of a multilinear opening of a table of 2^d entries; log_arity = 2: the
     counts of the opening folded by 4 (nroots = ceil(R / 2), four values and paths per fold-4 step); grouped (log_arity = 2 only): one path
-    of L - l - log_sides digests per step"""
+    of L - l - log_sides digests per step; k: the counts of k commitments opened together (open_multilinear_batch)"""
     out = [C.c_size_t(0) for _ in range(5)]
-    if grouped:
-        if log_arity != 2:
-            raise ValueError("grouped leaves need log_arity=2")
+    if grouped and log_arity != 2:
+        raise ValueError("grouped leaves need log_arity=2")
+    if k is not None:
+        L.check(L.lib().zk_fri_ml_sizes_batch(k, d, log_blowup, log_final, nqueries, log_arity, 2 if grouped else 0, *[C.byref(o) for o in out]))
+    elif grouped:
         L.check(L.lib().zk_fri_ml_sizes_grouped(d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
     elif log_arity == 1:
         L.check(L.lib().zk_fri_ml_sizes(d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
@@ -412,6 +414,72 @@ def verify_multilinear_points(root, points, opening, transcript=None, log_arity=
         L.check(L.lib().zk_fri_ml_verify_points(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, *rest))
     else:
         L.check(L.lib().zk_fri_ml_verify_points_arity(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, log_arity, *rest))
+    return bool(ok.value)
+
+
+# ---- several commitments opened together --------------------------------------------------------------------------------------------------
+def ml_fold_batch(codewords, coeffs, r0, r1=None, coset=None):
+    """the first step's fold of k codewords opened together: ml_fold4(sum_j coeffs[j] codewords[j], r0, r1, coset) -- r1 = None:
+    ml_fold(.., r0, coset) -- byte for byte, in one pass that never stores the sum.  coeffs: (k, limbs)"""
+    field = codewords[0].field
+    h = C.c_void_p()
+    cf = np.ascontiguousarray(coeffs, np.uint64)
+    if cf.shape != (len(codewords), limbs(field)):
+        raise L.ZkError(L.ZK_E_ARG, "one coefficient per codeword")
+    hs = (C.c_void_p * len(codewords))(*[c._h for c in codewords])
+    cs = None if coset is None else L.p64(_elem(field, coset))
+    p1 = None if r1 is None else L.p64(_elem(field, r1))
+    L.check(L.lib().zk_fri_ml_fold_batch(hs, len(codewords), L.p64(cf), L.p64(_elem(field, r0)), p1, cs, C.byref(h)))
+    return MultilinearPolynomial(field, _handle=h)
+
+
+class FriMlBatchOpening(FriMlPointsOpening):
+    """The opening of k commitments at the same P points: ys (k, P, limbs) table-major; roots (k + nroots - 1, 32), the k commitments' first;
+    query_values (Q, per, limbs) and query_paths with step 0's answers once per commitment, j-major, in front of the later steps'."""
+
+    def __init__(self, field, k, npoints, d, log_blowup, log_final, nqueries, coset=None, log_arity=1, grouped=False):
+        super().__init__(field, npoints, d, log_blowup, log_final, nqueries, coset, log_arity, grouped)
+        self.k = k
+        nroots, _, nvalues, path_bytes, _ = ml_sizes(d, log_blowup, log_final, nqueries, log_arity, grouped, k=k)
+        n = limbs(field)
+        self.ys = np.zeros((k, npoints, n), np.uint64)
+        self.roots = np.zeros((nroots, 32), np.uint8)
+        self.query_values = np.zeros((nqueries, nvalues // nqueries, n), np.uint64)
+        self.query_paths = np.zeros(path_bytes, np.uint8)
+
+
+def open_multilinear_batch(commitments, points, log_final, nqueries, log_arity=1, transcript=None):
+    """one proof that each of the k <= 16 committed tables has the values `.ys[j]` at the same P <= 8 points (P, d, limbs).  The commitments
+    share field, size, blow-up, coset and leaf grouping; grouped ones (commit(.., log_group=2)) need log_arity=2"""
+    c0 = commitments[0]
+    grouped = getattr(c0, "log_group", 0) != 0
+    if grouped and log_arity != 2:
+        raise ValueError("commitments with grouped leaves are opened with log_arity=2")
+    pts = _points(c0.field, c0.d, points)
+    op = FriMlBatchOpening(c0.field, len(commitments), pts.shape[0], c0.d, c0.log_blowup, log_final, nqueries, c0.coset, log_arity, grouped)
+    L.check(L.lib().zk_fri_ml_open_batch(_handles(commitments), len(commitments), L.p64(pts), pts.shape[0], log_final, nqueries, log_arity,
+                                         _handle(transcript), L.p64(op.ys), L.p64(op.gamma), L.p64(op.round_polys), L.p8(op.roots),
+                                         L.p64(op.final_table), L.p64(op.challenges), L.p64(op.query_indices), L.p64(op.query_values),
+                                         L.p8(op.query_paths)))
+    return op
+
+
+def verify_multilinear_batch(roots, points, opening, transcript=None):
+    """host only: `roots` = the k commitment roots (32 bytes each) in the prover's order; the claims checked are
+    evaluate(table_j, points[p]) = opening.ys[j, p]"""
+    ok = C.c_int(0)
+    op = opening
+    rf = np.frombuffer(b"".join(bytes(r) for r in roots), np.uint8).copy()
+    if rf.shape[0] != 32 * len(roots) or len(roots) != op.k:
+        raise L.ZkError(L.ZK_E_ARG, "one 32-byte Merkle root per commitment")
+    pts = _points(op.field, op.d, points)
+    ys, rp, fin, vals = (np.ascontiguousarray(a, np.uint64) for a in (op.ys, op.round_polys, op.final_table, op.query_values))
+    if ys.shape != (op.k, pts.shape[0], limbs(op.field)):
+        raise L.ZkError(L.ZK_E_ARG, "one claim per commitment and point")
+    rts, paths = np.ascontiguousarray(op.roots, np.uint8), np.ascontiguousarray(op.query_paths, np.uint8)
+    L.check(L.lib().zk_fri_ml_verify_batch(op.field, L.p8(rf), op.k, op.d, op.log_blowup, op.log_final, op.nqueries, op.log_arity,
+                                           2 if op.grouped else 0, op._coset(), L.p64(pts), pts.shape[0], L.p64(ys), _handle(transcript),
+                                           L.p64(rp), L.p8(rts), L.p64(fin), L.p64(vals), L.p8(paths), C.byref(ok)))
     return bool(ok.value)
 
 
