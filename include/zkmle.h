@@ -596,6 +596,66 @@ int zk_sumcheck_basic_verify_succinct(int field, const uint8_t *root32, uint32_t
                                       const uint64_t *round_polys, const uint64_t *y, const uint64_t *open_round_polys, const uint8_t *roots,
                                       const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, int *ok);
 
+/* ---- Proof-of-work grinding (extension; csrc/grind.cuh fri_grind_kernel, csrc/grind_host.h, csrc/zkmle_grind.hip) --------------------------------
+ * Lets a caller trade queries for prover work: before the query indices are drawn the prover must find a nonce whose hash with the transcript
+ * has g leading zero bits, 1 <= g <= ZK_FRI_GRIND_MAX_BITS.  Each bit of g costs the prover a factor of two and, under the count commonly used
+ * for FRI (b = log_blowup bits per query: an assumption about the protocol's soundness, not something this library proves), buys one bit of
+ * query-phase soundness: (Q, g) and (Q', g') are equal under it when b Q + g = b Q' + g'.
+ *   The step grind(t, g), plain appends on the transcript:
+ *     1. 8 bytes in one append: the ASCII tag "GRND", then g as a big-endian u32 -- a proof made for one g is no proof for another;
+ *     2. the nonce w is the SMALLEST unsigned 64-bit integer (at or above `start`, where there is one) such that
+ *        Keccak256(everything absorbed so far || w as 8 big-endian bytes) has its first g bits zero: bit i of the digest is bit 7 - i mod 8 of byte
+ *        i div 8.  In transcript terms the digest is what sample_random_challenge() returns after append(w).  w = 2^64 - 1 is never a candidate;
+ *     3. append(w as 8 big-endian bytes), then sample_random_challenge(): the digest of step 2, absorbed back as always.
+ *   The verifier appends the tag and g, appends w, samples the challenge and rejects unless its first g bits are zero.
+ *   g = 0 means no step at all: nothing is appended, no nonce exists, and every _pow function below is its counterpart byte for byte.
+ *   Placement.  zk_fri_prove_pow: between item 4 (the final coefficients) and item 5 (the indices) of zk_fri_prove's transcript.
+ *     zk_fri_ml_open_batch_pow: after T_R is absorbed and before the Q indices.  Nothing else of either transcript changes.
+ *     zk_fri_pcs_open, the single-commitment multilinear openers and the succinct sumcheck / GKR wrappers have no grinding form.
+ *   Search (GPU).  One candidate per lane per iteration on the Merkle tree's one-hash-per-lane Keccak; the sponge (25 lanes and the fill of its
+ *     open block, any of 0 .. 135) travels in the kernel's argument block.  One permutation per candidate while nonce and pad fit the open block
+ *     (fill <= 127), two otherwise.  Ranges of 2^log_batch candidates are launched in ascending order and a hit lowers one 64-bit word by
+ *     atomicMin, so the first range with a hit yields the smallest nonce.  The search gives up with ZK_E_RANGE once 2^(g + 6) candidates hold no
+ *     nonce (an honest search fails there with probability e^-64); the transcript is then as it was.
+ * Statuses: ZK_E_ARG (NULL, bits outside 1 .. 32, log_batch neither 0 nor 8 .. 30; grinding_bits > 32 for the _pow functions, or > 0 with a
+ * NULL pow_nonce in a prover) before everything else, ZK_E_NO_DEVICE only from the GPU search and the provers. */
+#define ZK_FRI_GRIND_MAX_BITS 32
+/* GPU.  Steps 1 - 3 on t; *nonce = the smallest w >= start.  log_batch = 0 selects the default (2^22 candidates a launch, more above 24 bits),
+ * else 8 .. 30.  start and log_batch exist for tests and measurements: the provers pass 0 and 0. */
+int zk_transcript_grind(zk_transcript *t, uint32_t bits, uint64_t start, uint32_t log_batch, uint64_t *nonce);
+/* HOST, one core: the same by the transcript's own Keccak256, cloned per candidate.  At most max_tries candidates (0: 2^(bits + 6)), then
+ * ZK_E_RANGE with t as it was.  About 10^6 candidates a second. */
+int zk_host_transcript_grind(zk_transcript *t, uint32_t bits, uint64_t start, uint64_t max_tries, uint64_t *nonce);
+/* HOST: the verifier's step.  *ok = 1 iff the challenge's first `bits` bits are zero; t ends in the prover's state either way. */
+int zk_transcript_grind_check(zk_transcript *t, uint32_t bits, uint64_t nonce, int *ok);
+/* the calling thread's last zk_transcript_grind (the provers' included): candidates = those up to and including the nonce (all that were
+ * covered when there was none) -- the lanes of the last launch hash somewhat more; launches; ms = HIP-event time of the launches with their
+ * result reads */
+typedef struct {
+    uint64_t candidates;
+    uint32_t launches;
+    float ms;
+} zk_grind_stats;
+int zk_transcript_grind_last_stats(zk_grind_stats *out);
+/* zk_fri_prove / zk_fri_verify with the step; pow_nonce: out (may be NULL at grinding_bits = 0, and is not written then) / in */
+int zk_fri_prove_pow(const zk_table *coeffs, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset,
+                     zk_transcript *t, uint8_t *roots, uint64_t *final_coeffs, uint64_t *betas, uint64_t *query_indices,
+                     uint64_t *query_values, uint8_t *query_paths, uint32_t grinding_bits, uint64_t *pow_nonce);
+int zk_fri_verify_pow(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset,
+                      zk_transcript *t, const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values,
+                      const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok);
+/* zk_fri_ml_open_batch / zk_fri_ml_verify_batch with the step: k commitments, P points, all three schedules (k = 1, P = 1 covers the simpler
+ * forms' statements, under the batch protocol's transcript) */
+int zk_fri_ml_open_batch_pow(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final,
+                             uint32_t nqueries, uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out,
+                             uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices,
+                             uint64_t *query_values, uint8_t *query_paths, uint32_t grinding_bits, uint64_t *pow_nonce);
+int zk_fri_ml_verify_batch_pow(int field, const uint8_t *roots_of_f, uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final,
+                               uint32_t nqueries, uint32_t log_arity, uint32_t log_group, const uint64_t *coset, const uint64_t *points,
+                               uint32_t npoints, const uint64_t *ys, zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots,
+                               const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits,
+                               uint64_t pow_nonce, int *ok);
+
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */
 int zk_uni_lagrange_interpolate(int field, const uint64_t *xs, const uint64_t *ys, size_t n, uint64_t *out); /* :74 */

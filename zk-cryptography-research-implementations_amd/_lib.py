@@ -156,6 +156,17 @@ def lib():
         "zk_fri_ml_sizes_batch": [C.c_uint32] * 7 + [C.POINTER(sz)] * 5,
         "zk_fri_ml_open_batch": [C.POINTER(vp), C.c_uint32, u64p] + [C.c_uint32] * 4 + [vp, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_fri_ml_verify_batch": [C.c_int, u8p] + [C.c_uint32] * 7 + [u64p, u64p, C.c_uint32, u64p, vp, u64p, u8p, u64p, u64p, u8p, C.POINTER(C.c_int)],
+        # proof-of-work grinding
+        "zk_transcript_grind": [vp, C.c_uint32, C.c_uint64, C.c_uint32, u64p],
+        "zk_host_transcript_grind": [vp, C.c_uint32, C.c_uint64, C.c_uint64, u64p],
+        "zk_transcript_grind_check": [vp, C.c_uint32, C.c_uint64, C.POINTER(C.c_int)],
+        "zk_transcript_grind_last_stats": [vp],
+        "zk_fri_prove_pow": [vp] + [C.c_uint32] * 3 + [u64p, vp, u8p, u64p, u64p, u64p, u64p, u8p, C.c_uint32, u64p],
+        "zk_fri_verify_pow": [C.c_int] + [C.c_uint32] * 4 + [u64p, vp, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64, C.POINTER(C.c_int)],
+        "zk_fri_ml_open_batch_pow": [C.POINTER(vp), C.c_uint32, u64p] + [C.c_uint32] * 4 + [vp, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p,
+                                                                                          C.c_uint32, u64p],
+        "zk_fri_ml_verify_batch_pow": [C.c_int, u8p] + [C.c_uint32] * 7 + [u64p, u64p, C.c_uint32, u64p, vp, u64p, u8p, u64p, u64p, u8p, C.c_uint32,
+                                                                          C.c_uint64, C.POINTER(C.c_int)],
         "zk_sumcheck_basic_prove_succinct": [vp, C.c_uint32, C.c_uint32, vp, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_sumcheck_basic_verify_succinct": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, vp, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u8p,
                                                                                  C.POINTER(C.c_int)],

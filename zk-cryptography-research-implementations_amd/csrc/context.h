@@ -123,9 +123,13 @@ struct FriMlClaim {
     // commitments' values and paths, j-major, and the step's values are their alpha-combination, alpha = gamma^npoints.  0: one table, as before
     uint32_t ntables = 0;
 };
+// grind_bits > 0: the proof-of-work step (include/zkmle.h "Proof-of-work grinding") with the nonce pow_nonce stands between the final
+// coefficients and the indices; a nonce that fails it gives *ok = 0.  grind_bits > ZK_FRI_GRIND_MAX_BITS: ZK_E_ARG
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,
-                    uint64_t *indices_out, const FriMlClaim *ml = nullptr);
+                    uint64_t *indices_out, const FriMlClaim *ml = nullptr, uint32_t grind_bits = 0, uint64_t pow_nonce = 0);
+// steps 1-3 of the proof-of-work step on `tr` with the search on the GPU (zkmle_grind.hip): zk_transcript_grind's checks and body
+int transcript_grind(Transcript &tr, uint32_t bits, uint64_t start, uint32_t log_batch, uint64_t *nonce);
 // Prover::prove (prover.rs:35-71) on a caller's Transcript whose binding append (:38-39) is the 32 bytes `bound` -- a commitment the caller
 // holds -- instead of the table's bytes; no checks (zkmle_sumcheck.hip; the succinct sumcheck of zkmle_fri_ml.hip)
 int sumcheck_basic_prove_bound(const zk_table *table, Transcript &tr, const uint8_t bound[32], uint64_t *claimed_sum, uint64_t *round_polys,

@@ -141,13 +141,22 @@ struct FriSchedule {
     }
 };
 
+// where every prover draws its Q indices.  grind_bits > 0: the proof-of-work step comes first (include/zkmle.h "Proof-of-work grinding";
+// the search runs on the GPU, zkmle_grind.hip) and *nonce_out, which is required then, receives its nonce
+inline int draw_indices(Transcript &tr, const FriSchedule &sc, uint32_t Q, std::vector<uint64_t> &idx, uint32_t grind_bits, uint64_t *nonce_out) {
+    if (grind_bits) ZK_TRY(transcript_grind(tr, grind_bits, 0, 0, nonce_out));
+    idx.resize(Q);
+    for (unsigned q = 0; q < Q; q++) idx[q] = sample_index(tr, sc.index_bits());
+    return ZK_OK;
+}
+
 // the queries: Q indices from the transcript, then every opened value and path of the steps of `fl` (= sc.layers() with its tables and
 // trees) with one launch each, one download each and one wait for both.  *ms (may be null) = the gather with its downloads; ends with the stream drained and its end as the latest event.
 template <class F> int answer_queries(Transcript &tr, const FriLayers &fl, const FriSchedule &sc, uint32_t Q, uint64_t *indices_out, uint64_t *values,
-                                      uint8_t *paths, Events &ev, float *ms) {
+                                      uint8_t *paths, Events &ev, float *ms, uint32_t grind_bits = 0, uint64_t *nonce_out = nullptr) {
     constexpr size_t ESZ = sizeof(Fe<F>);
-    std::vector<uint64_t> idx(Q);
-    for (unsigned q = 0; q < Q; q++) idx[q] = sample_index(tr, sc.index_bits());
+    std::vector<uint64_t> idx;
+    ZK_TRY(draw_indices(tr, sc, Q, idx, grind_bits, nonce_out));
     if (indices_out) memcpy(indices_out, idx.data(), Q * 8);
     const size_t nval = (size_t)Q * sc.nvalues, ndig = (size_t)Q * sc.ndigests;
     DevBuf didx, dval, dpath;

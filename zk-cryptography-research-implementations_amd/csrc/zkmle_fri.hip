@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "fri_host.h"
+#include "grind_host.h"
 #include "univariate.h"
 
 using namespace zk;
@@ -49,7 +50,7 @@ struct ProofOut {
 
 // `cw` = layer 0 (N = 2^L entries, L = d + b); events: `ev0` was recorded before the extension (or is the proof's first event)
 template <class F> int prove_layers(const zk_table *cw, unsigned b, unsigned f, unsigned Q, const uint64_t *coset, Transcript &tr, const ProofOut &o,
-                                    Events &ev, float *ms_trees, float *ms_folds, float *ms_queries) {
+                                    Events &ev, float *ms_trees, float *ms_folds, float *ms_queries, uint32_t grind_bits, uint64_t *nonce_out) {
     constexpr size_t ESZ = sizeof(Fe<F>);
     const unsigned L = ilog2(cw->len), d = L - b, R = d - f;
     const size_t N = cw->len, m = (size_t)1 << f;
@@ -100,7 +101,7 @@ template <class F> int prove_layers(const zk_table *cw, unsigned b, unsigned f, 
     ZK_HIP(zk::memcpy_on_stream(o.final_coeffs, last->dptr, m * ESZ, hipMemcpyDeviceToHost));
     for (size_t j = 0; j < m; j++) tr.append_be<F>(load_host<F>(o.final_coeffs + j * (F::N / 2)));
 
-    ZK_TRY((answer_queries<F>(tr, fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, nullptr)));
+    ZK_TRY((answer_queries<F>(tr, fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, nullptr, grind_bits, nonce_out)));
     *ms_trees = *ms_folds = 0.f;
     for (unsigned l = 0; l < R; l++) {
         *ms_trees += ev.ms(ta[l], tf[l]);
@@ -117,8 +118,11 @@ int shape_check(int field, unsigned L, uint32_t b, uint32_t f) {
     return L > two_adicity(field) ? ZK_E_RANGE : ZK_OK;
 }
 
-int prove_any(const zk_table *in, bool is_codeword, uint32_t b, uint32_t f, uint32_t Q, const uint64_t *coset, zk_transcript *t, const ProofOut &o) {
+// grind_bits > 0: the proof-of-work step in front of the indices, its nonce into *nonce_out
+int prove_any(const zk_table *in, bool is_codeword, uint32_t b, uint32_t f, uint32_t Q, const uint64_t *coset, zk_transcript *t, const ProofOut &o,
+              uint32_t grind_bits = 0, uint64_t *nonce_out = nullptr) {
     if (!in || !o.roots || !o.final_coeffs || !o.query_values || !o.query_paths || field_limbs64(in->field) < 0) return ZK_E_ARG;
+    if (grind_bits > ZK_FRI_GRIND_MAX_BITS || (grind_bits && !nonce_out)) return ZK_E_ARG;
     ZK_TRY(params_check(b, Q));
     if (coset && is_zero_element(in->field, coset)) return ZK_E_ARG;
     if (!is_pow2(in->len)) return ZK_E_NOT_POW2;
@@ -141,7 +145,7 @@ int prove_any(const zk_table *in, bool is_codeword, uint32_t b, uint32_t f, uint
     ZK_TRY(ev.mark(&e1));
     zk_fri_stats st{};
     int rc = ZK_OK;
-    FRI_DISPATCH(in->field, rc = prove_layers<F>(cw, b, f, Q, coset, tr, o, ev, &st.ms_trees, &st.ms_folds, &st.ms_queries));
+    FRI_DISPATCH(in->field, rc = prove_layers<F>(cw, b, f, Q, coset, tr, o, ev, &st.ms_trees, &st.ms_folds, &st.ms_queries, grind_bits, nonce_out));
     ZK_TRY(rc);
     st.layers = ilog2(cw->len) - b - f;
     st.queries = Q;
@@ -162,7 +166,8 @@ template <class F> struct Replayed {
 
 // the prover's transcript over again.  `ml`: the claim and round polynomials of the multilinear forms (context.h FriMlClaim), null = zk_fri_verify
 template <class F> Replayed<F> replay(uint32_t d, uint32_t b, uint32_t f, uint32_t Q, const uint64_t *coset, Transcript &tr, const FriSchedule &sc,
-                                      const uint8_t *roots, const uint64_t *final_coeffs, const FriMlClaim *ml) {
+                                      const uint8_t *roots, const uint64_t *final_coeffs, const FriMlClaim *ml, uint32_t grind_bits = 0,
+                                      uint64_t pow_nonce = 0) {
     constexpr int W = F::N / 2;
     const unsigned R = d - f;
     Replayed<F> rp;
@@ -209,6 +214,10 @@ template <class F> Replayed<F> replay(uint32_t d, uint32_t b, uint32_t f, uint32
         if (s + 1 < sc.nsteps && sc.step[s + 1].layer == l + 1) tr.append(roots + 32 * (size_t)(sc.step[++s].root + (nt ? nt - 1 : 0)), 32);   // layer l + 1 is committed
     }
     for (size_t j = 0; j < (size_t)1 << f; j++) rp.h.push_back(absorb(final_coeffs + j * W));
+    if (grind_bits) {                                        // the proof-of-work step: the tag, the nonce, the challenge and its leading bits
+        const bool pow_ok = grind_check(tr, grind_bits, pow_nonce);
+        rp.good = rp.good && pow_ok;
+    }
     for (unsigned q = 0; q < Q; q++) rp.idx.push_back(sample_index(tr, sc.index_bits()));
     return rp;
 }
@@ -324,9 +333,9 @@ template <class F> int queries_hold(const FriSchedule &sc, unsigned R, bool lagr
 // `indices_out` (Q words, may be null): the sampled i_q, for a caller that checks more at the queried positions (zkmle_fri_pcs.hip)
 template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t Q, const uint64_t *coset, Transcript &tr, const uint8_t *roots,
                                    const uint64_t *final_coeffs, const uint64_t *values, const uint8_t *paths, int *ok, uint64_t *indices_out,
-                                   const FriMlClaim *ml) {
+                                   const FriMlClaim *ml, uint32_t grind_bits, uint64_t pow_nonce) {
     const FriSchedule sc(d + b, d - f, ml ? ml->log_arity : 1, ml && ml->grouped);
-    Replayed<F> rp = replay<F>(d, b, f, Q, coset, tr, sc, roots, final_coeffs, ml);
+    Replayed<F> rp = replay<F>(d, b, f, Q, coset, tr, sc, roots, final_coeffs, ml, grind_bits, pow_nonce);
     if (indices_out) memcpy(indices_out, rp.idx.data(), Q * 8);
     *ok = 0;
     const unsigned nt = ml ? ml->ntables : 0;
@@ -343,7 +352,8 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
 namespace zk {
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,
-                    uint64_t *indices_out, const FriMlClaim *ml) {
+                    uint64_t *indices_out, const FriMlClaim *ml, uint32_t grind_bits, uint64_t pow_nonce) {
+    if (grind_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
     if (ml && (!ml->z || !ml->y || !ml->round_polys || ml->npoints > 8)) return ZK_E_ARG;
     if (ml && (ml->log_arity < 1 || ml->log_arity > 2 || (ml->log_arity == 2 && (ml->npoints < 1 || log_final >= d || d - log_final < 2)))) return ZK_E_ARG;
     if (ml && ml->grouped && ml->log_arity != 2) return ZK_E_ARG;
@@ -354,7 +364,7 @@ int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_fin
     if (d < 1 || log_final >= d) return ZK_E_ARG;
     if (d > 32) return ZK_E_RANGE;
     ZK_TRY(shape_check(field, d + log_blowup, log_blowup, log_final));
-    FRI_DISPATCH(field, return verify_host<F>(d, log_blowup, log_final, nqueries, coset, tr, roots, final_coeffs, query_values, query_paths, ok, indices_out, ml));
+    FRI_DISPATCH(field, return verify_host<F>(d, log_blowup, log_final, nqueries, coset, tr, roots, final_coeffs, query_values, query_paths, ok, indices_out, ml, grind_bits, pow_nonce));
     return ZK_OK;
 }
 }  // namespace zk
@@ -394,6 +404,21 @@ int zk_fri_verify(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final
                   const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok) {
     Transcript fresh;
     return fri_verify_core(field, d, log_blowup, log_final, nqueries, coset, t ? t->t : fresh, roots, final_coeffs, query_values, query_paths, ok, nullptr);
+}
+
+int zk_fri_prove_pow(const zk_table *coeffs, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, zk_transcript *t,
+                     uint8_t *roots, uint64_t *final_coeffs, uint64_t *betas, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
+                     uint32_t grinding_bits, uint64_t *pow_nonce) {
+    return prove_any(coeffs, false, log_blowup, log_final, nqueries, coset, t, ProofOut{roots, final_coeffs, betas, query_indices, query_values, query_paths},
+                     grinding_bits, pow_nonce);
+}
+
+int zk_fri_verify_pow(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, zk_transcript *t,
+                      const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths,
+                      uint32_t grinding_bits, uint64_t pow_nonce, int *ok) {
+    Transcript fresh;
+    return fri_verify_core(field, d, log_blowup, log_final, nqueries, coset, t ? t->t : fresh, roots, final_coeffs, query_values, query_paths, ok, nullptr,
+                           nullptr, grinding_bits, pow_nonce);
 }
 
 int zk_fri_last_stats(zk_fri_stats *out) {

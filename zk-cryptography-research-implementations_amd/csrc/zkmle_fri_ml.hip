@@ -375,10 +375,11 @@ template <class F> struct ManyTables : ManyPoints<F> {
 // later steps).  The alternative, a table of layer-0 sources inside FriLayers, would add 32 pointers to the argument block of both kernels
 // and a branch to every lane of the single-table provers for the sake of k - 1 small launches here.
 template <class F> int answer_queries_batch(Transcript &tr, const zk_fri_commitment *const *cms, unsigned k, const FriLayers &fl, const FriSchedule &sc, uint32_t Q,
-                                            uint64_t *indices_out, uint64_t *values, uint8_t *paths, Events &ev, float *ms) {
+                                            uint64_t *indices_out, uint64_t *values, uint8_t *paths, Events &ev, float *ms, uint32_t grind_bits = 0,
+                                            uint64_t *nonce_out = nullptr) {
     constexpr size_t ESZ = sizeof(Fe<F>);
-    std::vector<uint64_t> idx(Q);
-    for (unsigned q = 0; q < Q; q++) idx[q] = sample_index(tr, sc.index_bits());
+    std::vector<uint64_t> idx;
+    ZK_TRY(draw_indices(tr, sc, Q, idx, grind_bits, nonce_out));
     if (indices_out) memcpy(indices_out, idx.data(), Q * 8);
     // the two views: step 0 alone (its table and tree set per commitment), and the steps from 1 up with their offsets counted from step 1
     const size_t v0 = sc.nsteps > 1 ? sc.step[1].val_off : sc.nvalues, d0 = sc.nsteps > 1 ? sc.step[1].path_off : sc.ndigests;
@@ -443,7 +444,9 @@ template <class F> int answer_queries_batch(Transcript &tr, const zk_fri_commitm
 // f_l -> f_{l+2}, its tree and round l + 2's pass.  One host synchronisation per round either way.  A layer that is not committed is never built.
 // `grouped` (la = 2, a commitment with log_group = 2): every layer's leaves hold the sides of the step that starts there, so its tree is a quarter
 // (the final fold-2 step's: half) as large and a step opens one path.
-template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &form, uint32_t f, uint32_t Q, unsigned la, bool grouped, Transcript &tr, const OpenOut &o) {
+// grind_bits > 0: the proof-of-work step between T_R and the indices, its nonce into *nonce_out.
+template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &form, uint32_t f, uint32_t Q, unsigned la, bool grouped, Transcript &tr, const OpenOut &o,
+                                             uint32_t grind_bits = 0, uint64_t *nonce_out = nullptr) {
     constexpr size_t ESZ = sizeof(Fe<F>);
     constexpr int W = F::N / 2;
     constexpr unsigned K = Form::kSums;
@@ -589,8 +592,8 @@ template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &
     for (size_t j = 0; j < m; j++) tr.append_be<F>(load_host<F>(o.final_table + j * W));
 
     zk_fri_ml_stats st{};
-    if constexpr (Form::kBatch) ZK_TRY((answer_queries_batch<F>(tr, form.cms, form.ntables(), fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, &st.ms_queries)));
-    else ZK_TRY((answer_queries<F>(tr, fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, &st.ms_queries)));
+    if constexpr (Form::kBatch) ZK_TRY((answer_queries_batch<F>(tr, form.cms, form.ntables(), fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, &st.ms_queries, grind_bits, nonce_out)));
+    else ZK_TRY((answer_queries<F>(tr, fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, &st.ms_queries, grind_bits, nonce_out)));
     st.rounds = R;
     st.queries = Q;
     st.ms_sumcheck = ev.ms(e0, e1);                           // what precedes round 0, and round 0's pass
@@ -643,7 +646,8 @@ int open_one(const zk_fri_commitment *cm, const uint64_t *z, uint32_t f, uint32_
 // must be the same bytes and the core gets a copy of the roots that starts with the caller's
 int verify_opening(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset,
                    const FriMlClaim &ml, zk_transcript *t, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
-                   const uint8_t *query_paths, int *ok) {
+                   const uint8_t *query_paths, int *ok, uint32_t grind_bits = 0, uint64_t pow_nonce = 0) {
+    if (grind_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
     if (!root32 || !ml.z || !ml.y || !ml.round_polys || !roots || !final_table || !query_values || !query_paths || !ok) return ZK_E_ARG;
     if (field_limbs64(field) < 0 || log_blowup < 1 || log_blowup > 8 || nqueries < 1 || nqueries > 4096 || d < 1 || log_final >= d) return ZK_E_ARG;
     if (ml.log_arity == 2 && d - log_final < 2) return ZK_E_ARG;
@@ -655,7 +659,7 @@ int verify_opening(int field, const uint8_t *root32, uint32_t d, uint32_t log_bl
     memcpy(rs.data(), root32, 32 * own);
     Transcript fresh;
     int good = 0;
-    ZK_TRY(fri_verify_core(field, d, log_blowup, log_final, nqueries, coset, t ? t->t : fresh, rs.data(), final_table, query_values, query_paths, &good, nullptr, &ml));
+    ZK_TRY(fri_verify_core(field, d, log_blowup, log_final, nqueries, coset, t ? t->t : fresh, rs.data(), final_table, query_values, query_paths, &good, nullptr, &ml, grind_bits, pow_nonce));
     *ok = good && same_root ? 1 : 0;
     return ZK_OK;
 }
@@ -784,6 +788,15 @@ int zk_fri_ml_sizes_batch(uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t 
 int zk_fri_ml_open_batch(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
                          uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table,
                          uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths) {
+    return zk_fri_ml_open_batch_pow(cms, k, points, npoints, log_final, nqueries, log_arity, t, ys_out, gamma_out, round_polys, roots, final_table, challenges,
+                                    query_indices, query_values, query_paths, 0, nullptr);
+}
+
+int zk_fri_ml_open_batch_pow(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                             uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots,
+                             uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
+                             uint32_t grinding_bits, uint64_t *pow_nonce) {
+    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS || (grinding_bits && !pow_nonce)) return ZK_E_ARG;
     if (!cms || !points || !ys_out || !round_polys || !roots || !final_table || !query_values || !query_paths) return ZK_E_ARG;
     if (k < 1 || k > ZK_FRI_ML_BATCH_MAX || npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2 || !cms[0]) return ZK_E_ARG;
     const zk_fri_commitment *c0 = cms[0];
@@ -800,7 +813,7 @@ int zk_fri_ml_open_batch(const zk_fri_commitment *const *cms, uint32_t k, const 
     Transcript fresh;
     const OpenOut o{round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
     FRI_DISPATCH(c0->field, ManyTables<F> form(cms, k, points, npoints, ys_out, gamma_out, c0->d);
-                 return open_with<F>(c0, form, log_final, nqueries, log_arity, c0->log_group == 2, t ? t->t : fresh, o));
+                 return open_with<F>(c0, form, log_final, nqueries, log_arity, c0->log_group == 2, t ? t->t : fresh, o, grinding_bits, pow_nonce));
     return ZK_OK;
 }
 
@@ -808,6 +821,15 @@ int zk_fri_ml_verify_batch(int field, const uint8_t *roots_of_f, uint32_t k, uin
                            uint32_t log_arity, uint32_t log_group, const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys,
                            zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
                            const uint8_t *query_paths, int *ok) {
+    return zk_fri_ml_verify_batch_pow(field, roots_of_f, k, d, log_blowup, log_final, nqueries, log_arity, log_group, coset, points, npoints, ys, t, round_polys,
+                                      roots, final_table, query_values, query_paths, 0, 0, ok);
+}
+
+int zk_fri_ml_verify_batch_pow(int field, const uint8_t *roots_of_f, uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
+                               uint32_t log_arity, uint32_t log_group, const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys,
+                               zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table,
+                               const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok) {
+    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
     if (k < 1 || k > ZK_FRI_ML_BATCH_MAX || npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2) return ZK_E_ARG;
     if ((log_group != 0 && log_group != 2) || (log_group == 2 && log_arity != 2)) return ZK_E_ARG;
     FriMlClaim ml{points, ys, round_polys};
@@ -815,7 +837,8 @@ int zk_fri_ml_verify_batch(int field, const uint8_t *roots_of_f, uint32_t k, uin
     ml.log_arity = log_arity;
     ml.grouped = log_group == 2;
     ml.ntables = k;
-    return verify_opening(field, roots_of_f, d, log_blowup, log_final, nqueries, coset, ml, t, roots, final_table, query_values, query_paths, ok);
+    return verify_opening(field, roots_of_f, d, log_blowup, log_final, nqueries, coset, ml, t, roots, final_table, query_values, query_paths, ok, grinding_bits,
+                          pow_nonce);
 }
 
 int zk_fri_ml_sizes_grouped(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots, size_t *nfinal, size_t *nvalues,

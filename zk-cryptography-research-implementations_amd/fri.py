@@ -41,8 +41,9 @@ class FriProof:
     """The flat proof: roots (R, 32) bytes, final_coeffs (m, limbs), query_values (Q, R, 2, limbs), query_paths (path_bytes,) bytes;
     betas (R, limbs) and query_indices (Q,) are what the prover's transcript gave (diagnostic: the verifier derives its own)."""
 
-    def __init__(self, field, d, log_blowup, log_final, nqueries, coset=None):
+    def __init__(self, field, d, log_blowup, log_final, nqueries, coset=None, grinding_bits=0):
         self.field, self.d, self.log_blowup, self.log_final, self.nqueries = field, d, log_blowup, log_final, nqueries
+        self.grinding_bits, self.pow_nonce = grinding_bits, 0      # the proof-of-work step in front of the indices, and its nonce
         self.coset = None if coset is None else _elem(field, coset).copy()
         nroots, nfinal, nvalues, path_bytes = self.sizes
         n = limbs(field)
@@ -80,9 +81,16 @@ def _run(fn, poly, d, log_blowup, log_final, nqueries, coset, transcript):
     return pr
 
 
-def prove(coeffs, log_blowup, log_final, nqueries, coset=None, transcript=None):
-    """the proof that the coefficient table `coeffs` (2^d entries) has degree below 2^d"""
-    return _run(L.lib().zk_fri_prove, coeffs, len(coeffs).bit_length() - 1, log_blowup, log_final, nqueries, coset, transcript)
+def prove(coeffs, log_blowup, log_final, nqueries, coset=None, transcript=None, grinding_bits=0):
+    """the proof that the coefficient table `coeffs` (2^d entries) has degree below 2^d.  grinding_bits = g > 0: a proof-of-work nonce with g
+    leading zero bits is found on the GPU before the indices are drawn (include/zkmle.h "Proof-of-work grinding"); the proof carries g and it"""
+    pr = FriProof(coeffs.field, len(coeffs).bit_length() - 1, log_blowup, log_final, nqueries, coset, grinding_bits)
+    nonce = C.c_uint64(0)
+    L.check(L.lib().zk_fri_prove_pow(coeffs._h, log_blowup, log_final, nqueries, pr._coset(), _handle(transcript), L.p8(pr.roots),
+                                     L.p64(pr.final_coeffs), L.p64(pr.betas), L.p64(pr.query_indices), L.p64(pr.query_values),
+                                     L.p8(pr.query_paths), grinding_bits, C.byref(nonce)))
+    pr.pow_nonce = int(nonce.value)
+    return pr
 
 
 def prove_codeword(codeword, log_blowup, log_final, nqueries, coset=None, transcript=None):
@@ -98,9 +106,22 @@ def verify(proof, transcript=None):
     ok = C.c_int(0)
     vals, paths = np.ascontiguousarray(proof.query_values, np.uint64), np.ascontiguousarray(proof.query_paths, np.uint8)
     roots, fin = np.ascontiguousarray(proof.roots, np.uint8), np.ascontiguousarray(proof.final_coeffs, np.uint64)
-    L.check(L.lib().zk_fri_verify(proof.field, proof.d, proof.log_blowup, proof.log_final, proof.nqueries, proof._coset(),
-                                  _handle(transcript), L.p8(roots), L.p64(fin), L.p64(vals), L.p8(paths), C.byref(ok)))
+    L.check(L.lib().zk_fri_verify_pow(proof.field, proof.d, proof.log_blowup, proof.log_final, proof.nqueries, proof._coset(),
+                                      _handle(transcript), L.p8(roots), L.p64(fin), L.p64(vals), L.p8(paths),
+                                      getattr(proof, "grinding_bits", 0), getattr(proof, "pow_nonce", 0), C.byref(ok)))
     return bool(ok.value)
+
+
+class _GrindStats(C.Structure):
+    _fields_ = [("candidates", C.c_uint64), ("launches", C.c_uint32), ("ms", C.c_float)]
+
+
+def grind_last_stats():
+    """the calling thread's last GPU nonce search (Transcript.grind, or a prover's): the candidates up to and including the nonce, the launches,
+    and the milliseconds of the launches with their result reads"""
+    st = _GrindStats()
+    L.check(L.lib().zk_transcript_grind_last_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _GrindStats._fields_}
 
 
 def last_stats():
@@ -437,9 +458,10 @@ class FriMlBatchOpening(FriMlPointsOpening):
     """The opening of k commitments at the same P points: ys (k, P, limbs) table-major; roots (k + nroots - 1, 32), the k commitments' first;
     query_values (Q, per, limbs) and query_paths with step 0's answers once per commitment, j-major, in front of the later steps'."""
 
-    def __init__(self, field, k, npoints, d, log_blowup, log_final, nqueries, coset=None, log_arity=1, grouped=False):
+    def __init__(self, field, k, npoints, d, log_blowup, log_final, nqueries, coset=None, log_arity=1, grouped=False, grinding_bits=0):
         super().__init__(field, npoints, d, log_blowup, log_final, nqueries, coset, log_arity, grouped)
         self.k = k
+        self.grinding_bits, self.pow_nonce = grinding_bits, 0      # the proof-of-work step in front of the indices, and its nonce
         nroots, _, nvalues, path_bytes, _ = ml_sizes(d, log_blowup, log_final, nqueries, log_arity, grouped, k=k)
         n = limbs(field)
         self.ys = np.zeros((k, npoints, n), np.uint64)
@@ -448,19 +470,23 @@ class FriMlBatchOpening(FriMlPointsOpening):
         self.query_paths = np.zeros(path_bytes, np.uint8)
 
 
-def open_multilinear_batch(commitments, points, log_final, nqueries, log_arity=1, transcript=None):
+def open_multilinear_batch(commitments, points, log_final, nqueries, log_arity=1, transcript=None, grinding_bits=0):
     """one proof that each of the k <= 16 committed tables has the values `.ys[j]` at the same P <= 8 points (P, d, limbs).  The commitments
-    share field, size, blow-up, coset and leaf grouping; grouped ones (commit(.., log_group=2)) need log_arity=2"""
+    share field, size, blow-up, coset and leaf grouping; grouped ones (commit(.., log_group=2)) need log_arity=2.  grinding_bits = g > 0: a
+    proof-of-work nonce with g leading zero bits is found on the GPU before the indices are drawn; the opening carries g and it"""
     c0 = commitments[0]
     grouped = getattr(c0, "log_group", 0) != 0
     if grouped and log_arity != 2:
         raise ValueError("commitments with grouped leaves are opened with log_arity=2")
     pts = _points(c0.field, c0.d, points)
-    op = FriMlBatchOpening(c0.field, len(commitments), pts.shape[0], c0.d, c0.log_blowup, log_final, nqueries, c0.coset, log_arity, grouped)
-    L.check(L.lib().zk_fri_ml_open_batch(_handles(commitments), len(commitments), L.p64(pts), pts.shape[0], log_final, nqueries, log_arity,
-                                         _handle(transcript), L.p64(op.ys), L.p64(op.gamma), L.p64(op.round_polys), L.p8(op.roots),
-                                         L.p64(op.final_table), L.p64(op.challenges), L.p64(op.query_indices), L.p64(op.query_values),
-                                         L.p8(op.query_paths)))
+    op = FriMlBatchOpening(c0.field, len(commitments), pts.shape[0], c0.d, c0.log_blowup, log_final, nqueries, c0.coset, log_arity, grouped,
+                           grinding_bits)
+    nonce = C.c_uint64(0)
+    L.check(L.lib().zk_fri_ml_open_batch_pow(_handles(commitments), len(commitments), L.p64(pts), pts.shape[0], log_final, nqueries, log_arity,
+                                             _handle(transcript), L.p64(op.ys), L.p64(op.gamma), L.p64(op.round_polys), L.p8(op.roots),
+                                             L.p64(op.final_table), L.p64(op.challenges), L.p64(op.query_indices), L.p64(op.query_values),
+                                             L.p8(op.query_paths), grinding_bits, C.byref(nonce)))
+    op.pow_nonce = int(nonce.value)
     return op
 
 
@@ -477,9 +503,10 @@ def verify_multilinear_batch(roots, points, opening, transcript=None):
     if ys.shape != (op.k, pts.shape[0], limbs(op.field)):
         raise L.ZkError(L.ZK_E_ARG, "one claim per commitment and point")
     rts, paths = np.ascontiguousarray(op.roots, np.uint8), np.ascontiguousarray(op.query_paths, np.uint8)
-    L.check(L.lib().zk_fri_ml_verify_batch(op.field, L.p8(rf), op.k, op.d, op.log_blowup, op.log_final, op.nqueries, op.log_arity,
-                                           2 if op.grouped else 0, op._coset(), L.p64(pts), pts.shape[0], L.p64(ys), _handle(transcript),
-                                           L.p64(rp), L.p8(rts), L.p64(fin), L.p64(vals), L.p8(paths), C.byref(ok)))
+    L.check(L.lib().zk_fri_ml_verify_batch_pow(op.field, L.p8(rf), op.k, op.d, op.log_blowup, op.log_final, op.nqueries, op.log_arity,
+                                               2 if op.grouped else 0, op._coset(), L.p64(pts), pts.shape[0], L.p64(ys), _handle(transcript),
+                                               L.p64(rp), L.p8(rts), L.p64(fin), L.p64(vals), L.p8(paths), getattr(op, "grinding_bits", 0),
+                                               getattr(op, "pow_nonce", 0), C.byref(ok)))
     return bool(ok.value)
 
 

@@ -103,6 +103,25 @@ class Transcript:
         L.check(_decl().zk_transcript_challenge(self._h, field, L.p64(out)))
         return out
 
+    def grind(self, bits, start=0, log_batch=0):
+        """the proof-of-work step (include/zkmle.h "Proof-of-work grinding") with the search on the GPU: appends the tag and `bits`, finds the
+        smallest nonce >= start whose challenge has `bits` leading zero bits, appends it and samples that challenge.  -> the nonce"""
+        nonce = C.c_uint64(0)
+        L.check(L.lib().zk_transcript_grind(self._h, bits, start, log_batch, C.byref(nonce)))
+        return int(nonce.value)
+
+    def grind_host(self, bits, start=0, max_tries=0):
+        """the same on one host core; at most max_tries candidates (0: 2^(bits + 6))"""
+        nonce = C.c_uint64(0)
+        L.check(L.lib().zk_host_transcript_grind(self._h, bits, start, max_tries, C.byref(nonce)))
+        return int(nonce.value)
+
+    def check_grind(self, bits, nonce):
+        """the verifier's step: the tag, the nonce, the challenge.  -> whether its first `bits` bits are zero"""
+        ok = C.c_int(0)
+        L.check(L.lib().zk_transcript_grind_check(self._h, bits, nonce, C.byref(ok)))
+        return bool(ok.value)
+
     def export_state(self):
         """the running sponge: 26 uint64 words = 25 Keccak lanes + the fill of the open block (208 bytes)"""
         st = np.zeros(26, np.uint64)
