@@ -16,10 +16,9 @@ import pytest
 
 import __graft_entry__ as G
 import _fri_ml_arity_model as AM
+import _fri_ml_cases as FC
 import _fri_ml_model as ML
 import _fri_ml_points_model as PT
-import _fri_pcs_model as PM
-import _merkle_model as MM
 import _ntt_model as NM
 from oracle import pymodel as M
 
@@ -32,22 +31,17 @@ SHAPES = [(3, 1, 1), (4, 2, 1), (4, 1, 0), (6, 2, 1)]        # (d, b, f): R = 2,
 Q = 8
 
 
-@functools.lru_cache(maxsize=None)
-def hasher():
-    return MM.check_host_keccak(zk)
+hasher = functools.partial(FC.hasher, zk)
+padded = FC.padded
 
 
 @functools.lru_cache(maxsize=None)
 def commitment(field, d, b, with_coset):
-    coset = random.Random(43 * d + b + field).randrange(2, NM.MODULUS[field]) if with_coset else 1
-    return PM.commit(field, NM.random_ints(field, 1 << d, 7300 + 13 * d + field), b, coset, hasher())
+    return FC.commitment(field, d, b, FC.coset_of(field, d, b, with_coset, 43), 7300 + 13 * d + field, hasher())
 
 
 def points_for(field, d, P):
-    p, rng = NM.MODULUS[field], random.Random(101 * d + 7 * P + field)
-    pts = [[rng.randrange(p) for _ in range(d)] for _ in range(P)]
-    pts[0][d - 1] = p - 1
-    return pts
+    return FC.points_for(field, d, P, 101 * d + 7 * P + field)
 
 
 @functools.lru_cache(maxsize=None)
@@ -67,11 +61,6 @@ def lib_verify(op, fl=None, tr=None, a=2, flat=AM.flat, **over):
                                                 p64(fl["ys"]), None if tr is None else tr._h, p64(fl["polys"]), p8(fl["roots"]), p64(fl["final"]),
                                                 p64(fl["values"]), p8(fl["paths"]), C.byref(ok))
     return rc, ok.value
-
-
-def padded(fl):
-    """the flat arrays with room behind them: a verifier of another arity reads other counts"""
-    return {n: np.concatenate([v.reshape(-1), np.zeros(4 * v.size + 4096, v.dtype)]) for n, v in fl.items()}
 
 
 def test_new_exports_are_present():

@@ -20,10 +20,10 @@ import pytest
 import __graft_entry__ as G
 import _fri_ml_arity_model as AM
 import _fri_ml_batch_model as BM
+import _fri_ml_cases as FC
 import _fri_ml_grouped_model as GM
 import _fri_ml_model as ML
 import _fri_ml_points_model as PT
-import _fri_pcs_model as PM
 import _ntt_model as NM
 
 zk = G.import_package()
@@ -41,27 +41,19 @@ case_id = lambda c: "-".join(str(int(v)) for v in c)
 sched_id = lambda s: "a%d%s" % (s[0], "g" if s[1] else "")
 
 
-@functools.lru_cache(maxsize=None)
-def hasher():
-    return GM.check_host_keccak(zk)
-
-
-def coset_of(field, d, b, with_coset):
-    return random.Random(43 * d + b + field).randrange(2, NM.MODULUS[field]) if with_coset else 1
+hasher = functools.partial(FC.hasher, zk, True)
+tampered = FC.tampered
+padded = functools.partial(FC.padded, room=8192)
+coset_of = functools.partial(FC.coset_of, mul=43)
 
 
 @functools.lru_cache(maxsize=None)
 def commitment(field, d, b, with_coset, grouped, j):
-    coeffs = NM.random_ints(field, 1 << d, 8100 + 13 * d + field + 101 * j)
-    coset = coset_of(field, d, b, with_coset)
-    return GM.commit(field, coeffs, b, coset, hasher()) if grouped else PM.commit(field, coeffs, b, coset, hasher())
+    return FC.commitment(field, d, b, coset_of(field, d, b, with_coset), 8100 + 13 * d + field + 101 * j, hasher(), grouped)
 
 
 def points_for(field, d, P):
-    p, rng = NM.MODULUS[field], random.Random(103 * d + 7 * P + field)
-    pts = [[rng.randrange(p) for _ in range(d)] for _ in range(P)]
-    pts[0][d - 1] = p - 1
-    return pts
+    return FC.points_for(field, d, P, 103 * d + 7 * P + field)
 
 
 @functools.lru_cache(maxsize=None)
@@ -85,11 +77,6 @@ def lib_verify(op, fl=None, tr=None, **over):
                                          len(op["points"]), p64(fl["ys"]), None if tr is None else tr._h, p64(fl["polys"]), p8(fl["roots"]),
                                          p64(fl["final"]), p64(fl["values"]), p8(fl["paths"]), C.byref(ok))
     return rc, ok.value
-
-
-def padded(fl):
-    """the flat arrays with room behind them: a verifier told another k or protocol reads other counts"""
-    return {n: np.concatenate([v.reshape(-1), np.zeros(4 * v.size + 8192, v.dtype)]) for n, v in fl.items()}
 
 
 def test_new_exports_are_present():
@@ -128,13 +115,6 @@ def test_model_openings_pass_the_model_verifier_and_the_library_verifier(case, s
     o.ys, o.round_polys, o.roots, o.final_table, o.query_values, o.query_paths = fl["ys"], fl["polys"], fl["roots"], fl["final"], fl["values"], fl["paths"]
     assert zk.fri.verify_multilinear_batch(op["own_roots"], fl["points"], o)
     assert not zk.fri.verify_multilinear_batch([r[::-1] for r in op["own_roots"]], fl["points"], o)
-
-
-def tampered(base, name, at, rng):
-    fl = {n: v.copy() for n, v in base.items()}
-    bits = 8 if fl[name].dtype == np.uint8 else 64
-    fl[name][at] ^= fl[name].dtype.type(1 << rng.randrange(bits))
-    return fl
 
 
 # R = 4 (steps alone), R = 5 (a final fold-2 step behind fold-4 steps), R = 2 (at arity 2 step 0 is the only step)

@@ -20,6 +20,7 @@ import pytest
 
 import __graft_entry__ as G
 import _fri_ml_arity_model as AM
+import _fri_ml_cases as FC
 import _fri_ml_grouped_model as GM
 import _fri_ml_model as ML
 import _fri_pcs_model as PM
@@ -39,9 +40,8 @@ Q = 8
 case_id = lambda c: "-".join(str(int(v)) for v in c)
 
 
-@functools.lru_cache(maxsize=None)
-def hasher():
-    return GM.check_host_keccak(zk)
+hasher = functools.partial(FC.hasher, zk, True)
+padded, tampered = FC.padded, FC.tampered
 
 
 def test_new_exports_are_present():
@@ -180,10 +180,7 @@ def commitment(field, d, b, with_coset):
 
 
 def points_for(field, d, P):
-    p, rng = NM.MODULUS[field], random.Random(101 * d + 7 * P + field)
-    pts = [[rng.randrange(p) for _ in range(d)] for _ in range(P)]
-    pts[0][d - 1] = p - 1
-    return pts
+    return FC.points_for(field, d, P, 101 * d + 7 * P + field)
 
 
 @functools.lru_cache(maxsize=None)
@@ -206,11 +203,6 @@ def lib_verify(op, fl=None, tr=None, **over):
     return rc, ok.value
 
 
-def padded(fl):
-    """the flat arrays with room behind them: a verifier of another protocol reads other counts"""
-    return {n: np.concatenate([v.reshape(-1), np.zeros(4 * v.size + 4096, v.dtype)]) for n, v in fl.items()}
-
-
 @pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_model_openings_pass_the_model_verifier_and_the_library_verifier(case):
     field, d, b, f, P, with_coset = case
@@ -229,13 +221,6 @@ def test_model_openings_pass_the_model_verifier_and_the_library_verifier(case):
     o.ys, o.round_polys, o.roots, o.final_table, o.query_values, o.query_paths = fl["ys"], fl["polys"], fl["roots"], fl["final"], fl["values"], fl["paths"]
     assert zk.fri.verify_multilinear_points(op["root"], fl["points"], o)
     assert not zk.fri.verify_multilinear_points(op["root"][::-1], fl["points"], o)
-
-
-def tampered(base, name, at, rng):
-    fl = {n: v.copy() for n, v in base.items()}
-    bits = 8 if fl[name].dtype == np.uint8 else 64
-    fl[name][at] ^= fl[name].dtype.type(1 << rng.randrange(bits))
-    return fl
 
 
 TAMPER_CASES = [CASES[3], CASES[5], CASES[8]]                # R = 4, 5 and 9: fold-4 steps alone, and with the final fold-2 step

@@ -17,10 +17,9 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as G
+import _fri_ml_cases as FC
 import _fri_ml_model as ML
 import _fri_ml_points_model as PT
-import _fri_pcs_model as PM
-import _merkle_model as MM
 import _ntt_model as NM
 from oracle import pymodel as M
 
@@ -32,15 +31,12 @@ NEW_NAMES = ("zk_fri_ml_round", "zk_fri_ml_open_points", "zk_fri_ml_verify_point
 SHAPES = [(1, 1, 0), (4, 2, 1), (6, 1, 0), (5, 2, 4)]        # (d, b, f)
 
 
-@functools.lru_cache(maxsize=None)
-def hasher():
-    return MM.check_host_keccak(zk)
+hasher = functools.partial(FC.hasher, zk)
 
 
 @functools.lru_cache(maxsize=None)
 def commitment(field, d, b, with_coset, seed=0):
-    coset = random.Random(41 * d + b + field).randrange(2, NM.MODULUS[field]) if with_coset else 1
-    return PM.commit(field, NM.random_ints(field, 1 << d, 6300 + 13 * d + field + seed), b, coset, hasher())
+    return FC.commitment(field, d, b, FC.coset_of(field, d, b, with_coset, 41), 6300 + 13 * d + field + seed, hasher())
 
 
 def point_sets(field, d, P):

@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import _fri_ml_arity_model as AM
-import _fri_pcs_model as PM
+import _fri_ml_cases as FC
 import _ntt_model as NM
 from oracle import pymodel as M
 from test_gpu_fri import hasher_for, table_of, to_mont, zk  # noqa: F401  (zk: the module's fixture)
@@ -64,22 +64,13 @@ def test_fold4_equals_two_folds(zk, field, loglen, with_coset):
 
 
 # ---- the opening ------------------------------------------------------------------------------------------------------------------------
+gpu_commitment = FC.gpu_commitment
+points_for = functools.partial(FC.points_for, bit_at_1=True)
+
+
 @functools.lru_cache(maxsize=None)
 def model_commitment(zk, field, d, b, with_coset):
-    coset = random.Random(67 * d + b + field).randrange(2, NM.MODULUS[field]) if with_coset else 1
-    return PM.commit(field, NM.random_ints(field, 1 << d, 9700 + 17 * d + b + field), b, coset, hasher_for(zk, 2 << (d + b)))
-
-
-def gpu_commitment(zk, cm):
-    cs = None if cm["coset"] == 1 else elem(zk, cm["field"], cm["coset"])
-    return zk.fri.commit(table_of(zk, cm["field"], cm["coeffs"]), cm["b"], cs)
-
-
-def points_for(field, d, P, seed):
-    p, rng = NM.MODULUS[field], random.Random(seed)
-    pts = [[rng.randrange(p) for _ in range(d)] for _ in range(P)]
-    pts[0][1], pts[0][d - 1] = rng.choice((0, 1)), p - 1
-    return pts
+    return FC.commitment(field, d, b, FC.coset_of(field, d, b, with_coset, 67), 9700 + 17 * d + b + field, hasher_for(zk, 2 << (d + b)))
 
 
 def open_raw(zk, gc, pm, f, nq, a, transcript=None):

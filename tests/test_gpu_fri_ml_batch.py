@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import _fri_ml_batch_model as BM
+import _fri_ml_cases as FC
 import _ntt_model as NM
 from oracle import pymodel as M
 from test_fri_ml_batch_cpu import CASES, KS, SCHEDULES, case_id, commitment, hasher, points_for, sched_id
@@ -101,9 +102,7 @@ def test_fold_batch_at_operands_random_tables_never_reach(zk, field, with_coset)
 
 
 # ---- the opening --------------------------------------------------------------------------------------------------------------------------
-def gpu_commitment(zk, cm):
-    cs = None if cm["coset"] == 1 else elem(zk, cm["field"], cm["coset"])
-    return zk.fri.commit(table_of(zk, cm["field"], cm["coeffs"]), cm["b"], cs, log_group=cm.get("log_group", 0))
+gpu_commitment = FC.gpu_commitment
 
 
 def assert_same_opening(got, fl):

@@ -10,11 +10,11 @@ compares byte for byte with the model of tests/_fri_ml_grouped_model.py; no tole
              zk_fri_ml_open_points_grouped returns ZK_E_ARG on an ungrouped one"""
 import ctypes as C
 import functools
-import random
 
 import numpy as np
 import pytest
 
+import _fri_ml_cases as FC
 import _fri_ml_grouped_model as GM
 import _ntt_model as NM
 from oracle import pymodel as M
@@ -30,15 +30,12 @@ def hasher_for(zk, n):
     return GM.check_host_keccak(zk) if n > 1 << 10 else M.keccak256
 
 
+gpu_commitment = FC.gpu_commitment
+
+
 @functools.lru_cache(maxsize=None)
 def model_commitment(zk, field, d, b, with_coset):
-    coset = random.Random(67 * d + b + field).randrange(2, NM.MODULUS[field]) if with_coset else 1
-    return GM.commit(field, NM.random_ints(field, 1 << d, 9700 + 17 * d + b + field), b, coset, hasher_for(zk, 2 << (d + b)))
-
-
-def gpu_commitment(zk, cm, log_group=2):
-    cs = None if cm["coset"] == 1 else elem(zk, cm["field"], cm["coset"])
-    return zk.fri.commit(table_of(zk, cm["field"], cm["coeffs"]), cm["b"], cs, log_group=log_group)
+    return FC.commitment(field, d, b, FC.coset_of(field, d, b, with_coset, 67), 9700 + 17 * d + b + field, hasher_for(zk, 2 << (d + b)), True)
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join(str(int(v)) for v in c))

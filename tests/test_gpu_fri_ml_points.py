@@ -19,8 +19,8 @@ import random
 import numpy as np
 import pytest
 
+import _fri_ml_cases as FC
 import _fri_ml_points_model as PT
-import _fri_pcs_model as PM
 import _ntt_model as NM
 from oracle import pymodel as M
 from test_gpu_fri import hasher_for, table_of, to_mont, zk  # noqa: F401  (zk: the module's fixture)
@@ -73,19 +73,13 @@ def test_round_pass_at_operands_random_tables_never_reach(zk, field):
 
 
 # ---- the opening -----------------------------------------------------------------------------------------------------------------------
-def coset_of(field, d, b, with_coset):
-    return random.Random(61 * d + b + field).randrange(2, NM.MODULUS[field]) if with_coset else 1
+coset_of = functools.partial(FC.coset_of, mul=61)
+gpu_commitment = FC.gpu_commitment
 
 
 @functools.lru_cache(maxsize=None)
 def model_commitment(zk, field, d, b, with_coset):
-    coset = coset_of(field, d, b, with_coset)
-    return PM.commit(field, NM.random_ints(field, 1 << d, 9100 + 17 * d + b + field), b, coset, hasher_for(zk, 2 << (d + b)))
-
-
-def gpu_commitment(zk, cm):
-    cs = None if cm["coset"] == 1 else elem(zk, cm["field"], cm["coset"])
-    return zk.fri.commit(table_of(zk, cm["field"], cm["coeffs"]), cm["b"], cs)
+    return FC.commitment(field, d, b, coset_of(field, d, b, with_coset), 9100 + 17 * d + b + field, hasher_for(zk, 2 << (d + b)))
 
 
 def assert_same_opening(zk, got, op):

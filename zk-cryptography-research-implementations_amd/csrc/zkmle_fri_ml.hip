@@ -664,6 +664,29 @@ int verify_opening(int field, const uint8_t *root32, uint32_t d, uint32_t log_bl
     return ZK_OK;
 }
 
+// what the several-point openers of one commitment and of k check alike, every ZK_E_ARG before the device is asked for: the outputs, P, the
+// arity, open_check on the (first) commitment with the leaf grouping its protocol needs, R >= 2 at log_arity 2, reduced points
+int open_points_check(const zk_fri_commitment *cm, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                      unsigned log_group, const uint64_t *ys_out, const OpenOut &o) {
+    if (!cm || !points || !ys_out || !o.round_polys || !o.roots || !o.final_table || !o.query_values || !o.query_paths) return ZK_E_ARG;
+    if (npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2) return ZK_E_ARG;
+    ZK_TRY(open_check(cm, nullptr, log_final, nqueries, log_group));
+    if (log_arity == 2 && cm->d - log_final < 2) return ZK_E_ARG;
+    if (!all_reduced(cm->field, points, (size_t)npoints * cm->d)) return ZK_E_ARG;
+    return require_device();
+}
+
+// the several-point verifiers' claim; ntables = 0: one table
+FriMlClaim claim_of(const uint64_t *points, uint32_t npoints, const uint64_t *ys, const uint64_t *round_polys, uint32_t log_arity, bool grouped,
+                    uint32_t ntables) {
+    FriMlClaim ml{points, ys, round_polys};
+    ml.npoints = npoints;
+    ml.log_arity = log_arity;
+    ml.grouped = grouped;
+    ml.ntables = ntables;
+    return ml;
+}
+
 }  // namespace
 
 extern "C" {
@@ -717,14 +740,9 @@ int zk_fri_ml_open_points(const zk_fri_commitment *cm, const uint64_t *points, u
 int zk_fri_ml_open_points_arity(const zk_fri_commitment *cm, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
                                 zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table,
                                 uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths) {
-    if (!cm || !points || !ys_out || !round_polys || !roots || !final_table || !query_values || !query_paths) return ZK_E_ARG;
-    if (npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2) return ZK_E_ARG;
-    ZK_TRY(open_check(cm, nullptr, log_final, nqueries));
-    if (log_arity == 2 && cm->d - log_final < 2) return ZK_E_ARG;
-    if (!all_reduced(cm->field, points, (size_t)npoints * cm->d)) return ZK_E_ARG;
-    ZK_TRY(require_device());
-    Transcript fresh;
     const OpenOut o{round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
+    ZK_TRY(open_points_check(cm, points, npoints, log_final, nqueries, log_arity, 0, ys_out, o));
+    Transcript fresh;
     FRI_DISPATCH(cm->field, ManyPoints<F> form{points, npoints, ys_out, gamma_out, cm->d}; return open_with<F>(cm, form, log_final, nqueries, log_arity, false, t ? t->t : fresh, o));
     return ZK_OK;
 }
@@ -734,10 +752,8 @@ int zk_fri_ml_verify_points_arity(int field, const uint8_t *root32, uint32_t d, 
                                   const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
                                   const uint8_t *query_paths, int *ok) {
     if (npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2) return ZK_E_ARG;
-    FriMlClaim ml{points, ys, round_polys};
-    ml.npoints = npoints;
-    ml.log_arity = log_arity;
-    return verify_opening(field, root32, d, log_blowup, log_final, nqueries, coset, ml, t, roots, final_table, query_values, query_paths, ok);
+    return verify_opening(field, root32, d, log_blowup, log_final, nqueries, coset, claim_of(points, npoints, ys, round_polys, log_arity, false, 0), t, roots,
+                          final_table, query_values, query_paths, ok);
 }
 
 int zk_fri_ml_fold4(const zk_table *codeword, const uint64_t *r0, const uint64_t *r1, const uint64_t *coset, zk_table **out) {
@@ -797,8 +813,7 @@ int zk_fri_ml_open_batch_pow(const zk_fri_commitment *const *cms, uint32_t k, co
                              uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
                              uint32_t grinding_bits, uint64_t *pow_nonce) {
     if (grinding_bits > ZK_FRI_GRIND_MAX_BITS || (grinding_bits && !pow_nonce)) return ZK_E_ARG;
-    if (!cms || !points || !ys_out || !round_polys || !roots || !final_table || !query_values || !query_paths) return ZK_E_ARG;
-    if (k < 1 || k > ZK_FRI_ML_BATCH_MAX || npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2 || !cms[0]) return ZK_E_ARG;
+    if (!cms || k < 1 || k > ZK_FRI_ML_BATCH_MAX || !cms[0]) return ZK_E_ARG;
     const zk_fri_commitment *c0 = cms[0];
     for (uint32_t j = 1; j < k; j++) {                        // one field, size, blow-up, coset and leaf grouping
         const zk_fri_commitment *cj = cms[j];
@@ -806,12 +821,9 @@ int zk_fri_ml_open_batch_pow(const zk_fri_commitment *const *cms, uint32_t k, co
         if (c0->has_coset && memcmp(cj->coset, c0->coset, sizeof c0->coset) != 0) return ZK_E_ARG;
     }
     if ((c0->log_group != 0 && c0->log_group != 2) || (c0->log_group == 2 && log_arity != 2)) return ZK_E_ARG;
-    ZK_TRY(open_check(c0, nullptr, log_final, nqueries, c0->log_group));
-    if (log_arity == 2 && c0->d - log_final < 2) return ZK_E_ARG;
-    if (!all_reduced(c0->field, points, (size_t)npoints * c0->d)) return ZK_E_ARG;
-    ZK_TRY(require_device());
-    Transcript fresh;
     const OpenOut o{round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
+    ZK_TRY(open_points_check(c0, points, npoints, log_final, nqueries, log_arity, c0->log_group, ys_out, o));
+    Transcript fresh;
     FRI_DISPATCH(c0->field, ManyTables<F> form(cms, k, points, npoints, ys_out, gamma_out, c0->d);
                  return open_with<F>(c0, form, log_final, nqueries, log_arity, c0->log_group == 2, t ? t->t : fresh, o, grinding_bits, pow_nonce));
     return ZK_OK;
@@ -832,13 +844,8 @@ int zk_fri_ml_verify_batch_pow(int field, const uint8_t *roots_of_f, uint32_t k,
     if (grinding_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
     if (k < 1 || k > ZK_FRI_ML_BATCH_MAX || npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2) return ZK_E_ARG;
     if ((log_group != 0 && log_group != 2) || (log_group == 2 && log_arity != 2)) return ZK_E_ARG;
-    FriMlClaim ml{points, ys, round_polys};
-    ml.npoints = npoints;
-    ml.log_arity = log_arity;
-    ml.grouped = log_group == 2;
-    ml.ntables = k;
-    return verify_opening(field, roots_of_f, d, log_blowup, log_final, nqueries, coset, ml, t, roots, final_table, query_values, query_paths, ok, grinding_bits,
-                          pow_nonce);
+    return verify_opening(field, roots_of_f, d, log_blowup, log_final, nqueries, coset, claim_of(points, npoints, ys, round_polys, log_arity, log_group == 2, k), t,
+                          roots, final_table, query_values, query_paths, ok, grinding_bits, pow_nonce);
 }
 
 int zk_fri_ml_sizes_grouped(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots, size_t *nfinal, size_t *nvalues,
@@ -851,14 +858,9 @@ int zk_fri_ml_sizes_grouped(uint32_t d, uint32_t log_blowup, uint32_t log_final,
 int zk_fri_ml_open_points_grouped(const zk_fri_commitment *cm, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries, zk_transcript *t,
                                   uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *challenges,
                                   uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths) {
-    if (!cm || !points || !ys_out || !round_polys || !roots || !final_table || !query_values || !query_paths) return ZK_E_ARG;
-    if (npoints < 1 || npoints > 8) return ZK_E_ARG;
-    ZK_TRY(open_check(cm, nullptr, log_final, nqueries, 2));
-    if (cm->d - log_final < 2) return ZK_E_ARG;
-    if (!all_reduced(cm->field, points, (size_t)npoints * cm->d)) return ZK_E_ARG;
-    ZK_TRY(require_device());
-    Transcript fresh;
     const OpenOut o{round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
+    ZK_TRY(open_points_check(cm, points, npoints, log_final, nqueries, 2, 2, ys_out, o));
+    Transcript fresh;
     FRI_DISPATCH(cm->field, ManyPoints<F> form{points, npoints, ys_out, gamma_out, cm->d}; return open_with<F>(cm, form, log_final, nqueries, 2, true, t ? t->t : fresh, o));
     return ZK_OK;
 }
@@ -867,11 +869,8 @@ int zk_fri_ml_verify_points_grouped(int field, const uint8_t *root32, uint32_t d
                                     const uint64_t *points, uint32_t npoints, const uint64_t *ys, zk_transcript *t, const uint64_t *round_polys,
                                     const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, int *ok) {
     if (npoints < 1 || npoints > 8) return ZK_E_ARG;
-    FriMlClaim ml{points, ys, round_polys};
-    ml.npoints = npoints;
-    ml.log_arity = 2;
-    ml.grouped = 1;
-    return verify_opening(field, root32, d, log_blowup, log_final, nqueries, coset, ml, t, roots, final_table, query_values, query_paths, ok);
+    return verify_opening(field, root32, d, log_blowup, log_final, nqueries, coset, claim_of(points, npoints, ys, round_polys, 2, true, 0), t, roots, final_table,
+                          query_values, query_paths, ok);
 }
 
 int zk_fri_ml_verify_points(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset,

@@ -266,14 +266,8 @@ def ml_sizes(d, log_blowup, log_final, nqueries, log_arity=1, grouped=False, k=N
     out = [C.c_size_t(0) for _ in range(5)]
     if grouped and log_arity != 2:
         raise ValueError("grouped leaves need log_arity=2")
-    if k is not None:
-        L.check(L.lib().zk_fri_ml_sizes_batch(k, d, log_blowup, log_final, nqueries, log_arity, 2 if grouped else 0, *[C.byref(o) for o in out]))
-    elif grouped:
-        L.check(L.lib().zk_fri_ml_sizes_grouped(d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
-    elif log_arity == 1:
-        L.check(L.lib().zk_fri_ml_sizes(d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
-    else:
-        L.check(L.lib().zk_fri_ml_sizes_arity(d, log_blowup, log_final, nqueries, log_arity, *[C.byref(o) for o in out]))
+    L.check(L.lib().zk_fri_ml_sizes_batch(1 if k is None else k, d, log_blowup, log_final, nqueries, log_arity, 2 if grouped else 0,
+                                          *[C.byref(o) for o in out]))      # at k = 1 the single-table counts
     return tuple(int(o.value) for o in out)
 
 
@@ -336,20 +330,48 @@ def open_multilinear(commitment, z, log_final, nqueries, transcript=None):
     return op
 
 
+def _points(field, d, points):
+    pts = np.ascontiguousarray(points, np.uint64)
+    if pts.ndim != 3 or pts.shape[1] != d or pts.shape[2] != limbs(field):
+        raise L.ZkError(L.ZK_E_ARG, "the points are a (P, d, limbs) array of elements")
+    return pts
+
+
+def _verifier_inputs(op, roots, claims, points=None, k=None, arity=None):
+    """what the verifiers of the multilinear openings marshal alike -> (the roots' bytes, the points, the claims, the proof's arrays in the C
+    ABI's order), checked: 32 bytes per root (k: as many roots as a batch has commitments), the points' shape, one claim per point (and
+    commitment), and with arity = (log_arity, grouped) that the arrays hold the proof of that arity, whose counts may not be the opening's own"""
+    rf = np.frombuffer(b"".join(bytes(r) for r in roots), np.uint8).copy()
+    if rf.shape[0] != 32 * len(roots) or len(roots) != (1 if k is None else k):
+        raise L.ZkError(L.ZK_E_ARG, "a Merkle root is 32 bytes" if k is None else "one 32-byte Merkle root per commitment")
+    pts = None if points is None else _points(op.field, op.d, points)
+    ys, rp, fin, vals = (np.ascontiguousarray(a, np.uint64) for a in (claims, op.round_polys, op.final_table, op.query_values))
+    if pts is not None and ys.shape != (() if k is None else (k,)) + (pts.shape[0], limbs(op.field)):
+        raise L.ZkError(L.ZK_E_ARG, "one claim per point" if k is None else "one claim per commitment and point")
+    rts, paths = np.ascontiguousarray(op.roots, np.uint8), np.ascontiguousarray(op.query_paths, np.uint8)
+    if arity is not None:
+        nroots, nfinal, nvalues, path_bytes, nround = ml_sizes(op.d, op.log_blowup, op.log_final, op.nqueries, *arity)
+        n = limbs(op.field)
+        if rts.size < 32 * nroots or fin.size < nfinal * n or vals.size < nvalues * n or paths.size < path_bytes or rp.size < nround * n:
+            raise L.ZkError(L.ZK_E_ARG, "the opening's arrays are shorter than this arity's proof")
+    return L.p8(rf), pts, ys, (L.p64(rp), L.p8(rts), L.p64(fin), L.p64(vals), L.p8(paths))
+
+
+def _prover_outputs(op):
+    """the outputs of a several-point prover in the C ABI's order"""
+    return (L.p64(op.ys), L.p64(op.gamma), L.p64(op.round_polys), L.p8(op.roots), L.p64(op.final_table), L.p64(op.challenges),
+            L.p64(op.query_indices), L.p64(op.query_values), L.p8(op.query_paths))
+
+
 def verify_multilinear(root, z, opening, transcript=None):
     """host only: `root` = the commitment's 32 bytes; the claim checked is evaluate(table, z) = opening.y"""
-    ok = C.c_int(0)
-    op = opening
-    rbuf = np.frombuffer(bytes(root), np.uint8).copy()
-    if rbuf.shape[0] != 32:
-        raise L.ZkError(L.ZK_E_ARG, "a Merkle root is 32 bytes")
+    op, ok = opening, C.c_int(0)
+    rf, _, y, proof = _verifier_inputs(op, [root], op.y)
     z = _point(op.field, z)
     if z.shape[0] != op.d:
         raise L.ZkError(L.ZK_E_ARG, "the point needs one element per variable")
-    y, rp, fin, vals = (np.ascontiguousarray(a, np.uint64) for a in (op.y, op.round_polys, op.final_table, op.query_values))
-    roots, paths = np.ascontiguousarray(op.roots, np.uint8), np.ascontiguousarray(op.query_paths, np.uint8)
-    L.check(L.lib().zk_fri_ml_verify(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, op._coset(), L.p64(z), L.p64(y),
-                                     _handle(transcript), L.p64(rp), L.p8(roots), L.p64(fin), L.p64(vals), L.p8(paths), C.byref(ok)))
+    L.check(L.lib().zk_fri_ml_verify(op.field, rf, op.d, op.log_blowup, op.log_final, op.nqueries, op._coset(), L.p64(z), L.p64(y), _handle(transcript),
+                                     *proof, C.byref(ok)))
     return bool(ok.value)
 
 
@@ -365,13 +387,6 @@ class FriMlPointsOpening(FriMlOpening):
         self.npoints, self.log_arity, self.grouped = npoints, log_arity, grouped
         self.ys = np.zeros((npoints, limbs(field)), np.uint64)
         self.gamma = np.zeros(limbs(field), np.uint64)
-
-
-def _points(field, d, points):
-    pts = np.ascontiguousarray(points, np.uint64)
-    if pts.ndim != 3 or pts.shape[1] != d or pts.shape[2] != limbs(field):
-        raise L.ZkError(L.ZK_E_ARG, "the points are a (P, d, limbs) array of elements")
-    return pts
 
 
 def ml_round(T, W, r=None):
@@ -395,46 +410,33 @@ def open_multilinear_points(commitment, points, log_final, nqueries, transcript=
         raise ValueError("a commitment with grouped leaves is opened with log_arity=2")
     pts = _points(commitment.field, commitment.d, points)
     op = FriMlPointsOpening(commitment.field, pts.shape[0], commitment.d, commitment.log_blowup, log_final, nqueries, commitment.coset, log_arity, grouped)
-    out = (L.p64(op.ys), L.p64(op.gamma), L.p64(op.round_polys), L.p8(op.roots), L.p64(op.final_table), L.p64(op.challenges),
-           L.p64(op.query_indices), L.p64(op.query_values), L.p8(op.query_paths))
+    first = (commitment._h, L.p64(pts), pts.shape[0], log_final, nqueries)
     if grouped:
-        L.check(L.lib().zk_fri_ml_open_points_grouped(commitment._h, L.p64(pts), pts.shape[0], log_final, nqueries, _handle(transcript), *out))
+        L.check(L.lib().zk_fri_ml_open_points_grouped(*first, _handle(transcript), *_prover_outputs(op)))
     elif log_arity == 1:
-        L.check(L.lib().zk_fri_ml_open_points(commitment._h, L.p64(pts), pts.shape[0], log_final, nqueries, _handle(transcript), *out))
+        L.check(L.lib().zk_fri_ml_open_points(*first, _handle(transcript), *_prover_outputs(op)))
     else:
-        L.check(L.lib().zk_fri_ml_open_points_arity(commitment._h, L.p64(pts), pts.shape[0], log_final, nqueries, log_arity, _handle(transcript), *out))
+        L.check(L.lib().zk_fri_ml_open_points_arity(*first, log_arity, _handle(transcript), *_prover_outputs(op)))
     return op
 
 
 def verify_multilinear_points(root, points, opening, transcript=None, log_arity=None):
     """host only: `root` = the commitment's 32 bytes; the claims checked are evaluate(table, points[p]) = opening.ys[p].  log_arity: the
     opening's own unless given; an opening with `.grouped` set is checked by the grouped protocol's verifier"""
-    ok = C.c_int(0)
-    op = opening
+    op, ok = opening, C.c_int(0)
     log_arity = getattr(op, "log_arity", 1) if log_arity is None else log_arity
     grouped = bool(getattr(op, "grouped", False))
     if grouped and log_arity != 2:
         raise ValueError("an opening with grouped leaves has log_arity=2")
-    rbuf = np.frombuffer(bytes(root), np.uint8).copy()
-    if rbuf.shape[0] != 32:
-        raise L.ZkError(L.ZK_E_ARG, "a Merkle root is 32 bytes")
-    pts = _points(op.field, op.d, points)
-    ys, rp, fin, vals = (np.ascontiguousarray(a, np.uint64) for a in (op.ys, op.round_polys, op.final_table, op.query_values))
-    if ys.shape != (pts.shape[0], limbs(op.field)):
-        raise L.ZkError(L.ZK_E_ARG, "one claim per point")
-    roots, paths = np.ascontiguousarray(op.roots, np.uint8), np.ascontiguousarray(op.query_paths, np.uint8)
-    if log_arity != 1:                                        # the counts differ from the opening's own when the arity is overridden
-        nroots, nfinal, nvalues, path_bytes, nround = ml_sizes(op.d, op.log_blowup, op.log_final, op.nqueries, log_arity, grouped)
-        n = limbs(op.field)
-        if roots.size < 32 * nroots or fin.size < nfinal * n or vals.size < nvalues * n or paths.size < path_bytes or rp.size < nround * n:
-            raise L.ZkError(L.ZK_E_ARG, "the opening's arrays are shorter than this arity's proof")
-    rest = (op._coset(), L.p64(pts), pts.shape[0], L.p64(ys), _handle(transcript), L.p64(rp), L.p8(roots), L.p64(fin), L.p64(vals), L.p8(paths), C.byref(ok))
+    rf, pts, ys, proof = _verifier_inputs(op, [root], op.ys, points, arity=None if log_arity == 1 else (log_arity, grouped))
+    first = (op.field, rf, op.d, op.log_blowup, op.log_final, op.nqueries)
+    rest = (op._coset(), L.p64(pts), pts.shape[0], L.p64(ys), _handle(transcript), *proof, C.byref(ok))
     if grouped:
-        L.check(L.lib().zk_fri_ml_verify_points_grouped(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, *rest))
+        L.check(L.lib().zk_fri_ml_verify_points_grouped(*first, *rest))
     elif log_arity == 1:
-        L.check(L.lib().zk_fri_ml_verify_points(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, *rest))
+        L.check(L.lib().zk_fri_ml_verify_points(*first, *rest))
     else:
-        L.check(L.lib().zk_fri_ml_verify_points_arity(op.field, L.p8(rbuf), op.d, op.log_blowup, op.log_final, op.nqueries, log_arity, *rest))
+        L.check(L.lib().zk_fri_ml_verify_points_arity(*first, log_arity, *rest))
     return bool(ok.value)
 
 
@@ -483,9 +485,7 @@ def open_multilinear_batch(commitments, points, log_final, nqueries, log_arity=1
                            grinding_bits)
     nonce = C.c_uint64(0)
     L.check(L.lib().zk_fri_ml_open_batch_pow(_handles(commitments), len(commitments), L.p64(pts), pts.shape[0], log_final, nqueries, log_arity,
-                                             _handle(transcript), L.p64(op.ys), L.p64(op.gamma), L.p64(op.round_polys), L.p8(op.roots),
-                                             L.p64(op.final_table), L.p64(op.challenges), L.p64(op.query_indices), L.p64(op.query_values),
-                                             L.p8(op.query_paths), grinding_bits, C.byref(nonce)))
+                                             _handle(transcript), *_prover_outputs(op), grinding_bits, C.byref(nonce)))
     op.pow_nonce = int(nonce.value)
     return op
 
@@ -493,20 +493,11 @@ def open_multilinear_batch(commitments, points, log_final, nqueries, log_arity=1
 def verify_multilinear_batch(roots, points, opening, transcript=None):
     """host only: `roots` = the k commitment roots (32 bytes each) in the prover's order; the claims checked are
     evaluate(table_j, points[p]) = opening.ys[j, p]"""
-    ok = C.c_int(0)
-    op = opening
-    rf = np.frombuffer(b"".join(bytes(r) for r in roots), np.uint8).copy()
-    if rf.shape[0] != 32 * len(roots) or len(roots) != op.k:
-        raise L.ZkError(L.ZK_E_ARG, "one 32-byte Merkle root per commitment")
-    pts = _points(op.field, op.d, points)
-    ys, rp, fin, vals = (np.ascontiguousarray(a, np.uint64) for a in (op.ys, op.round_polys, op.final_table, op.query_values))
-    if ys.shape != (op.k, pts.shape[0], limbs(op.field)):
-        raise L.ZkError(L.ZK_E_ARG, "one claim per commitment and point")
-    rts, paths = np.ascontiguousarray(op.roots, np.uint8), np.ascontiguousarray(op.query_paths, np.uint8)
-    L.check(L.lib().zk_fri_ml_verify_batch_pow(op.field, L.p8(rf), op.k, op.d, op.log_blowup, op.log_final, op.nqueries, op.log_arity,
-                                               2 if op.grouped else 0, op._coset(), L.p64(pts), pts.shape[0], L.p64(ys), _handle(transcript),
-                                               L.p64(rp), L.p8(rts), L.p64(fin), L.p64(vals), L.p8(paths), getattr(op, "grinding_bits", 0),
-                                               getattr(op, "pow_nonce", 0), C.byref(ok)))
+    op, ok = opening, C.c_int(0)
+    rf, pts, ys, proof = _verifier_inputs(op, roots, op.ys, points, k=op.k)
+    L.check(L.lib().zk_fri_ml_verify_batch_pow(op.field, rf, op.k, op.d, op.log_blowup, op.log_final, op.nqueries, op.log_arity, 2 if op.grouped else 0,
+                                               op._coset(), L.p64(pts), pts.shape[0], L.p64(ys), _handle(transcript), *proof,
+                                               getattr(op, "grinding_bits", 0), getattr(op, "pow_nonce", 0), C.byref(ok)))
     return bool(ok.value)
 
 
