@@ -656,6 +656,62 @@ int zk_fri_ml_verify_batch_pow(int field, const uint8_t *roots_of_f, uint32_t k,
                                const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits,
                                uint64_t pow_nonce, int *ok);
 
+/* ---- Zerocheck of a product of committed tables (extension; csrc/zerocheck.cuh, csrc/zerocheck_host.h, csrc/zkmle_zerocheck.hip) --------------------
+ * The simplest non-linear statement over the commitment above: three commitments cmA, cmB, cmC (zk_fri_commit / zk_fri_commit_grouped; one
+ * field, d, log_blowup, coset and log_group) whose tables, read as evaluations over the cube {0,1}^d, satisfy  A[x] B[x] - C[x] = 0  for all x.
+ * The prover shows  sum_x eq(x, tau) (A[x] B[x] - C[x]) = 0  at a random tau by a sumcheck and opens the three tables at the point the
+ * sumcheck leaves, with ONE zk_fri_ml_open_batch_pow proof.  Transcript (t = NULL: a fresh Transcript::new()), plain appends in this order:
+ *   1. 8 bytes in one append: the ASCII tag "ZCML", then d as a big-endian u32; then the 32-byte roots of A, B, C, one append each;
+ *   2. tau_0 .. tau_{d-1} = d successive random_challenge_as_field_element();
+ *   3. (nothing is appended) E_0[x] = eq(x, tau) = prod_i (x_i ? tau_i : 1 - tau_i), variable 0 the most significant index bit, as everywhere;
+ *   4. for l = 0 .. d - 1, with X_{l+1} = zk_mle_fold(X_l, last, r_l) for X = A, B, C, E (a round binds the LAST variable, as zk_fri_ml_round):
+ *        g_l(X) = sum_x' E_l(x', X) (A_l(x', X) B_l(x', X) - C_l(x', X)),   Y_l(x', X) = Y_l[2x'] + X (Y_l[2x'+1] - Y_l[2x']),
+ *      a cubic, sent as g_l(0), g_l(1), g_l(2), g_l(3) (each the 32-byte canonical big-endian element); r_l = random_challenge_as_field_element();
+ *   5. (nothing is appended) the point z with z[d - 1 - l] = r_l: zk_mle_evaluate(X, z) is the one entry the d folds leave of X;
+ *   6. the whole protocol of zk_fri_ml_open_batch_pow on the transcript as step 4 left it: k = 3 (A, B, C in that order), npoints = 1, the point
+ *      z, and the caller's log_final, nqueries, log_arity and grinding_bits -- byte for byte what that function writes when handed this
+ *      transcript.  Its claims are yA, yB, yC.
+ * The prover does not check the relation: on a false statement it returns ZK_OK and a proof the verifier rejects.
+ * Verifier (HOST only: no table, no device; it holds the three roots).  It replays steps 1, 2 and 4 and checks  g_0(0) + g_0(1) = 0,
+ *   g_l(0) + g_l(1) = g_{l-1}(r_{l-1})  (the cubic through the four nodes), and  g_{d-1}(r_{d-1}) = eq(z, tau) (yA yB - yC);  then
+ *   zk_fri_ml_verify_batch_pow with ys = (yA, yB, yC).  *ok is the conjunction; anything unreduced gives *ok = 0.  Every status is decided
+ *   before the transcript is touched (zk_fri_ml_verify_batch_pow's, in its order); t ends in the prover's state whenever the status is ZK_OK.
+ * Prover.  E_0 by the eq-table builder (one or two launches); then one pass per round (zerocheck_mul_round_kernel) that folds the four tables of
+ *   the round before by its challenge -- A, B, C, E in turn, each stored before the next is loaded -- and accumulates g_l at the nodes 0, 1, 2
+ *   and infinity (the X^3 coefficient sum (E1 - E0)(A1 - A0)(B1 - B0), in which C has no share); the host forms
+ *   g_l(3) = 3 g_l(2) - 3 g_l(1) + g_l(0) + 6 g_l(inf).  Sixteen reads and eight writes of 32 bytes per lane where zk_sumcheck_gkr_rounds on
+ *   (E, A, B), (E, -C, 1) moves 36.  Round 0 reads the commitments' own coefficient tables, which are never written; E_0 and the two ping-pong
+ *   halves of the folded tables are one block of the caching pool (32 bytes x 4 n).  One host synchronisation per round.
+ * Not here: the eq factor taken out of the round (a degree-2 message), gates other than A B - C, several rounds per pass or a device-side
+ *   transcript, a sharded prover. */
+/* one round pass on its own (as zk_fri_ml_round).  r = NULL: round 0's form, nothing is folded or allocated, g4 = g(0), g(1), g(2), g(3) of
+ * (A, B, C, E), len >= 2.  r != NULL: outs[0 .. 3] = zk_mle_fold(X, last, r) for X = A, B, C, E (new tables, len / 2), g4 of the folded four;
+ * len >= 4.  ZK_E_ARG (NULL, mixed or unsupported field, too short, r not reduced), ZK_E_LEN_MISMATCH, ZK_E_NOT_POW2, then ZK_E_NO_DEVICE. */
+int zk_zerocheck_mul_round(const zk_table *A, const zk_table *B, const zk_table *C, const zk_table *E, const uint64_t *r, zk_table **outs, uint64_t *g4);
+/* host: nzc_round = 4 d elements of round polynomials, then the five counts of zk_fri_ml_sizes_batch(3, ..); any pointer may be NULL */
+int zk_zerocheck_sizes(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group, size_t *nzc_round,
+                       size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround);
+/* round_polys: 4 d elements; challenges: d elements (r_0 .. r_{d-1}; the point is their reverse); tau_out (d elements) is diagnostic and may be
+ * NULL; ys_out: 3 elements; from gamma_out on, the outputs of zk_fri_ml_open_batch_pow for k = 3 and one point, sized by zk_zerocheck_sizes.
+ * Statuses: ZK_E_ARG (NULL, commitments that differ in field, d, log_blowup, coset or log_group, and zk_fri_ml_open_batch_pow's own), all
+ * before ZK_E_NO_DEVICE and before the transcript moves. */
+int zk_zerocheck_mul_prove(const zk_fri_commitment *cmA, const zk_fri_commitment *cmB, const zk_fri_commitment *cmC, uint32_t log_final, uint32_t nqueries,
+                           uint32_t log_arity, uint32_t grinding_bits, zk_transcript *t, uint64_t *tau_out, uint64_t *round_polys, uint64_t *challenges,
+                           uint64_t *ys_out, uint64_t *gamma_out, uint64_t *open_round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *open_challenges,
+                           uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths, uint64_t *pow_nonce);
+/* HOST only.  roots_of_abc: the roots of A, B, C as the verifier holds them, 96 bytes; ys: yA, yB, yC. */
+int zk_zerocheck_mul_verify(int field, const uint8_t *roots_of_abc, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                            uint32_t log_group, const uint64_t *coset, zk_transcript *t, const uint64_t *round_polys, const uint64_t *ys,
+                            const uint64_t *open_round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
+                            const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok);
+/* the calling thread's last zk_zerocheck_mul_prove: HIP-event times of E_0's construction and of the d rounds (their passes, downloads and
+ * the host's transcript steps between them); ms_opening = zk_fri_ml_last_stats' ms_total of the opening; ms_total is the host clock over the call */
+typedef struct {
+    uint32_t rounds;
+    float ms_eq, ms_rounds, ms_opening, ms_total;
+} zk_zerocheck_stats;
+int zk_zerocheck_last_stats(zk_zerocheck_stats *out);
+
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */
 int zk_uni_lagrange_interpolate(int field, const uint64_t *xs, const uint64_t *ys, size_t n, uint64_t *out); /* :74 */

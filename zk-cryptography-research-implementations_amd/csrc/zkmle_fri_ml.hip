@@ -676,6 +676,22 @@ int open_points_check(const zk_fri_commitment *cm, const uint64_t *points, uint3
     return require_device();
 }
 
+// zk_fri_ml_open_batch_pow's statuses, every ZK_E_ARG and then the device check: the step's arguments, k, one field, size, blow-up, coset and
+// leaf grouping, the grouping's arity, and open_points_check on the first commitment
+int open_batch_check(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                     uint32_t log_arity, const uint64_t *ys_out, const OpenOut &o, uint32_t grinding_bits, const uint64_t *pow_nonce) {
+    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS || (grinding_bits && !pow_nonce)) return ZK_E_ARG;
+    if (!cms || k < 1 || k > ZK_FRI_ML_BATCH_MAX || !cms[0]) return ZK_E_ARG;
+    const zk_fri_commitment *c0 = cms[0];
+    for (uint32_t j = 1; j < k; j++) {                        // one field, size, blow-up, coset and leaf grouping
+        const zk_fri_commitment *cj = cms[j];
+        if (!cj || cj->field != c0->field || cj->d != c0->d || cj->b != c0->b || cj->log_group != c0->log_group || cj->has_coset != c0->has_coset) return ZK_E_ARG;
+        if (c0->has_coset && memcmp(cj->coset, c0->coset, sizeof c0->coset) != 0) return ZK_E_ARG;
+    }
+    if ((c0->log_group != 0 && c0->log_group != 2) || (c0->log_group == 2 && log_arity != 2)) return ZK_E_ARG;
+    return open_points_check(c0, points, npoints, log_final, nqueries, log_arity, c0->log_group, ys_out, o);
+}
+
 // the several-point verifiers' claim; ntables = 0: one table
 FriMlClaim claim_of(const uint64_t *points, uint32_t npoints, const uint64_t *ys, const uint64_t *round_polys, uint32_t log_arity, bool grouped,
                     uint32_t ntables) {
@@ -688,6 +704,13 @@ FriMlClaim claim_of(const uint64_t *points, uint32_t npoints, const uint64_t *ys
 }
 
 }  // namespace
+
+int zk::fri_ml_open_batch_check(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                                uint32_t log_arity, const uint64_t *ys_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *query_values,
+                                uint8_t *query_paths, uint32_t grinding_bits, const uint64_t *pow_nonce) {
+    return open_batch_check(cms, k, points, npoints, log_final, nqueries, log_arity, ys_out, OpenOut{round_polys, roots, final_table, nullptr, nullptr, query_values, query_paths},
+                            grinding_bits, pow_nonce);
+}
 
 extern "C" {
 
@@ -812,17 +835,9 @@ int zk_fri_ml_open_batch_pow(const zk_fri_commitment *const *cms, uint32_t k, co
                              uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots,
                              uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
                              uint32_t grinding_bits, uint64_t *pow_nonce) {
-    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS || (grinding_bits && !pow_nonce)) return ZK_E_ARG;
-    if (!cms || k < 1 || k > ZK_FRI_ML_BATCH_MAX || !cms[0]) return ZK_E_ARG;
-    const zk_fri_commitment *c0 = cms[0];
-    for (uint32_t j = 1; j < k; j++) {                        // one field, size, blow-up, coset and leaf grouping
-        const zk_fri_commitment *cj = cms[j];
-        if (!cj || cj->field != c0->field || cj->d != c0->d || cj->b != c0->b || cj->log_group != c0->log_group || cj->has_coset != c0->has_coset) return ZK_E_ARG;
-        if (c0->has_coset && memcmp(cj->coset, c0->coset, sizeof c0->coset) != 0) return ZK_E_ARG;
-    }
-    if ((c0->log_group != 0 && c0->log_group != 2) || (c0->log_group == 2 && log_arity != 2)) return ZK_E_ARG;
     const OpenOut o{round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
-    ZK_TRY(open_points_check(c0, points, npoints, log_final, nqueries, log_arity, c0->log_group, ys_out, o));
+    ZK_TRY(open_batch_check(cms, k, points, npoints, log_final, nqueries, log_arity, ys_out, o, grinding_bits, pow_nonce));
+    const zk_fri_commitment *c0 = cms[0];
     Transcript fresh;
     FRI_DISPATCH(c0->field, ManyTables<F> form(cms, k, points, npoints, ys_out, gamma_out, c0->d);
                  return open_with<F>(c0, form, log_final, nqueries, log_arity, c0->log_group == 2, t ? t->t : fresh, o, grinding_bits, pow_nonce));
