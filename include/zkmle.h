@@ -682,8 +682,8 @@ int zk_fri_ml_verify_batch_pow(int field, const uint8_t *roots_of_f, uint32_t k,
  *   g_l(3) = 3 g_l(2) - 3 g_l(1) + g_l(0) + 6 g_l(inf).  Sixteen reads and eight writes of 32 bytes per lane where zk_sumcheck_gkr_rounds on
  *   (E, A, B), (E, -C, 1) moves 36.  Round 0 reads the commitments' own coefficient tables, which are never written; E_0 and the two ping-pong
  *   halves of the folded tables are one block of the caching pool (32 bytes x 4 n).  One host synchronisation per round.
- * Not here: the eq factor taken out of the round (a degree-2 message), gates other than A B - C, several rounds per pass or a device-side
- *   transcript, a sharded prover. */
+ * Not here: the eq factor taken out of the round (a degree-2 message), several rounds per pass or a device-side transcript, a sharded prover.
+ *   Another gate: "Zerocheck of a Plonk gate over committed tables" below. */
 /* one round pass on its own (as zk_fri_ml_round).  r = NULL: round 0's form, nothing is folded or allocated, g4 = g(0), g(1), g(2), g(3) of
  * (A, B, C, E), len >= 2.  r != NULL: outs[0 .. 3] = zk_mle_fold(X, last, r) for X = A, B, C, E (new tables, len / 2), g4 of the folded four;
  * len >= 4.  ZK_E_ARG (NULL, mixed or unsupported field, too short, r not reduced), ZK_E_LEN_MISMATCH, ZK_E_NOT_POW2, then ZK_E_NO_DEVICE. */
@@ -704,13 +704,61 @@ int zk_zerocheck_mul_verify(int field, const uint8_t *roots_of_abc, uint32_t d, 
                             uint32_t log_group, const uint64_t *coset, zk_transcript *t, const uint64_t *round_polys, const uint64_t *ys,
                             const uint64_t *open_round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
                             const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok);
-/* the calling thread's last zk_zerocheck_mul_prove: HIP-event times of E_0's construction and of the d rounds (their passes, downloads and
+/* the calling thread's last zk_zerocheck_mul_prove or zk_zerocheck_gate_prove: HIP-event times of E_0's construction and of the d rounds (their passes, downloads and
  * the host's transcript steps between them); ms_opening = zk_fri_ml_last_stats' ms_total of the opening; ms_total is the host clock over the call */
 typedef struct {
     uint32_t rounds;
     float ms_eq, ms_rounds, ms_opening, ms_total;
 } zk_zerocheck_stats;
 int zk_zerocheck_last_stats(zk_zerocheck_stats *out);
+
+/* ---- Zerocheck of a Plonk gate over committed tables (extension; csrc/zerocheck.cuh, csrc/zerocheck_host.h, csrc/zkmle_zerocheck.hip) ----------------
+ * The product's zerocheck with selectors: EIGHT commitments of one shape (one field, d, log_blowup, coset and log_group), in this order
+ * everywhere: the wires A, B, C and the selectors qM, qL, qR, qO, qC.  Their tables, read as evaluations over the cube {0,1}^d, satisfy
+ *     qM[x] A[x] B[x] + qL[x] A[x] + qR[x] B[x] + qO[x] C[x] + qC[x] = 0     for all x,
+ * the vanilla Plonk gate: additions, multiplications, constants and public-constant rows in one relation.  Wiring (copy constraints) is not
+ * part of it.  Transcript (t = NULL: a fresh Transcript::new()), plain appends in this order:
+ *   1. 8 bytes in one append: the ASCII tag "ZCPG", then d as a big-endian u32; then the eight 32-byte roots in the order above, one append each;
+ *   2. tau_0 .. tau_{d-1} = d successive random_challenge_as_field_element();  E_0[x] = eq(x, tau), variable 0 the most significant index bit;
+ *   3. for l = 0 .. d - 1, with X_{l+1} = zk_mle_fold(X_l, last, r_l) for the nine tables X (a round binds the LAST variable) and
+ *      Y_l(x', X) = Y_l[2x'] + X (Y_l[2x'+1] - Y_l[2x']):
+ *        g_l(X) = sum_x' E_l (qM_l A_l B_l + qL_l A_l + qR_l B_l + qO_l C_l + qC_l)   at (x', X),
+ *      a quartic, sent as g_l(0), g_l(1), g_l(2), g_l(3), g_l(4) (each the 32-byte canonical big-endian element); then
+ *      r_l = random_challenge_as_field_element();
+ *   4. (nothing is appended) the point z with z[d - 1 - l] = r_l;
+ *   5. the whole protocol of zk_fri_ml_open_batch_pow on the transcript as step 3 left it: k = 8 in the order above, npoints = 1, the point z,
+ *      and the caller's log_final, nqueries, log_arity and grinding_bits.  Its claims are y_A, y_B, y_C, y_qM, y_qL, y_qR, y_qO, y_qC.
+ * The prover does not check the relation: on a false statement it returns ZK_OK and a proof the verifier rejects.
+ * Verifier (HOST only: no table, no device; it holds the eight roots, 256 bytes).  It replays steps 1 to 3 and checks  g_0(0) + g_0(1) = 0,
+ *   g_l(0) + g_l(1) = g_{l-1}(r_{l-1})  (the quartic through the five nodes), and
+ *   g_{d-1}(r_{d-1}) = eq(z, tau) (y_qM y_A y_B + y_qL y_A + y_qR y_B + y_qO y_C + y_qC);  then zk_fri_ml_verify_batch_pow on the eight claims.
+ *   *ok is the conjunction; anything unreduced gives *ok = 0.  Every status is decided before the transcript is touched
+ *   (zk_fri_ml_verify_batch_pow's, in its order); t ends in the prover's state whenever the status is ZK_OK.
+ * Prover.  As the product's: E_0, then one pass per round (zerocheck_gate_round_kernel) that folds the nine tables of the round before by its
+ *   challenge and accumulates g_l at the nodes 0, 1, 2, 3 and infinity (the X^4 coefficient sum (E1 - E0)(qM1 - qM0)(A1 - A0)(B1 - B0): only
+ *   qM A B has a share in it); the host forms g_l(4) = 4 g_l(3) - 6 g_l(2) + 4 g_l(1) - g_l(0) + 24 g_l(inf).  36 reads and 18 writes of 32 bytes
+ *   and 41 products per lane.  Round 0 reads the commitments' own coefficient tables, which are never written; E_0 and the two ping-pong halves
+ *   of the folded nine are one block of the caching pool (32 bytes x 7.75 n).  One host synchronisation per round.
+ * Not here: copy constraints or any permutation or lookup argument, public inputs, custom or higher-degree gates, node 1 dropped from the pass
+ *   by the known claimed sum, the eq factor taken out of the round, several rounds per pass, a sharded prover. */
+/* one round pass on its own.  tables: A, B, C, qM, qL, qR, qO, qC, E.  r = NULL: round 0's form, nothing is folded or allocated,
+ * g5 = g(0) .. g(4) of the nine, len >= 2.  r != NULL: outs[0 .. 8] = zk_mle_fold(X, last, r) of each (new tables, len / 2), g5 of the folded
+ * nine; len >= 4.  Statuses and their order as zk_zerocheck_mul_round. */
+int zk_zerocheck_gate_round(const zk_table *const tables[9], const uint64_t *r, zk_table **outs, uint64_t *g5);
+/* host: nzc_round = 5 d elements of round polynomials, then the five counts of zk_fri_ml_sizes_batch(8, ..); any pointer may be NULL */
+int zk_zerocheck_gate_sizes(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group, size_t *nzc_round,
+                            size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround);
+/* As zk_zerocheck_mul_prove with cms[0 .. 7] = A, B, C, qM, qL, qR, qO, qC: round_polys 5 d elements, ys_out 8 elements, the opening's outputs
+ * for k = 8 and one point, sized by zk_zerocheck_gate_sizes.  The same statuses, all before ZK_E_NO_DEVICE and before the transcript moves. */
+int zk_zerocheck_gate_prove(const zk_fri_commitment *const cms[8], uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t grinding_bits, zk_transcript *t,
+                            uint64_t *tau_out, uint64_t *round_polys, uint64_t *challenges, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *open_round_polys,
+                            uint8_t *roots, uint64_t *final_table, uint64_t *open_challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
+                            uint64_t *pow_nonce);
+/* HOST only.  roots_of_eight: the eight roots as the verifier holds them, 256 bytes; ys: the eight claims. */
+int zk_zerocheck_gate_verify(int field, const uint8_t *roots_of_eight, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                             uint32_t log_group, const uint64_t *coset, zk_transcript *t, const uint64_t *round_polys, const uint64_t *ys,
+                             const uint64_t *open_round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
+                             const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok);
 
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */

@@ -174,6 +174,12 @@ def lib():
         "zk_zerocheck_mul_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + [u64p, vp, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
                                                                        C.POINTER(C.c_int)],
         "zk_zerocheck_last_stats": [vp],
+        # zerocheck of a Plonk gate over committed tables
+        "zk_zerocheck_gate_round": [C.POINTER(vp), u64p, C.POINTER(vp), u64p],
+        "zk_zerocheck_gate_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 6,
+        "zk_zerocheck_gate_prove": [C.POINTER(vp)] + [C.c_uint32] * 4 + [vp, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
+        "zk_zerocheck_gate_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + [u64p, vp, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
+                                                                       C.POINTER(C.c_int)],
         "zk_sumcheck_basic_prove_succinct": [vp, C.c_uint32, C.c_uint32, vp, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_sumcheck_basic_verify_succinct": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, vp, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u8p,
                                                                                  C.POINTER(C.c_int)],

@@ -1,21 +1,19 @@
-// zerocheck_host.h -- the host side of the zerocheck of a product (include/zkmle.h "Zerocheck of a product of committed tables") that prover
-// and verifier share: the statement's absorption, the round message from the pass's sums, and the verifier's replay of the sumcheck.  It
-// touches no device; tools/zerocheck_selftest.hip runs it under a sanitizer.  Library-internal; included by .hip files only.
+// zerocheck_host.h -- the host side of the zerochecks over FRI commitments (include/zkmle.h "Zerocheck of a product of committed tables" and
+// "Zerocheck of a Plonk gate over committed tables") that prover and verifier share: the statement's absorption, the round message from the
+// pass's sums, and the verifier's replay of the sumcheck.  The two protocols differ in a statement (ZerocheckMul, ZerocheckGate): the tag, the
+// number of commitments K, the number of nodes a round message is sent at, how the message comes from the pass's sums, and the relation the
+// last check evaluates on the K claims.  It touches no device; tools/zerocheck_selftest.hip runs it under a sanitizer.  Library-internal;
+// included by .hip files only.
 #pragma once
+#include <string.h>
+
+#include <vector>
+
 #include "host_util.h"
 #include "transcript.h"
 
 namespace zk {
 namespace host {
-
-// steps 1 and 2: "ZCML", d, the roots of A, B, C; then tau_0 .. tau_{d-1} (tau: d elements, u64 limbs)
-template <class F> void zerocheck_statement(Transcript &tr, const uint8_t *roots96, uint32_t d, uint64_t *tau) {
-    uint8_t tag[8] = {'Z', 'C', 'M', 'L'};
-    put_be32(tag + 4, d);
-    tr.append(tag, sizeof tag);
-    for (int j = 0; j < 3; j++) tr.append(roots96 + 32 * j, 32);
-    for (uint32_t i = 0; i < d; i++) store_host<F>(tau + (size_t)i * (F::N / 2), tr.random_challenge_as_field_element<F>());
-}
 
 // g(0), g(1), g(2), g(3) from the pass's sums at the nodes 0, 1, 2 and infinity: g(3) = 3 g(2) - 3 g(1) + g(0) + 6 s_inf
 template <class F> void zerocheck_g4(const Fe<F> S[4], Fe<F> g[4]) {
@@ -26,28 +24,73 @@ template <class F> void zerocheck_g4(const Fe<F> S[4], Fe<F> g[4]) {
     g[3] = fe_add<F>(fe_add<F>(fe_dbl<F>(t), t), S[0]);
 }
 
-// the cubic through (0, g[0]) .. (3, g[3]) at r
-template <class F> Fe<F> zerocheck_cubic_at(const Fe<F> g[4], const Fe<F> &r) {
-    const Fe<F> one = fe_one<F>(), r1 = fe_sub<F>(r, one), r2 = fe_sub<F>(r1, one), r3 = fe_sub<F>(r2, one);
-    const Fe<F> inv2 = fe_inv<F>(fe_from_u64<F>(2)), inv6 = fe_inv<F>(fe_from_u64<F>(6));
-    const Fe<F> l0 = fe_mul<F>(fe_mul<F>(r1, fe_mul<F>(r2, r3)), inv6), l1 = fe_mul<F>(fe_mul<F>(r, fe_mul<F>(r2, r3)), inv2);
-    const Fe<F> l2 = fe_mul<F>(fe_mul<F>(r, fe_mul<F>(r1, r3)), inv2), l3 = fe_mul<F>(fe_mul<F>(r, fe_mul<F>(r1, r2)), inv6);
-    return fe_add<F>(fe_sub<F>(fe_mul<F>(g[1], l1), fe_mul<F>(g[0], l0)), fe_sub<F>(fe_mul<F>(g[3], l3), fe_mul<F>(g[2], l2)));
+// g(0) .. g(4) from the pass's sums at the nodes 0, 1, 2, 3 and infinity: g(4) = 4 g(3) - 6 g(2) + 4 g(1) - g(0) + 24 s_inf
+template <class F> void zerocheck_g5(const Fe<F> S[5], Fe<F> g[5]) {
+    for (int k = 0; k < 4; k++) g[k] = S[k];
+    const Fe<F> a = fe_add<F>(S[3], S[1]), s4 = fe_dbl<F>(fe_dbl<F>(S[4]));                     // g(3) + g(1); 4 s_inf
+    const Fe<F> s12 = fe_add<F>(fe_dbl<F>(s4), s4), g2x3 = fe_add<F>(fe_dbl<F>(S[2]), S[2]);
+    const Fe<F> t = fe_sub<F>(fe_add<F>(fe_dbl<F>(a), s12), g2x3);                              // 2 (g(3) + g(1)) - 3 g(2) + 12 s_inf
+    g[4] = fe_sub<F>(fe_dbl<F>(t), S[0]);
 }
 
-// The verifier's steps 1, 2 and 4 on `tr` and its three checks: g_0(0) + g_0(1) = 0, g_l(0) + g_l(1) = g_{l-1}(r_{l-1}), and
-// g_{d-1}(r_{d-1}) = eq(z, tau) (yA yB - yC).  round_polys: 4 d elements, ys: 3.  z (d elements) receives the point, z[d - 1 - l] = r_l;
-// *good = every check held and every element read is reduced.  The transcript advances the same way whatever *good is.
-template <class F> void zerocheck_replay(Transcript &tr, const uint8_t *roots96, uint32_t d, const uint64_t *round_polys, const uint64_t *ys, uint64_t *z, bool *good) {
+// the polynomial of degree NODES - 1 through (0, g[0]) .. (NODES - 1, g[NODES - 1]) at r, by Lagrange's formula
+template <class F, int NODES> Fe<F> zerocheck_interpolate_at(const Fe<F> *g, const Fe<F> &r) {
+    Fe<F> node[NODES], out = fe_zero<F>();
+    for (int j = 0; j < NODES; j++) node[j] = fe_from_u64<F>((uint64_t)j);
+    for (int i = 0; i < NODES; i++) {
+        Fe<F> num = g[i], den = fe_one<F>();
+        for (int j = 0; j < NODES; j++) {
+            if (j == i) continue;
+            num = fe_mul<F>(num, fe_sub<F>(r, node[j]));
+            den = fe_mul<F>(den, fe_sub<F>(node[i], node[j]));
+        }
+        out = fe_add<F>(out, fe_mul<F>(num, fe_inv<F>(den)));
+    }
+    return out;
+}
+
+// A o B = C over (A, B, C): a cubic at the nodes 0 .. 3
+struct ZerocheckMul {
+    static constexpr int K = 3, NODES = 4;
+    static constexpr const char *tag = "ZCML";
+    template <class F> static void message(const Fe<F> *S, Fe<F> *g) { zerocheck_g4<F>(S, g); }
+    template <class F> static Fe<F> relation(const Fe<F> *y) { return fe_sub<F>(fe_mul<F>(y[0], y[1]), y[2]); }
+};
+
+// qM A B + qL A + qR B + qO C + qC = 0 over (A, B, C, qM, qL, qR, qO, qC): a quartic at the nodes 0 .. 4
+struct ZerocheckGate {
+    static constexpr int K = 8, NODES = 5;
+    static constexpr const char *tag = "ZCPG";
+    template <class F> static void message(const Fe<F> *S, Fe<F> *g) { zerocheck_g5<F>(S, g); }
+    template <class F> static Fe<F> relation(const Fe<F> *y) {
+        const Fe<F> ab = fe_add<F>(fe_mul<F>(fe_add<F>(fe_mul<F>(y[3], y[1]), y[4]), y[0]), fe_mul<F>(y[5], y[1]));   // (qM B + qL) A + qR B
+        return fe_add<F>(fe_add<F>(ab, fe_mul<F>(y[6], y[2])), y[7]);
+    }
+};
+
+// steps 1 and 2: the tag, d, the K roots; then tau_0 .. tau_{d-1} (tau: d elements, u64 limbs)
+template <class F, class St> void zerocheck_statement(Transcript &tr, const uint8_t *roots, uint32_t d, uint64_t *tau) {
+    uint8_t tag[8];
+    memcpy(tag, St::tag, 4);
+    put_be32(tag + 4, d);
+    tr.append(tag, sizeof tag);
+    for (int j = 0; j < St::K; j++) tr.append(roots + 32 * j, 32);
+    for (uint32_t i = 0; i < d; i++) store_host<F>(tau + (size_t)i * (F::N / 2), tr.random_challenge_as_field_element<F>());
+}
+
+// The verifier's replay of the statement and the rounds on `tr` and its three checks: g_0(0) + g_0(1) = 0, g_l(0) + g_l(1) = g_{l-1}(r_{l-1}),
+// and g_{d-1}(r_{d-1}) = eq(z, tau) relation(ys).  round_polys: NODES d elements, ys: K.  z (d elements) receives the point,
+// z[d - 1 - l] = r_l; *good = every check held and every element read is reduced.  The transcript advances the same way whatever *good is.
+template <class F, class St> void zerocheck_replay(Transcript &tr, const uint8_t *roots, uint32_t d, const uint64_t *round_polys, const uint64_t *ys, uint64_t *z, bool *good) {
     constexpr int W = F::N / 2;
     std::vector<uint64_t> tau((size_t)d * W);
-    zerocheck_statement<F>(tr, roots96, d, tau.data());
+    zerocheck_statement<F, St>(tr, roots, d, tau.data());
     bool ok = true;
     Fe<F> cur = fe_zero<F>();
     for (uint32_t l = 0; l < d; l++) {
-        Fe<F> g[4];
-        for (int k = 0; k < 4; k++) {
-            const uint64_t *src = round_polys + ((size_t)l * 4 + k) * W;
+        Fe<F> g[St::NODES];
+        for (int k = 0; k < St::NODES; k++) {
+            const uint64_t *src = round_polys + ((size_t)l * St::NODES + k) * W;
             ok = ok && is_reduced<F>(src);
             g[k] = load_host<F>(src);
             tr.append_be<F>(g[k]);
@@ -55,7 +98,7 @@ template <class F> void zerocheck_replay(Transcript &tr, const uint8_t *roots96,
         ok = ok && fe_eq<F>(fe_add<F>(g[0], g[1]), cur);
         const Fe<F> r = tr.random_challenge_as_field_element<F>();
         store_host<F>(z + (size_t)(d - 1 - l) * W, r);
-        cur = zerocheck_cubic_at<F>(g, r);
+        cur = zerocheck_interpolate_at<F, St::NODES>(g, r);
     }
     const Fe<F> one = fe_one<F>();
     Fe<F> eq = one;
@@ -63,9 +106,12 @@ template <class F> void zerocheck_replay(Transcript &tr, const uint8_t *roots96,
         const Fe<F> a = load_host<F>(z + (size_t)i * W), b = load_host<F>(tau.data() + (size_t)i * W);
         eq = fe_mul<F>(eq, fe_add<F>(fe_mul<F>(a, b), fe_mul<F>(fe_sub<F>(one, a), fe_sub<F>(one, b))));
     }
-    for (int j = 0; j < 3; j++) ok = ok && is_reduced<F>(ys + (size_t)j * W);
-    const Fe<F> gate = fe_sub<F>(fe_mul<F>(load_host<F>(ys), load_host<F>(ys + W)), load_host<F>(ys + 2 * W));
-    *good = ok && fe_eq<F>(cur, fe_mul<F>(eq, gate));
+    Fe<F> y[St::K];
+    for (int j = 0; j < St::K; j++) {
+        ok = ok && is_reduced<F>(ys + (size_t)j * W);
+        y[j] = load_host<F>(ys + (size_t)j * W);
+    }
+    *good = ok && fe_eq<F>(cur, fe_mul<F>(eq, St::template relation<F>(y)));
 }
 
 }  // namespace host
