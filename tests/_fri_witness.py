@@ -29,8 +29,9 @@ def stored(field, value):
     return value * R % NM.MODULUS[field]
 
 
-def load(field):
-    """-> (gamma, s, [t, ...]) of one field, stored-form integers"""
-    with open(os.path.join(ROOT, "tests", "golden", "fri_fold_witnesses.json")) as f:
+def load(field, name="fri_fold_witnesses.json"):
+    """-> (gamma, s, [t, ...]) of one field, stored-form integers.  name = "gkr_ufold_witnesses.json": the operands (r, a, [b, ...]) of
+    ufold, the fold of the GKR round kernels (same tool, ufold mode)"""
+    with open(os.path.join(ROOT, "tests", "golden", name)) as f:
         d = json.load(f)["fields"][str(field)]
     return limbs_to_int(d["gamma"]), limbs_to_int(d["s"]), [limbs_to_int(w["t"]) for w in d["witnesses"]]

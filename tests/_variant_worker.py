@@ -36,6 +36,42 @@ def main():
             checked += 1
             if not ok:
                 bad.append(["basic", field, logn])
+    # the same prover on tables at and just below p: 2^16 and 2^19 on BLS12-381 Fr.  By rounds_per_pass (csrc/round_schedule.h) 2^16 is
+    # one pass of 5 variables (foldk_split_kernel<5>) and 2^19 two passes of 4 (foldk_seg_sums_kernel<4>, foldk_split_kernel<4>) or, with
+    # ZK_BASIC_ROUNDS_PER_PASS=8, one of 8 (foldk_split_kernel<8>, 32 terms per lane).  All of these sum at most 32 terms per reduction: the
+    # cases pin the provers on such tables under every switch; the forms that sum more are run by tests/test_gpu_foldk_edges.py.
+    pm1 = O.int_to_limbs(O.modulus(0) - 1, 4)
+
+    def near_p(rand):
+        """(p - 1) - (rand mod 2^200), limb by limb with borrow: stored integers in [p - 2^200, p)"""
+        x = rand.copy()
+        x[:, 3] &= np.uint64(0xFF)
+        out = np.zeros_like(x)
+        borrow = np.zeros(x.shape[0], bool)
+        for k in range(4):
+            out[:, k] = pm1[k] - x[:, k] - borrow.astype(np.uint64)
+            borrow = (x[:, k] > pm1[k]) | ((x[:, k] == pm1[k]) & borrow)
+        assert not borrow.any()
+        return out
+    for logn in (16, 19):
+        n = 1 << logn
+        rand = rand_table(0, n, 4700 + logn)
+        near = near_p(rand)
+        const_high = np.tile(near_p(np.array([[0xC0FFEE, 0, 0, 0x80]], np.uint64)), (n, 1))
+        mix = near.copy()
+        sel = rand_table(0, n, 4800 + logn)[:, 0] % np.uint64(3)
+        mix[sel == 0] = 0
+        mix[sel == 1] = pm1
+        for kind, table in (("all_pm1", np.tile(pm1, (n, 1))), ("const_high", const_high), ("mix", mix), ("near", near)):
+            table = np.ascontiguousarray(table)
+            prover = zk.Prover.init(0, table)
+            proof = prover.prove()
+            cs, rp, ch = O.sumcheck_basic_prove(0, table)
+            ok = (np.array_equal(proof.initial_claimed_sum, cs) and np.array_equal(proof.round_univariate_polynomials.reshape(rp.shape), rp)
+                  and np.array_equal(prover.challenges.reshape(ch.shape), ch) and zk.Verifier.init().verify(proof) is True)
+            checked += 1
+            if not ok:
+                bad.append(["basic_near_p", kind, logn])
     # the same prover through the sharded entry point on a one-rank communicator (zk_rounds_* handle)
     S = zk.sharded
     comm = S.Comm()

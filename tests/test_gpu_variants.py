@@ -1,5 +1,6 @@
 """The environment switches that select another code path for the same result -- the transcript step on the device
-(ZK_HOST_TRANSCRIPT=0), the rounds-per-pass cap of the basic sumcheck (ZK_BASIC_ROUNDS_PER_PASS, csrc/basic_multi.cuh) and the sparse GKR
+(ZK_HOST_TRANSCRIPT=0), the rounds-per-pass cap of the basic sumcheck (ZK_BASIC_ROUNDS_PER_PASS, csrc/basic_multi.cuh), its folds with one
+lane per output where two are the default (ZK_FOLD_SPLIT2=0, csrc/fold_multi.h) and the sparse GKR
 prover's gate weights from a table instead of the eq half tables (ZK_GKR_WEIGHT_TABLE=1, csrc/zkmle_gkr_sparse.hip), one or two GKR rounds per
 launch / exchange (ZK_GRID_TWO_ROUNDS, ZK_GRID_TWO_BITS, ZK_TAIL_TWO_ROUNDS: r4), the dense API on its dense tables (ZK_GKR_DENSE_TABLES=1) -- are read
 once per process (the last one per call): each variant runs tests/_variant_worker.py in a child process and must reproduce the oracle's proofs."""
@@ -19,10 +20,10 @@ DIGESTS = {}
 
 @pytest.mark.parametrize("env", [{}, {"ZK_HOST_TRANSCRIPT": "0"}, {"ZK_BASIC_ROUNDS_PER_PASS": "1"}, {"ZK_BASIC_ROUNDS_PER_PASS": "2"},
                                  {"ZK_BASIC_ROUNDS_PER_PASS": "3"}, {"ZK_BASIC_ROUNDS_PER_PASS": "4"}, {"ZK_BASIC_ROUNDS_PER_PASS": "6"},
-                                 {"ZK_BASIC_ROUNDS_PER_PASS": "8"}, {"ZK_GKR_WEIGHT_TABLE": "1"},
+                                 {"ZK_BASIC_ROUNDS_PER_PASS": "8"}, {"ZK_FOLD_SPLIT2": "0"}, {"ZK_GKR_WEIGHT_TABLE": "1"},
                                  {"ZK_GRID_TWO_ROUNDS": "0"}, {"ZK_TAIL_TWO_ROUNDS": "0"}, {"ZK_GRID_TWO_ROUNDS": "0", "ZK_TAIL_TWO_ROUNDS": "0"},
                                  {"ZK_GRID_TWO_BITS": "13"}, {"ZK_TAIL_TWO_ROUNDS": "16"}, {"ZK_GKR_DENSE_TABLES": "1"}],
-                         ids=["default", "device_step", "k1", "k2", "k3", "k4", "k6", "k8", "weight_table",
+                         ids=["default", "device_step", "k1", "k2", "k3", "k4", "k6", "k8", "no_split2", "weight_table",
                               "grid_single_rounds", "tail_single_rounds", "single_rounds", "grid_two_from_2p13", "tail_two_upto_16_pairs", "dense_tables"])
 def test_variant_reproduces_oracle_proofs(env):
     e = dict(os.environ)
@@ -31,7 +32,7 @@ def test_variant_reproduces_oracle_proofs(env):
                        cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    assert out["checked"] >= 20
+    assert out["checked"] >= 28
     assert out["mismatches"] == [], out
     # the sparse GKR proof of a 2^15-wide circuit: the same bytes whichever way the gate weights and the transcript step are computed
     DIGESTS[tuple(sorted(env.items()))] = out["sparse_gkr_digest"]

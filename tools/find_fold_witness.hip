@@ -4,7 +4,11 @@
 // (tests/test_fri_arith_cpu.py on the host, tests/test_gpu_fri_edges.py through fri_fold_kernel).  Not run by the suite.
 //
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 -pthread tools/find_fold_witness.hip -o find_fold_witness
-//   find_fold_witness <field: 0 = BLS12-381 Fr, 3 = BN254 Fr> <seed> [want = 3] [max_rounds = 40] [threads = 16]
+//   find_fold_witness <field: 0 = BLS12-381 Fr, 3 = BN254 Fr> <seed> [want = 3] [max_rounds = 40] [threads = 16] [mode = muladd | ufold]
+//
+// mode ufold: the same search for the fold of the GKR round kernels (csrc/sumcheck_kernels.cuh: ufold of csrc/ufield.cuh, a + r (b - a)
+// with the challenge r in gamma's place, a = s = p - 1 as stored limbs, b = t), whose result feeds fe_from_u_below_2p and, un-reduced, the
+// lazy products of the next round's evaluations; tests/golden/gkr_ufold_witnesses.json holds what it found (tests/test_gpu_gkr_round_edges.py).
 //
 // One gamma per run (stored form, drawn from the seed), s = p - 1 as stored limbs, t canonical and uniform: trial i draws t from
 // SplitMix64 words of (seed, i), so a hit is reproducible from (field, seed, i) alone.  A round is 2^28 trials whatever the thread count;
@@ -55,7 +59,7 @@ template <class F> void print_fe(const char *name, const Fe<F> &x) {
     printf("\n");
 }
 
-template <class F> int search(const char *name, uint64_t seed, size_t want, uint64_t max_rounds, unsigned threads) {
+template <class F, bool UFOLD> int search(const char *name, uint64_t seed, size_t want, uint64_t max_rounds, unsigned threads) {
     Fe<F> gamma;
     for (uint64_t i = 0;; i++) {
         gamma = draw<F>(splitmix64(seed ^ 0x67616d6d61ull), i);
@@ -82,7 +86,8 @@ template <class F> int search(const char *name, uint64_t seed, size_t want, uint
                 for (uint64_t i = first; i < first + kChunk; i++) {
                     const Fe<F> t = draw<F>(tseed, i);
                     if (!below_p<F>(t)) continue;
-                    if (at_least_2p<F>(uni_muladd<F>(um, su, u_from_limbs32<F>(t)))) {
+                    const Ufe<F> tu = u_from_limbs32<F>(t);
+                    if (at_least_2p<F>(UFOLD ? ufold<F>(um, su, tu) : uni_muladd<F>(um, su, tu))) {
                         std::lock_guard<std::mutex> g(mu);
                         hits.push_back(i);
                     }
@@ -96,8 +101,8 @@ template <class F> int search(const char *name, uint64_t seed, size_t want, uint
         fprintf(stderr, "%s: round %llu, %zu hits\n", name, (unsigned long long)rounds, hits.size());
     }
     std::sort(hits.begin(), hits.end());
-    printf("field %d %s seed %llu trials %llu hits %zu\n", F::ID, name, (unsigned long long)seed, (unsigned long long)(rounds * kChunksPerRound * kChunk),
-           hits.size());
+    printf("field %d %s mode %s seed %llu trials %llu hits %zu\n", F::ID, name, UFOLD ? "ufold" : "muladd", (unsigned long long)seed,
+           (unsigned long long)(rounds * kChunksPerRound * kChunk), hits.size());
     print_fe<F>("gamma", gamma);
     print_fe<F>("s", s);
     for (uint64_t i : hits) {
@@ -109,7 +114,7 @@ template <class F> int search(const char *name, uint64_t seed, size_t want, uint
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <field: 0 | 3> <seed> [want] [max_rounds] [threads]\n", argv[0]);
+        fprintf(stderr, "usage: %s <field: 0 | 3> <seed> [want] [max_rounds] [threads] [muladd | ufold]\n", argv[0]);
         return 2;
     }
     const int field = atoi(argv[1]);
@@ -117,8 +122,9 @@ int main(int argc, char **argv) {
     const size_t want = argc > 3 ? strtoull(argv[3], nullptr, 0) : 3;
     const uint64_t max_rounds = argc > 4 ? strtoull(argv[4], nullptr, 0) : 40;
     const unsigned threads = argc > 5 ? (unsigned)atoi(argv[5]) : 16;
-    if (field == 0) return search<Fr381>("Fr381", seed, want, max_rounds, threads);
-    if (field == 3) return search<Bn254Fr>("Bn254Fr", seed, want, max_rounds, threads);
+    const bool uf = argc > 6 && argv[6][0] == 'u';
+    if (field == 0) return uf ? search<Fr381, true>("Fr381", seed, want, max_rounds, threads) : search<Fr381, false>("Fr381", seed, want, max_rounds, threads);
+    if (field == 3) return uf ? search<Bn254Fr, true>("Bn254Fr", seed, want, max_rounds, threads) : search<Bn254Fr, false>("Bn254Fr", seed, want, max_rounds, threads);
     fprintf(stderr, "field must be 0 (BLS12-381 Fr) or 3 (BN254 Fr)\n");
     return 2;
 }

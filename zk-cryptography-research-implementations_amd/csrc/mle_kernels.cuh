@@ -322,7 +322,7 @@ template <class F> __device__ __forceinline__ void raw_normalize(RawAcc<F> &acc)
         acc.c[j] &= UMASK;
     }
 }
-// acc / 2^(29 L) mod p for normalized columns: below acc / 2^(29 L) + p
+// acc / 2^(29 L) mod p for normalized columns: below acc / 2^(29 L) + p -- NOT below 2 p unless acc < p 2^(29 L) (kRawTermsMax below)
 template <class F> __device__ __forceinline__ Ufe<F> raw_mont_reduce(RawAcc<F> &acc) {
     constexpr int L = UParams<F>::L;
 #pragma unroll
@@ -343,6 +343,30 @@ template <class F> __device__ __forceinline__ Ufe<F> raw_mont_reduce(RawAcc<F> &
     return r;
 }
 constexpr int kRawCarryEvery = 4;       // products between two normalizations: 4 L 2^58 + 2^30 < 2^64 for L <= 14
+// THE BOUND of one reduction.  u_reduce_once finishes values below 2 p only, and raw_mont_reduce leaves acc / 2^(29 L) + (< p), so one
+// raw_mont_reduce + u_reduce_once needs acc < p 2^(29 L).  T products of canonical operands (entries AND weights below p; the weights
+// are residues, their integer sum can be anything up to T p) are below T p^2: in range for every input iff T p < 2^(29 L), that is
+// T <= kRawTermsMax = floor(2^(29 L) / p).  A form with more terms reduces every raw_chunk() of them and adds the reduced parts in
+// the field (exact), so no challenge tuple and no table leaves a stored element at or above p.
+template <class F> constexpr int kRawTermsMax = 0;
+template <> inline constexpr int kRawTermsMax<Fr381> = 70;
+template <> inline constexpr int kRawTermsMax<Fq381> = 41291124;
+template <> inline constexpr int kRawTermsMax<Bn254Fq> = 169;
+template <> inline constexpr int kRawTermsMax<Bn254Fr> = 169;
+template <class F> constexpr bool raw_terms_fit(uint64_t t) {            // t p < 2^(29 L)
+    uint64_t c = 0;
+    for (int i = 0; i < UParams<F>::L; i++) c = (c + t * UParams<F>::p(i)) >> UB;
+    return c == 0;
+}
+template <class F> constexpr bool raw_terms_max_is_exact() { return raw_terms_fit<F>(kRawTermsMax<F>) && !raw_terms_fit<F>((uint64_t)kRawTermsMax<F> + 1); }
+static_assert(raw_terms_max_is_exact<Fr381>() && raw_terms_max_is_exact<Fq381>() && raw_terms_max_is_exact<Bn254Fq>() && raw_terms_max_is_exact<Bn254Fr>(),
+              "kRawTermsMax = floor(2^(29 L) / p)");
+// terms per reduction of a lane that sums `terms` (a power of two) inputs: the largest power of two within the bound
+template <class F> constexpr int raw_chunk(int terms) {
+    int c = terms;
+    while (c > kRawTermsMax<F>) c /= 2;
+    return c;
+}
 
 // FIN: the pass's last workgroup runs the exchange on the partials (`fin`; translation units that include basic_multi.cuh only)
 template <class F, int K, bool FIN = false> __global__ void __launch_bounds__(kBlock) foldk_seg_sums_kernel(FoldKArgs a, MultiFin fin) {
@@ -373,6 +397,9 @@ template <class F, int K, bool FIN = false> __global__ void __launch_bounds__(kB
             sw[threadIdx.x] = u_reduce_once<F>(u_from_std<F>(w));
         }
         __syncthreads();
+        // one reduction per kChunk terms: the whole sum wherever the bound allows (K <= 6 everywhere, K = 7 on the BN254 fields)
+        constexpr int kChunk = raw_chunk<F>(1 << K);
+        static_assert(kChunk <= kRawTermsMax<F> && kChunk % kRawCarryEvery == 0 && (1 << K) % kChunk == 0, "terms of one reduction");
         for (size_t t = (size_t)bq * blockDim.x + threadIdx.x; t < seglen; t += stride) {
             const size_t j = base + t;
             RawAcc<F> ra;
@@ -381,7 +408,7 @@ template <class F, int K, bool FIN = false> __global__ void __launch_bounds__(kB
             // (r3: fetching the next batch while this one is multiplied changed nothing -- 2^24 inputs x 81 multiply-adds each is what the
             // pass costs, ~105 us whatever K -- and took the kernel from 117 to 160 VGPRs)
 #pragma unroll 1
-            for (int i0 = 0; i0 < (1 << K); i0 += kRawCarryEvery) {
+            for (int i0 = 0; i0 < kChunk; i0 += kRawCarryEvery) {
                 Fe<F> x[kRawCarryEvery];
 #pragma unroll
                 for (int i = 0; i < kRawCarryEvery; i++) x[i] = fe_load<F>(a.in, j + (size_t)(i0 + i) * a.n);
@@ -389,7 +416,24 @@ template <class F, int K, bool FIN = false> __global__ void __launch_bounds__(kB
                 for (int i = 0; i < kRawCarryEvery; i++) raw_mul_add<F>(ra, u_from_limbs32<F>(x[i]), sw[i0 + i]);
                 raw_normalize<F>(ra);
             }
-            const Fe<F> v = u_to_limbs32<F>(u_reduce_once<F>(raw_mont_reduce<F>(ra)));
+            Fe<F> v = u_to_limbs32<F>(u_reduce_once<F>(raw_mont_reduce<F>(ra)));
+            if constexpr (kChunk < (1 << K)) {                  // the chunks after the first, each reduced and added in the field
+#pragma unroll 1
+                for (int c0 = kChunk; c0 < (1 << K); c0 += kChunk) {
+#pragma unroll
+                    for (int c = 0; c < 2 * UParams<F>::L; c++) ra.c[c] = 0;
+#pragma unroll 1
+                    for (int i0 = c0; i0 < c0 + kChunk; i0 += kRawCarryEvery) {
+                        Fe<F> x[kRawCarryEvery];
+#pragma unroll
+                        for (int i = 0; i < kRawCarryEvery; i++) x[i] = fe_load<F>(a.in, j + (size_t)(i0 + i) * a.n);
+#pragma unroll
+                        for (int i = 0; i < kRawCarryEvery; i++) raw_mul_add<F>(ra, u_from_limbs32<F>(x[i]), sw[i0 + i]);
+                        raw_normalize<F>(ra);
+                    }
+                    v = fe_add<F>(v, u_to_limbs32<F>(u_reduce_once<F>(raw_mont_reduce<F>(ra))));
+                }
+            }
             fe_store<F>(a.out, j, v);
             wide_add_fe<F>(acc[0], v);
         }
@@ -412,7 +456,8 @@ template <class F, int K, bool FIN = false> __global__ void __launch_bounds__(kB
 // a.bps counts workgroups of kBlock / 2 outputs per segment; seglen is a multiple of a.bps * kBlock / 2 (fold_multi.h).
 template <class F, int K, bool FIN = false> __global__ void __launch_bounds__(kBlock) foldk_seg_sums_split2_kernel(FoldKArgs a, MultiFin fin) {
     static_assert(K >= 4 && K <= 8, "2^(K-1) inputs per lane");
-    constexpr int kOut = kBlock / 2, kPer = (1 << K) / 2;
+    constexpr int kOut = kBlock / 2, kPer = (1 << K) / 2, kChunk = raw_chunk<F>(kPer);      // one reduction per kChunk terms (kPer but for K = 8 on BLS12-381 Fr)
+    static_assert(kChunk <= kRawTermsMax<F> && kChunk % kRawCarryEvery == 0 && kPer % kChunk == 0, "terms of one reduction");
     __shared__ Wide<F> sh[kBlock / 64];
     __shared__ Ufe<F> sw[1 << K];
     __shared__ Fe<F> parts[kOut];
@@ -437,7 +482,7 @@ template <class F, int K, bool FIN = false> __global__ void __launch_bounds__(kB
 #pragma unroll
         for (int c = 0; c < 2 * UParams<F>::L; c++) ra.c[c] = 0;
 #pragma unroll 1
-        for (int i0 = 0; i0 < kPer; i0 += kRawCarryEvery) {
+        for (int i0 = 0; i0 < kChunk; i0 += kRawCarryEvery) {
             Fe<F> x[kRawCarryEvery];
 #pragma unroll
             for (int i = 0; i < kRawCarryEvery; i++) x[i] = fe_load<F>(a.in, j + (size_t)(q * kPer + i0 + i) * a.n);
@@ -446,6 +491,23 @@ template <class F, int K, bool FIN = false> __global__ void __launch_bounds__(kB
             raw_normalize<F>(ra);
         }
         Fe<F> v = u_to_limbs32<F>(u_reduce_once<F>(raw_mont_reduce<F>(ra)));
+        if constexpr (kChunk < kPer) {                          // the chunks after the first, each reduced and added in the field
+#pragma unroll 1
+            for (int c0 = kChunk; c0 < kPer; c0 += kChunk) {
+#pragma unroll
+                for (int c = 0; c < 2 * UParams<F>::L; c++) ra.c[c] = 0;
+#pragma unroll 1
+                for (int i0 = c0; i0 < c0 + kChunk; i0 += kRawCarryEvery) {
+                    Fe<F> x[kRawCarryEvery];
+#pragma unroll
+                    for (int i = 0; i < kRawCarryEvery; i++) x[i] = fe_load<F>(a.in, j + (size_t)(q * kPer + i0 + i) * a.n);
+#pragma unroll
+                    for (int i = 0; i < kRawCarryEvery; i++) raw_mul_add<F>(ra, u_from_limbs32<F>(x[i]), sw[q * kPer + i0 + i]);
+                    raw_normalize<F>(ra);
+                }
+                v = fe_add<F>(v, u_to_limbs32<F>(u_reduce_once<F>(raw_mont_reduce<F>(ra))));
+            }
+        }
         if (q == 1) parts[jj] = v;
         __syncthreads();
         if (q == 0) {
@@ -477,6 +539,7 @@ constexpr int kFoldSplitBlock = 64;          // one wave per workgroup: 2^11 out
 template <class F, int K> __global__ void __launch_bounds__(kFoldSplitBlock) foldk_split_kernel(FoldKArgs a) {
     static_assert(K >= 4 && K <= 8, "2^K inputs per output, at least two per lane");
     constexpr int kOut = kFoldSplitBlock / kFoldSplit, kPer = (1 << K) / kFoldSplit, kStep = kPer < kRawCarryEvery ? kPer : kRawCarryEvery;
+    static_assert(kPer <= kRawTermsMax<F>, "terms of one reduction");
     __shared__ Ufe<F> sw[1 << K];
     __shared__ Fe<F> parts[kFoldSplit][kOut];
     for (unsigned e = threadIdx.x; e < (1u << K); e += kFoldSplitBlock) {
@@ -540,6 +603,28 @@ template <class F> __global__ void __launch_bounds__(1 << kFoldABMax) fold_alpha
     }
     w[e] = u_reduce_once<F>(u_from_std<F>(fe_add<F>(wb, wc)));
 }
+// lanes per output of fold_alpha_beta_kernel for an output of n entries from 2^k inputs each: enough lanes to fill the chip (2^20), at least two
+// inputs per lane, at least 16 neighbouring outputs per part (512 contiguous bytes) -- and never more inputs per lane than ONE reduction
+// finishes (kRawTermsMax above: the weights alpha eq(rb, h) + beta eq(rc, h) are canonical residues whatever alpha + beta is, so the bound
+// is the weighted fold's).  Without the last rule outputs of 2^19 entries and more summed 128 or 256 terms per lane at k = 7, 8.
+template <class F> constexpr unsigned fold_ab_split(size_t n, int k) {
+    unsigned split = 1;
+    while ((n * split) < ((size_t)1 << 20) && split * 2 <= (1u << k) / 2 && split * 2 <= (unsigned)kBlock / 16) split *= 2;
+    while ((1u << k) / split > (unsigned)raw_chunk<F>(1 << k)) split *= 2;
+    return split;
+}
+template <class F> constexpr bool fold_ab_split_ok() {
+    for (int k = 1; k <= kFoldABMax; k++)
+        for (int lg = 0; lg <= 40; lg++) {
+            const unsigned s = fold_ab_split<F>((size_t)1 << lg, k);
+            if (s > (unsigned)kBlock / 16 || (s > 1 && s > (1u << k) / 2) || (1u << k) / s > (unsigned)kRawTermsMax<F>) return false;
+        }
+    return true;
+}
+static_assert(fold_ab_split_ok<Fr381>() && fold_ab_split_ok<Fq381>() && fold_ab_split_ok<Bn254Fq>() && fold_ab_split_ok<Bn254Fr>(),
+              "fold_alpha_beta_kernel: terms of one reduction, lanes per output");
+static_assert(fold_ab_split<Fr381>((size_t)1 << 20, 8) == 4 && fold_ab_split<Fr381>((size_t)1 << 20, 7) == 2 && fold_ab_split<Bn254Fr>((size_t)1 << 20, 8) == 2 &&
+              fold_ab_split<Fr381>((size_t)1 << 16, 7) == 16 && fold_ab_split<Fr381>((size_t)1 << 20, 6) == 1, "fold_ab_split");
 template <class F> __global__ void __launch_bounds__(kBlock) fold_alpha_beta_kernel(const void *__restrict__ in, void *__restrict__ out, size_t n, int k,
                                                                                     const Ufe<F> *__restrict__ w, unsigned split) {
     __shared__ Ufe<F> sw[1 << kFoldABMax];
@@ -547,7 +632,7 @@ template <class F> __global__ void __launch_bounds__(kBlock) fold_alpha_beta_ker
     const unsigned nw = 1u << k;
     for (unsigned e = threadIdx.x; e < nw; e += blockDim.x) sw[e] = w[e];
     __syncthreads();
-    const unsigned kout = kBlock / split, per = nw / split;          // outputs per workgroup, inputs per lane (>= 2)
+    const unsigned kout = kBlock / split, per = nw / split;          // outputs per workgroup, inputs per lane (>= 2, <= kRawTermsMax: fold_ab_split)
     const unsigned q = threadIdx.x / kout, jj = threadIdx.x % kout;
     const size_t nblk = (n + kout - 1) / kout;
     for (size_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {    // the same trip count for every lane of a workgroup
@@ -596,8 +681,8 @@ template <class F> __global__ void __launch_bounds__(kBlock) fold_alpha_beta_ker
 // Bounds.  Columns: normalized after every kRawCarryEvery = 4 products (4 L 2^58 + 2^30 < 2^64 for L <= 14, as in foldk).  Value: the
 // entries are canonical (< p, every kernel of the library leaves canonical elements) and so are the coefficients, so the integer sum is
 // below k p^2 and raw_mont_reduce leaves k p (p / 2^(29 L)) + p, which is below 2 p -- the range u_reduce_once finishes -- for
-// k < 2^(29 L) / p: 141 for BLS12-381 Fr, 169 for both BN254 fields, 2^25 for BLS12-381 Fq.  So k <= kLinCombMax = 64 takes ONE
-// reduction per output and no intermediate one.
+// k <= kRawTermsMax = floor(2^(29 L) / p): 70 for BLS12-381 Fr, 169 for both BN254 fields, 41291124 for BLS12-381 Fq.  So
+// k <= kLinCombMax = 64 takes ONE reduction per output and no intermediate one (static_assert in lincomb_at).
 // The coefficients are the same for every lane: they live in the kernel's argument block (constant memory) and each is read with one
 // uniform (scalar) load where it is used; the multiply-adds take it as their scalar operand.
 constexpr int kLinCombMax = 64;
@@ -610,6 +695,7 @@ template <class F> struct LinCombArgs {
 template <class F> ZK_HD Fe<F> lincomb_coeff(const Fe<F> &c_std) { return u_to_limbs32<F>(u_reduce_once<F>(u_from_std<F>(c_std))); }
 // `Args`: LinCombArgs, or another block of the same three members with fewer slots (fri_ml.cuh FriMlBatchArgs)
 template <class F, class Args> __device__ __forceinline__ Fe<F> lincomb_at(const Args &a, size_t i) {
+    static_assert((int)(sizeof(a.t) / sizeof(a.t[0])) <= kRawTermsMax<F>, "terms of one reduction");
     RawAcc<F> ra;
 #pragma unroll
     for (int c = 0; c < 2 * UParams<F>::L; c++) ra.c[c] = 0;

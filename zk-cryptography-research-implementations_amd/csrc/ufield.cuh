@@ -25,7 +25,7 @@ template <> struct UParams<Fr381> {
     static constexpr int L = 9;        // 29-bit limbs
     static constexpr int SH = 5;       // 29 L - 32 N
     static constexpr uint32_t INV = 0x1fffffffu;   // -p^-1 mod 2^29
-    static ZK_HD uint32_t p(int i) {
+    static ZK_HD constexpr uint32_t p(int i) {
         constexpr uint32_t t[L] = {0x00000001u, 0x1ffffff8u, 0x1f96ffbfu, 0x1b4805ffu, 0x1d80553bu, 0x0c0404d0u, 0x1520cce7u, 0x0a6533afu, 0x0073eda7u};
         return t[i];
     }
@@ -60,7 +60,7 @@ template <> struct UParams<Fq381> {
     static constexpr int L = 14;        // 29-bit limbs
     static constexpr int SH = 22;       // 29 L - 32 N
     static constexpr uint32_t INV = 0x1ffcfffdu;   // -p^-1 mod 2^29
-    static ZK_HD uint32_t p(int i) {
+    static ZK_HD constexpr uint32_t p(int i) {
         constexpr uint32_t t[L] = {0x1fffaaabu, 0x0ff7ffffu, 0x14ffffeeu, 0x17fffd62u, 0x0f6241eau, 0x09507b58u, 0x0afd9cc3u, 0x109e70a2u, 0x1764774bu, 0x121a5d66u, 0x12c6e9edu, 0x12ffcd34u, 0x00111ea3u, 0x0000000du};
         return t[i];
     }
@@ -82,7 +82,7 @@ template <> struct UParams<Bn254Fq> {
     static constexpr int L = 9;        // 29-bit limbs
     static constexpr int SH = 5;       // 29 L - 32 N
     static constexpr uint32_t INV = 0x04866389u;   // -p^-1 mod 2^29
-    static ZK_HD uint32_t p(int i) {
+    static ZK_HD constexpr uint32_t p(int i) {
         constexpr uint32_t t[L] = {0x187cfd47u, 0x010460b6u, 0x1c72a34fu, 0x02d522d0u, 0x1585d978u, 0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu};
         return t[i];
     }
@@ -117,7 +117,7 @@ template <> struct UParams<Bn254Fr> {
     static constexpr int L = 9;        // 29-bit limbs
     static constexpr int SH = 5;       // 29 L - 32 N
     static constexpr uint32_t INV = 0x0fffffffu;   // -p^-1 mod 2^29
-    static ZK_HD uint32_t p(int i) {
+    static ZK_HD constexpr uint32_t p(int i) {
         constexpr uint32_t t[L] = {0x10000001u, 0x1f0fac9fu, 0x0e5c2450u, 0x07d090f3u, 0x1585d283u, 0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu};
         return t[i];
     }

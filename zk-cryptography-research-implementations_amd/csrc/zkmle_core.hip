@@ -238,9 +238,7 @@ int mle_fold_alpha_beta(const zk_table *in, size_t k, const uint64_t *alpha, con
         a.alpha = load_host<F>(alpha);
         a.beta = load_host<F>(beta);
         a.k = (int)k;
-        // lanes per output: enough lanes to fill the chip (2^20), at least two inputs per lane, at least 16 neighbouring outputs per part (512 contiguous bytes)
-        unsigned split = 1;
-        while ((n * split) < ((size_t)1 << 20) && split * 2 <= (1u << k) / 2 && split * 2 <= (unsigned)kBlock / 16) split *= 2;
+        const unsigned split = fold_ab_split<F>(n, (int)k);          // lanes per output (mle_kernels.cuh: never more inputs per lane than one reduction finishes)
         const size_t nblk = (n + kBlock / split - 1) / (kBlock / split);
         void *w = nullptr;
         ZK_TRY(pool_alloc(sizeof(Ufe<F>) << k, &w));
