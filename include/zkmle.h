@@ -717,7 +717,7 @@ int zk_zerocheck_last_stats(zk_zerocheck_stats *out);
  * everywhere: the wires A, B, C and the selectors qM, qL, qR, qO, qC.  Their tables, read as evaluations over the cube {0,1}^d, satisfy
  *     qM[x] A[x] B[x] + qL[x] A[x] + qR[x] B[x] + qO[x] C[x] + qC[x] = 0     for all x,
  * the vanilla Plonk gate: additions, multiplications, constants and public-constant rows in one relation.  Wiring (copy constraints) is not
- * part of it.  Transcript (t = NULL: a fresh Transcript::new()), plain appends in this order:
+ * part of it: see the block after this one.  Transcript (t = NULL: a fresh Transcript::new()), plain appends in this order:
  *   1. 8 bytes in one append: the ASCII tag "ZCPG", then d as a big-endian u32; then the eight 32-byte roots in the order above, one append each;
  *   2. tau_0 .. tau_{d-1} = d successive random_challenge_as_field_element();  E_0[x] = eq(x, tau), variable 0 the most significant index bit;
  *   3. for l = 0 .. d - 1, with X_{l+1} = zk_mle_fold(X_l, last, r_l) for the nine tables X (a round binds the LAST variable) and
@@ -739,7 +739,7 @@ int zk_zerocheck_last_stats(zk_zerocheck_stats *out);
  *   qM A B has a share in it); the host forms g_l(4) = 4 g_l(3) - 6 g_l(2) + 4 g_l(1) - g_l(0) + 24 g_l(inf).  36 reads and 18 writes of 32 bytes
  *   and 41 products per lane.  Round 0 reads the commitments' own coefficient tables, which are never written; E_0 and the two ping-pong halves
  *   of the folded nine are one block of the caching pool (32 bytes x 7.75 n).  One host synchronisation per round.
- * Not here: copy constraints or any permutation or lookup argument, public inputs, custom or higher-degree gates, node 1 dropped from the pass
+ * Not here: copy constraints ("Wiring: a permutation check over committed tables" below, a proof of its own), any lookup argument, public inputs, custom or higher-degree gates, node 1 dropped from the pass
  *   by the known claimed sum, the eq factor taken out of the round, several rounds per pass, a sharded prover. */
 /* one round pass on its own.  tables: A, B, C, qM, qL, qR, qO, qC, E.  r = NULL: round 0's form, nothing is folded or allocated,
  * g5 = g(0) .. g(4) of the nine, len >= 2.  r != NULL: outs[0 .. 8] = zk_mle_fold(X, last, r) of each (new tables, len / 2), g5 of the folded
@@ -759,6 +759,84 @@ int zk_zerocheck_gate_verify(int field, const uint8_t *roots_of_eight, uint32_t 
                              uint32_t log_group, const uint64_t *coset, zk_transcript *t, const uint64_t *round_polys, const uint64_t *ys,
                              const uint64_t *open_round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
                              const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok);
+
+/* ---- Wiring: a permutation check over committed tables (extension; csrc/wiring.cuh, csrc/wiring_host.h, csrc/zkmle_wiring.hip) -----------------------
+ * Plonk's copy constraints beside the gate above: SIX commitments of one shape (one field, d, log_blowup, coset and log_group), in this order
+ * everywhere: the wires A, B, C (W_0, W_1, W_2) and the permutation tables SA, SB, SC (S_0, S_1, S_2).  With n = 2^d the cell (j, x) has the
+ * global index id_j(x) = j n + x, and S_j[x] is the field element of the global index the circuit's permutation sigma sends (j, x) to.  The
+ * statement:  W(sigma(c)) = W(c)  for all 3 n cells c: W takes one value on every cycle of sigma.  The S tables belong to the circuit, as the
+ * selectors do: the verifier holds their roots and trusts that they commit to a permutation.
+ * The argument is the logarithmic-derivative one with three helper commitments.  Transcript (t = NULL: a fresh Transcript::new()), plain appends:
+ *   1. 8 bytes in one append: the ASCII tag "ZCPW", then d as a big-endian u32; then the six 32-byte roots in the order above, one append each;
+ *   2. beta, then gamma = two successive random_challenge_as_field_element();
+ *   3. for j = 0, 1, 2 the helper table
+ *        H_j[x] = inv0(Did_j[x]) - inv0(Dsig_j[x]),   Did_j[x] = beta + W_j[x] + gamma id_j(x),   Dsig_j[x] = beta + W_j[x] + gamma S_j[x],
+ *      inv0(0) = 0 and inv0(a) = 1 / a otherwise (for that entry alone); each H_j is committed with the shape of the six (zk_fri_commit, or
+ *      zk_fri_commit_grouped by the inputs' log_group) and the three 32-byte roots are appended, one append each.  They are part of the proof;
+ *   4. alpha, then mu, then tau_0 .. tau_{d-1} = 2 + d successive challenges;  E_0[x] = eq(x, tau), variable 0 the most significant index bit;
+ *   5. a sumcheck with the claimed sum 0 of
+ *        mu (H_0 + H_1 + H_2)(x) + E(x) sum_j alpha^j ( H_j(x) Did_j(x) Dsig_j(x) - gamma (S_j(x) - id_j(x)) ):
+ *      the second part is the zerocheck that every H_j is what step 3 says (1/Did - 1/Dsig = gamma (S - id) / (Did Dsig)), the first the multiset
+ *      equality sum_j sum_x H_j(x) = 0.  For l = 0 .. d - 1, with X_{l+1} = zk_mle_fold(X_l, last, r_l) for the ten tables A, B, C, SA, SB, SC, H0,
+ *      H1, H2, E (a round binds the LAST variable) and the id tables folded the same way -- they are never stored: after l folds
+ *      ID_{j,l}[x'] = j 2^d + c_l + 2^l x' with c_l = sum_{i<l} 2^i r_i -- the quartic g_l(X) is sent as g_l(0) .. g_l(4) (each the 32-byte
+ *      canonical big-endian element); then r_l = random_challenge_as_field_element();
+ *   6. (nothing is appended) the point z with z[d - 1 - l] = r_l;
+ *   7. the whole protocol of zk_fri_ml_open_batch_pow on the transcript as step 5 left it: k = 9 in the order A, B, C, SA, SB, SC, H0, H1, H2,
+ *      npoints = 1, the point z, and the caller's log_final, nqueries, log_arity and grinding_bits.
+ * The prover does not check the statement: on a false one it returns ZK_OK and a proof the verifier rejects.
+ * Verifier (HOST only; it holds the six roots, 192 bytes).  It replays steps 1 to 5 with the H roots of the proof and checks g_0(0) + g_0(1) = 0,
+ *   g_l(0) + g_l(1) = g_{l-1}(r_{l-1})  (the quartic through the five nodes), and
+ *   g_{d-1}(r_{d-1}) = mu (yH0 + yH1 + yH2) + eq(z, tau) sum_j alpha^j ( yH_j (beta + yW_j + gamma id_j(z)) (beta + yW_j + gamma yS_j)
+ *                                                                         - gamma (yS_j - id_j(z)) ),   id_j(z) = j 2^d + sum_i 2^(d-1-i) z_i;
+ *   then zk_fri_ml_verify_batch_pow on the nine claims.  *ok is the conjunction; anything unreduced gives *ok = 0.  Every status is decided
+ *   before the transcript is touched (zk_fri_ml_verify_batch_pow's, in its order); t ends in the prover's state whenever the status is ZK_OK.
+ * Soundness, as a count and not a proof: the multiset equality by logarithmic derivatives needs the characteristic to exceed the 6 n fractions
+ *   (both scalar fields: about 2^254 against d <= 28 or 32) and fails for a false statement with probability about 6 n / p over beta (with gamma:
+ *   another 3 n / p for two cells meeting in beta + w + gamma id); the zerocheck adds d / p for tau and 2 / p for alpha, the sumcheck 4 d / p,
+ *   mu 1 / p, and the opening its own error.
+ * Prover.  Three launches of wiring_fractions_kernel (Montgomery's trick: one Fermat inversion for the sixteen denominators of a lane), three
+ *   commitments, E_0, then one pass per round (wiring_round_kernel) that folds the ten tables and accumulates the quartic's zerocheck part at the
+ *   nodes 0, 1, 2, 3 and infinity and the two plain sums of H_0 + H_1 + H_2 over the even and the odd entries; the host adds mu times the line
+ *   through those two and forms g_l(4) by the fourth difference.  40 reads and 20 writes of 32 bytes and 75 products per lane (round 0: 20 reads,
+ *   55 products).  No committed table is written; E_0 and the two ping-pong halves of the folded ten are one block of the caching pool
+ *   (32 bytes x 8.5 n).  The helper commitments are freed before the call returns.  One host synchronisation per round.
+ * Not here: gate and wiring in ONE sumcheck with one opening of A, B, C (the two proofs open the wires at two points), lookup arguments, public
+ *   inputs, more than three wire columns, a grand-product form, the eq factor taken out of the round, several rounds per pass, a sharded
+ *   prover, and any check that the S tables commit to a permutation. */
+/* the helper table of one wire on its own: *H (a new table) = inv0(beta + W[x] + gamma (first + x)) - inv0(beta + W[x] + gamma S[x]); len >= 2.
+ * Statuses and their order as zk_zerocheck_mul_round (beta and gamma reduced). */
+int zk_wiring_fractions(const zk_table *W, const zk_table *S, uint64_t first, const uint64_t *beta, const uint64_t *gamma, zk_table **H);
+/* one round pass on its own.  tables: A, B, C, SA, SB, SC, H0, H1, H2, E.  r = NULL: round 0's form, nothing is folded or allocated, len >= 2.
+ * r != NULL: outs[0 .. 9] = zk_mle_fold(X, last, r) of each (new tables, len / 2), the sums over the folded ten; len >= 4.  The id tables that
+ * go with the tables the sums are taken over (with r != NULL: after the fold) are ID_j[x'] = j 2^d + id_base + 2^log_step x', d = log2 of
+ * that length + log_step <= 32; id_base is a field element.  g5 = g(0) .. g(4), the message as sent (mu's line included).  Statuses and their
+ * order as zk_zerocheck_mul_round; the five elements and r reduced. */
+int zk_wiring_round(const zk_table *const tables[10], const uint64_t *beta, const uint64_t *gamma, const uint64_t *alpha, const uint64_t *mu, const uint64_t *id_base,
+                    uint32_t log_step, const uint64_t *r, zk_table **outs, uint64_t *g5);
+/* host: nround = 5 d elements of round polynomials, nhroots = 3, then the five counts of zk_fri_ml_sizes_batch(9, ..); any pointer may be NULL */
+int zk_wiring_sizes(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group, size_t *nround, size_t *nhroots,
+                    size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nopen_round);
+/* cms[0 .. 5] = A, B, C, SA, SB, SC.  h_roots: 96 bytes; round_polys: 5 d elements; challenges: d elements (r_0 .. r_{d-1}; the point is their
+ * reverse); chal_out (4 + d elements: beta, gamma, alpha, mu, tau) is diagnostic and may be NULL; ys_out: 9 elements; from gamma_out on, the
+ * outputs of zk_fri_ml_open_batch_pow for k = 9 and one point, sized by zk_wiring_sizes.  Statuses: ZK_E_ARG (NULL, commitments that differ
+ * in field, d, log_blowup, coset or log_group, and zk_fri_ml_open_batch_pow's own), all before ZK_E_NO_DEVICE and before the transcript moves. */
+int zk_wiring_prove(const zk_fri_commitment *const cms[6], uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t grinding_bits, zk_transcript *t,
+                    uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys, uint64_t *challenges, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *open_round_polys,
+                    uint8_t *roots, uint64_t *final_table, uint64_t *open_challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
+                    uint64_t *pow_nonce);
+/* HOST only.  roots_of_six: the six roots as the verifier holds them, 192 bytes; h_roots: the proof's three, 96 bytes; ys: the nine claims. */
+int zk_wiring_verify(int field, const uint8_t *roots_of_six, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
+                     const uint64_t *coset, zk_transcript *t, const uint8_t *h_roots, const uint64_t *round_polys, const uint64_t *ys, const uint64_t *open_round_polys,
+                     const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce,
+                     int *ok);
+/* the calling thread's last zk_wiring_prove: HIP-event times of the three helper tables, their three commitments, E_0's construction and the d
+ * rounds; ms_opening = zk_fri_ml_last_stats' ms_total of the opening; ms_total is the host clock over the call */
+typedef struct {
+    uint32_t rounds;
+    float ms_fractions, ms_commit, ms_eq, ms_rounds, ms_opening, ms_total;
+} zk_wiring_stats;
+int zk_wiring_last_stats(zk_wiring_stats *out);
 
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */

@@ -21,6 +21,8 @@ from .ntt import two_adicity, root_of_unity, ntt_inplace, low_degree_extend, pol
 from . import fri  # noqa: F401  (the module: zk.fri.prove, zk.fri.verify, ...)
 from .fri import FriProof, FriCommitment, FriOpening, FriMlOpening  # noqa: F401
 from . import zerocheck  # noqa: F401  (the module: zk.zerocheck.prove_mul, zk.zerocheck.verify_mul, ...)
+from . import wiring  # noqa: F401  (the module: zk.wiring.prove, zk.wiring.verify, ...)
+from .wiring import WiringProof  # noqa: F401
 from . import gkr  # noqa: F401
 from .gkr import Circuit, Gate, Layer, Operator  # noqa: F401
 from . import kzg  # noqa: F401

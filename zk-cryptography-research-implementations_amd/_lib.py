@@ -180,6 +180,14 @@ def lib():
         "zk_zerocheck_gate_prove": [C.POINTER(vp)] + [C.c_uint32] * 4 + [vp, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
         "zk_zerocheck_gate_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + [u64p, vp, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
                                                                        C.POINTER(C.c_int)],
+        # wiring: a permutation check over committed tables
+        "zk_wiring_fractions": [vp, vp, C.c_uint64, u64p, u64p, C.POINTER(vp)],
+        "zk_wiring_round": [C.POINTER(vp), u64p, u64p, u64p, u64p, u64p, C.c_uint32, u64p, C.POINTER(vp), u64p],
+        "zk_wiring_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 7,
+        "zk_wiring_prove": [C.POINTER(vp)] + [C.c_uint32] * 4 + [vp, u8p, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
+        "zk_wiring_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
+                                                                C.POINTER(C.c_int)],
+        "zk_wiring_last_stats": [vp],
         "zk_sumcheck_basic_prove_succinct": [vp, C.c_uint32, C.c_uint32, vp, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_sumcheck_basic_verify_succinct": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, vp, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u8p,
                                                                                  C.POINTER(C.c_int)],
