@@ -739,7 +739,8 @@ int zk_zerocheck_last_stats(zk_zerocheck_stats *out);
  *   qM A B has a share in it); the host forms g_l(4) = 4 g_l(3) - 6 g_l(2) + 4 g_l(1) - g_l(0) + 24 g_l(inf).  36 reads and 18 writes of 32 bytes
  *   and 41 products per lane.  Round 0 reads the commitments' own coefficient tables, which are never written; E_0 and the two ping-pong halves
  *   of the folded nine are one block of the caching pool (32 bytes x 7.75 n).  One host synchronisation per round.
- * Not here: copy constraints ("Wiring: a permutation check over committed tables" below, a proof of its own), any lookup argument, public inputs, custom or higher-degree gates, node 1 dropped from the pass
+ * Not here: copy constraints ("Wiring: a permutation check over committed tables" below, a proof of its own) and public inputs (both with this gate in
+ *   ONE sumcheck: "Plonk: gate, wiring and public inputs in one sumcheck" below), any lookup argument, custom or higher-degree gates, node 1 dropped from the pass
  *   by the known claimed sum, the eq factor taken out of the round, several rounds per pass, a sharded prover. */
 /* one round pass on its own.  tables: A, B, C, qM, qL, qR, qO, qC, E.  r = NULL: round 0's form, nothing is folded or allocated,
  * g5 = g(0) .. g(4) of the nine, len >= 2.  r != NULL: outs[0 .. 8] = zk_mle_fold(X, last, r) of each (new tables, len / 2), g5 of the folded
@@ -801,9 +802,9 @@ int zk_zerocheck_gate_verify(int field, const uint8_t *roots_of_eight, uint32_t 
  *   through those two and forms g_l(4) by the fourth difference.  40 reads and 20 writes of 32 bytes and 75 products per lane (round 0: 20 reads,
  *   55 products).  No committed table is written; E_0 and the two ping-pong halves of the folded ten are one block of the caching pool
  *   (32 bytes x 8.5 n).  The helper commitments are freed before the call returns.  One host synchronisation per round.
- * Not here: gate and wiring in ONE sumcheck with one opening of A, B, C (the two proofs open the wires at two points), lookup arguments, public
- *   inputs, more than three wire columns, a grand-product form, the eq factor taken out of the round, several rounds per pass, a sharded
- *   prover, and any check that the S tables commit to a permutation. */
+ * Not here: gate and wiring in ONE sumcheck with one opening of A, B, C and public inputs (the block after this one: "Plonk: gate, wiring and
+ *   public inputs in one sumcheck"), lookup arguments, more than three wire columns, a grand-product form, the eq factor taken out of the
+ *   round, several rounds per pass, a sharded prover, and any check that the S tables commit to a permutation. */
 /* the helper table of one wire on its own: *H (a new table) = inv0(beta + W[x] + gamma (first + x)) - inv0(beta + W[x] + gamma S[x]); len >= 2.
  * Statuses and their order as zk_zerocheck_mul_round (beta and gamma reduced). */
 int zk_wiring_fractions(const zk_table *W, const zk_table *S, uint64_t first, const uint64_t *beta, const uint64_t *gamma, zk_table **H);
@@ -837,6 +838,79 @@ typedef struct {
     float ms_fractions, ms_commit, ms_eq, ms_rounds, ms_opening, ms_total;
 } zk_wiring_stats;
 int zk_wiring_last_stats(zk_wiring_stats *out);
+
+/* ---- Plonk: gate, wiring and public inputs in one sumcheck (extension; csrc/plonk.cuh, csrc/plonk_host.h, csrc/zkmle_plonk.hip) --------------------
+ * The two blocks above as ONE proof, with public inputs: ELEVEN commitments of one shape (one field, d, log_blowup, coset and log_group), in this
+ * order everywhere: the wires A, B, C, the selectors qM, qL, qR, qO, qC and the permutation tables SA, SB, SC.  The public inputs are
+ * pi_0 .. pi_{l-1}, 0 <= l <= 2^d, reduced field elements in a host array (4 u64 limbs each, stored form); PI[x] = pi_x for x < l and 0 otherwise.
+ * The statement has two parts:
+ *     qM[x] A[x] B[x] + qL[x] A[x] + qR[x] B[x] + qO[x] C[x] + qC[x] - PI[x] = 0     for all x
+ * (a row x < l with qL = 1 and the other selectors 0 says A[x] = pi_x), and the wiring's statement W(sigma(c)) = W(c) on A, B, C, SA, SB, SC.
+ * Transcript (t = NULL: a fresh Transcript::new()), plain appends:
+ *   1. 12 bytes in one append: the ASCII tag "ZCPK", then d as a big-endian u32, then l as a big-endian u32;
+ *   2. the eleven 32-byte roots in the order above, one append each;
+ *   3. the l public values, each the 32-byte canonical big-endian element, one append each;
+ *   4. beta, then gamma = two successive random_challenge_as_field_element();
+ *   5. the helper tables H_0, H_1, H_2 exactly as step 3 of the wiring (wiring_fractions_kernel, inv0, id_j(x) = j 2^d + x), each committed with
+ *      the shape of the eleven; the three 32-byte roots are appended, one append each.  They are part of the proof;
+ *   6. alpha, then mu, then tau_0 .. tau_{d-1} = 2 + d successive challenges;  E_0[x] = eq(x, tau), variable 0 the most significant index bit;
+ *   7. ONE sumcheck of
+ *        mu (H_0 + H_1 + H_2)(x) + E(x) [ sum_{j<3} alpha^j ( H_j Did_j Dsig_j - gamma (S_j - id_j) )(x) + alpha^3 (qM A B + qL A + qR B + qO C + qC)(x) ]
+ *      with the claimed sum  c = alpha^3 PIeval(tau),  PIeval(tau) = sum_{x<l} pi_x eq(x, tau)  (0 when l = 0): the public inputs, taken to the
+ *      other side of the gate's zerocheck, are in no table and in no kernel.  d rounds of a quartic sent as g_l(0) .. g_l(4) (each the 32-byte
+ *      canonical big-endian element), then r_l; each round binds the LAST variable, all fifteen tables A, B, C, qM, qL, qR, qO, qC, SA, SB, SC, H0,
+ *      H1, H2, E fold by r_l, and the id tables are implicit as in the wiring: ID_{j,l}[x'] = j 2^d + c_l + 2^l x', c_l = sum_{i<l} 2^i r_i;
+ *   8. (nothing is appended) the point z with z[d - 1 - l] = r_l;
+ *   9. the whole protocol of zk_fri_ml_open_batch_pow on the transcript as step 7 left it: k = 14 in the order A, B, C, qM, qL, qR, qO, qC, SA, SB,
+ *      SC, H0, H1, H2, npoints = 1, the point z, and the caller's log_final, nqueries, log_arity and grinding_bits.
+ * The prover does not check the statement: on a false one it returns ZK_OK and a proof the verifier rejects.
+ * Verifier (HOST only: no table, no device; it holds the eleven roots, 352 bytes, and the public values).  It replays steps 1 to 7 with the H
+ *   roots of the proof and checks  g_0(0) + g_0(1) = c,  g_l(0) + g_l(1) = g_{l-1}(r_{l-1})  (the quartic through the five nodes), and
+ *   g_{d-1}(r_{d-1}) = mu (yH0 + yH1 + yH2) + eq(z, tau) [ sum_j alpha^j ( yH_j (beta + yW_j + gamma id_j(z)) (beta + yW_j + gamma yS_j)
+ *                        - gamma (yS_j - id_j(z)) ) + alpha^3 (y_qM y_A y_B + y_qL y_A + y_qR y_B + y_qO y_C + y_qC) ],   id_j(z) = j 2^d + sum_i 2^(d-1-i) z_i;
+ *   then zk_fri_ml_verify_batch_pow on the fourteen claims.  *ok is the conjunction; anything unreduced -- a public value >= p among it -- gives
+ *   *ok = 0 with the status ZK_OK.  Every status is decided before the transcript is touched (zk_fri_ml_verify_batch_pow's, in its order, then
+ *   npublic > 2^d and public_inputs == NULL with npublic > 0: ZK_E_ARG); the replay runs on a copy and t ends in the prover's state whenever the
+ *   status is ZK_OK.
+ * Prover.  The wiring's three launches of wiring_fractions_kernel and three commitments, E_0, then one pass per round (plonk_round_kernel) that
+ *   folds the fifteen tables and accumulates the seven sums of the wiring's pass, the gate's share scaled by the line alpha^3 E going into the
+ *   same five zerocheck sums (only qM A B has a share in the X^4 coefficient); the host forms the message as the wiring's does.  60 reads and 30
+ *   writes of 32 bytes per lane that reach HBM, 6 more reads of entries the lane itself touched a phase earlier, and 110 products (round 0: 30 + 6
+ *   reads, 80 products).  No committed table is written; E_0 and the two ping-pong halves of the folded fifteen are one block of the caching
+ *   pool (32 bytes x 12.25 n).  The helper commitments are freed before the call returns.  One host synchronisation per round.
+ * Not here: lookup arguments, more than three wire columns, custom gates, a circuit-builder API, any check that the S tables commit to a
+ *   permutation, several rounds per pass, a sharded prover, pooled memory for the helper trees. */
+/* one round pass on its own.  tables: A, B, C, qM, qL, qR, qO, qC, SA, SB, SC, H0, H1, H2, E.  The contract of zk_wiring_round with fifteen
+ * tables: r = NULL: round 0's form, nothing is folded or allocated, len >= 2; r != NULL: outs[0 .. 14] = zk_mle_fold(X, last, r) of each (new
+ * tables, len / 2), the sums over the folded fifteen, len >= 4; the id tables ID_j[x'] = j 2^d + id_base + 2^log_step x', d = log2 of the
+ * summed length + log_step <= 32; g5 = g(0) .. g(4), the message as sent.  The same statuses in the same order. */
+int zk_plonk_round(const zk_table *const tables[15], const uint64_t *beta, const uint64_t *gamma, const uint64_t *alpha, const uint64_t *mu, const uint64_t *id_base,
+                   uint32_t log_step, const uint64_t *r, zk_table **outs, uint64_t *g5);
+/* host: *out = PIeval(tau) = sum_{x < npublic} public_inputs[x] eq(x, tau), tau: d elements, variable 0 the most significant index bit; at most
+ * 2 npublic + d products and no table.  ZK_E_ARG: NULL (public_inputs may be NULL with npublic = 0), d outside 1 .. 32, npublic > 2^d, a field other than the two scalar
+ * fields, anything unreduced. */
+int zk_plonk_public_eval(int field, const uint64_t *public_inputs, uint32_t npublic, const uint64_t *tau, uint32_t d, uint64_t *out);
+/* host: nround = 5 d elements of round polynomials, nhroots = 3, then the five counts of zk_fri_ml_sizes_batch(14, ..); any pointer may be NULL */
+int zk_plonk_sizes(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group, size_t *nround, size_t *nhroots,
+                   size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nopen_round);
+/* cms[0 .. 10] = A, B, C, qM, qL, qR, qO, qC, SA, SB, SC; public_inputs: npublic elements (NULL with npublic = 0).  h_roots: 96 bytes;
+ * round_polys: 5 d elements; challenges: d elements (the point is their reverse); chal_out (4 + d elements: beta, gamma, alpha, mu, tau) is
+ * diagnostic and may be NULL; ys_out: 14 elements; from gamma_out on, the outputs of zk_fri_ml_open_batch_pow for k = 14 and one point, sized
+ * by zk_plonk_sizes.  ZK_E_ARG, with nothing written and the transcript as it was: what zk_wiring_prove refuses, in each of the eleven places;
+ * npublic > 2^d; public_inputs == NULL with npublic > 0; an unreduced public value.  All before ZK_E_NO_DEVICE. */
+int zk_plonk_prove(const zk_fri_commitment *const cms[11], const uint64_t *public_inputs, uint32_t npublic, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                   uint32_t grinding_bits, zk_transcript *t, uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys, uint64_t *challenges, uint64_t *ys_out,
+                   uint64_t *gamma_out, uint64_t *open_round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *open_challenges, uint64_t *query_indices,
+                   uint64_t *query_values, uint8_t *query_paths, uint64_t *pow_nonce);
+/* HOST only.  roots_of_eleven: the eleven roots as the verifier holds them, 352 bytes; public_inputs: the verifier's own npublic values;
+ * h_roots: the proof's three, 96 bytes; ys: the fourteen claims. */
+int zk_plonk_verify(int field, const uint8_t *roots_of_eleven, const uint64_t *public_inputs, uint32_t npublic, uint32_t d, uint32_t log_blowup, uint32_t log_final,
+                    uint32_t nqueries, uint32_t log_arity, uint32_t log_group, const uint64_t *coset, zk_transcript *t, const uint8_t *h_roots, const uint64_t *round_polys,
+                    const uint64_t *ys, const uint64_t *open_round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
+                    const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok);
+/* the calling thread's last zk_plonk_prove: the fields of zk_wiring_stats */
+typedef zk_wiring_stats zk_plonk_stats;
+int zk_plonk_last_stats(zk_plonk_stats *out);
 
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */

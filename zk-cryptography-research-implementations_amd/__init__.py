@@ -23,6 +23,8 @@ from .fri import FriProof, FriCommitment, FriOpening, FriMlOpening  # noqa: F401
 from . import zerocheck  # noqa: F401  (the module: zk.zerocheck.prove_mul, zk.zerocheck.verify_mul, ...)
 from . import wiring  # noqa: F401  (the module: zk.wiring.prove, zk.wiring.verify, ...)
 from .wiring import WiringProof  # noqa: F401
+from . import plonk  # noqa: F401  (the module: zk.plonk.prove, zk.plonk.verify, ...)
+from .plonk import PlonkProof  # noqa: F401
 from . import gkr  # noqa: F401
 from .gkr import Circuit, Gate, Layer, Operator  # noqa: F401
 from . import kzg  # noqa: F401

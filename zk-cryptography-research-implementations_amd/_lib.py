@@ -188,6 +188,14 @@ def lib():
         "zk_wiring_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
                                                                 C.POINTER(C.c_int)],
         "zk_wiring_last_stats": [vp],
+        # Plonk: gate, wiring and public inputs in one sumcheck
+        "zk_plonk_round": [C.POINTER(vp), u64p, u64p, u64p, u64p, u64p, C.c_uint32, u64p, C.POINTER(vp), u64p],
+        "zk_plonk_public_eval": [C.c_int, u64p, C.c_uint32, u64p, C.c_uint32, u64p],
+        "zk_plonk_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 7,
+        "zk_plonk_prove": [C.POINTER(vp), u64p] + [C.c_uint32] * 5 + [vp, u8p, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
+        "zk_plonk_verify": [C.c_int, u8p, u64p] + [C.c_uint32] * 7 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
+                                                                       C.POINTER(C.c_int)],
+        "zk_plonk_last_stats": [vp],
         "zk_sumcheck_basic_prove_succinct": [vp, C.c_uint32, C.c_uint32, vp, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_sumcheck_basic_verify_succinct": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, vp, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u8p,
                                                                                  C.POINTER(C.c_int)],

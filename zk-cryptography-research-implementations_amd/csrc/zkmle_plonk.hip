@@ -1,14 +1,16 @@
-// zkmle_wiring.hip -- C ABI of the permutation check over FRI commitments (wiring.cuh, wiring_host.h): the helper tables of one wire and one
-// round pass on their own, the prover (the three helper tables and their commitments, the sumcheck of the logarithmic-derivative relation on
-// the nine coefficient tables and E, then zk_fri_ml_open_batch_pow of the nine commitments at the point the rounds leave, on the same
-// transcript) and its host verifier.  Extension: the protocol is defined in include/zkmle.h "Wiring: a permutation check over committed tables".
+// zkmle_plonk.hip -- C ABI of the Plonk proof over FRI commitments (plonk.cuh, plonk_host.h): one round pass on its own, the public inputs' value
+// at a point, the prover (the wiring's three helper tables and their commitments, ONE sumcheck of the gate and the wiring on the fourteen
+// coefficient tables and E whose claimed sum carries the public inputs, then zk_fri_ml_open_batch_pow of the fourteen commitments at the point the
+// rounds leave, on the same transcript) and its host verifier.  Extension: the protocol is defined in include/zkmle.h "Plonk: gate, wiring and
+// public inputs in one sumcheck".
 #include <string.h>
 
 #include <chrono>
 #include <vector>
 
 #include "eq_table.cuh"
-#include "fri_host.h"
+#include "plonk.cuh"
+#include "plonk_host.h"
 #include "wiring_driver.cuh"
 
 using namespace zk;
@@ -16,37 +18,29 @@ using namespace zk::host;
 
 namespace {
 
-thread_local zk_wiring_stats g_wiring_stats{};
+thread_local zk_plonk_stats g_plonk_stats{};
 
-constexpr int kTables = kWiringOpened + 1;                   // A, B, C, SA, SB, SC, H0, H1, H2, E
+constexpr int kTables = kPlonkTables;                        // the fourteen opened and E
+static_assert(kTables == kPlonkOpened + 1, "the pass folds the opened tables and E");
 
 // sums (device, 7 elements) of a pass over q pairs whose id tables are c_l + 2^l x + j 2^d.  Launches only.
-template <class F> int launch_round(bool fold, const WiringTables &t, size_t q, const Fe<F> &r, const WiringChallenges<F> &ch, const Fe<F> &id_base, unsigned log_step, unsigned d,
+template <class F> int launch_round(bool fold, const PlonkTables &t, size_t q, const Fe<F> &r, const WiringChallenges<F> &ch, const Fe<F> &id_base, unsigned log_step, unsigned d,
                                     void *partials, void *sums) {
     const int grid = reduce_grid_for(q);
-    WiringConsts<F> c;
+    PlonkConsts<F> c;
     c.beta = ch.beta;
     c.gamma = ch.gamma;
     c.alpha = ch.alpha;
+    c.alpha3 = fe_mul<F>(ch.alpha, fe_mul<F>(ch.alpha, ch.alpha));
     c.gstep = fe_mul<F>(ch.gamma, fe_from_u64<F>((uint64_t)1 << log_step));
     c.gwire = fe_mul<F>(ch.gamma, fe_from_u64<F>((uint64_t)1 << d));
     c.gid0 = fe_mul<F>(ch.gamma, id_base);
     c.gnext = fe_sub<F>(fe_mul<F>(fe_dbl<F>(c.gstep), fe_from_u64<F>((uint64_t)grid * kBlock)), fe_dbl<F>(c.gwire));
-    if (fold) wiring_round_kernel<F, true><<<grid, kBlock, 0, cur_stream()>>>(t, q, r, c, partials);
-    else wiring_round_kernel<F, false><<<grid, kBlock, 0, cur_stream()>>>(t, q, r, c, partials);
+    if (fold) plonk_round_kernel<F, true><<<grid, kBlock, 0, cur_stream()>>>(t, q, r, c, partials);
+    else plonk_round_kernel<F, false><<<grid, kBlock, 0, cur_stream()>>>(t, q, r, c, partials);
     ZK_HIP(hipGetLastError());
     finish_sums_kernel<F><<<1, kBlock, 0, cur_stream()>>>(partials, (size_t)grid, kWiringSums, sums);
     ZK_HIP(hipGetLastError());
-    return ZK_OK;
-}
-
-template <class F> int fractions_once(const zk_table *W, const zk_table *S, uint64_t first, const uint64_t *beta, const uint64_t *gamma, zk_table **H) {
-    zk_table *h = nullptr;
-    ZK_TRY(zk_table_alloc(W->field, W->len, &h));
-    int rc = launch_fractions<F>(W->dptr, S->dptr, h->dptr, W->len, first, load_host<F>(beta), load_host<F>(gamma));
-    if (rc == ZK_OK && hipStreamSynchronize(cur_stream()) != hipSuccess) rc = ZK_E_HIP;
-    if (rc != ZK_OK) { zk_table_free(h); return rc; }
-    *H = h;
     return ZK_OK;
 }
 
@@ -60,9 +54,9 @@ template <class F> int round_once(const zk_table *const *in, const WiringChallen
     ZK_TRY(sb.alloc(ESZ));
     zk_table *o[kTables] = {};
     const auto drop = [&] { for (zk_table *t : o) zk_table_free(t); };
-    // the pass writes the folded ten into one block; the caller's new tables are copies of its tenths
+    // the pass writes the folded fifteen into one block; the caller's new tables are copies of its fifteenths
     DevBuf folded;
-    WiringTables t{};
+    PlonkTables t{};
     for (int j = 0; j < kTables; j++) t.in[j] = in[j]->dptr;
     if (fold) {
         ZK_TRY(folded.alloc(kTables * (len / 2) * ESZ));
@@ -73,31 +67,31 @@ template <class F> int round_once(const zk_table *const *in, const WiringChallen
             if (rc != ZK_OK) { drop(); return rc; }
         }
     }
-    Fe<F> S[kWiringSums], g[kWiringNodes];
+    Fe<F> S[kWiringSums], g[kPlonkNodes];
     int rc = launch_round<F>(fold, t, q, fold ? load_host<F>(r) : fe_one<F>(), ch, load_host<F>(id_base), log_step, ilog2(2 * q) + log_step, sb.buf.p, sb.sums);
     for (int j = 0; fold && rc == ZK_OK && j < kTables; j++)
         if (hipMemcpyAsync(o[j]->dptr, (char *)folded.p + (size_t)j * t.ostride, t.ostride, hipMemcpyDeviceToDevice, cur_stream()) != hipSuccess) rc = ZK_E_HIP;
     if (rc == ZK_OK && zk::memcpy_on_stream(S, sb.sums, kWiringSums * ESZ, hipMemcpyDeviceToHost) != hipSuccess) rc = ZK_E_HIP;
     if (rc != ZK_OK) { drop(); return rc; }
     wiring_message<F>(S, ch.mu, g);
-    for (int k = 0; k < kWiringNodes; k++) store_host<F>(gout + (size_t)k * W, g[k]);
+    for (int k = 0; k < kPlonkNodes; k++) store_host<F>(gout + (size_t)k * W, g[k]);
     for (int j = 0; fold && j < kTables; j++) outs[j] = o[j];
     return ZK_OK;
 }
 
-// steps 1 to 6 on `tr`: the statement, the helper tables and their commitments (hc, h_roots), E_0 and the d rounds; z (d elements) = the point
+// steps 1 to 8 on `tr`: the statement, the helper tables and their commitments (hc, h_roots), E_0 and the d rounds; z (d elements) = the point
 // the opening is made at.  One host synchronisation per round.
-template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcript &tr, CommitHolder &hc, uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys,
-                                    uint64_t *challenges, uint64_t *z, zk_wiring_stats &st) {
+template <class F> int prove_rounds(const zk_fri_commitment *const *cms, const uint64_t *pub, uint32_t npublic, Transcript &tr, CommitHolder &hc, uint8_t *h_roots,
+                                    uint64_t *chal_out, uint64_t *round_polys, uint64_t *challenges, uint64_t *z, zk_plonk_stats &st) {
     constexpr size_t ESZ = sizeof(Fe<F>);
-    constexpr int W = F::N / 2, T = kTables, K = kWiringOpened;
+    constexpr int W = F::N / 2, T = kTables, K = kPlonkOpened;
     const zk_fri_commitment *c0 = cms[0];
     const unsigned d = c0->d;
     const size_t n = (size_t)1 << d;
-    uint8_t roots[32 * kWiringGiven];
-    for (int j = 0; j < kWiringGiven; j++) memcpy(roots + 32 * j, cms[j]->root, 32);
+    uint8_t roots[32 * kPlonkGiven];
+    for (int j = 0; j < kPlonkGiven; j++) memcpy(roots + 32 * j, cms[j]->root, 32);
     WiringChallenges<F> ch;
-    wiring_statement<F>(tr, roots, d, ch);
+    plonk_statement<F>(tr, roots, d, pub, npublic, ch);
 
     Events ev;
     size_t e0, e1, e2, e3, e4;
@@ -107,7 +101,7 @@ template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcr
         zk_table *H[kWiringWires];
         for (int j = 0; j < kWiringWires; j++) {
             ZK_TRY(th.alloc(c0->field, n, &H[j]));
-            ZK_TRY(launch_fractions<F>(cms[j]->coeffs->dptr, cms[3 + j]->coeffs->dptr, H[j]->dptr, n, (uint64_t)j * n, ch.beta, ch.gamma));
+            ZK_TRY(launch_fractions<F>(cms[j]->coeffs->dptr, cms[PLONK_S + j]->coeffs->dptr, H[j]->dptr, n, (uint64_t)j * n, ch.beta, ch.gamma));
         }
         ZK_TRY(ev.mark(&e1));
         for (int j = 0; j < kWiringWires; j++) {
@@ -126,16 +120,16 @@ template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcr
         memcpy(chal_out + 4 * W, ch.tau.data(), ch.tau.size() * 8);
     }
 
-    // one block: E_0 (n elements), then the two ping-pong halves: the ten tables of an odd round (n / 2 entries each at round 1) and of an
+    // one block: E_0 (n elements), then the two ping-pong halves: the fifteen tables of an odd round (n / 2 entries each at round 1) and of an
     // even one (n / 4 each at round 2); a round's tables never outgrow the half they first had
     DevBuf blk;
     SumsBuf sb;
     ZK_TRY(blk.alloc((n + T * (n / 2) + T * (n / 4) + 1) * ESZ));
     ZK_TRY(sb.alloc(ESZ));
     char *E0 = (char *)blk.p, *half[2] = {E0 + n * ESZ, E0 + (n + T * (n / 2)) * ESZ};
-    const auto tables_at = [&](unsigned l, const void **out) {   // the nine tables and E at round l: n >> l entries each
+    const auto tables_at = [&](unsigned l, const void **out) {   // the fourteen tables and E at round l: n >> l entries each
         for (int j = 0; j < T; j++) {
-            const void *own = j < kWiringGiven ? cms[j]->coeffs->dptr : j < K ? hc.cm[j - kWiringGiven]->coeffs->dptr : (void *)E0;
+            const void *own = j < kPlonkGiven ? cms[j]->coeffs->dptr : j < K ? hc.cm[j - kPlonkGiven]->coeffs->dptr : (void *)E0;
             out[j] = l == 0 ? own : half[(l - 1) & 1] + (size_t)j * (n >> l) * ESZ;
         }
     };
@@ -144,7 +138,7 @@ template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcr
     ZK_TRY(ev.mark(&e3));
     Fe<F> r = fe_one<F>(), id_base = fe_zero<F>();             // c_l = sum_{i < l} 2^i r_i
     for (unsigned l = 0; l < d; l++) {
-        WiringTables t{};
+        PlonkTables t{};
         if (l == 0) {
             tables_at(0, t.in);
         } else {
@@ -154,12 +148,12 @@ template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcr
             id_base = fe_add<F>(id_base, fe_mul<F>(fe_from_u64<F>((uint64_t)1 << (l - 1)), r));
         }
         ZK_TRY(launch_round<F>(l != 0, t, n >> (l + 1), r, ch, id_base, l, d, sb.buf.p, sb.sums));
-        Fe<F> S[kWiringSums], g[kWiringNodes];
+        Fe<F> S[kWiringSums], g[kPlonkNodes];
         ZK_HIP(zk::memcpy_on_stream(S, sb.sums, kWiringSums * ESZ, hipMemcpyDeviceToHost));   // the round's synchronisation
         if (l == 0) eqb.release();
         wiring_message<F>(S, ch.mu, g);
-        for (int k = 0; k < kWiringNodes; k++) {
-            store_host<F>(round_polys + ((size_t)l * kWiringNodes + k) * W, g[k]);
+        for (int k = 0; k < kPlonkNodes; k++) {
+            store_host<F>(round_polys + ((size_t)l * kPlonkNodes + k) * W, g[k]);
             tr.append_be<F>(g[k]);
         }
         r = tr.random_challenge_as_field_element<F>();
@@ -176,22 +170,15 @@ template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcr
     return ZK_OK;
 }
 
+// npublic <= 2^d, a NULL array only with npublic = 0
+bool public_shape_ok(const uint64_t *pub, uint32_t npublic, uint32_t d) { return (d >= 32 || npublic <= ((uint32_t)1 << d)) && (pub || npublic == 0); }
+
 }  // namespace
 
 extern "C" {
 
-int zk_wiring_fractions(const zk_table *W, const zk_table *S, uint64_t first, const uint64_t *beta, const uint64_t *gamma, zk_table **H) {
-    if (!W || !S || !beta || !gamma || !H || W->field != S->field || (W->field != ZK_FR381 && W->field != ZK_BN254_FR)) return ZK_E_ARG;
-    if (W->len != S->len) return ZK_E_LEN_MISMATCH;
-    if (!is_pow2(W->len)) return ZK_E_NOT_POW2;
-    if (W->len < 2 || !all_reduced(W->field, beta, 1) || !all_reduced(W->field, gamma, 1)) return ZK_E_ARG;
-    ZK_TRY(require_device());
-    FRI_DISPATCH(W->field, return fractions_once<F>(W, S, first, beta, gamma, H));
-    return ZK_OK;
-}
-
-int zk_wiring_round(const zk_table *const tables[10], const uint64_t *beta, const uint64_t *gamma, const uint64_t *alpha, const uint64_t *mu, const uint64_t *id_base,
-                    uint32_t log_step, const uint64_t *r, zk_table **outs, uint64_t *g5) {
+int zk_plonk_round(const zk_table *const tables[15], const uint64_t *beta, const uint64_t *gamma, const uint64_t *alpha, const uint64_t *mu, const uint64_t *id_base,
+                   uint32_t log_step, const uint64_t *r, zk_table **outs, uint64_t *g5) {
     if (!tables) return ZK_E_ARG;
     for (int j = 0; j < kTables; j++)
         if (!tables[j]) return ZK_E_ARG;
@@ -219,77 +206,86 @@ int zk_wiring_round(const zk_table *const tables[10], const uint64_t *beta, cons
     return ZK_OK;
 }
 
-int zk_wiring_sizes(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group, size_t *nround, size_t *nhroots,
-                    size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nopen_round) {
-    ZK_TRY(zk_fri_ml_sizes_batch(kWiringOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, nroots, nfinal, nvalues, path_bytes, nopen_round));
-    if (nround) *nround = (size_t)kWiringNodes * d;
+int zk_plonk_public_eval(int field, const uint64_t *public_inputs, uint32_t npublic, const uint64_t *tau, uint32_t d, uint64_t *out) {
+    if (!tau || !out || d < 1 || d > 32 || (field != ZK_FR381 && field != ZK_BN254_FR) || !public_shape_ok(public_inputs, npublic, d)) return ZK_E_ARG;
+    if (!all_reduced(field, public_inputs, npublic) || !all_reduced(field, tau, d)) return ZK_E_ARG;
+    FRI_DISPATCH(field, store_host<F>(out, plonk_public_eval<F>(public_inputs, npublic, tau, d)));
+    return ZK_OK;
+}
+
+int zk_plonk_sizes(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group, size_t *nround, size_t *nhroots,
+                   size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nopen_round) {
+    ZK_TRY(zk_fri_ml_sizes_batch(kPlonkOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, nroots, nfinal, nvalues, path_bytes, nopen_round));
+    if (nround) *nround = (size_t)kPlonkNodes * d;
     if (nhroots) *nhroots = kWiringWires;
     return ZK_OK;
 }
 
-int zk_wiring_prove(const zk_fri_commitment *const cms[6], uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t grinding_bits, zk_transcript *t,
-                    uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys, uint64_t *challenges, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *open_round_polys,
-                    uint8_t *roots, uint64_t *final_table, uint64_t *open_challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
-                    uint64_t *pow_nonce) {
+int zk_plonk_prove(const zk_fri_commitment *const cms[11], const uint64_t *public_inputs, uint32_t npublic, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                   uint32_t grinding_bits, zk_transcript *t, uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys, uint64_t *challenges, uint64_t *ys_out,
+                   uint64_t *gamma_out, uint64_t *open_round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *open_challenges, uint64_t *query_indices,
+                   uint64_t *query_values, uint8_t *query_paths, uint64_t *pow_nonce) {
     const auto t0 = std::chrono::steady_clock::now();
     if (!cms) return ZK_E_ARG;
-    for (int j = 0; j < kWiringGiven; j++)
+    for (int j = 0; j < kPlonkGiven; j++)
         if (!cms[j]) return ZK_E_ARG;
     if (!h_roots || !round_polys || !challenges) return ZK_E_ARG;
     if (cms[0]->d < 1 || cms[0]->d > 32) return ZK_E_ARG;     // what sizes the point below; no commitment is made outside it
-    // the point and the helper commitments do not exist yet: the opener's statuses are taken on the six and a stand-in of zeros, before the
-    // transcript moves (the helpers get the shape of the six, and nine is within the opener's count)
+    // the point and the helper commitments do not exist yet: the opener's statuses are taken on the eleven and a stand-in of zeros, before the
+    // transcript moves (the helpers get the shape of the eleven, and fourteen is within the opener's count)
     std::vector<uint64_t> z((size_t)cms[0]->d * 4, 0);
-    ZK_TRY(fri_ml_open_batch_check(cms, kWiringGiven, z.data(), 1, log_final, nqueries, log_arity, ys_out, open_round_polys, roots, final_table, query_values, query_paths,
+    ZK_TRY(fri_ml_open_batch_check(cms, kPlonkGiven, z.data(), 1, log_final, nqueries, log_arity, ys_out, open_round_polys, roots, final_table, query_values, query_paths,
                                    grinding_bits, pow_nonce));
+    if (!public_shape_ok(public_inputs, npublic, cms[0]->d) || !all_reduced(cms[0]->field, public_inputs, npublic)) return ZK_E_ARG;
     zk_transcript own;
     zk_transcript *tt = t ? t : &own;
-    zk_wiring_stats st{};
+    zk_plonk_stats st{};
     CommitHolder hc;
-    FRI_DISPATCH(cms[0]->field, ZK_TRY((prove_rounds<F>(cms, tt->t, hc, h_roots, chal_out, round_polys, challenges, z.data(), st))));
-    const zk_fri_commitment *all[kWiringOpened];
-    for (int j = 0; j < kWiringOpened; j++) all[j] = j < kWiringGiven ? cms[j] : hc.cm[j - kWiringGiven];
-    ZK_TRY(zk_fri_ml_open_batch_pow(all, kWiringOpened, z.data(), 1, log_final, nqueries, log_arity, tt, ys_out, gamma_out, open_round_polys, roots, final_table,
+    FRI_DISPATCH(cms[0]->field, ZK_TRY((prove_rounds<F>(cms, public_inputs, npublic, tt->t, hc, h_roots, chal_out, round_polys, challenges, z.data(), st))));
+    const zk_fri_commitment *all[kPlonkOpened];
+    for (int j = 0; j < kPlonkOpened; j++) all[j] = j < kPlonkGiven ? cms[j] : hc.cm[j - kPlonkGiven];
+    ZK_TRY(zk_fri_ml_open_batch_pow(all, kPlonkOpened, z.data(), 1, log_final, nqueries, log_arity, tt, ys_out, gamma_out, open_round_polys, roots, final_table,
                                     open_challenges, query_indices, query_values, query_paths, grinding_bits, pow_nonce));
     zk_fri_ml_stats ml{};
     (void)zk_fri_ml_last_stats(&ml);
     st.ms_opening = ml.ms_total;
     st.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    g_wiring_stats = st;
+    g_plonk_stats = st;
     return ZK_OK;
 }
 
-int zk_wiring_verify(int field, const uint8_t *roots_of_six, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
-                     const uint64_t *coset, zk_transcript *t, const uint8_t *h_roots, const uint64_t *round_polys, const uint64_t *ys, const uint64_t *open_round_polys,
-                     const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce,
-                     int *ok) {
+int zk_plonk_verify(int field, const uint8_t *roots_of_eleven, const uint64_t *public_inputs, uint32_t npublic, uint32_t d, uint32_t log_blowup, uint32_t log_final,
+                    uint32_t nqueries, uint32_t log_arity, uint32_t log_group, const uint64_t *coset, zk_transcript *t, const uint8_t *h_roots, const uint64_t *round_polys,
+                    const uint64_t *ys, const uint64_t *open_round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
+                    const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok) {
     if (grinding_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
-    if (!roots_of_six || !h_roots || !round_polys || !ys || !open_round_polys || !roots || !final_table || !query_values || !query_paths || !ok) return ZK_E_ARG;
+    if (!roots_of_eleven || !h_roots || !round_polys || !ys || !open_round_polys || !roots || !final_table || !query_values || !query_paths || !ok) return ZK_E_ARG;
     // every status before the transcript is touched: the opening's own on an empty replay; the replay and the opening's verifier run on a copy
     // that becomes the caller's transcript only with ZK_OK
     if (field_limbs64(field) < 0) return ZK_E_ARG;
-    ZK_TRY(zk_fri_ml_sizes_batch(kWiringOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, nullptr, nullptr, nullptr, nullptr, nullptr));
+    ZK_TRY(zk_fri_ml_sizes_batch(kPlonkOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, nullptr, nullptr, nullptr, nullptr, nullptr));
     if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
     if ((field != ZK_FR381 && field != ZK_BN254_FR) || d + log_blowup > two_adicity(field)) return ZK_E_RANGE;
-    uint8_t nine[32 * kWiringOpened];
-    memcpy(nine, roots_of_six, 32 * kWiringGiven);
-    memcpy(nine + 32 * kWiringGiven, h_roots, 32 * kWiringWires);
+    if (!public_shape_ok(public_inputs, npublic, d)) return ZK_E_ARG;
+    uint8_t all[32 * kPlonkOpened];
+    memcpy(all, roots_of_eleven, 32 * kPlonkGiven);
+    memcpy(all + 32 * kPlonkGiven, h_roots, 32 * kWiringWires);
     zk_transcript work;
     if (t) work.t = t->t;
     std::vector<uint64_t> z((size_t)d * 4);
     bool good = false;
-    FRI_DISPATCH(field, (wiring_replay<F>(work.t, roots_of_six, d, h_roots, round_polys, ys, z.data(), &good)));
+    FRI_DISPATCH(field, (plonk_replay<F>(work.t, roots_of_eleven, d, public_inputs, npublic, h_roots, round_polys, ys, z.data(), &good)));
     int open_ok = 0;
-    ZK_TRY(zk_fri_ml_verify_batch_pow(field, nine, kWiringOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, coset, z.data(), 1, ys, &work, open_round_polys,
+    ZK_TRY(zk_fri_ml_verify_batch_pow(field, all, kPlonkOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, coset, z.data(), 1, ys, &work, open_round_polys,
                                       roots, final_table, query_values, query_paths, grinding_bits, pow_nonce, &open_ok));
     if (t) t->t = work.t;
     *ok = good && open_ok ? 1 : 0;
     return ZK_OK;
 }
 
-int zk_wiring_last_stats(zk_wiring_stats *out) {
+int zk_plonk_last_stats(zk_plonk_stats *out) {
     if (!out) return ZK_E_ARG;
-    *out = g_wiring_stats;
+    *out = g_plonk_stats;
     return ZK_OK;
 }
 
