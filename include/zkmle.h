@@ -878,8 +878,9 @@ int zk_wiring_last_stats(zk_wiring_stats *out);
  *   writes of 32 bytes per lane that reach HBM, 6 more reads of entries the lane itself touched a phase earlier, and 110 products (round 0: 30 + 6
  *   reads, 80 products).  No committed table is written; E_0 and the two ping-pong halves of the folded fifteen are one block of the caching
  *   pool (32 bytes x 12.25 n).  The helper commitments are freed before the call returns.  One host synchronisation per round.
- * Not here: lookup arguments, more than three wire columns, custom gates, a circuit-builder API, any check that the S tables commit to a
- *   permutation, several rounds per pass, a sharded prover, pooled memory for the helper trees. */
+ * Not here: lookup arguments inside this sumcheck (a proof of its own on the same transcript: "Lookup: rows of a committed table" below), more
+ *   than three wire columns, custom gates, a circuit-builder API, any check that the S tables commit to a permutation, several rounds per
+ *   pass, a sharded prover, pooled memory for the helper trees. */
 /* one round pass on its own.  tables: A, B, C, qM, qL, qR, qO, qC, SA, SB, SC, H0, H1, H2, E.  The contract of zk_wiring_round with fifteen
  * tables: r = NULL: round 0's form, nothing is folded or allocated, len >= 2; r != NULL: outs[0 .. 14] = zk_mle_fold(X, last, r) of each (new
  * tables, len / 2), the sums over the folded fifteen, len >= 4; the id tables ID_j[x'] = j 2^d + id_base + 2^log_step x', d = log2 of the
@@ -911,6 +912,95 @@ int zk_plonk_verify(int field, const uint8_t *roots_of_eleven, const uint64_t *p
 /* the calling thread's last zk_plonk_prove: the fields of zk_wiring_stats */
 typedef zk_wiring_stats zk_plonk_stats;
 int zk_plonk_last_stats(zk_plonk_stats *out);
+
+/* ---- Lookup: rows of a committed table (extension; csrc/lookup.cuh, csrc/lookup_host.h, csrc/zkmle_lookup.hip) --------------------------------------
+ * A lookup argument beside the blocks above, a proof of its own on the caller's transcript: SEVEN commitments of one shape (one field, d,
+ * log_blowup, coset and log_group), in this order everywhere: the wires A, B, C, the lookup selector qK and the table columns T0, T1, T2.  With
+ * n = 2^d the statement:  for every row x with qK[x] = 1 there is a y with (A[x], B[x], C[x]) = (T0[y], T1[y], T2[y]).  qK and the T columns belong
+ * to the circuit, as the selectors and the S tables do: the verifier holds the seven roots and trusts that qK holds only 0 and 1.  A table shorter
+ * than n is padded by repeating a row; a table longer than the witness is not supported.
+ * The argument is the logarithmic-derivative one (logUp) with two helper commitments.  Transcript (t = NULL: a fresh Transcript::new()), plain appends:
+ *   1. 8 bytes in one append: the ASCII tag "ZCLK", then d as a big-endian u32; then the seven 32-byte roots in the order above, one append each;
+ *   2. the multiplicity table M: M[y] = the number of rows x with qK[x] equal to the field's one whose triple (A[x], B[x], C[x]) equals the table's
+ *      row y, credited to the SMALLEST y that holds that triple; every other index of a repeated row gets 0, and a row whose triple is nowhere in
+ *      the table is counted nowhere.  M is a function of the inputs (no challenge has been drawn yet).  It is committed with the shape of the
+ *      seven (zk_fri_commit, or zk_fri_commit_grouped by the inputs' log_group) and its 32-byte root is appended.  It is part of the proof;
+ *   3. beta, then gamma = two successive random_challenge_as_field_element();
+ *   4. the ONE helper table
+ *        H[x] = qK[x] inv0(Dw[x]) - M[x] inv0(Dt[x]),   Dw = beta + A + gamma B + gamma^2 C,   Dt = beta + T0 + gamma T1 + gamma^2 T2,
+ *      inv0(0) = 0 and inv0(a) = 1 / a otherwise (for that entry alone); committed with the shape of the seven, its 32-byte root appended.  It is
+ *      part of the proof;
+ *   5. mu, then tau_0 .. tau_{d-1} = 1 + d successive challenges;  E_0[x] = eq(x, tau), variable 0 the most significant index bit;
+ *   6. ONE sumcheck with the claimed sum 0 of
+ *        mu H(x) + E(x) ( H(x) Dw(x) Dt(x) - qK(x) Dt(x) + M(x) Dw(x) ):
+ *      the second part is the zerocheck that H is what step 4 says, the first the equality sum_x qK / Dw = sum_y M / Dt.  For l = 0 .. d - 1, with
+ *      X_{l+1} = zk_mle_fold(X_l, last, r_l) for the ten tables A, B, C, qK, T0, T1, T2, M, H, E (a round binds the LAST variable), the quartic
+ *      g_l(X) is sent as g_l(0) .. g_l(4) (each the 32-byte canonical big-endian element); then r_l = random_challenge_as_field_element().  There
+ *      is no alpha: there is one relation;
+ *   7. (nothing is appended) the point z with z[d - 1 - l] = r_l;
+ *   8. the whole protocol of zk_fri_ml_open_batch_pow on the transcript as step 6 left it: k = 9 in the order A, B, C, qK, T0, T1, T2, M, H,
+ *      npoints = 1, the point z, and the caller's log_final, nqueries, log_arity and grinding_bits.
+ * The prover does not check the statement: on a false one it returns ZK_OK and a proof the verifier rejects; the number of rows with qK = 1 whose
+ * triple is in no table row is in zk_lookup_last_stats' `misses`.
+ * Verifier (HOST only; it holds the seven roots, 224 bytes).  It replays steps 1 to 6 with the proof's two roots (M, then H) and checks
+ *   g_0(0) + g_0(1) = 0,  g_l(0) + g_l(1) = g_{l-1}(r_{l-1})  (the quartic through the five nodes), and
+ *   g_{d-1}(r_{d-1}) = mu yH + eq(z, tau) ( yH dw dt - yqK dt + yM dw ),   dw = beta + yA + gamma yB + gamma^2 yC,  dt = beta + yT0 + gamma yT1 + gamma^2 yT2;
+ *   then zk_fri_ml_verify_batch_pow on the nine claims.  *ok is the conjunction; anything unreduced gives *ok = 0.  Every status is decided
+ *   before the transcript is touched (zk_fri_ml_verify_batch_pow's, in its order); the replay runs on a copy and t ends in the prover's state
+ *   whenever the status is ZK_OK.
+ * Soundness, as a count and not a proof: the equality of the two sums of fractions as rational functions of beta needs the characteristic to
+ *   exceed the 2 n fractions (every multiplicity is at most n; both scalar fields: about 2^254 against d <= 31) and fails for a false statement
+ *   with probability about 2 n / p over beta; gamma adds 2 (2 n)^2 / p in the crudest count for two distinct triples among the 2 n meeting in one
+ *   combined value; the zerocheck adds d / p for tau, the sumcheck 4 d / p, mu 1 / p, and the opening its own error.
+ * Prover.  The multiplicities by a hash table of 2^(d+1) 32-bit slots holding table-row indices (open addressing, linear probing; three launches:
+ *   a lane per table row inserts by atomicCAS and lowers an equal row's slot by atomicMin, a lane per witness row probes and counts by atomicAdd,
+ *   and the counts become field elements); every probe loop is bounded by the capacity, and one that runs out gives ZK_E_HIP with
+ *   zk_last_error naming it.  Then the two denominators' columns into pool memory (lookup_denominators_kernel), lookup_fractions_kernel
+ *   (Montgomery's trick: one Fermat inversion for the sixteen denominators of a lane), the two commitments, E_0, then one pass per round
+ *   (lookup_round_kernel) that folds the ten tables and accumulates the quartic's zerocheck part at the nodes 0, 1, 2, 3 and infinity and the two
+ *   plain sums of H over the even and the odd entries; the host forms the message as the wiring's does.  40 reads and 20 writes of 32 bytes and
+ *   47 products per lane (round 0: 20 reads, 27 products).  No committed table is written; E_0 and the two ping-pong halves of the folded ten are
+ *   one block of the caching pool (32 bytes x 8.5 n); the hash table, the counts and the denominators come from the pool and go back to it.  The
+ *   two helper commitments are freed before the call returns.  One host synchronisation per round and one for the miss count.
+ * Not here: the lookup inside zk_plonk_prove's sumcheck and its one opening, a column count other than three, several tables or a table
+ *   selector, a table of another length than the witness, a sharded prover, and any check that qK is boolean. */
+/* the multiplicity table on its own.  tables: A, B, C, qK, T0, T1, T2 (len >= 2, at most 2^31: the counts are 32 bits); *M (a new table) as
+ * step 2 says, *misses = the number of rows with qK = 1 whose triple is in no table row.  Statuses and their order as zk_wiring_fractions. */
+int zk_lookup_multiplicities(const zk_table *const tables[7], zk_table **M, uint64_t *misses);
+/* the helper table on its own.  tables: A, B, C, qK, T0, T1, T2, M; *H (a new table) as step 4 says; len >= 2.  Statuses and their order as
+ * zk_wiring_fractions (beta and gamma reduced). */
+int zk_lookup_fractions(const zk_table *const tables[8], const uint64_t *beta, const uint64_t *gamma, zk_table **H);
+/* one round pass on its own.  tables: A, B, C, qK, T0, T1, T2, M, H, E.  r = NULL: round 0's form, nothing is folded or allocated, len >= 2.
+ * r != NULL: outs[0 .. 9] = zk_mle_fold(X, last, r) of each (new tables, len / 2), the sums over the folded ten; len >= 4.  g5 = g(0) .. g(4),
+ * the message as sent (mu's line included).  Statuses and their order as zk_wiring_round; the three elements and r reduced. */
+int zk_lookup_round(const zk_table *const tables[10], const uint64_t *beta, const uint64_t *gamma, const uint64_t *mu, const uint64_t *r, zk_table **outs,
+                    uint64_t *g5);
+/* host: nround = 5 d elements of round polynomials, nhroots = 2, then the five counts of zk_fri_ml_sizes_batch(9, ..); any pointer may be NULL */
+int zk_lookup_sizes(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group, size_t *nround, size_t *nhroots,
+                    size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nopen_round);
+/* cms[0 .. 6] = A, B, C, qK, T0, T1, T2.  h_roots: 64 bytes (M, then H); round_polys: 5 d elements; challenges: d elements (r_0 .. r_{d-1}; the
+ * point is their reverse); chal_out (3 + d elements: beta, gamma, mu, tau) is diagnostic and may be NULL; ys_out: 9 elements; from gamma_out on,
+ * the outputs of zk_fri_ml_open_batch_pow for k = 9 and one point, sized by zk_lookup_sizes.  Statuses: ZK_E_ARG (NULL, d > 31, commitments that
+ * differ in field, d, log_blowup, coset or log_group, and zk_fri_ml_open_batch_pow's own), all before ZK_E_NO_DEVICE and before the transcript
+ * moves. */
+int zk_lookup_prove(const zk_fri_commitment *const cms[7], uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t grinding_bits, zk_transcript *t,
+                    uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys, uint64_t *challenges, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *open_round_polys,
+                    uint8_t *roots, uint64_t *final_table, uint64_t *open_challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
+                    uint64_t *pow_nonce);
+/* HOST only.  roots_of_seven: the seven roots as the verifier holds them, 224 bytes; h_roots: the proof's two, 64 bytes; ys: the nine claims. */
+int zk_lookup_verify(int field, const uint8_t *roots_of_seven, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
+                     const uint64_t *coset, zk_transcript *t, const uint8_t *h_roots, const uint64_t *round_polys, const uint64_t *ys, const uint64_t *open_round_polys,
+                     const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce,
+                     int *ok);
+/* the calling thread's last zk_lookup_prove: the rows with qK = 1 whose triple is in no table row; HIP-event times of the multiplicity count,
+ * the helper table (denominators and fractions), the two commitments together, E_0's construction and the d rounds; ms_opening =
+ * zk_fri_ml_last_stats' ms_total of the opening; ms_total is the host clock over the call */
+typedef struct {
+    uint32_t rounds;
+    uint64_t misses;
+    float ms_multiplicities, ms_fractions, ms_commit, ms_eq, ms_rounds, ms_opening, ms_total;
+} zk_lookup_stats;
+int zk_lookup_last_stats(zk_lookup_stats *out);
 
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */

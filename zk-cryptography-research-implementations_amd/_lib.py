@@ -196,6 +196,15 @@ def lib():
         "zk_plonk_verify": [C.c_int, u8p, u64p] + [C.c_uint32] * 7 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
                                                                        C.POINTER(C.c_int)],
         "zk_plonk_last_stats": [vp],
+        # lookup: rows of a committed table
+        "zk_lookup_multiplicities": [C.POINTER(vp), C.POINTER(vp), u64p],
+        "zk_lookup_fractions": [C.POINTER(vp), u64p, u64p, C.POINTER(vp)],
+        "zk_lookup_round": [C.POINTER(vp), u64p, u64p, u64p, u64p, C.POINTER(vp), u64p],
+        "zk_lookup_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 7,
+        "zk_lookup_prove": [C.POINTER(vp)] + [C.c_uint32] * 4 + [vp, u8p, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
+        "zk_lookup_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
+                                                                C.POINTER(C.c_int)],
+        "zk_lookup_last_stats": [vp],
         "zk_sumcheck_basic_prove_succinct": [vp, C.c_uint32, C.c_uint32, vp, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_sumcheck_basic_verify_succinct": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, vp, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u8p,
                                                                                  C.POINTER(C.c_int)],

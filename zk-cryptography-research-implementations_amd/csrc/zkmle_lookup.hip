@@ -1,0 +1,380 @@
+// zkmle_lookup.hip -- C ABI of the lookup argument over FRI commitments (lookup.cuh, lookup_host.h): the multiplicity table, the helper table
+// and one round pass on their own, the prover (the multiplicities and their commitment, the helper table and its commitment, the sumcheck of
+// the logarithmic-derivative relation on the nine coefficient tables and E, then zk_fri_ml_open_batch_pow of the nine commitments at the
+// point the rounds leave, on the same transcript) and its host verifier.  Extension: the protocol is defined in include/zkmle.h "Lookup: rows
+// of a committed table".
+#include <string.h>
+
+#include <chrono>
+#include <vector>
+
+#include "eq_table.cuh"
+#include "fri_host.h"
+#include "lookup.cuh"
+#include "lookup_host.h"
+#include "wiring_driver.cuh"
+
+using namespace zk;
+using namespace zk::host;
+
+namespace {
+
+thread_local zk_lookup_stats g_lookup_stats{};
+
+constexpr int kTables = LOOKUP_TABLES;                       // A, B, C, qK, T0, T1, T2, M, H, E
+constexpr int kMaxLog = 31;                                  // the counts and the slots are 32 bits
+
+inline unsigned blocks_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
+// M (n elements, device) and the miss count from the seven tables A, B, C, qK, T0, T1, T2 of n <= 2^31 entries.  One synchronisation.
+template <class F> int multiplicities_into(const void *const *in, size_t n, void *M, uint64_t *misses) {
+    const size_t cap = 2 * n;
+    DevBuf slots, counts, status;
+    ZK_TRY(slots.alloc(cap * 4));
+    ZK_TRY(counts.alloc(n * 4));
+    ZK_TRY(status.alloc(sizeof(LookupStatus)));
+    ZK_HIP(hipMemsetAsync(slots.p, 0xFF, cap * 4, cur_stream()));
+    ZK_HIP(hipMemsetAsync(counts.p, 0, n * 4, cur_stream()));
+    ZK_HIP(hipMemsetAsync(status.p, 0, sizeof(LookupStatus), cur_stream()));
+    lookup_insert_kernel<F><<<blocks_for(n), kBlock, 0, cur_stream()>>>(in[4], in[5], in[6], n, (uint32_t *)slots.p, cap, (LookupStatus *)status.p);
+    ZK_HIP(hipGetLastError());
+    lookup_count_kernel<F><<<blocks_for(n), kBlock, 0, cur_stream()>>>(in[0], in[1], in[2], in[3], in[4], in[5], in[6], n, (const uint32_t *)slots.p, cap,
+                                                                      (uint32_t *)counts.p, (LookupStatus *)status.p);
+    ZK_HIP(hipGetLastError());
+    lookup_finish_kernel<F><<<blocks_for(n), kBlock, 0, cur_stream()>>>((const uint32_t *)counts.p, n, M);
+    ZK_HIP(hipGetLastError());
+    LookupStatus st{};
+    ZK_HIP(zk::memcpy_on_stream(&st, status.p, sizeof st, hipMemcpyDeviceToHost));
+    if (st.error) {
+        set_last_error("lookup multiplicities: a probe of the hash table ran through its whole capacity");
+        return ZK_E_HIP;
+    }
+    *misses = st.misses;
+    return ZK_OK;
+}
+
+// H (n elements, device) from the eight tables A, B, C, qK, T0, T1, T2, M.  Launches only; the two columns of denominators go back to the pool
+// when the call returns (stream-ordered: what reuses them runs after the kernels that read them)
+template <class F> int launch_fractions_lookup(const void *const *in, size_t n, void *H, const Fe<F> &beta, const Fe<F> &gamma) {
+    constexpr size_t ESZ = sizeof(Fe<F>);
+    DevBuf den;
+    ZK_TRY(den.alloc(2 * n * ESZ));
+    void *DW = den.p, *DT = (char *)den.p + n * ESZ;
+    lookup_denominators_kernel<F><<<blocks_for(n), kBlock, 0, cur_stream()>>>(in[0], in[1], in[2], in[4], in[5], in[6], DW, DT, n, beta, gamma, fe_mul<F>(gamma, gamma));
+    ZK_HIP(hipGetLastError());
+    const size_t per = (size_t)kLookupBatch * kPcsBlock;
+    lookup_fractions_kernel<F><<<(unsigned)((n + per - 1) / per), kPcsBlock, 0, cur_stream()>>>(DW, DT, in[3], in[7], H, n);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+
+// sums (device, 7 elements) of a pass over q pairs.  Launches only.
+template <class F> int launch_round(bool fold, const LookupTables &t, size_t q, const Fe<F> &r, const LookupChallenges<F> &ch, void *partials, void *sums) {
+    const int grid = reduce_grid_for(q);
+    LookupConsts<F> c;
+    c.beta = ch.beta;
+    c.gamma = ch.gamma;
+    c.gamma2 = fe_mul<F>(ch.gamma, ch.gamma);
+    if (fold) lookup_round_kernel<F, true><<<grid, kBlock, 0, cur_stream()>>>(t, q, r, c, partials);
+    else lookup_round_kernel<F, false><<<grid, kBlock, 0, cur_stream()>>>(t, q, r, c, partials);
+    ZK_HIP(hipGetLastError());
+    finish_sums_kernel<F><<<1, kBlock, 0, cur_stream()>>>(partials, (size_t)grid, kWiringSums, sums);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+
+template <class F> int multiplicities_once(const zk_table *const *in, zk_table **M, uint64_t *misses) {
+    zk_table *m = nullptr;
+    ZK_TRY(zk_table_alloc(in[0]->field, in[0]->len, &m));
+    const void *p[kLookupGiven];
+    for (int j = 0; j < kLookupGiven; j++) p[j] = in[j]->dptr;
+    uint64_t lost = 0;
+    const int rc = multiplicities_into<F>(p, in[0]->len, m->dptr, &lost);
+    if (rc != ZK_OK) { zk_table_free(m); return rc; }
+    *M = m;
+    *misses = lost;
+    return ZK_OK;
+}
+
+template <class F> int fractions_once(const zk_table *const *in, const uint64_t *beta, const uint64_t *gamma, zk_table **H) {
+    zk_table *h = nullptr;
+    ZK_TRY(zk_table_alloc(in[0]->field, in[0]->len, &h));
+    const void *p[kLookupGiven + 1];
+    for (int j = 0; j <= kLookupGiven; j++) p[j] = in[j]->dptr;
+    int rc = launch_fractions_lookup<F>(p, in[0]->len, h->dptr, load_host<F>(beta), load_host<F>(gamma));
+    if (rc == ZK_OK && hipStreamSynchronize(cur_stream()) != hipSuccess) rc = ZK_E_HIP;
+    if (rc != ZK_OK) { zk_table_free(h); return rc; }
+    *H = h;
+    return ZK_OK;
+}
+
+template <class F> int round_once(const zk_table *const *in, const LookupChallenges<F> &ch, const uint64_t *r, zk_table **outs, uint64_t *gout) {
+    constexpr size_t ESZ = sizeof(Fe<F>);
+    constexpr int W = F::N / 2;
+    const bool fold = r != nullptr;
+    const size_t len = in[0]->len, q = fold ? len / 4 : len / 2;
+    SumsBuf sb;
+    ZK_TRY(sb.alloc(ESZ));
+    zk_table *o[kTables] = {};
+    const auto drop = [&] { for (zk_table *t : o) zk_table_free(t); };
+    // the pass writes the folded ten into one block; the caller's new tables are copies of its tenths
+    DevBuf folded;
+    LookupTables t{};
+    for (int j = 0; j < kTables; j++) t.in[j] = in[j]->dptr;
+    if (fold) {
+        ZK_TRY(folded.alloc(kTables * (len / 2) * ESZ));
+        t.out0 = folded.p;
+        t.ostride = (len / 2) * ESZ;
+        for (int j = 0; j < kTables; j++) {
+            const int rc = zk_table_alloc(in[0]->field, len / 2, &o[j]);
+            if (rc != ZK_OK) { drop(); return rc; }
+        }
+    }
+    Fe<F> S[kWiringSums], g[kWiringNodes];
+    int rc = launch_round<F>(fold, t, q, fold ? load_host<F>(r) : fe_one<F>(), ch, sb.buf.p, sb.sums);
+    for (int j = 0; fold && rc == ZK_OK && j < kTables; j++)
+        if (hipMemcpyAsync(o[j]->dptr, (char *)folded.p + (size_t)j * t.ostride, t.ostride, hipMemcpyDeviceToDevice, cur_stream()) != hipSuccess) rc = ZK_E_HIP;
+    if (rc == ZK_OK && zk::memcpy_on_stream(S, sb.sums, kWiringSums * ESZ, hipMemcpyDeviceToHost) != hipSuccess) rc = ZK_E_HIP;
+    if (rc != ZK_OK) { drop(); return rc; }
+    wiring_message<F>(S, ch.mu, g);
+    for (int k = 0; k < kWiringNodes; k++) store_host<F>(gout + (size_t)k * W, g[k]);
+    for (int j = 0; fold && j < kTables; j++) outs[j] = o[j];
+    return ZK_OK;
+}
+
+int commit_like(const zk_fri_commitment *c0, const zk_table *t, zk_fri_commitment **out) {
+    const uint64_t *coset = c0->has_coset ? c0->coset : nullptr;
+    return c0->log_group ? zk_fri_commit_grouped(t, c0->b, coset, c0->log_group, out) : zk_fri_commit(t, c0->b, coset, out);
+}
+
+// steps 1 to 7 on `tr`: the statement, M and H with their commitments (hc.cm[0], hc.cm[1]; h_roots), E_0 and the d rounds; z (d elements) = the
+// point the opening is made at.  One host synchronisation per round and one for the miss count.
+template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcript &tr, CommitHolder &hc, uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys,
+                                    uint64_t *challenges, uint64_t *z, zk_lookup_stats &st) {
+    constexpr size_t ESZ = sizeof(Fe<F>);
+    constexpr int W = F::N / 2, T = kTables, K = kLookupOpened;
+    const zk_fri_commitment *c0 = cms[0];
+    const unsigned d = c0->d;
+    const size_t n = (size_t)1 << d;
+    uint8_t roots[32 * kLookupGiven];
+    const void *in[kLookupGiven + 1];
+    for (int j = 0; j < kLookupGiven; j++) {
+        memcpy(roots + 32 * j, cms[j]->root, 32);
+        in[j] = cms[j]->coeffs->dptr;
+    }
+    lookup_statement(tr, roots, d);
+    LookupChallenges<F> ch;
+
+    Events ev;
+    size_t e0, e1, e2, e3, e4, e5, e6;
+    ZK_TRY(ev.mark(&e0));
+    {
+        TableHolder th;
+        zk_table *M = nullptr, *H = nullptr;
+        ZK_TRY(th.alloc(c0->field, n, &M));
+        ZK_TRY(multiplicities_into<F>(in, n, M->dptr, &st.misses));
+        ZK_TRY(ev.mark(&e1));
+        ZK_TRY(commit_like(c0, M, &hc.cm[0]));
+        memcpy(h_roots, hc.cm[0]->root, 32);
+        ZK_TRY(ev.mark(&e2));
+        lookup_multiplicity_root<F>(tr, h_roots, ch);
+        in[kLookupGiven] = hc.cm[0]->coeffs->dptr;
+        ZK_TRY(th.alloc(c0->field, n, &H));
+        ZK_TRY(launch_fractions_lookup<F>(in, n, H->dptr, ch.beta, ch.gamma));
+        ZK_TRY(ev.mark(&e3));
+        ZK_TRY(commit_like(c0, H, &hc.cm[1]));
+        memcpy(h_roots + 32, hc.cm[1]->root, 32);
+        ZK_TRY(ev.mark(&e4));
+    }
+    lookup_helper_root<F>(tr, h_roots + 32, d, ch);
+    if (chal_out) {
+        store_host<F>(chal_out, ch.beta);
+        store_host<F>(chal_out + W, ch.gamma);
+        store_host<F>(chal_out + 2 * W, ch.mu);
+        memcpy(chal_out + 3 * W, ch.tau.data(), ch.tau.size() * 8);
+    }
+
+    // one block: E_0 (n elements), then the two ping-pong halves: the ten tables of an odd round (n / 2 entries each at round 1) and of an
+    // even one (n / 4 each at round 2); a round's tables never outgrow the half they first had
+    DevBuf blk;
+    SumsBuf sb;
+    ZK_TRY(blk.alloc((n + T * (n / 2) + T * (n / 4) + 1) * ESZ));
+    ZK_TRY(sb.alloc(ESZ));
+    char *E0 = (char *)blk.p, *half[2] = {E0 + n * ESZ, E0 + (n + T * (n / 2)) * ESZ};
+    const auto tables_at = [&](unsigned l, const void **out) {   // the nine tables and E at round l: n >> l entries each
+        for (int j = 0; j < T; j++) {
+            const void *own = j < kLookupGiven ? cms[j]->coeffs->dptr : j < K ? hc.cm[j - kLookupGiven]->coeffs->dptr : (void *)E0;
+            out[j] = l == 0 ? own : half[(l - 1) & 1] + (size_t)j * (n >> l) * ESZ;
+        }
+    };
+    EqBuilder<F> eqb;
+    ZK_TRY(eqb.build(ch.tau.data(), d, E0));
+    ZK_TRY(ev.mark(&e5));
+    Fe<F> r = fe_one<F>();
+    for (unsigned l = 0; l < d; l++) {
+        LookupTables t{};
+        if (l == 0) {
+            tables_at(0, t.in);
+        } else {
+            tables_at(l - 1, t.in);
+            t.out0 = half[(l - 1) & 1];
+            t.ostride = (n >> l) * ESZ;
+        }
+        ZK_TRY(launch_round<F>(l != 0, t, n >> (l + 1), r, ch, sb.buf.p, sb.sums));
+        Fe<F> S[kWiringSums], g[kWiringNodes];
+        ZK_HIP(zk::memcpy_on_stream(S, sb.sums, kWiringSums * ESZ, hipMemcpyDeviceToHost));   // the round's synchronisation
+        if (l == 0) eqb.release();
+        wiring_message<F>(S, ch.mu, g);
+        for (int k = 0; k < kWiringNodes; k++) {
+            store_host<F>(round_polys + ((size_t)l * kWiringNodes + k) * W, g[k]);
+            tr.append_be<F>(g[k]);
+        }
+        r = tr.random_challenge_as_field_element<F>();
+        store_host<F>(challenges + (size_t)l * W, r);
+        store_host<F>(z + (size_t)(d - 1 - l) * W, r);
+    }
+    ZK_TRY(ev.mark(&e6));
+    ZK_HIP(hipEventSynchronize(ev.ev[e6]));
+    st.rounds = d;
+    st.ms_multiplicities = ev.ms(e0, e1);
+    st.ms_fractions = ev.ms(e2, e3);
+    st.ms_commit = ev.ms(e1, e2) + ev.ms(e3, e4);
+    st.ms_eq = ev.ms(e4, e5);
+    st.ms_rounds = ev.ms(e5, e6);
+    return ZK_OK;
+}
+
+// what the three hooks check alike: `count` tables, none NULL, one of the two scalar fields, one length, a power of two of at least `least`
+int check_tables(const zk_table *const *tables, int count, size_t least) {
+    if (!tables) return ZK_E_ARG;
+    for (int j = 0; j < count; j++)
+        if (!tables[j]) return ZK_E_ARG;
+    const int field = tables[0]->field;
+    if (field != ZK_FR381 && field != ZK_BN254_FR) return ZK_E_ARG;
+    for (int j = 1; j < count; j++)
+        if (tables[j]->field != field) return ZK_E_ARG;
+    for (int j = 1; j < count; j++)
+        if (tables[j]->len != tables[0]->len) return ZK_E_LEN_MISMATCH;
+    if (!is_pow2(tables[0]->len)) return ZK_E_NOT_POW2;
+    if (tables[0]->len < least) return ZK_E_ARG;
+    return ZK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zk_lookup_multiplicities(const zk_table *const tables[7], zk_table **M, uint64_t *misses) {
+    if (!M || !misses) return ZK_E_ARG;
+    ZK_TRY(check_tables(tables, kLookupGiven, 2));
+    if (tables[0]->len > ((size_t)1 << kMaxLog)) return ZK_E_ARG;
+    ZK_TRY(require_device());
+    FRI_DISPATCH(tables[0]->field, return multiplicities_once<F>(tables, M, misses));
+    return ZK_OK;
+}
+
+int zk_lookup_fractions(const zk_table *const tables[8], const uint64_t *beta, const uint64_t *gamma, zk_table **H) {
+    if (!beta || !gamma || !H) return ZK_E_ARG;
+    ZK_TRY(check_tables(tables, kLookupGiven + 1, 2));
+    if (!all_reduced(tables[0]->field, beta, 1) || !all_reduced(tables[0]->field, gamma, 1)) return ZK_E_ARG;
+    ZK_TRY(require_device());
+    FRI_DISPATCH(tables[0]->field, return fractions_once<F>(tables, beta, gamma, H));
+    return ZK_OK;
+}
+
+int zk_lookup_round(const zk_table *const tables[10], const uint64_t *beta, const uint64_t *gamma, const uint64_t *mu, const uint64_t *r, zk_table **outs, uint64_t *g5) {
+    if (!tables) return ZK_E_ARG;
+    for (int j = 0; j < kTables; j++)
+        if (!tables[j]) return ZK_E_ARG;
+    if (!beta || !gamma || !mu || !g5 || (r && !outs)) return ZK_E_ARG;
+    ZK_TRY(check_tables(tables, kTables, r ? 4 : 2));
+    const int field = tables[0]->field;
+    if (r && !all_reduced(field, r, 1)) return ZK_E_ARG;
+    for (const uint64_t *e : {beta, gamma, mu})
+        if (!all_reduced(field, e, 1)) return ZK_E_ARG;
+    ZK_TRY(require_device());
+    FRI_DISPATCH(field, {
+        LookupChallenges<F> ch;
+        ch.beta = load_host<F>(beta);
+        ch.gamma = load_host<F>(gamma);
+        ch.mu = load_host<F>(mu);
+        return round_once<F>(tables, ch, r, outs, g5);
+    });
+    return ZK_OK;
+}
+
+int zk_lookup_sizes(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group, size_t *nround, size_t *nhroots,
+                    size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nopen_round) {
+    ZK_TRY(zk_fri_ml_sizes_batch(kLookupOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, nroots, nfinal, nvalues, path_bytes, nopen_round));
+    if (nround) *nround = (size_t)kWiringNodes * d;
+    if (nhroots) *nhroots = kLookupHelpers;
+    return ZK_OK;
+}
+
+int zk_lookup_prove(const zk_fri_commitment *const cms[7], uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t grinding_bits, zk_transcript *t,
+                    uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys, uint64_t *challenges, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *open_round_polys,
+                    uint8_t *roots, uint64_t *final_table, uint64_t *open_challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
+                    uint64_t *pow_nonce) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!cms) return ZK_E_ARG;
+    for (int j = 0; j < kLookupGiven; j++)
+        if (!cms[j]) return ZK_E_ARG;
+    if (!h_roots || !round_polys || !challenges) return ZK_E_ARG;
+    if (cms[0]->d < 1 || cms[0]->d > kMaxLog) return ZK_E_ARG;   // what sizes the point below, and the 32-bit counts; no commitment is made outside it
+    // the point and the helper commitments do not exist yet: the opener's statuses are taken on the seven and a stand-in of zeros, before the
+    // transcript moves (the helpers get the shape of the seven, and nine is within the opener's count)
+    std::vector<uint64_t> z((size_t)cms[0]->d * 4, 0);
+    ZK_TRY(fri_ml_open_batch_check(cms, kLookupGiven, z.data(), 1, log_final, nqueries, log_arity, ys_out, open_round_polys, roots, final_table, query_values, query_paths,
+                                   grinding_bits, pow_nonce));
+    zk_transcript own;
+    zk_transcript *tt = t ? t : &own;
+    zk_lookup_stats st{};
+    CommitHolder hc;
+    FRI_DISPATCH(cms[0]->field, ZK_TRY((prove_rounds<F>(cms, tt->t, hc, h_roots, chal_out, round_polys, challenges, z.data(), st))));
+    const zk_fri_commitment *all[kLookupOpened];
+    for (int j = 0; j < kLookupOpened; j++) all[j] = j < kLookupGiven ? cms[j] : hc.cm[j - kLookupGiven];
+    ZK_TRY(zk_fri_ml_open_batch_pow(all, kLookupOpened, z.data(), 1, log_final, nqueries, log_arity, tt, ys_out, gamma_out, open_round_polys, roots, final_table,
+                                    open_challenges, query_indices, query_values, query_paths, grinding_bits, pow_nonce));
+    zk_fri_ml_stats ml{};
+    (void)zk_fri_ml_last_stats(&ml);
+    st.ms_opening = ml.ms_total;
+    st.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    g_lookup_stats = st;
+    return ZK_OK;
+}
+
+int zk_lookup_verify(int field, const uint8_t *roots_of_seven, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
+                     const uint64_t *coset, zk_transcript *t, const uint8_t *h_roots, const uint64_t *round_polys, const uint64_t *ys, const uint64_t *open_round_polys,
+                     const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce,
+                     int *ok) {
+    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
+    if (!roots_of_seven || !h_roots || !round_polys || !ys || !open_round_polys || !roots || !final_table || !query_values || !query_paths || !ok) return ZK_E_ARG;
+    // every status before the transcript is touched: the opening's own on an empty replay; the replay and the opening's verifier run on a copy
+    // that becomes the caller's transcript only with ZK_OK
+    if (field_limbs64(field) < 0) return ZK_E_ARG;
+    ZK_TRY(zk_fri_ml_sizes_batch(kLookupOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, nullptr, nullptr, nullptr, nullptr, nullptr));
+    if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
+    if ((field != ZK_FR381 && field != ZK_BN254_FR) || d + log_blowup > two_adicity(field)) return ZK_E_RANGE;
+    uint8_t nine[32 * kLookupOpened];
+    memcpy(nine, roots_of_seven, 32 * kLookupGiven);
+    memcpy(nine + 32 * kLookupGiven, h_roots, 32 * kLookupHelpers);
+    zk_transcript work;
+    if (t) work.t = t->t;
+    std::vector<uint64_t> z((size_t)d * 4);
+    bool good = false;
+    FRI_DISPATCH(field, (lookup_replay<F>(work.t, roots_of_seven, d, h_roots, round_polys, ys, z.data(), &good)));
+    int open_ok = 0;
+    ZK_TRY(zk_fri_ml_verify_batch_pow(field, nine, kLookupOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, coset, z.data(), 1, ys, &work, open_round_polys,
+                                      roots, final_table, query_values, query_paths, grinding_bits, pow_nonce, &open_ok));
+    if (t) t->t = work.t;
+    *ok = good && open_ok ? 1 : 0;
+    return ZK_OK;
+}
+
+int zk_lookup_last_stats(zk_lookup_stats *out) {
+    if (!out) return ZK_E_ARG;
+    *out = g_lookup_stats;
+    return ZK_OK;
+}
+
+}  // extern "C"
