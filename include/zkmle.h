@@ -656,6 +656,36 @@ int zk_fri_ml_verify_batch_pow(int field, const uint8_t *roots_of_f, uint32_t k,
                                const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits,
                                uint64_t pow_nonce, int *ok);
 
+/* ---- FRI commitments opened together, wide: up to 32 (extension; csrc/fri_ml.cuh fri_ml_fold_batch_wide_kernel, csrc/zkmle_fri_ml.hip) ------------
+ * The protocol of "FRI commitments opened together" with the proof-of-work step of "Proof-of-work grinding", byte for byte, for
+ * 1 <= k <= ZK_FRI_ML_WIDE_MAX.  Nothing in that transcript or its layout depends on the cap: the "BTCH" line carries k as a u32, the roots, the
+ * claims and a query's step-0 answers are k of a kind.  So for k <= ZK_FRI_ML_BATCH_MAX each function below gives exactly the bytes, the
+ * statuses and the launches of its narrow counterpart (the same instantiation of fri_ml_fold_batch_kernel), and for 17 <= k <= 32 it gives
+ * what that protocol defines there.  k outside 1 .. 32 is ZK_E_ARG, where the narrow functions refuse k outside 1 .. 16.  The narrow
+ * functions keep their cap: a caller who relied on the refusal of k = 17 still gets it.
+ *   Prover.  The first step's fold takes a second argument block of 32 pointers and 32 coefficients (1284 bytes of kernel arguments) and a
+ *     second set of instantiations, launched only when k > 16; one reduction per entry still covers the 32 terms.  Everything else is the
+ *     narrow driver with its host arrays sized for 32.
+ *   Verifier (HOST only).  fri_verify_core with the cap as a parameter. */
+#define ZK_FRI_ML_WIDE_MAX 32
+/* zk_fri_ml_fold_batch for k <= 32: the arguments, the statuses and the result of the narrow hook */
+int zk_fri_ml_fold_batch_wide(const zk_table *const *codewords, uint32_t k, const uint64_t *coeffs, const uint64_t *r0, const uint64_t *r1,
+                              const uint64_t *coset, zk_table **out);
+/* host: zk_fri_ml_sizes_batch for k <= 32 */
+int zk_fri_ml_sizes_batch_wide(uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                               uint32_t log_group, size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround);
+/* zk_fri_ml_open_batch_pow for k <= 32, sized by zk_fri_ml_sizes_batch_wide */
+int zk_fri_ml_open_batch_wide_pow(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final,
+                                  uint32_t nqueries, uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out,
+                                  uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices,
+                                  uint64_t *query_values, uint8_t *query_paths, uint32_t grinding_bits, uint64_t *pow_nonce);
+/* HOST only: zk_fri_ml_verify_batch_pow for k <= 32 */
+int zk_fri_ml_verify_batch_wide_pow(int field, const uint8_t *roots_of_f, uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final,
+                                    uint32_t nqueries, uint32_t log_arity, uint32_t log_group, const uint64_t *coset, const uint64_t *points,
+                                    uint32_t npoints, const uint64_t *ys, zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots,
+                                    const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths,
+                                    uint32_t grinding_bits, uint64_t pow_nonce, int *ok);
+
 /* ---- Zerocheck of a product of committed tables (extension; csrc/zerocheck.cuh, csrc/zerocheck_host.h, csrc/zkmle_zerocheck.hip) --------------------
  * The simplest non-linear statement over the commitment above: three commitments cmA, cmB, cmC (zk_fri_commit / zk_fri_commit_grouped; one
  * field, d, log_blowup, coset and log_group) whose tables, read as evaluations over the cube {0,1}^d, satisfy  A[x] B[x] - C[x] = 0  for all x.
@@ -1001,6 +1031,81 @@ typedef struct {
     float ms_multiplicities, ms_fractions, ms_commit, ms_eq, ms_rounds, ms_opening, ms_total;
 } zk_lookup_stats;
 int zk_lookup_last_stats(zk_lookup_stats *out);
+
+/* ---- Plonk with lookups: gate, wiring, public inputs and lookup rows in one sumcheck (extension; csrc/plonk_lookup.cuh, csrc/plonk_lookup_host.h,
+ *      csrc/zkmle_plonk_lookup.hip) ------------------------------------------------------------------------------------------------------------------
+ * zk_plonk_prove and zk_lookup_prove as ONE proof: one sumcheck, one point, one opening.  FIFTEEN commitments of one shape (field, d <= 31,
+ * log_blowup, coset, log_group), in this order everywhere: A, B, C, qM, qL, qR, qO, qC, SA, SB, SC, qK, T0, T1, T2, and l <= 2^d public values.
+ *   Statement.  That of "Plonk: gate, wiring and public inputs in one sumcheck" on the first eleven (the gate with the public inputs on the
+ *     first l rows, and the wiring), and that of "Lookup: rows of a committed table" on A, B, C, qK, T0, T1, T2 (every row with qK = 1 is a
+ *     row of the table).
+ *   Transcript (t = NULL: a fresh Transcript::new()), plain appends in this order:
+ *     1. 12 bytes in one append: the ASCII tag "ZCPL", then d, then l, each a big-endian u32;
+ *     2. the fifteen roots, one append each;
+ *     3. the l public values, each the 32-byte canonical big-endian element;
+ *     4. the table M exactly as step 2 of the lookup (the same three kernels on A, B, C, qK, T0, T1, T2, a repeated table row credited at
+ *        its smallest index), committed with the shape of the fifteen; its root;
+ *     5. beta, then gamma: ONE pair, used by the wiring and by the lookup;
+ *     6. the four helper tables with that beta and gamma: H0, H1, H2 exactly as the wiring's (wiring_fractions_kernel), HL exactly as the
+ *        lookup's H (lookup_denominators_kernel, lookup_fractions_kernel); each is committed; the roots in the order H0, H1, H2, HL.  The
+ *        proof's h_roots are M, H0, H1, H2, HL: 160 bytes;
+ *     7. alpha, mu, tau_0 .. tau_{d-1}; E = eq(., tau);
+ *     8. ONE sumcheck, d rounds that bind the LAST variable, each a quartic sent at the nodes 0 .. 4 and followed by its challenge, of
+ *            mu (H0 + H1 + H2)(x) + mu^2 HL(x)
+ *              + E(x) [ sum_{j<3} alpha^j ( H_j Did_j Dsig_j - gamma (S_j - id_j) )(x)
+ *                       + alpha^3 (qM A B + qL A + qR B + qO C + qC)(x)
+ *                       + alpha^4 ( HL Dw Dt - qK Dt + M Dw )(x) ]
+ *        with Did_j, Dsig_j and the implicit id tables as in the wiring, Dw = beta + A + gamma B + gamma^2 C and
+ *        Dt = beta + T0 + gamma T1 + gamma^2 T2.  The claimed sum is alpha^3 PIeval(tau) (zk_plonk_public_eval);
+ *     9. the point z, z[d - 1 - l] = r_l;
+ *    10. the whole protocol of zk_fri_ml_open_batch_wide_pow on the transcript as step 8 left it: k = 20 in the order of the fifteen, then M, H0,
+ *        H1, H2, HL, npoints = 1, the point z.
+ *   Soundness, as a count and not a proof.  Both arguments' counts hold unchanged because beta and gamma are drawn after EVERY
+ *     witness-dependent commitment that either argument needs before them: the wiring (7n's count) needs A, B, C, SA, SB, SC fixed, the lookup
+ *     (7p's count) needs A, B, C, qK, T0, T1, T2 and M fixed; here the fifteen and M all precede the pair.  The helpers H0, H1, H2, HL depend on
+ *     beta and gamma in both originals too and precede alpha, mu and tau, as there.  The three zerochecks share E and are separated by powers of
+ *     alpha (alpha^0 .. alpha^2 the wires, alpha^3 the gate, alpha^4 the lookup): one more power than 7o, so the batching term of the count is
+ *     4 / p where 7o has 3 / p.  The two plain sums are separated by mu and mu^2: 2 / p where each original has 1 / p.  The rounds are d
+ *     quartics as in both.  Nothing here is proved; DESIGN.md 7q repeats the count.
+ *   Verifier (HOST only).  It replays steps 1 to 9 on a copy of the transcript, checks g_0(0) + g_0(1) = alpha^3 PIeval(tau),
+ *     g_l(0) + g_l(1) = g_{l-1}(r_{l-1}) and, on the twenty claims with eq = eq(z, tau),
+ *         g_{d-1}(r_{d-1}) = [the wiring's relation] + eq alpha^3 [the gate's relation] + eq alpha^4 (yHL dw dt - yqK dt + yM dw) + mu^2 yHL,
+ *     then zk_fri_ml_verify_batch_wide_pow on the twenty claims.  *ok is the conjunction; anything unreduced -- a public value >= p among it --
+ *     gives *ok = 0 with the status ZK_OK.  Every status is decided before the transcript is touched (zk_fri_ml_verify_batch_wide_pow's, in
+ *     its order, then d > 31 and the public inputs' shape); t ends in the prover's state whenever the status is ZK_OK.
+ *   Prover.  It does not check the statement: a false one gives ZK_OK, the rows with qK = 1 that are in no table row in the stats' `misses`,
+ *     and a proof the verifier rejects.  The five helper commitments are freed before it returns; no committed table is written.  The
+ *     rounds are one pass each (plonk_lookup_round_kernel: plonk_round_kernel with a fifth phase) over twenty-one tables folded into ONE pool
+ *     block with E_0, 32 bytes x 16.75 n.
+ * Not here: a column count other than three, several tables or a table selector, a table longer than the witness, a check that qK is boolean
+ * or that the S tables commit to a permutation, more than three wires, custom gates, several rounds per pass, a sharded prover. */
+/* one round pass on its own, for tests and measurements: zk_plonk_round's contract with the twenty-one tables A, B, C, qM, qL, qR, qO, qC, SA,
+ * SB, SC, qK, T0, T1, T2, M, H0, H1, H2, HL, E.  r = NULL: g5 = the message of round 0's form on the tables as they are; otherwise the tables
+ * folded by r in their last variable come back in outs (21 new tables) and g5 is the message on the folded ones.  The id tables are
+ * id_base + 2^log_step x + j 2^(log2 of the tables a message is taken over + log_step). */
+int zk_plonk_lookup_round(const zk_table *const tables[21], const uint64_t *beta, const uint64_t *gamma, const uint64_t *alpha, const uint64_t *mu,
+                          const uint64_t *id_base, uint32_t log_step, const uint64_t *r, zk_table **outs, uint64_t *g5);
+/* host: nround = 5 d, nhroots = 5, and zk_fri_ml_sizes_batch_wide's counts for k = 20 */
+int zk_plonk_lookup_sizes(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group, size_t *nround,
+                          size_t *nhroots, size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nopen_round);
+/* h_roots: 160 bytes (M, H0, H1, H2, HL); chal_out (may be NULL): beta, gamma, alpha, mu, tau: 4 + d elements, diagnostic; round_polys: 5 d
+ * elements; challenges: d; ys_out: 20 elements; from gamma_out on, the outputs of zk_fri_ml_open_batch_wide_pow for k = 20 and one point, sized
+ * by zk_plonk_lookup_sizes.  ZK_E_ARG, with nothing written and the transcript as it was: what zk_plonk_prove refuses, in each of the fifteen
+ * places and for the public inputs, and d > 31; all before ZK_E_NO_DEVICE. */
+int zk_plonk_lookup_prove(const zk_fri_commitment *const cms[15], const uint64_t *public_inputs, uint32_t npublic, uint32_t log_final, uint32_t nqueries,
+                          uint32_t log_arity, uint32_t grinding_bits, zk_transcript *t, uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys,
+                          uint64_t *challenges, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *open_round_polys, uint8_t *roots, uint64_t *final_table,
+                          uint64_t *open_challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths, uint64_t *pow_nonce);
+/* HOST only.  roots_of_fifteen: 480 bytes in the order above; the rest as zk_plonk_verify with twenty claims and five helper roots */
+int zk_plonk_lookup_verify(int field, const uint8_t *roots_of_fifteen, const uint64_t *public_inputs, uint32_t npublic, uint32_t d, uint32_t log_blowup,
+                           uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group, const uint64_t *coset, zk_transcript *t,
+                           const uint8_t *h_roots, const uint64_t *round_polys, const uint64_t *ys, const uint64_t *open_round_polys, const uint8_t *roots,
+                           const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits,
+                           uint64_t pow_nonce, int *ok);
+/* the calling thread's last zk_plonk_lookup_prove: the fields of zk_lookup_stats; ms_fractions covers all four helper tables, ms_commit the
+ * five commitments together */
+typedef zk_lookup_stats zk_plonk_lookup_stats;
+int zk_plonk_lookup_last_stats(zk_plonk_lookup_stats *out);
 
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */

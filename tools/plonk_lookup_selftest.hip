@@ -1,0 +1,217 @@
+// plonk_lookup_selftest.hip -- the host verifier of the Plonk proof with lookup rows (zk_plonk_lookup_verify: csrc/plonk_lookup_host.h's replay and the
+// wide opening's verifier behind it) as a stand-alone HOST program, for a sanitizer build.  It opens no device and launches nothing; the verifier
+// reaches into most of the library's translation units, so they are all compiled with the host side instrumented and linked in:
+//   for f in zk-cryptography-research-implementations_amd/csrc/*.hip tools/plonk_lookup_selftest.hip; do
+//       hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Wno-pass-failed -c $f -o build/$(basename $f .hip).o; done
+//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined build/*.o -o plonk_lookup_selftest
+//   ./plonk_lookup_selftest tests/golden/plonk_lookup_proof.bin
+// The fixture is one small valid proof written by the Python model (tests/golden/make_plonk_lookup_fixture.py: magic "ZKFX", the layout of
+// tests/golden/plonk_proof.bin with fifteen roots, five helper roots and twenty claims).  Every array is copied into a heap block of exactly
+// its size, so a read past an end is the sanitizer's to report.  Checked, as tools/plonk_selftest.hip checks for the proof without lookups: the
+// proof verifies, on a fresh transcript and with coset = NULL refused as another statement; every array (the five helper roots among them) with
+// one byte changed (first, middle, last) is rejected with ZK_OK, the public values among them; one public value fewer, one more (a zero) and
+// an unreduced one are rejected with ZK_OK, more values than rows and no array with npublic > 0 with ZK_E_ARG; the proof shown with one query
+// fewer, with d - 1, with d + 1, with log_final + 1 and with log_arity 1, its arrays cut to exactly the counts zk_plonk_lookup_sizes gives for
+// those parameters, is rejected without a read past any end; a nonce off by one is rejected; the statuses that precede the transcript leave a
+// caller's transcript as it was.  Exit status 0 = every check held.
+#include <stdio.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../include/zkmle.h"
+
+static int failures = 0;
+#define CHECK(cond)                                                          \
+    do {                                                                     \
+        if (!(cond)) {                                                       \
+            fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);       \
+            failures++;                                                      \
+        }                                                                    \
+    } while (0)
+
+enum { OWN, PUB, HROOTS, POLYS, YS, OPEN_POLYS, ROOTS, FINAL, VALUES, PATHS, NARR };
+
+struct Proof {
+    uint32_t field, d, b, f, Q, a, lg, g;
+    uint64_t nonce, coset[4];
+    std::vector<uint8_t> arr[NARR];
+};
+
+// a heap copy of exactly `n` bytes (at least one, so that the pointer is never NULL)
+struct Exact {
+    uint8_t *p;
+    Exact(const std::vector<uint8_t> &v, size_t n) : p(new uint8_t[n ? n : 1]) { memcpy(p, v.data(), n < v.size() ? n : v.size()); }
+    ~Exact() { delete[] p; }
+    Exact(const Exact &) = delete;
+};
+
+static bool read_fixture(const char *path, Proof &pr) {
+    FILE *fh = fopen(path, "rb");
+    if (!fh) return false;
+    char magic[4];
+    uint32_t head[8];
+    bool ok = fread(magic, 1, 4, fh) == 4 && memcmp(magic, "ZKFX", 4) == 0 && fread(head, 4, 8, fh) == 8 &&
+              fread(&pr.nonce, 8, 1, fh) == 1 && fread(pr.coset, 8, 4, fh) == 4;
+    if (ok) {
+        pr.field = head[0]; pr.d = head[1]; pr.b = head[2]; pr.f = head[3]; pr.Q = head[4]; pr.a = head[5]; pr.lg = head[6]; pr.g = head[7];
+    }
+    for (int k = 0; ok && k < NARR; k++) {
+        uint64_t n = 0;
+        ok = fread(&n, 8, 1, fh) == 1 && n < (1u << 24);
+        if (!ok) break;
+        pr.arr[k].resize(n);
+        ok = fread(pr.arr[k].data(), 1, n, fh) == n;
+    }
+    ok = ok && fgetc(fh) == EOF;
+    fclose(fh);
+    return ok;
+}
+
+// the byte counts of the ten arrays (fifteen roots, twenty claims) for the given parameters; false when zk_plonk_lookup_sizes refuses them
+static bool counts(uint32_t d, uint32_t b, uint32_t f, uint32_t Q, uint32_t a, uint32_t lg, size_t npublic, size_t out[NARR]) {
+    size_t nzc, nh, nroots, nfinal, nvalues, pbytes, nround;
+    if (zk_plonk_lookup_sizes(d, b, f, Q, a, lg, &nzc, &nh, &nroots, &nfinal, &nvalues, &pbytes, &nround) != ZK_OK) return false;
+    out[OWN] = 480; out[PUB] = npublic * 32; out[HROOTS] = nh * 32; out[YS] = 640; out[POLYS] = nzc * 32; out[OPEN_POLYS] = nround * 32; out[ROOTS] = nroots * 32; out[FINAL] = nfinal * 32;
+    out[VALUES] = nvalues * 32; out[PATHS] = pbytes;
+    return true;
+}
+
+// zk_plonk_lookup_verify on exact-size copies of pr's arrays, cut or zero-extended to the counts of the parameters shown; the public values as they are
+static int verify(const Proof &pr, zk_transcript *t, int *ok, bool with_coset = true, bool null_public = false) {
+    size_t n[NARR];
+    if (!counts(pr.d, pr.b, pr.f, pr.Q, pr.a, pr.lg, pr.arr[PUB].size() / 32, n)) return ZK_E_ARG;
+    std::vector<uint8_t> grown[NARR];
+    for (int k = 0; k < NARR; k++) {
+        grown[k] = pr.arr[k];
+        grown[k].resize(n[k], 0);
+    }
+    Exact own(grown[OWN], n[OWN]), pub(grown[PUB], n[PUB]), hr(grown[HROOTS], n[HROOTS]), polys(grown[POLYS], n[POLYS]), ys(grown[YS], n[YS]), opolys(grown[OPEN_POLYS], n[OPEN_POLYS]),
+        roots(grown[ROOTS], n[ROOTS]), fin(grown[FINAL], n[FINAL]), vals(grown[VALUES], n[VALUES]), paths(grown[PATHS], n[PATHS]);
+    return zk_plonk_lookup_verify((int)pr.field, own.p, null_public ? nullptr : (const uint64_t *)pub.p, (uint32_t)(n[PUB] / 32), pr.d, pr.b, pr.f, pr.Q, pr.a, pr.lg, with_coset ? pr.coset : nullptr, t, hr.p, (const uint64_t *)polys.p,
+                            (const uint64_t *)ys.p, (const uint64_t *)opolys.p, roots.p, (const uint64_t *)fin.p, (const uint64_t *)vals.p, paths.p, pr.g, pr.nonce, ok);
+}
+
+int main(int argc, char **argv) {
+    Proof pr;
+    if (argc < 2 || !read_fixture(argv[1], pr)) {
+        fprintf(stderr, "usage: plonk_lookup_selftest tests/golden/plonk_lookup_proof.bin\n");
+        return 2;
+    }
+    size_t n[NARR];
+    CHECK(pr.arr[PUB].size() % 32 == 0 && pr.arr[PUB].size() >= 64);
+    CHECK(counts(pr.d, pr.b, pr.f, pr.Q, pr.a, pr.lg, pr.arr[PUB].size() / 32, n));
+    for (int k = 0; k < NARR; k++) CHECK(pr.arr[k].size() == n[k]);
+    int ok = -1;
+    CHECK(verify(pr, nullptr, &ok) == ZK_OK && ok == 1);
+    ok = -1;
+    CHECK(verify(pr, nullptr, &ok, false) == ZK_OK && ok == 0);
+
+    // one byte changed
+    for (int k = 0; k < NARR; k++) {
+        const size_t len = pr.arr[k].size();
+        for (size_t at : {(size_t)0, len / 2, len - 1}) {
+            Proof bad = pr;
+            bad.arr[k][at] ^= 0x10;
+            ok = -1;
+            CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        }
+    }
+    // the public values: another count, an unreduced value, and the refusals
+    {
+        const size_t l = pr.arr[PUB].size() / 32;
+        Proof bad = pr;
+        bad.arr[PUB].resize(32 * (l - 1));
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        bad = pr;
+        bad.arr[PUB].resize(32 * (l + 1), 0);
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        bad = pr;
+        memset(bad.arr[PUB].data() + 32 * (l - 1), 0xFF, 32);
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        bad = pr;
+        bad.arr[PUB].resize(32 * (((size_t)1 << pr.d) + 1), 0);
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_E_ARG && ok == -1);
+        CHECK(verify(pr, nullptr, &ok, true, true) == ZK_E_ARG && ok == -1);
+        // zk_plonk_public_eval on exact-size copies: tau = the bits of row x picks pi_x, or 0 past the end
+        for (size_t x = 0; x <= l && x < ((size_t)1 << pr.d); x++) {
+            std::vector<uint8_t> tau(32 * pr.d, 0), one(32, 0);
+            uint64_t out[4] = {7, 7, 7, 7}, c1[4] = {1, 0, 0, 0};
+            CHECK(zk_vec_from_canonical((int)pr.field, c1, 1, (uint64_t *)one.data()) == ZK_OK);
+            for (uint32_t i = 0; i < pr.d; i++)
+                if ((x >> (pr.d - 1 - i)) & 1) memcpy(tau.data() + 32 * i, one.data(), 32);
+            Exact pub(pr.arr[PUB], pr.arr[PUB].size()), te(tau, tau.size());
+            CHECK(zk_plonk_public_eval((int)pr.field, (const uint64_t *)pub.p, (uint32_t)l, (const uint64_t *)te.p, pr.d, out) == ZK_OK);
+            const uint64_t zero[4] = {0, 0, 0, 0};
+            CHECK(memcmp(out, x < l ? (const void *)(pr.arr[PUB].data() + 32 * x) : (const void *)zero, 32) == 0);
+        }
+    }
+    // cut to another statement's counts
+    {
+        Proof cut = pr;
+        cut.Q = pr.Q - 1;
+        ok = -1;
+        CHECK(verify(cut, nullptr, &ok) == ZK_OK && ok == 0);
+        cut = pr;
+        cut.d = pr.d - 1;
+        ok = -1;
+        CHECK(verify(cut, nullptr, &ok) == ZK_OK && ok == 0);
+        cut = pr;
+        cut.f = pr.f + 1;
+        ok = -1;
+        CHECK(verify(cut, nullptr, &ok) == ZK_OK && ok == 0);
+        cut = pr;
+        cut.a = 1;
+        cut.lg = 0;
+        ok = -1;
+        CHECK(verify(cut, nullptr, &ok) == ZK_OK && ok == 0);
+        cut = pr;
+        cut.d = pr.d + 1;                                     // grown with zeros
+        ok = -1;
+        CHECK(verify(cut, nullptr, &ok) == ZK_OK && ok == 0);
+    }
+    // the proof of work
+    {
+        Proof bad = pr;
+        bad.nonce = pr.nonce + 1;
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        bad = pr;
+        bad.g = pr.g + 1;
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+    }
+    // a caller's transcript: the statuses leave it alone, ZK_OK moves it, and the proof is bound to what it held
+    {
+        zk_transcript *t = nullptr;
+        CHECK(zk_transcript_new(&t) == ZK_OK);
+        const uint8_t prior[] = "the caller's own";
+        CHECK(zk_transcript_append(t, prior, sizeof prior) == ZK_OK);
+        uint64_t before[25], after[25];
+        uint32_t fb = 0, fa = 0;
+        CHECK(zk_transcript_export_state(t, before, &fb) == ZK_OK);
+        Proof bad = pr;
+        bad.field = 1;
+        ok = -1;
+        CHECK(verify(bad, t, &ok, false) == ZK_E_RANGE && ok == -1);
+        bad = pr;
+        memset(bad.coset, 0, sizeof bad.coset);
+        CHECK(verify(bad, t, &ok) == ZK_E_ARG && ok == -1);
+        bad = pr;
+        bad.g = 33;
+        CHECK(verify(bad, t, &ok) == ZK_E_ARG && ok == -1);
+        CHECK(verify(pr, t, nullptr) == ZK_E_ARG);
+        CHECK(zk_transcript_export_state(t, after, &fa) == ZK_OK && fa == fb && memcmp(before, after, sizeof before) == 0);
+        CHECK(verify(pr, t, &ok) == ZK_OK && ok == 0);        // made on a fresh transcript, shown on another
+        CHECK(zk_transcript_export_state(t, after, &fa) == ZK_OK && memcmp(before, after, sizeof before) != 0);
+        zk_transcript_free(t);
+    }
+    if (failures) printf("plonk_lookup_selftest: %d check(s) FAILED\n", failures);
+    else printf("plonk_lookup_selftest ok\n");
+    return failures ? 1 : 0;
+}

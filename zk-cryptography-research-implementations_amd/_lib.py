@@ -167,6 +167,13 @@ def lib():
                                                                                           C.c_uint32, u64p],
         "zk_fri_ml_verify_batch_pow": [C.c_int, u8p] + [C.c_uint32] * 7 + [u64p, u64p, C.c_uint32, u64p, vp, u64p, u8p, u64p, u64p, u8p, C.c_uint32,
                                                                           C.c_uint64, C.POINTER(C.c_int)],
+        # FRI commitments opened together, wide: up to 32
+        "zk_fri_ml_fold_batch_wide": [C.POINTER(vp), C.c_uint32, u64p, u64p, u64p, u64p, C.POINTER(vp)],
+        "zk_fri_ml_sizes_batch_wide": [C.c_uint32] * 7 + [C.POINTER(sz)] * 5,
+        "zk_fri_ml_open_batch_wide_pow": [C.POINTER(vp), C.c_uint32, u64p] + [C.c_uint32] * 4 + [vp, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p,
+                                                                                               C.c_uint32, u64p],
+        "zk_fri_ml_verify_batch_wide_pow": [C.c_int, u8p] + [C.c_uint32] * 7 + [u64p, u64p, C.c_uint32, u64p, vp, u64p, u8p, u64p, u64p, u8p, C.c_uint32,
+                                                                               C.c_uint64, C.POINTER(C.c_int)],
         # zerocheck of a product of committed tables
         "zk_zerocheck_mul_round": [vp, vp, vp, vp, u64p, C.POINTER(vp), u64p],
         "zk_zerocheck_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 6,
@@ -205,6 +212,13 @@ def lib():
         "zk_lookup_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
                                                                 C.POINTER(C.c_int)],
         "zk_lookup_last_stats": [vp],
+        # Plonk with lookups: gate, wiring, public inputs and lookup rows in one sumcheck
+        "zk_plonk_lookup_round": [C.POINTER(vp), u64p, u64p, u64p, u64p, u64p, C.c_uint32, u64p, C.POINTER(vp), u64p],
+        "zk_plonk_lookup_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 7,
+        "zk_plonk_lookup_prove": [C.POINTER(vp), u64p] + [C.c_uint32] * 5 + [vp, u8p, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
+        "zk_plonk_lookup_verify": [C.c_int, u8p, u64p] + [C.c_uint32] * 7 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
+                                                                            C.POINTER(C.c_int)],
+        "zk_plonk_lookup_last_stats": [vp],
         "zk_sumcheck_basic_prove_succinct": [vp, C.c_uint32, C.c_uint32, vp, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_sumcheck_basic_verify_succinct": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, vp, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u8p,
                                                                                  C.POINTER(C.c_int)],

@@ -127,12 +127,13 @@ struct FriMlClaim {
 // coefficients and the indices; a nonce that fails it gives *ok = 0.  grind_bits > ZK_FRI_GRIND_MAX_BITS: ZK_E_ARG
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,
-                    uint64_t *indices_out, const FriMlClaim *ml = nullptr, uint32_t grind_bits = 0, uint64_t pow_nonce = 0);
+                    uint64_t *indices_out, const FriMlClaim *ml = nullptr, uint32_t grind_bits = 0, uint64_t pow_nonce = 0,
+                    uint32_t max_tables = ZK_FRI_ML_BATCH_MAX);   // the most commitments opened together: the wide verifier passes ZK_FRI_ML_WIDE_MAX
 // zk_fri_ml_open_batch_pow's own statuses (zkmle_fri_ml.hip), every ZK_E_ARG and then ZK_E_NO_DEVICE, for a prover that runs rounds of its own on
 // the transcript before it calls that opener at a point those rounds produce (zkmle_zerocheck.hip): `points` is then any reduced stand-in
 int fri_ml_open_batch_check(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
                             uint32_t log_arity, const uint64_t *ys_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *query_values,
-                            uint8_t *query_paths, uint32_t grinding_bits, const uint64_t *pow_nonce);
+                            uint8_t *query_paths, uint32_t grinding_bits, const uint64_t *pow_nonce, uint32_t max_tables = ZK_FRI_ML_BATCH_MAX);   // ZK_FRI_ML_WIDE_MAX: zk_fri_ml_open_batch_wide_pow's
 // steps 1-3 of the proof-of-work step on `tr` with the search on the GPU (zkmle_grind.hip): zk_transcript_grind's checks and body
 int transcript_grind(Transcript &tr, uint32_t bits, uint64_t start, uint32_t log_batch, uint64_t *nonce);
 // Prover::prove (prover.rs:35-71) on a caller's Transcript whose binding append (:38-39) is the 32 bytes `bound` -- a commitment the caller

@@ -206,10 +206,10 @@ template <class F, bool COSET> __device__ __forceinline__ Fe<F> fri_ml_fold_by(c
     else t = fe_sub<F>(t, s);
     return fe_add<F>(fe_halve<F>(s), g.times(t));
 }
-template <class F, int SIDES, bool COSET> __global__ void __launch_bounds__(kFriBlock) fri_ml_fold_batch_kernel(FriMlBatchArgs<F> a, void *__restrict__ out, size_t part,
-                                                                                                          const void *__restrict__ pw_lo,
-                                                                                                          const void *__restrict__ pw_hi,
-                                                                                                          FriMlShift2<F, COSET> c, Fe<F> g0, Fe<F> g1) {
+// the pass's body, generic over the argument block (FriMlBatchArgs, or FriMlBatchArgsCap of another capacity: lincomb_at reads t, c and k)
+template <class F, int SIDES, bool COSET, class Args>
+__device__ __forceinline__ void fri_ml_fold_batch_body(const Args &a, void *__restrict__ out, size_t part, const void *__restrict__ pw_lo, const void *__restrict__ pw_hi,
+                                                       const FriMlShift2<F, COSET> &c, const Fe<F> &g0, const Fe<F> &g1) {
     static_assert(SIDES == 2 || SIDES == 4, "a fold by 2 or by 4");
     const size_t stride = (size_t)gridDim.x * kFriBlock;
     Fe<F> c1 = g0, c2 = g0;                                  // the shifts; not read without a coset
@@ -230,6 +230,31 @@ template <class F, int SIDES, bool COSET> __global__ void __launch_bounds__(kFri
             fe_store<F>(out, i, fri_ml_fold_by<F, COSET>(Multiplier<F>(g1), ntt_pow2t<F>(pw_lo, pw_hi, (uint64_t)i << 1), v0, v1, c2));
         }
     }
+}
+template <class F, int SIDES, bool COSET> __global__ void __launch_bounds__(kFriBlock) fri_ml_fold_batch_kernel(FriMlBatchArgs<F> a, void *__restrict__ out, size_t part,
+                                                                                                          const void *__restrict__ pw_lo,
+                                                                                                          const void *__restrict__ pw_hi,
+                                                                                                          FriMlShift2<F, COSET> c, Fe<F> g0, Fe<F> g1) {
+    fri_ml_fold_batch_body<F, SIDES, COSET>(a, out, part, pw_lo, pw_hi, c, g0, g1);
+}
+
+// The same pass for 17 .. 32 codewords ("FRI commitments opened together, wide": ZK_FRI_ML_WIDE_MAX).  The argument block has a capacity
+// parameter; the 16-slot block above stays the type it was, so k <= 16 launches the instantiation it always did, through either door.  The
+// 32-slot block is 32 pointers, 32 coefficients and k: 256 + 1024 + 4 = 1284 bytes of kernel arguments (static_assert below), read where
+// they are used like the narrow one's.  lincomb_at takes one reduction for up to kRawTermsMax = 70 (BLS12-381 Fr) terms, so 32 need no
+// intermediate one; its static_assert checks the block's slots.
+constexpr int kFriMlWideMax = 32;                            // ZK_FRI_ML_WIDE_MAX
+template <class F, int CAP> struct FriMlBatchArgsCap {
+    const void *t[CAP];
+    Fe<F> c[CAP];
+    int k;
+};
+using FriMlWideArgs381 = FriMlBatchArgsCap<Fr381, kFriMlWideMax>;
+static_assert(sizeof(FriMlWideArgs381::t) + sizeof(FriMlWideArgs381::c) + sizeof(int) == 1284, "the wide block: 32 pointers, 32 coefficients, k");
+template <class F, int CAP, int SIDES, bool COSET>
+__global__ void __launch_bounds__(kFriBlock) fri_ml_fold_batch_wide_kernel(FriMlBatchArgsCap<F, CAP> a, void *__restrict__ out, size_t part, const void *__restrict__ pw_lo,
+                                                                           const void *__restrict__ pw_hi, FriMlShift2<F, COSET> c, Fe<F> g0, Fe<F> g1) {
+    fri_ml_fold_batch_body<F, SIDES, COSET>(a, out, part, pw_lo, pw_hi, c, g0, g1);
 }
 
 }  // namespace zk

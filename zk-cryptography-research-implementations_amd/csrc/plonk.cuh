@@ -68,9 +68,10 @@ template <class F> struct PlonkUniform {
 
 enum { PLONK_A, PLONK_B, PLONK_C, PLONK_QM, PLONK_QL, PLONK_QR, PLONK_QO, PLONK_QC, PLONK_S, PLONK_H = 11, PLONK_E = 14 };
 
-// the gate's share of the five zerocheck sums; (e0, de) = the line of E at the pair, which the wires go on with
-template <class F, bool FOLD>
-__device__ __forceinline__ void plonk_gate(const PlonkTables &t, size_t i, const Multiplier<F> &mr, const PlonkUniform<F> &cs, Fe<F> &e0, Fe<F> &de, Wide<F> &s0,
+// the gate's share of the five zerocheck sums; (e0, de) = the line of E at the pair, which the wires go on with.  T, E_AT: the pass's argument
+// block and E's place in it (plonk_lookup.cuh has a longer block; the gate's eight tables stand first in both)
+template <class F, bool FOLD, class T = PlonkTables, int E_AT = PLONK_E>
+__device__ __forceinline__ void plonk_gate(const T &t, size_t i, const Multiplier<F> &mr, const PlonkUniform<F> &cs, Fe<F> &e0, Fe<F> &de, Wide<F> &s0,
                                            Wide<F> &s1, Wide<F> &s2, Wide<F> &s3, Wide<F> &sinf) {
     Fe<F> u[4], v[4], uinf, x0, x1, y[4];                     // zerocheck_gate_round_kernel's running values
     {
@@ -110,7 +111,7 @@ __device__ __forceinline__ void plonk_gate(const PlonkTables &t, size_t i, const
     zerocheck_nodes<F>(x0, x1, y);
 #pragma unroll
     for (int k = 0; k < 4; k++) u[k] = fe_add<F>(u[k], y[k]);
-    zerocheck_pair<F, FOLD>(plonk_in(PLONK_E), t.out(PLONK_E), i, mr, e0, x1);
+    zerocheck_pair<F, FOLD>(plonk_in(E_AT), t.out(E_AT), i, mr, e0, x1);
     de = fe_sub<F>(x1, e0);
     {
         const Multiplier<F> ma3(cs[PlonkUniform<F>::ALPHA3]);
@@ -129,7 +130,7 @@ __device__ __forceinline__ void plonk_gate(const PlonkTables &t, size_t i, const
 
 // the pair of wire J a second time: what the gate stored (FOLD) or read (round 0).  The pointer is laundered: the compiler must take the read for
 // one that may alias the gate's store and may not replace it by the stored value
-template <class F, bool FOLD, int J> __device__ __forceinline__ void plonk_pair_again(const PlonkTables &t, size_t i, Fe<F> &x0, Fe<F> &x1) {
+template <class F, bool FOLD, int J, class T = PlonkTables> __device__ __forceinline__ void plonk_pair_again(const T &t, size_t i, Fe<F> &x0, Fe<F> &x1) {
     const void *p;
     if constexpr (FOLD) {
         PlonkGlobal g = (PlonkGlobal)t.out(J);
@@ -142,9 +143,10 @@ template <class F, bool FOLD, int J> __device__ __forceinline__ void plonk_pair_
     x1 = fe_load<F>(p, 2 * i + 1);
 }
 
-// wire J's share of the seven sums: wiring.cuh's wiring_wire on the tables of this pass, W_J read back
-template <class F, bool FOLD, int J>
-__device__ __forceinline__ void plonk_wire(const PlonkTables &t, size_t i, const Multiplier<F> &mr, const PlonkUniform<F> &cs, const Fe<F> &gid, Fe<F> e, const Fe<F> &de,
+// wire J's share of the seven sums: wiring.cuh's wiring_wire on the tables of this pass, W_J read back.  T, H_AT: the pass's argument block and
+// H0's place in it
+template <class F, bool FOLD, int J, class T = PlonkTables, int H_AT = PLONK_H>
+__device__ __forceinline__ void plonk_wire(const T &t, size_t i, const Multiplier<F> &mr, const PlonkUniform<F> &cs, const Fe<F> &gid, Fe<F> e, const Fe<F> &de,
                                            Wide<F> &s0, Wide<F> &s1, Wide<F> &s2, Wide<F> &s3, Wide<F> &sinf, Wide<F> &sev, Wide<F> &sod) {
     Fe<F> x0, x1;
     const Fe<F> gid1 = fe_add<F>(gid, cs[PlonkUniform<F>::GSTEP]);
@@ -162,7 +164,7 @@ __device__ __forceinline__ void plonk_wire(const PlonkTables &t, size_t i, const
         nn = fe_sub<F>(mg.times(x0), gid);
         dn = fe_sub<F>(fe_sub<F>(mg.times(x1), gid1), nn);
     }
-    zerocheck_pair<F, FOLD>(plonk_in(PLONK_H + J), t.out(PLONK_H + J), i, mr, x0, x1);
+    zerocheck_pair<F, FOLD>(plonk_in(H_AT + J), t.out(H_AT + J), i, mr, x0, x1);
     wide_add_fe<F>(sev, x0);
     wide_add_fe<F>(sod, x1);
     const Fe<F> dh = fe_sub<F>(x1, x0);

@@ -13,6 +13,9 @@ constexpr int kPlonkGiven = 11, kPlonkOpened = 14, kPlonkNodes = kWiringNodes;
 // the places of the wiring's nine (A, B, C, SA, SB, SC, H0, H1, H2) among the fourteen (A, B, C, qM, qL, qR, qO, qC, SA, SB, SC, H0, H1, H2)
 constexpr int kPlonkWiringPlace[kWiringOpened] = {0, 1, 2, 8, 9, 10, 11, 12, 13};
 
+// the public inputs' shape, which prover and verifier refuse alike: npublic <= 2^d, a NULL array only with npublic = 0
+inline bool plonk_public_shape_ok(const uint64_t *pub, uint32_t npublic, uint32_t d) { return (d >= 32 || npublic <= ((uint32_t)1 << d)) && (pub || npublic == 0); }
+
 // steps 1 to 4: the tag, d and l; the eleven roots; the l public values (each the 32-byte canonical big-endian element); then beta, gamma
 template <class F> void plonk_statement(Transcript &tr, const uint8_t *roots, uint32_t d, const uint64_t *pub, uint32_t npublic, WiringChallenges<F> &ch) {
     uint8_t tag[12];

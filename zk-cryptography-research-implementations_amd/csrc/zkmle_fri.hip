@@ -352,12 +352,12 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
 namespace zk {
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,
-                    uint64_t *indices_out, const FriMlClaim *ml, uint32_t grind_bits, uint64_t pow_nonce) {
+                    uint64_t *indices_out, const FriMlClaim *ml, uint32_t grind_bits, uint64_t pow_nonce, uint32_t max_tables) {
     if (grind_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
     if (ml && (!ml->z || !ml->y || !ml->round_polys || ml->npoints > 8)) return ZK_E_ARG;
     if (ml && (ml->log_arity < 1 || ml->log_arity > 2 || (ml->log_arity == 2 && (ml->npoints < 1 || log_final >= d || d - log_final < 2)))) return ZK_E_ARG;
     if (ml && ml->grouped && ml->log_arity != 2) return ZK_E_ARG;
-    if (ml && (ml->ntables > ZK_FRI_ML_BATCH_MAX || (ml->ntables && ml->npoints < 1))) return ZK_E_ARG;
+    if (ml && (ml->ntables > max_tables || (ml->ntables && ml->npoints < 1))) return ZK_E_ARG;
     if (!roots || !final_coeffs || !query_values || !query_paths || !ok || field_limbs64(field) < 0) return ZK_E_ARG;
     ZK_TRY(params_check(log_blowup, nqueries));
     if (coset && is_zero_element(field, coset)) return ZK_E_ARG;

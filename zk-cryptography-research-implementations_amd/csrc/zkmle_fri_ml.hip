@@ -75,9 +75,10 @@ template <class F> int fold4_once(const zk_table *cw, const uint64_t *r0, const 
 
 // out[i], i < len / sides, from the k codewords of `len` entries each: the fold (g1 null) or fold4 of sum_j coef_j f_j at layer 0, one pass.
 // coef: k stored-form elements.  g0 = r0 / (2 c), g1 = r1 / (2 c^2), c = the coset's shift (null: 1)
-template <class F> int launch_fold_batch(const void *const *cws, unsigned k, const Fe<F> *coef, void *out, size_t len, const FoldTables<F> &tb, const Fe<F> &g0,
-                                         const Fe<F> *g1, const Fe<F> *c) {
-    FriMlBatchArgs<F> a{};
+// `Args`: FriMlBatchArgs<F> with fri_ml_fold_batch_kernel, or the 32-slot block with fri_ml_fold_batch_wide_kernel
+template <class F, class Args, bool WIDE> int launch_fold_batch_as(const void *const *cws, unsigned k, const Fe<F> *coef, void *out, size_t len, const FoldTables<F> &tb,
+                                                                  const Fe<F> &g0, const Fe<F> *g1, const Fe<F> *c) {
+    Args a{};
     for (unsigned j = 0; j < k; j++) {
         a.t[j] = cws[j];
         a.c[j] = lincomb_coeff<F>(coef[j]);
@@ -86,16 +87,35 @@ template <class F> int launch_fold_batch(const void *const *cws, unsigned k, con
     const size_t part = g1 ? len / 4 : len / 2, want = (part + kFriBlock - 1) / kFriBlock;
     const unsigned blocks = (unsigned)(want < (size_t)kFriMlBatchBlocks ? want : (size_t)kFriMlBatchBlocks);
     const Fe<F> gg1 = g1 ? *g1 : fe_one<F>();
-    if (c) {
-        const FriMlShift2<F, true> sh{*c, fe_sqr<F>(*c)};
-        if (g1) fri_ml_fold_batch_kernel<F, 4, true><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, sh, g0, gg1);
-        else fri_ml_fold_batch_kernel<F, 2, true><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, sh, g0, gg1);
+    if constexpr (WIDE) {
+        constexpr int CAP = kFriMlWideMax;
+        if (c) {
+            const FriMlShift2<F, true> sh{*c, fe_sqr<F>(*c)};
+            if (g1) fri_ml_fold_batch_wide_kernel<F, CAP, 4, true><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, sh, g0, gg1);
+            else fri_ml_fold_batch_wide_kernel<F, CAP, 2, true><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, sh, g0, gg1);
+        } else {
+            if (g1) fri_ml_fold_batch_wide_kernel<F, CAP, 4, false><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, FriMlShift2<F, false>{}, g0, gg1);
+            else fri_ml_fold_batch_wide_kernel<F, CAP, 2, false><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, FriMlShift2<F, false>{}, g0, gg1);
+        }
     } else {
-        if (g1) fri_ml_fold_batch_kernel<F, 4, false><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, FriMlShift2<F, false>{}, g0, gg1);
-        else fri_ml_fold_batch_kernel<F, 2, false><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, FriMlShift2<F, false>{}, g0, gg1);
+        if (c) {
+            const FriMlShift2<F, true> sh{*c, fe_sqr<F>(*c)};
+            if (g1) fri_ml_fold_batch_kernel<F, 4, true><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, sh, g0, gg1);
+            else fri_ml_fold_batch_kernel<F, 2, true><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, sh, g0, gg1);
+        } else {
+            if (g1) fri_ml_fold_batch_kernel<F, 4, false><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, FriMlShift2<F, false>{}, g0, gg1);
+            else fri_ml_fold_batch_kernel<F, 2, false><<<blocks, kFriBlock, 0, cur_stream()>>>(a, out, part, tb.lo, tb.hi, FriMlShift2<F, false>{}, g0, gg1);
+        }
     }
     ZK_HIP(hipGetLastError());
     return ZK_OK;
+}
+// k <= kFriMlBatchMax: the 16-slot block and its kernel, whichever entry point asks; above (the wide entry points only, k <= kFriMlWideMax): the 32-slot one
+template <class F> int launch_fold_batch(const void *const *cws, unsigned k, const Fe<F> *coef, void *out, size_t len, const FoldTables<F> &tb, const Fe<F> &g0,
+                                         const Fe<F> *g1, const Fe<F> *c) {
+    if (k > (unsigned)kFriMlWideMax) return ZK_E_ARG;
+    if (k > (unsigned)kFriMlBatchMax) return launch_fold_batch_as<F, FriMlBatchArgsCap<F, kFriMlWideMax>, true>(cws, k, coef, out, len, tb, g0, g1, c);
+    return launch_fold_batch_as<F, FriMlBatchArgs<F>, false>(cws, k, coef, out, len, tb, g0, g1, c);
 }
 
 template <class F> int fold_batch_once(const zk_table *const *cws, unsigned k, const uint64_t *coeffs, const uint64_t *r0, const uint64_t *r1, const uint64_t *coset,
@@ -108,8 +128,8 @@ template <class F> int fold_batch_once(const zk_table *const *cws, unsigned k, c
     const Fe<F> g0 = fe_mul<F>(load_host<F>(r0), fe_inv<F>(fe_mul<F>(two, c)));
     Fe<F> g1 = fe_one<F>();
     if (r1) g1 = fe_mul<F>(load_host<F>(r1), fe_inv<F>(fe_mul<F>(two, fe_sqr<F>(c))));
-    const void *ptrs[kFriMlBatchMax];
-    Fe<F> coef[kFriMlBatchMax];
+    const void *ptrs[kFriMlWideMax];
+    Fe<F> coef[kFriMlWideMax];
     for (unsigned j = 0; j < k; j++) {
         ptrs[j] = cws[j]->dptr;
         coef[j] = load_host<F>(coeffs + (size_t)j * W);
@@ -313,7 +333,7 @@ template <class F> struct ManyTables : ManyPoints<F> {
     static constexpr bool kBatch = true;
     const zk_fri_commitment *const *cms;
     uint32_t k;
-    Fe<F> coef[kFriMlBatchMax];                              // alpha^j
+    Fe<F> coef[kFriMlWideMax];                               // alpha^j
     void *table0 = nullptr;                                  // T_0's n elements of the pool block: the driver sets it before start
 
     ManyTables(const zk_fri_commitment *const *cms_, uint32_t k_, const uint64_t *pts_, uint32_t P_, uint64_t *ys, uint64_t *gamma, unsigned d_)
@@ -348,8 +368,8 @@ template <class F> struct ManyTables : ManyPoints<F> {
         if (this->gamma_out) store_host<F>(this->gamma_out, gamma);
         Fe<F> alpha = fe_one<F>();
         for (unsigned p = 0; p < P; p++) alpha = fe_mul<F>(alpha, gamma);
-        const void *tabs[kFriMlBatchMax];
-        uint64_t cw[kFriMlBatchMax * W];
+        const void *tabs[kFriMlWideMax];
+        uint64_t cw[kFriMlWideMax * W];
         Fe<F> aj = fe_one<F>();
         for (uint32_t j = 0; j < k; j++) {
             coef[j] = aj;
@@ -363,7 +383,7 @@ template <class F> struct ManyTables : ManyPoints<F> {
     }
     // layer 0 -> the layer of step 1: out gets len / 2 entries (g1 null) or len / 4
     int fold0(void *out, size_t len, const FoldTables<F> &tb, const Fe<F> &g0, const Fe<F> *g1, const Fe<F> *shift) const {
-        const void *cws[kFriMlBatchMax];
+        const void *cws[kFriMlWideMax];
         for (uint32_t j = 0; j < k; j++) cws[j] = cms[j]->codeword->dptr;
         return launch_fold_batch<F>(cws, k, coef, out, len, tb, g0, g1, shift);
     }
@@ -646,7 +666,7 @@ int open_one(const zk_fri_commitment *cm, const uint64_t *z, uint32_t f, uint32_
 // must be the same bytes and the core gets a copy of the roots that starts with the caller's
 int verify_opening(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset,
                    const FriMlClaim &ml, zk_transcript *t, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
-                   const uint8_t *query_paths, int *ok, uint32_t grind_bits = 0, uint64_t pow_nonce = 0) {
+                   const uint8_t *query_paths, int *ok, uint32_t grind_bits = 0, uint64_t pow_nonce = 0, uint32_t max_tables = ZK_FRI_ML_BATCH_MAX) {
     if (grind_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
     if (!root32 || !ml.z || !ml.y || !ml.round_polys || !roots || !final_table || !query_values || !query_paths || !ok) return ZK_E_ARG;
     if (field_limbs64(field) < 0 || log_blowup < 1 || log_blowup > 8 || nqueries < 1 || nqueries > 4096 || d < 1 || log_final >= d) return ZK_E_ARG;
@@ -659,7 +679,7 @@ int verify_opening(int field, const uint8_t *root32, uint32_t d, uint32_t log_bl
     memcpy(rs.data(), root32, 32 * own);
     Transcript fresh;
     int good = 0;
-    ZK_TRY(fri_verify_core(field, d, log_blowup, log_final, nqueries, coset, t ? t->t : fresh, rs.data(), final_table, query_values, query_paths, &good, nullptr, &ml, grind_bits, pow_nonce));
+    ZK_TRY(fri_verify_core(field, d, log_blowup, log_final, nqueries, coset, t ? t->t : fresh, rs.data(), final_table, query_values, query_paths, &good, nullptr, &ml, grind_bits, pow_nonce, max_tables));
     *ok = good && same_root ? 1 : 0;
     return ZK_OK;
 }
@@ -679,9 +699,10 @@ int open_points_check(const zk_fri_commitment *cm, const uint64_t *points, uint3
 // zk_fri_ml_open_batch_pow's statuses, every ZK_E_ARG and then the device check: the step's arguments, k, one field, size, blow-up, coset and
 // leaf grouping, the grouping's arity, and open_points_check on the first commitment
 int open_batch_check(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
-                     uint32_t log_arity, const uint64_t *ys_out, const OpenOut &o, uint32_t grinding_bits, const uint64_t *pow_nonce) {
+                     uint32_t log_arity, const uint64_t *ys_out, const OpenOut &o, uint32_t grinding_bits, const uint64_t *pow_nonce,
+                     uint32_t max_tables = ZK_FRI_ML_BATCH_MAX) {
     if (grinding_bits > ZK_FRI_GRIND_MAX_BITS || (grinding_bits && !pow_nonce)) return ZK_E_ARG;
-    if (!cms || k < 1 || k > ZK_FRI_ML_BATCH_MAX || !cms[0]) return ZK_E_ARG;
+    if (!cms || k < 1 || k > max_tables || !cms[0]) return ZK_E_ARG;
     const zk_fri_commitment *c0 = cms[0];
     for (uint32_t j = 1; j < k; j++) {                        // one field, size, blow-up, coset and leaf grouping
         const zk_fri_commitment *cj = cms[j];
@@ -707,9 +728,9 @@ FriMlClaim claim_of(const uint64_t *points, uint32_t npoints, const uint64_t *ys
 
 int zk::fri_ml_open_batch_check(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
                                 uint32_t log_arity, const uint64_t *ys_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *query_values,
-                                uint8_t *query_paths, uint32_t grinding_bits, const uint64_t *pow_nonce) {
+                                uint8_t *query_paths, uint32_t grinding_bits, const uint64_t *pow_nonce, uint32_t max_tables) {
     return open_batch_check(cms, k, points, npoints, log_final, nqueries, log_arity, ys_out, OpenOut{round_polys, roots, final_table, nullptr, nullptr, query_values, query_paths},
-                            grinding_bits, pow_nonce);
+                            grinding_bits, pow_nonce, max_tables);
 }
 
 extern "C" {
@@ -798,9 +819,10 @@ int zk_fri_ml_sizes_arity(uint32_t d, uint32_t log_blowup, uint32_t log_final, u
     return ZK_OK;
 }
 
-int zk_fri_ml_fold_batch(const zk_table *const *codewords, uint32_t k, const uint64_t *coeffs, const uint64_t *r0, const uint64_t *r1, const uint64_t *coset,
-                         zk_table **out) {
-    if (!codewords || k < 1 || k > ZK_FRI_ML_BATCH_MAX || !codewords[0]) return ZK_E_ARG;
+// the hook's statuses and body for k <= max_tables
+static int fold_batch_capped(const zk_table *const *codewords, uint32_t k, uint32_t max_tables, const uint64_t *coeffs, const uint64_t *r0, const uint64_t *r1,
+                             const uint64_t *coset, zk_table **out) {
+    if (!codewords || k < 1 || k > max_tables || !codewords[0]) return ZK_E_ARG;
     for (uint32_t j = 1; j < k; j++) {
         if (!codewords[j] || codewords[j]->field != codewords[0]->field) return ZK_E_ARG;
         if (codewords[j]->len != codewords[0]->len) return ZK_E_LEN_MISMATCH;
@@ -809,10 +831,18 @@ int zk_fri_ml_fold_batch(const zk_table *const *codewords, uint32_t k, const uin
     FRI_DISPATCH(codewords[0]->field, return fold_batch_once<F>(codewords, k, coeffs, r0, r1, coset, out));
     return ZK_OK;
 }
+int zk_fri_ml_fold_batch(const zk_table *const *codewords, uint32_t k, const uint64_t *coeffs, const uint64_t *r0, const uint64_t *r1, const uint64_t *coset,
+                         zk_table **out) {
+    return fold_batch_capped(codewords, k, ZK_FRI_ML_BATCH_MAX, coeffs, r0, r1, coset, out);
+}
+int zk_fri_ml_fold_batch_wide(const zk_table *const *codewords, uint32_t k, const uint64_t *coeffs, const uint64_t *r0, const uint64_t *r1, const uint64_t *coset,
+                              zk_table **out) {
+    return fold_batch_capped(codewords, k, ZK_FRI_ML_WIDE_MAX, coeffs, r0, r1, coset, out);
+}
 
-int zk_fri_ml_sizes_batch(uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
-                          size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround) {
-    if (k < 1 || k > ZK_FRI_ML_BATCH_MAX || (log_group != 0 && log_group != 2) || (log_group == 2 && log_arity != 2)) return ZK_E_ARG;
+static int sizes_batch_capped(uint32_t k, uint32_t max_tables, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                              uint32_t log_group, size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround) {
+    if (k < 1 || k > max_tables || (log_group != 0 && log_group != 2) || (log_group == 2 && log_arity != 2)) return ZK_E_ARG;
     size_t nr = 0, nv = 0, pb = 0;
     if (log_group) ZK_TRY(zk_fri_ml_sizes_grouped(d, log_blowup, log_final, nqueries, &nr, nfinal, &nv, &pb, nround));
     else ZK_TRY(zk_fri_ml_sizes_arity(d, log_blowup, log_final, nqueries, log_arity, &nr, nfinal, &nv, &pb, nround));
@@ -823,6 +853,14 @@ int zk_fri_ml_sizes_batch(uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t 
     if (path_bytes) *path_bytes = pb + (size_t)(k - 1) * nqueries * d0 * 32;
     return ZK_OK;
 }
+int zk_fri_ml_sizes_batch(uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
+                          size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround) {
+    return sizes_batch_capped(k, ZK_FRI_ML_BATCH_MAX, d, log_blowup, log_final, nqueries, log_arity, log_group, nroots, nfinal, nvalues, path_bytes, nround);
+}
+int zk_fri_ml_sizes_batch_wide(uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
+                               size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround) {
+    return sizes_batch_capped(k, ZK_FRI_ML_WIDE_MAX, d, log_blowup, log_final, nqueries, log_arity, log_group, nroots, nfinal, nvalues, path_bytes, nround);
+}
 
 int zk_fri_ml_open_batch(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
                          uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table,
@@ -831,17 +869,31 @@ int zk_fri_ml_open_batch(const zk_fri_commitment *const *cms, uint32_t k, const 
                                     query_indices, query_values, query_paths, 0, nullptr);
 }
 
-int zk_fri_ml_open_batch_pow(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
-                             uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots,
+static int open_batch_capped(const zk_fri_commitment *const *cms, uint32_t k, uint32_t max_tables, const uint64_t *points, uint32_t npoints, uint32_t log_final,
+                             uint32_t nqueries, uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots,
                              uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
                              uint32_t grinding_bits, uint64_t *pow_nonce) {
     const OpenOut o{round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
-    ZK_TRY(open_batch_check(cms, k, points, npoints, log_final, nqueries, log_arity, ys_out, o, grinding_bits, pow_nonce));
+    ZK_TRY(open_batch_check(cms, k, points, npoints, log_final, nqueries, log_arity, ys_out, o, grinding_bits, pow_nonce, max_tables));
     const zk_fri_commitment *c0 = cms[0];
     Transcript fresh;
     FRI_DISPATCH(c0->field, ManyTables<F> form(cms, k, points, npoints, ys_out, gamma_out, c0->d);
                  return open_with<F>(c0, form, log_final, nqueries, log_arity, c0->log_group == 2, t ? t->t : fresh, o, grinding_bits, pow_nonce));
     return ZK_OK;
+}
+int zk_fri_ml_open_batch_pow(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                             uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots,
+                             uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
+                             uint32_t grinding_bits, uint64_t *pow_nonce) {
+    return open_batch_capped(cms, k, ZK_FRI_ML_BATCH_MAX, points, npoints, log_final, nqueries, log_arity, t, ys_out, gamma_out, round_polys, roots, final_table,
+                             challenges, query_indices, query_values, query_paths, grinding_bits, pow_nonce);
+}
+int zk_fri_ml_open_batch_wide_pow(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                                  uint32_t log_arity, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots,
+                                  uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
+                                  uint32_t grinding_bits, uint64_t *pow_nonce) {
+    return open_batch_capped(cms, k, ZK_FRI_ML_WIDE_MAX, points, npoints, log_final, nqueries, log_arity, t, ys_out, gamma_out, round_polys, roots, final_table,
+                             challenges, query_indices, query_values, query_paths, grinding_bits, pow_nonce);
 }
 
 int zk_fri_ml_verify_batch(int field, const uint8_t *roots_of_f, uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
@@ -852,15 +904,29 @@ int zk_fri_ml_verify_batch(int field, const uint8_t *roots_of_f, uint32_t k, uin
                                       roots, final_table, query_values, query_paths, 0, 0, ok);
 }
 
+static int verify_batch_capped(int field, const uint8_t *roots_of_f, uint32_t k, uint32_t max_tables, uint32_t d, uint32_t log_blowup, uint32_t log_final,
+                               uint32_t nqueries, uint32_t log_arity, uint32_t log_group, const uint64_t *coset, const uint64_t *points, uint32_t npoints,
+                               const uint64_t *ys, zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table,
+                               const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok) {
+    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
+    if (k < 1 || k > max_tables || npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2) return ZK_E_ARG;
+    if ((log_group != 0 && log_group != 2) || (log_group == 2 && log_arity != 2)) return ZK_E_ARG;
+    return verify_opening(field, roots_of_f, d, log_blowup, log_final, nqueries, coset, claim_of(points, npoints, ys, round_polys, log_arity, log_group == 2, k), t,
+                          roots, final_table, query_values, query_paths, ok, grinding_bits, pow_nonce, max_tables);
+}
 int zk_fri_ml_verify_batch_pow(int field, const uint8_t *roots_of_f, uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
                                uint32_t log_arity, uint32_t log_group, const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys,
                                zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table,
                                const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok) {
-    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
-    if (k < 1 || k > ZK_FRI_ML_BATCH_MAX || npoints < 1 || npoints > 8 || log_arity < 1 || log_arity > 2) return ZK_E_ARG;
-    if ((log_group != 0 && log_group != 2) || (log_group == 2 && log_arity != 2)) return ZK_E_ARG;
-    return verify_opening(field, roots_of_f, d, log_blowup, log_final, nqueries, coset, claim_of(points, npoints, ys, round_polys, log_arity, log_group == 2, k), t,
-                          roots, final_table, query_values, query_paths, ok, grinding_bits, pow_nonce);
+    return verify_batch_capped(field, roots_of_f, k, ZK_FRI_ML_BATCH_MAX, d, log_blowup, log_final, nqueries, log_arity, log_group, coset, points, npoints, ys, t,
+                               round_polys, roots, final_table, query_values, query_paths, grinding_bits, pow_nonce, ok);
+}
+int zk_fri_ml_verify_batch_wide_pow(int field, const uint8_t *roots_of_f, uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
+                                    uint32_t log_arity, uint32_t log_group, const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys,
+                                    zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table,
+                                    const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok) {
+    return verify_batch_capped(field, roots_of_f, k, ZK_FRI_ML_WIDE_MAX, d, log_blowup, log_final, nqueries, log_arity, log_group, coset, points, npoints, ys, t,
+                               round_polys, roots, final_table, query_values, query_paths, grinding_bits, pow_nonce, ok);
 }
 
 int zk_fri_ml_sizes_grouped(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots, size_t *nfinal, size_t *nvalues,

@@ -11,6 +11,7 @@
 #include "eq_table.cuh"
 #include "fri_host.h"
 #include "lookup.cuh"
+#include "lookup_driver.cuh"
 #include "lookup_host.h"
 #include "wiring_driver.cuh"
 
@@ -22,52 +23,6 @@ namespace {
 thread_local zk_lookup_stats g_lookup_stats{};
 
 constexpr int kTables = LOOKUP_TABLES;                       // A, B, C, qK, T0, T1, T2, M, H, E
-constexpr int kMaxLog = 31;                                  // the counts and the slots are 32 bits
-
-inline unsigned blocks_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
-// M (n elements, device) and the miss count from the seven tables A, B, C, qK, T0, T1, T2 of n <= 2^31 entries.  One synchronisation.
-template <class F> int multiplicities_into(const void *const *in, size_t n, void *M, uint64_t *misses) {
-    const size_t cap = 2 * n;
-    DevBuf slots, counts, status;
-    ZK_TRY(slots.alloc(cap * 4));
-    ZK_TRY(counts.alloc(n * 4));
-    ZK_TRY(status.alloc(sizeof(LookupStatus)));
-    ZK_HIP(hipMemsetAsync(slots.p, 0xFF, cap * 4, cur_stream()));
-    ZK_HIP(hipMemsetAsync(counts.p, 0, n * 4, cur_stream()));
-    ZK_HIP(hipMemsetAsync(status.p, 0, sizeof(LookupStatus), cur_stream()));
-    lookup_insert_kernel<F><<<blocks_for(n), kBlock, 0, cur_stream()>>>(in[4], in[5], in[6], n, (uint32_t *)slots.p, cap, (LookupStatus *)status.p);
-    ZK_HIP(hipGetLastError());
-    lookup_count_kernel<F><<<blocks_for(n), kBlock, 0, cur_stream()>>>(in[0], in[1], in[2], in[3], in[4], in[5], in[6], n, (const uint32_t *)slots.p, cap,
-                                                                      (uint32_t *)counts.p, (LookupStatus *)status.p);
-    ZK_HIP(hipGetLastError());
-    lookup_finish_kernel<F><<<blocks_for(n), kBlock, 0, cur_stream()>>>((const uint32_t *)counts.p, n, M);
-    ZK_HIP(hipGetLastError());
-    LookupStatus st{};
-    ZK_HIP(zk::memcpy_on_stream(&st, status.p, sizeof st, hipMemcpyDeviceToHost));
-    if (st.error) {
-        set_last_error("lookup multiplicities: a probe of the hash table ran through its whole capacity");
-        return ZK_E_HIP;
-    }
-    *misses = st.misses;
-    return ZK_OK;
-}
-
-// H (n elements, device) from the eight tables A, B, C, qK, T0, T1, T2, M.  Launches only; the two columns of denominators go back to the pool
-// when the call returns (stream-ordered: what reuses them runs after the kernels that read them)
-template <class F> int launch_fractions_lookup(const void *const *in, size_t n, void *H, const Fe<F> &beta, const Fe<F> &gamma) {
-    constexpr size_t ESZ = sizeof(Fe<F>);
-    DevBuf den;
-    ZK_TRY(den.alloc(2 * n * ESZ));
-    void *DW = den.p, *DT = (char *)den.p + n * ESZ;
-    lookup_denominators_kernel<F><<<blocks_for(n), kBlock, 0, cur_stream()>>>(in[0], in[1], in[2], in[4], in[5], in[6], DW, DT, n, beta, gamma, fe_mul<F>(gamma, gamma));
-    ZK_HIP(hipGetLastError());
-    const size_t per = (size_t)kLookupBatch * kPcsBlock;
-    lookup_fractions_kernel<F><<<(unsigned)((n + per - 1) / per), kPcsBlock, 0, cur_stream()>>>(DW, DT, in[3], in[7], H, n);
-    ZK_HIP(hipGetLastError());
-    return ZK_OK;
-}
-
 // sums (device, 7 elements) of a pass over q pairs.  Launches only.
 template <class F> int launch_round(bool fold, const LookupTables &t, size_t q, const Fe<F> &r, const LookupChallenges<F> &ch, void *partials, void *sums) {
     const int grid = reduce_grid_for(q);
@@ -140,11 +95,6 @@ template <class F> int round_once(const zk_table *const *in, const LookupChallen
     for (int k = 0; k < kWiringNodes; k++) store_host<F>(gout + (size_t)k * W, g[k]);
     for (int j = 0; fold && j < kTables; j++) outs[j] = o[j];
     return ZK_OK;
-}
-
-int commit_like(const zk_fri_commitment *c0, const zk_table *t, zk_fri_commitment **out) {
-    const uint64_t *coset = c0->has_coset ? c0->coset : nullptr;
-    return c0->log_group ? zk_fri_commit_grouped(t, c0->b, coset, c0->log_group, out) : zk_fri_commit(t, c0->b, coset, out);
 }
 
 // steps 1 to 7 on `tr`: the statement, M and H with their commitments (hc.cm[0], hc.cm[1]; h_roots), E_0 and the d rounds; z (d elements) = the
@@ -267,7 +217,7 @@ extern "C" {
 int zk_lookup_multiplicities(const zk_table *const tables[7], zk_table **M, uint64_t *misses) {
     if (!M || !misses) return ZK_E_ARG;
     ZK_TRY(check_tables(tables, kLookupGiven, 2));
-    if (tables[0]->len > ((size_t)1 << kMaxLog)) return ZK_E_ARG;
+    if (tables[0]->len > ((size_t)1 << kLookupMaxLog)) return ZK_E_ARG;
     ZK_TRY(require_device());
     FRI_DISPATCH(tables[0]->field, return multiplicities_once<F>(tables, M, misses));
     return ZK_OK;
@@ -320,7 +270,7 @@ int zk_lookup_prove(const zk_fri_commitment *const cms[7], uint32_t log_final, u
     for (int j = 0; j < kLookupGiven; j++)
         if (!cms[j]) return ZK_E_ARG;
     if (!h_roots || !round_polys || !challenges) return ZK_E_ARG;
-    if (cms[0]->d < 1 || cms[0]->d > kMaxLog) return ZK_E_ARG;   // what sizes the point below, and the 32-bit counts; no commitment is made outside it
+    if (cms[0]->d < 1 || cms[0]->d > kLookupMaxLog) return ZK_E_ARG;   // what sizes the point below, and the 32-bit counts; no commitment is made outside it
     // the point and the helper commitments do not exist yet: the opener's statuses are taken on the seven and a stand-in of zeros, before the
     // transcript moves (the helpers get the shape of the seven, and nine is within the opener's count)
     std::vector<uint64_t> z((size_t)cms[0]->d * 4, 0);

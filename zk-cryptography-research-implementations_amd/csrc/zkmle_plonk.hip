@@ -170,9 +170,6 @@ template <class F> int prove_rounds(const zk_fri_commitment *const *cms, const u
     return ZK_OK;
 }
 
-// npublic <= 2^d, a NULL array only with npublic = 0
-bool public_shape_ok(const uint64_t *pub, uint32_t npublic, uint32_t d) { return (d >= 32 || npublic <= ((uint32_t)1 << d)) && (pub || npublic == 0); }
-
 }  // namespace
 
 extern "C" {
@@ -207,7 +204,7 @@ int zk_plonk_round(const zk_table *const tables[15], const uint64_t *beta, const
 }
 
 int zk_plonk_public_eval(int field, const uint64_t *public_inputs, uint32_t npublic, const uint64_t *tau, uint32_t d, uint64_t *out) {
-    if (!tau || !out || d < 1 || d > 32 || (field != ZK_FR381 && field != ZK_BN254_FR) || !public_shape_ok(public_inputs, npublic, d)) return ZK_E_ARG;
+    if (!tau || !out || d < 1 || d > 32 || (field != ZK_FR381 && field != ZK_BN254_FR) || !plonk_public_shape_ok(public_inputs, npublic, d)) return ZK_E_ARG;
     if (!all_reduced(field, public_inputs, npublic) || !all_reduced(field, tau, d)) return ZK_E_ARG;
     FRI_DISPATCH(field, store_host<F>(out, plonk_public_eval<F>(public_inputs, npublic, tau, d)));
     return ZK_OK;
@@ -236,7 +233,7 @@ int zk_plonk_prove(const zk_fri_commitment *const cms[11], const uint64_t *publi
     std::vector<uint64_t> z((size_t)cms[0]->d * 4, 0);
     ZK_TRY(fri_ml_open_batch_check(cms, kPlonkGiven, z.data(), 1, log_final, nqueries, log_arity, ys_out, open_round_polys, roots, final_table, query_values, query_paths,
                                    grinding_bits, pow_nonce));
-    if (!public_shape_ok(public_inputs, npublic, cms[0]->d) || !all_reduced(cms[0]->field, public_inputs, npublic)) return ZK_E_ARG;
+    if (!plonk_public_shape_ok(public_inputs, npublic, cms[0]->d) || !all_reduced(cms[0]->field, public_inputs, npublic)) return ZK_E_ARG;
     zk_transcript own;
     zk_transcript *tt = t ? t : &own;
     zk_plonk_stats st{};
@@ -266,7 +263,7 @@ int zk_plonk_verify(int field, const uint8_t *roots_of_eleven, const uint64_t *p
     ZK_TRY(zk_fri_ml_sizes_batch(kPlonkOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, nullptr, nullptr, nullptr, nullptr, nullptr));
     if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
     if ((field != ZK_FR381 && field != ZK_BN254_FR) || d + log_blowup > two_adicity(field)) return ZK_E_RANGE;
-    if (!public_shape_ok(public_inputs, npublic, d)) return ZK_E_ARG;
+    if (!plonk_public_shape_ok(public_inputs, npublic, d)) return ZK_E_ARG;
     uint8_t all[32 * kPlonkOpened];
     memcpy(all, roots_of_eleven, 32 * kPlonkGiven);
     memcpy(all + 32 * kPlonkGiven, h_roots, 32 * kWiringWires);

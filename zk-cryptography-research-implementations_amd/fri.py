@@ -501,6 +501,73 @@ def verify_multilinear_batch(roots, points, opening, transcript=None):
     return bool(ok.value)
 
 
+# ---- several commitments opened together, wide: up to 32 ----------------------------------------------------------------------------------
+# The narrow functions above keep their cap of 16.  These are the same protocol byte for byte, for k <= 32.
+def ml_sizes_wide(d, log_blowup, log_final, nqueries, log_arity=1, grouped=False, k=1):
+    """ml_sizes(.., k=k) for k <= 32"""
+    out = [C.c_size_t(0) for _ in range(5)]
+    if grouped and log_arity != 2:
+        raise ValueError("grouped leaves need log_arity=2")
+    L.check(L.lib().zk_fri_ml_sizes_batch_wide(k, d, log_blowup, log_final, nqueries, log_arity, 2 if grouped else 0, *[C.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+def ml_fold_batch_wide(codewords, coeffs, r0, r1=None, coset=None):
+    """ml_fold_batch for k <= 32 codewords"""
+    field = codewords[0].field
+    h = C.c_void_p()
+    cf = np.ascontiguousarray(coeffs, np.uint64)
+    if cf.shape != (len(codewords), limbs(field)):
+        raise L.ZkError(L.ZK_E_ARG, "one coefficient per codeword")
+    hs = (C.c_void_p * len(codewords))(*[c._h for c in codewords])
+    cs = None if coset is None else L.p64(_elem(field, coset))
+    p1 = None if r1 is None else L.p64(_elem(field, r1))
+    L.check(L.lib().zk_fri_ml_fold_batch_wide(hs, len(codewords), L.p64(cf), L.p64(_elem(field, r0)), p1, cs, C.byref(h)))
+    return MultilinearPolynomial(field, _handle=h)
+
+
+class FriMlWideOpening(FriMlBatchOpening):
+    """FriMlBatchOpening for k <= 32: the same arrays, sized by ml_sizes_wide"""
+
+    def __init__(self, field, k, npoints, d, log_blowup, log_final, nqueries, coset=None, log_arity=1, grouped=False, grinding_bits=0):
+        FriMlPointsOpening.__init__(self, field, npoints, d, log_blowup, log_final, nqueries, coset, log_arity, grouped)
+        self.k = k
+        self.grinding_bits, self.pow_nonce = grinding_bits, 0
+        nroots, _, nvalues, path_bytes, _ = ml_sizes_wide(d, log_blowup, log_final, nqueries, log_arity, grouped, k=k)
+        n = limbs(field)
+        self.ys = np.zeros((k, npoints, n), np.uint64)
+        self.roots = np.zeros((nroots, 32), np.uint8)
+        self.query_values = np.zeros((nqueries, nvalues // nqueries, n), np.uint64)
+        self.query_paths = np.zeros(path_bytes, np.uint8)
+
+
+def open_multilinear_batch_wide(commitments, points, log_final, nqueries, log_arity=1, transcript=None, grinding_bits=0):
+    """open_multilinear_batch for k <= 32 commitments: the same proof bytes for k <= 16"""
+    c0 = commitments[0]
+    grouped = getattr(c0, "log_group", 0) != 0
+    if grouped and log_arity != 2:
+        raise ValueError("commitments with grouped leaves are opened with log_arity=2")
+    if not 1 <= len(commitments) <= 32:
+        raise L.ZkError(L.ZK_E_ARG, "1 to 32 commitments")
+    pts = _points(c0.field, c0.d, points)
+    op = FriMlWideOpening(c0.field, len(commitments), pts.shape[0], c0.d, c0.log_blowup, log_final, nqueries, c0.coset, log_arity, grouped, grinding_bits)
+    nonce = C.c_uint64(0)
+    L.check(L.lib().zk_fri_ml_open_batch_wide_pow(_handles(commitments), len(commitments), L.p64(pts), pts.shape[0], log_final, nqueries, log_arity,
+                                                  _handle(transcript), *_prover_outputs(op), grinding_bits, C.byref(nonce)))
+    op.pow_nonce = int(nonce.value)
+    return op
+
+
+def verify_multilinear_batch_wide(roots, points, opening, transcript=None):
+    """host only: verify_multilinear_batch for k <= 32"""
+    op, ok = opening, C.c_int(0)
+    rf, pts, ys, proof = _verifier_inputs(op, roots, op.ys, points, k=op.k)
+    L.check(L.lib().zk_fri_ml_verify_batch_wide_pow(op.field, rf, op.k, op.d, op.log_blowup, op.log_final, op.nqueries, op.log_arity,
+                                                    2 if op.grouped else 0, op._coset(), L.p64(pts), pts.shape[0], L.p64(ys), _handle(transcript), *proof,
+                                                    getattr(op, "grinding_bits", 0), getattr(op, "pow_nonce", 0), C.byref(ok)))
+    return bool(ok.value)
+
+
 def ml_last_stats():
     """milliseconds of the calling thread's last open_multilinear / open_multilinear_points: the sumcheck's passes, the codeword folds, the trees, the query gather"""
     st = _MlStats()

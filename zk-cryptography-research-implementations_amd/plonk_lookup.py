@@ -1,0 +1,128 @@
+"""A Plonk proof with lookup rows over FRI commitments: gate, wiring, public inputs and a lookup into a committed table in ONE sumcheck with ONE
+opening (include/zkmle.h "Plonk with lookups: gate, wiring, public inputs and lookup rows in one sumcheck").
+
+  `prove(wires, selectors, sigmas, lookup_selector, table, public_inputs, ..)` proves for the fifteen committed tables A, B, C, qM, qL, qR, qO,
+  qC, SA, SB, SC, qK, T0, T1, T2 what zk.plonk.prove proves for the first eleven and what zk.lookup.prove proves for A, B, C, qK, T0, T1, T2:
+  the gate with the public inputs on the first rows, the wiring, and that every row with qK = 1 is a row of the table.  The multiplicities, the
+  wiring's three helper tables and the lookup's one are computed and committed on the GPU, one sumcheck whose round is one fused pass over
+  twenty-one tables (csrc/plonk_lookup.cuh) proves all three parts, and ONE wide batch opening of the twenty commitments
+  (fri.open_multilinear_batch_wide) at the point the rounds leave ends the proof, all on one transcript.  The prover does not check the
+  statement: a false one gets a proof that does not verify, and `last_stats()["misses"]` counts the rows whose triple is in no table row.
+  `verify` is host code and needs nothing but the fifteen roots and the public values.  `round` is the kernel on its own.  `table_columns` and
+  `sigma_from_cycles` are zk.lookup's and zk.wiring's.  Proving runs on the GPU (there is no CPU path)."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from . import fri
+from .lookup import _Stats, table_columns  # noqa: F401
+from .mle import MultilinearPolynomial, _elem, limbs
+from .plonk import _public
+from .wiring import sigma_from_cycles  # noqa: F401
+
+WIRES, SELECTORS, COLUMNS, GIVEN, HELPERS, OPENED, TABLES, NODES = 3, 5, 3, 15, 5, 20, 21, 5
+ORDER = "A, B, C, qM, qL, qR, qO, qC, SA, SB, SC, qK, T0, T1, T2"
+
+
+def sizes(d, log_blowup, log_final, nqueries, log_arity=1, grouped=False):
+    """-> (nround, nhroots, nroots, nfinal, nvalues, path_bytes, nopen_round): the 5 d elements of the round polynomials, the 5 helper roots,
+    then the counts of fri.ml_sizes_wide(.., k=20), the opening of the twenty commitments"""
+    out = [C.c_size_t(0) for _ in range(7)]
+    if grouped and log_arity != 2:
+        raise ValueError("grouped leaves need log_arity=2")
+    L.check(L.lib().zk_plonk_lookup_sizes(d, log_blowup, log_final, nqueries, log_arity, 2 if grouped else 0, *[C.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+def round(tables, beta, gamma, alpha, mu, id_base=0, log_step=0, r=None):
+    """one round pass on its own; tables = (A, B, C, qM, qL, qR, qO, qC, SA, SB, SC, qK, T0, T1, T2, M, H0, H1, H2, HL, E).  r = None: -> g5
+    (5, limbs) = g(0) .. g(4) of the summand along the last variable, nothing folded.  Otherwise -> (the twenty-one tables folded by r in their
+    last variable, g5 of the folded ones).  The id tables are those of zk.wiring.round."""
+    if len(tables) != TABLES:
+        raise ValueError("the pass takes twenty-one tables: " + ORDER + ", M, H0, H1, H2, HL, E")
+    field = tables[0].field
+    g5 = np.zeros((NODES, limbs(field)), np.uint64)
+    ins = (C.c_void_p * TABLES)(*[t._h for t in tables])
+    ch = [L.p64(_elem(field, v)) for v in (beta, gamma, alpha, mu, id_base)]
+    if r is None:
+        L.check(L.lib().zk_plonk_lookup_round(ins, *ch, log_step, None, None, L.p64(g5)))
+        return g5
+    outs = (C.c_void_p * TABLES)()
+    L.check(L.lib().zk_plonk_lookup_round(ins, *ch, log_step, L.p64(_elem(field, r)), outs, L.p64(g5)))
+    return tuple(MultilinearPolynomial(field, _handle=C.c_void_p(h)) for h in outs), g5
+
+
+class PlonkLookupProof:
+    """h_roots (5, 32): the roots of M, H0, H1, H2, HL; round_polys (d, 5, limbs); ys (20, limbs) = the values of the fifteen and of M, H0, H1,
+    H2, HL at the point; opening: the fri.FriMlWideOpening of the twenty commitments there (its ys are the same array).  drawn (4 + d, limbs) =
+    beta, gamma, alpha, mu, tau and challenges (d, limbs) are what the prover's transcript gave (diagnostic: the verifier derives its own; the
+    opening's point is the challenges reversed).  The public values are the statement's, not the proof's."""
+
+    K, NODES = OPENED, NODES
+
+    def __init__(self, field, d, log_blowup, log_final, nqueries, coset=None, log_arity=1, grouped=False, grinding_bits=0):
+        n = limbs(field)
+        self.field, self.d = field, d
+        self.h_roots = np.zeros((HELPERS, 32), np.uint8)
+        self.drawn = np.zeros((4 + d, n), np.uint64)
+        self.round_polys = np.zeros((d, self.NODES, n), np.uint64)
+        self.challenges = np.zeros((d, n), np.uint64)
+        self.opening = fri.FriMlWideOpening(field, self.K, 1, d, log_blowup, log_final, nqueries, coset, log_arity, grouped, grinding_bits)
+
+    @property
+    def ys(self):
+        return self.opening.ys[:, 0]
+
+    @property
+    def point(self):
+        """(1, d, limbs): where the tables are opened"""
+        return np.ascontiguousarray(self.challenges[::-1])[None]
+
+
+def prove(wires, selectors, sigmas, lookup_selector, table, public_inputs, log_final, nqueries, log_arity=1, transcript=None, grinding_bits=0):
+    """the proof for the fifteen commitments wires = (A, B, C), selectors = (qM, qL, qR, qO, qC), sigmas = (SA, SB, SC), lookup_selector = qK and
+    table = (T0, T1, T2), all of one shape (field, size, blow-up, coset and leaf grouping; grouped ones need log_arity=2), and the public values
+    public_inputs ((l, limbs), l <= 2^d, or None).  grinding_bits: the opening's proof-of-work step"""
+    if len(wires) != WIRES or len(selectors) != SELECTORS or len(sigmas) != WIRES or len(table) != COLUMNS:
+        raise ValueError("the proof takes three wires, five selectors, three permutation tables, the lookup selector and three table columns: " + ORDER)
+    cms = tuple(wires) + tuple(selectors) + tuple(sigmas) + (lookup_selector,) + tuple(table)
+    c0 = cms[0]
+    grouped = getattr(c0, "log_group", 0) != 0
+    if grouped and log_arity != 2:
+        raise ValueError("commitments with grouped leaves are opened with log_arity=2")
+    pub, pp = _public(c0.field, public_inputs)
+    pr = PlonkLookupProof(c0.field, c0.d, c0.log_blowup, log_final, nqueries, c0.coset, log_arity, grouped, grinding_bits)
+    op, nonce = pr.opening, C.c_uint64(0)
+    arr = (C.c_void_p * GIVEN)(*[c._h for c in cms])
+    L.check(L.lib().zk_plonk_lookup_prove(arr, pp, pub.shape[0], log_final, nqueries, log_arity, grinding_bits, fri._handle(transcript), L.p8(pr.h_roots),
+                                          L.p64(pr.drawn), L.p64(pr.round_polys), L.p64(pr.challenges), *fri._prover_outputs(op), C.byref(nonce)))
+    op.pow_nonce = int(nonce.value)
+    return pr
+
+
+def verify(roots, public_inputs, proof, transcript=None):
+    """host only: `roots` = the fifteen roots (32 bytes each) in the order A, B, C, qM, qL, qR, qO, qC, SA, SB, SC, qK, T0, T1, T2;
+    public_inputs as for prove"""
+    op, ok = proof.opening, C.c_int(0)
+    if len(roots) != GIVEN:
+        raise L.ZkError(L.ZK_E_ARG, "one 32-byte Merkle root per commitment: " + ORDER)
+    hr = np.ascontiguousarray(proof.h_roots, np.uint8)
+    if hr.shape != (HELPERS, 32):
+        raise L.ZkError(L.ZK_E_ARG, "five 32-byte helper roots")
+    pub, pp = _public(op.field, public_inputs)
+    # the opening's roots and claims are those of the twenty; only the fifteen are the verifier's own
+    rf, _, ys, arrays = fri._verifier_inputs(op, list(roots) + [hr[j].tobytes() for j in range(HELPERS)], op.ys, k=proof.K)
+    rp = np.ascontiguousarray(proof.round_polys, np.uint64)
+    L.check(L.lib().zk_plonk_lookup_verify(op.field, rf, pp, pub.shape[0], op.d, op.log_blowup, op.log_final, op.nqueries, op.log_arity, 2 if op.grouped else 0,
+                                           op._coset(), fri._handle(transcript), L.p8(hr), L.p64(rp), L.p64(ys), *arrays, getattr(op, "grinding_bits", 0),
+                                           getattr(op, "pow_nonce", 0), C.byref(ok)))
+    return bool(ok.value)
+
+
+def last_stats():
+    """the calling thread's last prove: `misses` (rows with qK = 1 whose triple is in no table row) and milliseconds of the multiplicity count,
+    the four helper tables, the five commitments together, the eq table, the rounds, the opening, and the host clock over the call"""
+    st = _Stats()
+    L.check(L.lib().zk_plonk_lookup_last_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _Stats._fields_}
