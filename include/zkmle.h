@@ -188,6 +188,21 @@ int zk_mle_merkle_root_grouped(const zk_table *t, uint32_t log_group, uint8_t ro
  * to root32; an element that is not reduced gives *ok = 0.  log_group > 2 or a 48-byte field: ZK_E_ARG; index >= 2^depth: ZK_E_RANGE. */
 int zk_merkle_verify_grouped(int field, const uint8_t root32[32], size_t depth, size_t index, uint32_t log_group, const uint64_t *elements,
                              const uint8_t *path, int *ok);
+/* Merkle commitment of several columns (csrc/merkle_columns.cuh merkle_leaf_columns_kernel).  k tables ("columns") f_0 .. f_{k-1} of one
+ * scalar field (ZK_FR381 or ZK_BN254_FR) and one length len = 2^d >= 4 under ONE tree, 1 <= k <= 32.  With part = len >> 2:
+ *   leaf_j = Keccak256(0x00 || for c < k: for s < 4: bytes(f_c[j + s part])),  j < part
+ * -- 1 + 128 k bytes: each column's quad in the order of the grouped leaf with log_group = 2, behind one tag; elements canonical big-endian;
+ * the hash is the transcript's Keccak (rate 136, pad 0x01 .. 0x80), B(k) = floor((1 + 128 k) / 136) + 1 permutations a leaf.  k = 1 is the
+ * grouped quad leaf byte for byte, so a one-column tree has zk_merkle_build_grouped(t, 2)'s root.  Nodes and root are as above over `part`
+ * leaves: 2 part - 1 digests, depth d - 2, and zk_merkle_open (indices below part), zk_merkle_root, zk_merkle_depth and zk_merkle_free work
+ * on the tree as they are.  ZK_E_ARG for NULL, k outside 1 .. 32, any other field, mixed fields or len < 4, then ZK_E_LEN_MISMATCH for unequal
+ * lengths, then ZK_E_NOT_POW2, all before the device is touched. */
+int zk_merkle_build_columns(const zk_table *const *tables, uint32_t k, zk_merkle_tree **out);
+int zk_mle_merkle_root_columns(const zk_table *const *tables, uint32_t k, uint8_t root32[32]);   /* root-only mode: scratch of 64 bytes x part */
+/* HOST only: *ok = 1 when the 4 k `elements` (Montgomery limbs, in the leaf's order: column, then side) of leaf `index` hash up `path` (depth
+ * digests) to root32; an element that is not reduced gives *ok = 0.  k outside 1 .. 32 or another field: ZK_E_ARG; index >= 2^depth: ZK_E_RANGE. */
+int zk_merkle_verify_columns(int field, const uint8_t root32[32], size_t depth, size_t index, uint32_t k, const uint64_t *elements,
+                             const uint8_t *path, int *ok);
 
 /* ---- number-theoretic transform (extension: the reference's fft/ crate is empty; csrc/ntt.cuh) -------------------------------
  * The definition is arkworks' Radix2EvaluationDomain.  p - 1 = 2^s t with t odd, g the field's multiplicative generator (7 for
@@ -685,6 +700,63 @@ int zk_fri_ml_verify_batch_wide_pow(int field, const uint8_t *roots_of_f, uint32
                                     uint32_t npoints, const uint64_t *ys, zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots,
                                     const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths,
                                     uint32_t grinding_bits, uint64_t pow_nonce, int *ok);
+
+/* ---- Column commitments opened together (extension; csrc/merkle_columns.cuh, csrc/zkmle_fri_pcs.hip, csrc/zkmle_fri_ml.hip) -----------------------
+ * A commitment to a MATRIX: k tables of one field and one length n = 2^d, 1 <= k <= ZK_FRI_COLUMNS_MAX, each extended to its own codeword f_c of
+ * N = 2^(d + log_blowup) entries as zk_fri_commit does, and ONE tree over the k codewords ("Merkle commitment of several columns"): leaf j < N / 4
+ * holds the first fold's coset of every column.  One path then answers all k columns at a queried position.  k = 1 has
+ * zk_fri_commit_grouped(.., 2)'s root.
+ *   Commitment.  zk_fri_commit_columns: k clones of the tables, k codewords by the transform zk_fri_commit uses, ONE device allocation of
+ *     2 (N / 4) - 1 digests, one tree, one 32-byte download.  Statuses: ZK_E_ARG for NULL, k outside 1 .. 32, log_blowup outside 1 .. 8, a 48-byte
+ *     field, mixed fields, len = 1 or a zero coset; ZK_E_LEN_MISMATCH for unequal lengths; ZK_E_NOT_POW2; ZK_E_RANGE for a field without a domain
+ *     or d + log_blowup beyond its two-adicity; then the device.  The accessors give the device views (not owned by the caller) a prover runs
+ *     its rounds on.
+ *   Opening.  m column commitments of widths w_0 .. w_{m-1}, K = sum w_i <= ZK_FRI_ML_WIDE_MAX, one field, d, log_blowup and coset, all K columns
+ *     opened as multilinear polynomials at the same P <= 8 points with one proof.  The protocol is "FRI commitments opened together" at
+ *     log_arity = 2 with grouped leaves (R = d - log_final >= 2), changed only as follows.
+ *     Transcript.  After the 48-byte header: the ASCII tag "COLS", then 2 (the arity), m and the m widths, each a big-endian u32, one append; then
+ *       the m roots; then P, the points and the K P claims in global column order (commitment, then column, then point); gamma.  The coefficient
+ *       of y_{c,p} is gamma^(c P + p) over the global column index c; alpha = gamma^P, T = sum_c alpha^c T_c, f_0 = sum_c alpha^c f_c.  The rounds,
+ *       the later roots, T_R, the proof-of-work step and the indices (mod N / 4) are the grouped batch opening's.
+ *     Step 0 of a query.  Values: 4 K elements, column-major then side.  Paths: m paths of d + log_blowup - 2 digests in commitment order, the
+ *       sibling of leaf i_q first.  Later steps are unchanged.
+ *     roots.  The m commitment roots first, then the later layers'.
+ *     Counts.  nroots = m + (the single grouped form's - 1); nvalues = its + 4 Q (K - 1); path_bytes = its + 32 Q (L - 2)(m - 1); nfinal and nround
+ *       are unchanged.
+ *   Verifier (HOST only).  fri_verify_core: at step 0 it hashes each commitment's 4 w_i values into the leaf (zk_merkle_verify_columns), climbs
+ *     its one path to root_i and forms u_s = sum_c alpha^c v_{c,s}; it carries on as the grouped batch verifier.  The proof's first m roots must
+ *     be the verifier's own; anything unreduced gives *ok = 0 with ZK_OK; every status is decided before the transcript moves: ZK_E_ARG for NULL,
+ *     m = 0, a zero width, K > 32, P outside 1 .. 8, R < 2 and zk_fri_ml_verify_batch_wide_pow's others, ZK_E_RANGE as there.
+ *   Prover.  The batch driver with its table and codeword pointers taken from the columns; the first fold is the batch opening's kernel.  Step-0
+ *     values are gathered per column, step-0 paths once per commitment.  All commitments must share field, d, log_blowup and coset (ZK_E_ARG).
+ *     zk_fri_ml_last_stats reports the call. */
+typedef struct zk_fri_columns zk_fri_columns;
+#define ZK_FRI_COLUMNS_MAX 32
+int zk_fri_commit_columns(const zk_table *const *tables, uint32_t k, uint32_t log_blowup, const uint64_t *coset, zk_fri_columns **out);
+int zk_fri_columns_free(zk_fri_columns *cm);
+int zk_fri_columns_root(const zk_fri_columns *cm, uint8_t root32[32]);                       /* host copy */
+uint32_t zk_fri_columns_count(const zk_fri_columns *cm);                                     /* k; 0 for NULL */
+int zk_fri_columns_table(const zk_fri_columns *cm, uint32_t j, const zk_table **out);        /* column j's table; j >= k: ZK_E_RANGE */
+int zk_fri_columns_codeword(const zk_fri_columns *cm, uint32_t j, const zk_table **out);     /* column j's codeword */
+typedef struct {
+    uint32_t columns;
+    float ms_extend, ms_leaves, ms_nodes;   /* the k transforms, the leaf launch, the node launches (events) */
+    float ms_total;                         /* host wall clock of the call */
+} zk_fri_columns_stats;
+int zk_fri_columns_last_stats(zk_fri_columns_stats *out);
+/* host: the counts above */
+int zk_fri_ml_sizes_columns(const uint32_t *widths, uint32_t m, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots,
+                            size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround);
+/* ys_out: K x npoints elements; roots: nroots x 32 bytes; the other outputs as zk_fri_ml_open_batch_pow's, sized by zk_fri_ml_sizes_columns */
+int zk_fri_ml_open_columns_pow(const zk_fri_columns *const *cms, uint32_t m, const uint64_t *points, uint32_t npoints, uint32_t log_final,
+                               uint32_t nqueries, uint32_t grinding_bits, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out,
+                               uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices,
+                               uint64_t *query_values, uint8_t *query_paths, uint64_t *pow_nonce);
+/* HOST only.  roots_of_f: the m commitments' roots */
+int zk_fri_ml_verify_columns_pow(int field, const uint8_t *roots_of_f, const uint32_t *widths, uint32_t m, uint32_t d, uint32_t log_blowup,
+                                 uint32_t log_final, uint32_t nqueries, uint32_t grinding_bits, const uint64_t *coset, const uint64_t *points,
+                                 uint32_t npoints, const uint64_t *ys, zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots,
+                                 const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint64_t pow_nonce, int *ok);
 
 /* ---- Zerocheck of a product of committed tables (extension; csrc/zerocheck.cuh, csrc/zerocheck_host.h, csrc/zkmle_zerocheck.hip) --------------------
  * The simplest non-linear statement over the commitment above: three commitments cmA, cmB, cmC (zk_fri_commit / zk_fri_commit_grouped; one

@@ -55,6 +55,7 @@ def lib():
     L.zk_table_device_ptr.restype = vp
     L.zk_merkle_depth.restype = sz
     L.zk_fri_commitment_log_group.restype = C.c_uint32
+    L.zk_fri_columns_count.restype = C.c_uint32
     sigs = {
         "zk_device_count": [C.POINTER(C.c_int)],
         "zk_init": [C.c_int],
@@ -174,6 +175,21 @@ def lib():
                                                                                                C.c_uint32, u64p],
         "zk_fri_ml_verify_batch_wide_pow": [C.c_int, u8p] + [C.c_uint32] * 7 + [u64p, u64p, C.c_uint32, u64p, vp, u64p, u8p, u64p, u64p, u8p, C.c_uint32,
                                                                                C.c_uint64, C.POINTER(C.c_int)],
+        # column commitments: several tables under one tree, opened together
+        "zk_merkle_build_columns": [C.POINTER(vp), C.c_uint32, C.POINTER(vp)],
+        "zk_mle_merkle_root_columns": [C.POINTER(vp), C.c_uint32, u8p],
+        "zk_merkle_verify_columns": [C.c_int, u8p, sz, sz, C.c_uint32, u64p, u8p, C.POINTER(C.c_int)],
+        "zk_fri_commit_columns": [C.POINTER(vp), C.c_uint32, C.c_uint32, u64p, C.POINTER(vp)],
+        "zk_fri_columns_free": [vp],
+        "zk_fri_columns_root": [vp, u8p],
+        "zk_fri_columns_count": [vp],
+        "zk_fri_columns_table": [vp, C.c_uint32, C.POINTER(vp)],
+        "zk_fri_columns_codeword": [vp, C.c_uint32, C.POINTER(vp)],
+        "zk_fri_columns_last_stats": [vp],
+        "zk_fri_ml_sizes_columns": [C.POINTER(C.c_uint32)] + [C.c_uint32] * 5 + [C.POINTER(sz)] * 5,
+        "zk_fri_ml_open_columns_pow": [C.POINTER(vp), C.c_uint32, u64p] + [C.c_uint32] * 4 + [vp, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
+        "zk_fri_ml_verify_columns_pow": [C.c_int, u8p, C.POINTER(C.c_uint32)] + [C.c_uint32] * 6 + [u64p, u64p, C.c_uint32, u64p, vp, u64p, u8p, u64p, u64p, u8p,
+                                                                                                   C.c_uint64, C.POINTER(C.c_int)],
         # zerocheck of a product of committed tables
         "zk_zerocheck_mul_round": [vp, vp, vp, vp, u64p, C.POINTER(vp), u64p],
         "zk_zerocheck_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 6,

@@ -90,6 +90,17 @@ struct zk_fri_commitment {
     unsigned log_group;              // 0, or 2: a leaf per coset of the first fold by 4 (zk_fri_commit_grouped).  Who walks `levels` as 2 N - 1 digests refuses the latter
 };
 
+// the prover's side of a commitment to k columns under ONE tree (zkmle_fri_pcs.hip makes and frees it; zkmle_fri_ml.hip opens several together)
+struct zk_fri_columns {
+    int field;
+    unsigned d, b, k;
+    bool has_coset;
+    uint64_t coset[4];
+    zk_table *coeffs[ZK_FRI_COLUMNS_MAX], *codeword[ZK_FRI_COLUMNS_MAX];   // long-lived tables of their own, k of each
+    uint64_t *levels;                // 2 (N / 4) - 1 digests (ONE hipMalloc), zk_merkle_build_columns' layout
+    uint8_t root[32];
+};
+
 namespace zk {
 class Transcript;
 // transcript.append(convert_to_bytes(table)) (evaluation_form.rs:35-43, prover.rs:38-39): the GPU converts Montgomery ->
@@ -103,6 +114,13 @@ int merkle_levels_device(const zk_table *t, uint64_t *levels);
 // the same with grouped leaves (merkle.cuh; log_group <= 2, 32-byte elements, len >= 2^log_group): 2 (len >> log_group) - 1 digests, zk_merkle_build_grouped's
 // layout; launches only, no checks.  log_group = 0 is merkle_levels_device
 int merkle_levels_grouped_device(const zk_table *t, unsigned log_group, uint64_t *levels);
+// several columns under one tree (merkle_columns.cuh; the two scalar fields): merkle_columns_check gives the statuses that need no device --
+// ZK_E_ARG for a null, k outside 1 .. 32, another field, mixed fields or len < min_len, ZK_E_LEN_MISMATCH, ZK_E_NOT_POW2 -- the others are launches
+// only, no checks: the len >> 2 leaves into `levels`, the nodes above `leaves` digests (zk_merkle_build_grouped's layout), and both
+int merkle_columns_check(const zk_table *const *tables, uint32_t k, size_t min_len = 4);
+int merkle_leaves_columns_device(const zk_table *const *tables, uint32_t k, uint64_t *levels);
+int merkle_nodes_device(uint64_t *levels, size_t leaves);
+int merkle_levels_columns_device(const zk_table *const *tables, uint32_t k, uint64_t *levels);
 // zk_uni_low_degree_extend into a table the caller allocated (out->len = coeffs->len << log_blowup); launches only, no checks (zkmle_ntt.hip)
 int ntt_extend_into(const zk_table *coeffs, const uint64_t *coset, zk_table *out);
 // zk_fri_verify's checks and body on a caller's Transcript; indices_out (nqueries words, may be null) receives the sampled query indices
@@ -122,7 +140,17 @@ struct FriMlClaim {
     // `roots` starts with the k commitments' roots (the verifier's own copies), the later layers' behind them; a query's step 0 holds the k
     // commitments' values and paths, j-major, and the step's values are their alpha-combination, alpha = gamma^npoints.  0: one table, as before
     uint32_t ntables = 0;
+    // ncommit > 0: COLUMN commitments opened together ("Column commitments opened together"; needs log_arity = 2, grouped and ntables = the sum
+    // of the widths): `widths` holds the ncommit widths, `roots` starts with the ncommit roots, the statement carries "COLS", and a query's step 0
+    // holds the ntables columns' values as ever but ONE path per commitment, whose leaf is hashed from that commitment's 4 w_i values
+    const uint32_t *widths = nullptr;
+    uint32_t ncommit = 0;
 };
+// zk_fri_ml_open_columns_pow's own statuses (zkmle_fri_ml.hip), every ZK_E_ARG and then ZK_E_NO_DEVICE, as fri_ml_open_batch_check for a prover
+// that runs rounds of its own before it opens column commitments
+int fri_ml_open_columns_check(const zk_fri_columns *const *cms, uint32_t m, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                              const uint64_t *ys_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *query_values,
+                              uint8_t *query_paths, uint32_t grinding_bits, const uint64_t *pow_nonce);
 // grind_bits > 0: the proof-of-work step (include/zkmle.h "Proof-of-work grinding") with the nonce pow_nonce stands between the final
 // coefficients and the indices; a nonce that fails it gives *ok = 0.  grind_bits > ZK_FRI_GRIND_MAX_BITS: ZK_E_ARG
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,

@@ -180,9 +180,19 @@ template <class F> Replayed<F> replay(uint32_t d, uint32_t b, uint32_t f, uint32
     };
     uint8_t cbe[32], be[16] = {'B', 'T', 'C', 'H'};
     const unsigned nt = ml ? ml->ntables : 0;                 // commitments opened together: their roots lead `roots`
+    const unsigned nc = ml ? ml->ncommit : 0;                 // column commitments: nc roots lead, over nt columns
+    const unsigned lead = nc ? nc : nt;
     host_to_bytes_be<F>(coset ? load_host<F>(coset) : fe_one<F>(), cbe);
     transcript_header(tr, d, b, f, Q, cbe);
-    if (nt) {                                                // the tag, the arity, the grouped flag, k; the k roots
+    if (nc) {                                                // "COLS", the arity, m, the m widths; the m roots
+        std::vector<uint8_t> line(12 + 4 * (size_t)nc);
+        memcpy(line.data(), "COLS", 4);
+        put_be32(line.data() + 4, sc.log_arity);
+        put_be32(line.data() + 8, nc);
+        for (unsigned i = 0; i < nc; i++) put_be32(line.data() + 12 + 4 * i, ml->widths[i]);
+        tr.append(line.data(), line.size());
+        tr.append(roots, (size_t)32 * nc);
+    } else if (nt) {                                         // the tag, the arity, the grouped flag, k; the k roots
         put_be32(be + 4, sc.log_arity);
         put_be32(be + 8, sc.grouped ? 1 : 0);
         put_be32(be + 12, nt);
@@ -211,7 +221,7 @@ template <class F> Replayed<F> replay(uint32_t d, uint32_t b, uint32_t f, uint32
     for (unsigned l = 0, s = 0; l < R; l++) {
         for (unsigned k = 0; ml && k < 3; k++) absorb(ml->round_polys + ((size_t)l * 3 + k) * W);   // g_l(0), g_l(1), g_l(2)
         rp.beta[l] = tr.random_challenge_as_field_element<F>();
-        if (s + 1 < sc.nsteps && sc.step[s + 1].layer == l + 1) tr.append(roots + 32 * (size_t)(sc.step[++s].root + (nt ? nt - 1 : 0)), 32);   // layer l + 1 is committed
+        if (s + 1 < sc.nsteps && sc.step[s + 1].layer == l + 1) tr.append(roots + 32 * (size_t)(sc.step[++s].root + (lead ? lead - 1 : 0)), 32);   // layer l + 1 is committed
     }
     for (size_t j = 0; j < (size_t)1 << f; j++) rp.h.push_back(absorb(final_coeffs + j * W));
     if (grind_bits) {                                        // the proof-of-work step: the tag, the nonce, the challenge and its leading bits
@@ -268,8 +278,11 @@ template <class F> bool sumcheck_holds(uint32_t d, uint32_t f, const FriMlClaim 
 // fold of the multilinear forms, (1 - r) (a + b) / 2 + r (a - b) / (2 x); else the monomial (a + b) / 2 + r (a - b) / (2 x)
 // `nt` > 0 (commitments opened together): step 0 of a query holds the nt commitments' values and paths one commitment after the other, each
 // checked against its own root (roots[j]); the step's values are u_side = sum_j alpha^j v_{j,side}; the later steps' roots follow the nt
+// `widths` (nc of them, together nt; column commitments opened together): step 0 holds the nt columns' values but ONE path per commitment, whose
+// leaf is hashed from that commitment's columns' values (zk_merkle_verify_columns), and nc roots lead
 template <class F> int queries_hold(const FriSchedule &sc, unsigned R, bool lagrange, const Fe<F> &c, const Replayed<F> &rp, const uint8_t *roots,
-                                    const uint64_t *values, const uint8_t *paths, int *ok, unsigned nt = 0, const Fe<F> &alpha = fe_one<F>()) {
+                                    const uint64_t *values, const uint8_t *paths, int *ok, unsigned nt = 0, const Fe<F> &alpha = fe_one<F>(),
+                                    const uint32_t *widths = nullptr, unsigned nc = 0) {
     constexpr int W = F::N / 2;
     const unsigned L = sc.step[0].log_len;
     const Fe<F> w = root_of_unity<F>(L), winv = fe_inv<F>(w), inv2 = fe_inv<F>(fe_from_u64<F>(2));
@@ -288,7 +301,7 @@ template <class F> int queries_hold(const FriSchedule &sc, unsigned R, bool lagr
     };
     // step 0's share of one query's answer, and what the further commitments add in front of the later steps
     const size_t v0 = sc.nsteps > 1 ? sc.step[1].val_off : sc.nvalues, d0 = sc.nsteps > 1 ? sc.step[1].path_off : sc.ndigests;
-    const size_t more = nt ? nt - 1 : 0, more_v = more * v0, more_d = more * d0;
+    const size_t more = nt ? nt - 1 : 0, more_r = nc ? nc - 1 : more, more_v = more * v0, more_d = more_r * d0;
     for (size_t q = 0; q < rp.idx.size(); q++) {
         const uint64_t *vq = values + q * (sc.nvalues + more_v) * W;
         const uint8_t *pq = paths + q * (sc.ndigests + more_d) * 32;
@@ -297,10 +310,18 @@ template <class F> int queries_hold(const FriSchedule &sc, unsigned R, bool lagr
             const unsigned l = st.layer, sides = 1u << st.log_sides;
             const size_t part = ((size_t)1 << st.log_len) >> st.log_sides, j = rp.idx[q] & (part - 1);
             Fe<F> e[4] = {fe_zero<F>(), fe_zero<F>(), fe_zero<F>(), fe_zero<F>()}, aj = fe_one<F>();
+            if (nc && s == 0) {                               // each commitment's leaf over its columns' values, and its one path
+                size_t col = 0;
+                for (unsigned i = 0; i < nc; col += widths[i], i++) {
+                    int ok_s = 0;
+                    ZK_TRY(zk_merkle_verify_columns(F::ID, roots + 32 * (size_t)i, st.log_len - st.log_sides, j, widths[i], vq + col * v0 * W, pq + 32 * i * d0, &ok_s));
+                    if (!ok_s) return ZK_OK;
+                }
+            }
             for (size_t tb = 0; tb < (s == 0 ? more + 1 : 1); tb++) {   // the commitments of step 0; one table otherwise
                 const uint64_t *v = vq + (st.val_off + (s ? more_v : tb * v0)) * W;
-                const uint8_t *pt = pq + 32 * (st.path_off + (s ? more_d : tb * d0)), *root = roots + 32 * (s ? st.root + more : tb);
-                if (sc.grouped) {                             // one leaf over the step's sides, one path
+                const uint8_t *pt = pq + 32 * (st.path_off + (s ? more_d : tb * d0)), *root = roots + 32 * (s ? st.root + more_r : tb);
+                if (sc.grouped && !(nc && s == 0)) {                             // one leaf over the step's sides, one path
                     int ok_s = 0;
                     ZK_TRY(zk_merkle_verify_grouped(F::ID, root, st.log_len - st.log_sides, j, st.log_sides, v, pt, &ok_s));
                     if (!ok_s) return ZK_OK;
@@ -344,7 +365,8 @@ template <class F> int verify_host(uint32_t d, uint32_t b, uint32_t f, uint32_t 
     if (!rp.good || (ml && !sumcheck_holds<F>(d, f, *ml, rp))) return ZK_OK;
     Fe<F> alpha = fe_one<F>();                                // gamma^P
     for (unsigned p = 0; nt && p < ml->npoints; p++) alpha = fe_mul<F>(alpha, rp.gamma);
-    return queries_hold<F>(sc, d - f, ml != nullptr, coset ? load_host<F>(coset) : fe_one<F>(), rp, roots, values, paths, ok, nt, alpha);
+    return queries_hold<F>(sc, d - f, ml != nullptr, coset ? load_host<F>(coset) : fe_one<F>(), rp, roots, values, paths, ok, nt, alpha, ml ? ml->widths : nullptr,
+                           ml ? ml->ncommit : 0);
 }
 
 }  // namespace
@@ -358,6 +380,15 @@ int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_fin
     if (ml && (ml->log_arity < 1 || ml->log_arity > 2 || (ml->log_arity == 2 && (ml->npoints < 1 || log_final >= d || d - log_final < 2)))) return ZK_E_ARG;
     if (ml && ml->grouped && ml->log_arity != 2) return ZK_E_ARG;
     if (ml && (ml->ntables > max_tables || (ml->ntables && ml->npoints < 1))) return ZK_E_ARG;
+    if (ml && ml->ncommit) {                                 // column commitments: grouped leaves, and the widths make up the tables
+        if (!ml->widths || !ml->grouped || ml->ncommit > ml->ntables) return ZK_E_ARG;
+        size_t total = 0;
+        for (uint32_t i = 0; i < ml->ncommit; i++) {
+            if (ml->widths[i] < 1 || ml->widths[i] > ZK_FRI_COLUMNS_MAX) return ZK_E_ARG;
+            total += ml->widths[i];
+        }
+        if (total != ml->ntables) return ZK_E_ARG;
+    }
     if (!roots || !final_coeffs || !query_values || !query_paths || !ok || field_limbs64(field) < 0) return ZK_E_ARG;
     ZK_TRY(params_check(log_blowup, nqueries));
     if (coset && is_zero_element(field, coset)) return ZK_E_ARG;

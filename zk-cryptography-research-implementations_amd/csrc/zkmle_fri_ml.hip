@@ -331,36 +331,70 @@ template <class F> struct ManyTables : ManyPoints<F> {
     using Base = ManyPoints<F>;
     static constexpr int W = F::N / 2;
     static constexpr bool kBatch = true;
-    const zk_fri_commitment *const *cms;
-    uint32_t k;
+    // the k tables and their codewords; the m trees they sit under and their roots: m = k, one each, for k commitments; for m COLUMN
+    // commitments ("Column commitments opened together") the k columns of all of them in order, and `widths` (else null) = the m widths
+    const zk_table *tabs[kFriMlWideMax];
+    const void *cws[kFriMlWideMax];
+    const uint64_t *trees[kFriMlWideMax];
+    const uint8_t *own_roots[kFriMlWideMax];
+    uint32_t k, m;
+    const uint32_t *widths = nullptr;
     Fe<F> coef[kFriMlWideMax];                               // alpha^j
     void *table0 = nullptr;                                  // T_0's n elements of the pool block: the driver sets it before start
 
     ManyTables(const zk_fri_commitment *const *cms_, uint32_t k_, const uint64_t *pts_, uint32_t P_, uint64_t *ys, uint64_t *gamma, unsigned d_)
-        : Base{pts_, P_, ys, gamma, d_, {}}, cms(cms_), k(k_) {}
+        : Base{pts_, P_, ys, gamma, d_, {}}, k(k_), m(k_) {
+        for (uint32_t j = 0; j < k; j++) {
+            tabs[j] = cms_[j]->coeffs;
+            cws[j] = cms_[j]->codeword->dptr;
+            trees[j] = cms_[j]->levels;
+            own_roots[j] = cms_[j]->root;
+        }
+    }
+    // widths_: m words that outlive the form
+    ManyTables(const zk_fri_columns *const *cols, uint32_t m_, const uint32_t *widths_, const uint64_t *pts_, uint32_t P_, uint64_t *ys, uint64_t *gamma, unsigned d_)
+        : Base{pts_, P_, ys, gamma, d_, {}}, k(0), m(m_), widths(widths_) {
+        for (uint32_t i = 0; i < m; i++) {
+            trees[i] = cols[i]->levels;
+            own_roots[i] = cols[i]->root;
+            for (uint32_t c = 0; c < cols[i]->k; c++, k++) {
+                tabs[k] = cols[i]->coeffs[c];
+                cws[k] = cols[i]->codeword[c]->dptr;
+            }
+        }
+    }
     unsigned ntables() const { return k; }
+    unsigned nroots() const { return m; }
     size_t weight_room(size_t n) const { return Base::weight_room(n) + n; }   // the base's, then T_0
     size_t table0_off(size_t n) const { return Base::weight_room(n); }        // in elements from the weights
-    // "BTCH", a, the grouped flag, k; the k roots, which are also the proof's first k
+    // "BTCH", a, the grouped flag, k -- columns: "COLS", a, m, the m widths -- then the m roots, which are also the proof's first m
     void statement(Transcript &tr, unsigned la, bool grouped, uint8_t *roots) const {
-        uint8_t tag[16] = {'B', 'T', 'C', 'H'};
+        uint8_t tag[12 + 4 * kFriMlWideMax] = {'B', 'T', 'C', 'H'};
+        size_t len = 16;
         put_be32(tag + 4, la);
-        put_be32(tag + 8, grouped ? 1 : 0);
-        put_be32(tag + 12, k);
-        tr.append(tag, sizeof tag);
-        for (uint32_t j = 0; j < k; j++) {
-            memcpy(roots + 32 * (size_t)j, cms[j]->root, 32);
-            tr.append(cms[j]->root, 32);
+        if (widths) {
+            memcpy(tag, "COLS", 4);
+            put_be32(tag + 8, m);
+            for (uint32_t i = 0; i < m; i++) put_be32(tag + 12 + 4 * i, widths[i]);
+            len = 12 + 4 * (size_t)m;
+        } else {
+            put_be32(tag + 8, grouped ? 1 : 0);
+            put_be32(tag + 12, k);
+        }
+        tr.append(tag, len);
+        for (uint32_t j = 0; j < m; j++) {
+            memcpy(roots + 32 * (size_t)j, own_roots[j], 32);
+            tr.append(own_roots[j], 32);
         }
     }
     // y_{j,p} table-major, a pass each; gamma; W_0; T_0 = sum_j alpha^j T_j in one pass; round 0's pass on T_0 and W_0
-    int start(const zk_fri_commitment *, Transcript &tr, const PassMem &m) {
+    int start(const zk_fri_commitment *, Transcript &tr, const PassMem &mem) {
         const unsigned P = this->P, d = this->d;
         const size_t n = (size_t)1 << d;
         for (uint32_t j = 0; j < k; j++) {
             for (unsigned p = 0; p < P; p++) {
                 uint64_t *y = this->ys_out + ((size_t)j * P + p) * W;
-                ZK_TRY(zk_mle_evaluate(cms[j]->coeffs, this->pts + (size_t)p * d * W, d, y));
+                ZK_TRY(zk_mle_evaluate(tabs[j], this->pts + (size_t)p * d * W, d, y));
                 tr.append_be<F>(load_host<F>(y));
             }
         }
@@ -368,33 +402,32 @@ template <class F> struct ManyTables : ManyPoints<F> {
         if (this->gamma_out) store_host<F>(this->gamma_out, gamma);
         Fe<F> alpha = fe_one<F>();
         for (unsigned p = 0; p < P; p++) alpha = fe_mul<F>(alpha, gamma);
-        const void *tabs[kFriMlWideMax];
+        const void *src[kFriMlWideMax];
         uint64_t cw[kFriMlWideMax * W];
         Fe<F> aj = fe_one<F>();
         for (uint32_t j = 0; j < k; j++) {
             coef[j] = aj;
             store_host<F>(cw + (size_t)j * W, aj);
-            tabs[j] = cms[j]->coeffs->dptr;
+            src[j] = tabs[j]->dptr;
             aj = fe_mul<F>(aj, alpha);
         }
-        ZK_TRY(this->weights(gamma, m));
-        ZK_HIP((lincomb_launch<F, false>(tabs, k, cw, table0, n, fe_zero<F>(), fe_zero<F>(), nullptr, cur_stream())));
-        return Base::pass(false, m.T0, m.weights, nullptr, nullptr, n / 2, fe_one<F>(), m.partials, m.sums);
+        ZK_TRY(this->weights(gamma, mem));
+        ZK_HIP((lincomb_launch<F, false>(src, k, cw, table0, n, fe_zero<F>(), fe_zero<F>(), nullptr, cur_stream())));
+        return Base::pass(false, mem.T0, mem.weights, nullptr, nullptr, n / 2, fe_one<F>(), mem.partials, mem.sums);
     }
     // layer 0 -> the layer of step 1: out gets len / 2 entries (g1 null) or len / 4
     int fold0(void *out, size_t len, const FoldTables<F> &tb, const Fe<F> &g0, const Fe<F> *g1, const Fe<F> *shift) const {
-        const void *cws[kFriMlWideMax];
-        for (uint32_t j = 0; j < k; j++) cws[j] = cms[j]->codeword->dptr;
         return launch_fold_batch<F>(cws, k, coef, out, len, tb, g0, g1, shift);
     }
 };
 
-// The queries of an opening of k commitments.  Step 0 has no table and no tree of its own: its answers are the k commitments', gathered by
+// The queries of an opening of k tables under m trees (k commitments: m = k, a tree each; column commitments: the k columns of m trees, whose
+// leaves hold every column of theirs, so step 0 has k tables' values and m paths).  Step 0 has no table and no tree of its own: its answers are the k commitments', gathered by
 // the existing kernels once per commitment over a one-step view of the schedule, and once more over the steps from 1 up; every launch
 // writes its own part of one device block and the host lays a query's answer out as the protocol orders it (j-major for step 0, then the
 // later steps).  The alternative, a table of layer-0 sources inside FriLayers, would add 32 pointers to the argument block of both kernels
 // and a branch to every lane of the single-table provers for the sake of k - 1 small launches here.
-template <class F> int answer_queries_batch(Transcript &tr, const zk_fri_commitment *const *cms, unsigned k, const FriLayers &fl, const FriSchedule &sc, uint32_t Q,
+template <class F> int answer_queries_batch(Transcript &tr, const void *const *cws, unsigned k, const uint64_t *const *trees, unsigned m, const FriLayers &fl, const FriSchedule &sc, uint32_t Q,
                                             uint64_t *indices_out, uint64_t *values, uint8_t *paths, Events &ev, float *ms, uint32_t grind_bits = 0,
                                             uint64_t *nonce_out = nullptr) {
     constexpr size_t ESZ = sizeof(Fe<F>);
@@ -410,7 +443,7 @@ template <class F> int answer_queries_batch(Transcript &tr, const zk_fri_commitm
         rest.table[s - 1] = fl.table[s];
         rest.tree[s - 1] = fl.tree[s];
     }
-    const size_t nval = (size_t)Q * (k * v0 + v1), ndig = (size_t)Q * (k * d0 + d1);
+    const size_t nval = (size_t)Q * (k * v0 + v1), ndig = (size_t)Q * (m * d0 + d1);
     DevBuf didx, dval, dpath;
     ZK_TRY(didx.alloc(Q * 8));
     ZK_TRY(dval.alloc(nval * ESZ));
@@ -420,21 +453,22 @@ template <class F> int answer_queries_batch(Transcript &tr, const zk_fri_commitm
     size_t q0, q1;
     ZK_TRY(ev.mark(&q0));
     ZK_HIP(hipMemcpyAsync(didx.p, idx.data(), Q * 8, hipMemcpyHostToDevice, cur_stream()));
+    // nv or nd = 0: that kernel is not launched
     const auto gather = [&](const FriLayers &view, size_t nv, size_t nd, size_t voff, size_t doff) -> int {
-        fri_query_values_kernel<F><<<(unsigned)((nv + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(view, (const uint64_t *)didx.p, Q, (char *)dval.p + voff * ESZ);
+        if (nv) fri_query_values_kernel<F><<<(unsigned)((nv + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(view, (const uint64_t *)didx.p, Q, (char *)dval.p + voff * ESZ);
         ZK_HIP(hipGetLastError());
-        fri_query_paths_kernel<<<(unsigned)((nd + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(view, (const uint64_t *)didx.p, Q, (uint64_t *)((char *)dpath.p + doff * 32));
+        if (nd) fri_query_paths_kernel<<<(unsigned)((nd + kFriBlock - 1) / kFriBlock), kFriBlock, 0, cur_stream()>>>(view, (const uint64_t *)didx.p, Q, (uint64_t *)((char *)dpath.p + doff * 32));
         ZK_HIP(hipGetLastError());
         return ZK_OK;
     };
     // the downloads land in this function's own buffers: whatever fails below, the stream is drained before they go
     const auto run = [&]() -> int {
-        for (unsigned j = 0; j < k; j++) {
-            first.table[0] = cms[j]->codeword->dptr;
-            first.tree[0] = cms[j]->levels;
-            ZK_TRY(gather(first, (size_t)Q * v0, (size_t)Q * d0, (size_t)j * Q * v0, (size_t)j * Q * d0));
+        for (unsigned j = 0; j < k; j++) {                    // m <= k: table j's values, and tree j's paths while there is one
+            first.table[0] = cws[j];
+            first.tree[0] = trees[j < m ? j : 0];
+            ZK_TRY(gather(first, (size_t)Q * v0, j < m ? (size_t)Q * d0 : 0, (size_t)j * Q * v0, (size_t)j * Q * d0));
         }
-        if (sc.nsteps > 1) ZK_TRY(gather(rest, (size_t)Q * v1, (size_t)Q * d1, (size_t)k * Q * v0, (size_t)k * Q * d0));
+        if (sc.nsteps > 1) ZK_TRY(gather(rest, (size_t)Q * v1, (size_t)Q * d1, (size_t)k * Q * v0, (size_t)m * Q * d0));
         ZK_HIP(hipMemcpyAsync(hval.data(), dval.p, nval * ESZ, hipMemcpyDeviceToHost, cur_stream()));
         ZK_HIP(zk::memcpy_on_stream(hpath.data(), dpath.p, ndig * 32, hipMemcpyDeviceToHost));
         ZK_TRY(ev.mark(&q1));
@@ -447,14 +481,12 @@ template <class F> int answer_queries_batch(Transcript &tr, const zk_fri_commitm
         return rc;
     }
     if (ms) *ms = ev.ms(q0, q1);
-    const size_t pv = k * v0 + v1, pd = k * d0 + d1;          // of one query's answer
+    const size_t pv = k * v0 + v1, pd = m * d0 + d1;          // of one query's answer
     for (size_t q = 0; q < Q; q++) {
-        for (unsigned j = 0; j < k; j++) {
-            memcpy((char *)values + (q * pv + j * v0) * ESZ, (const char *)hval.data() + ((size_t)j * Q + q) * v0 * ESZ, v0 * ESZ);
-            memcpy(paths + (q * pd + j * d0) * 32, hpath.data() + ((size_t)j * Q + q) * d0 * 32, d0 * 32);
-        }
+        for (unsigned j = 0; j < k; j++) memcpy((char *)values + (q * pv + j * v0) * ESZ, (const char *)hval.data() + ((size_t)j * Q + q) * v0 * ESZ, v0 * ESZ);
+        for (unsigned j = 0; j < m; j++) memcpy(paths + (q * pd + j * d0) * 32, hpath.data() + ((size_t)j * Q + q) * d0 * 32, d0 * 32);
         memcpy((char *)values + (q * pv + k * v0) * ESZ, (const char *)hval.data() + ((size_t)k * Q * v0 + q * v1) * ESZ, v1 * ESZ);
-        memcpy(paths + (q * pd + k * d0) * 32, hpath.data() + ((size_t)k * Q * d0 + q * d1) * 32, d1 * 32);
+        memcpy(paths + (q * pd + m * d0) * 32, hpath.data() + ((size_t)m * Q * d0 + q * d1) * 32, d1 * 32);
     }
     return ZK_OK;
 }
@@ -483,7 +515,7 @@ template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &
     unsigned root_shift = 0;                                  // the roots in front of the later layers' beyond root_0
     if constexpr (Form::kBatch) {
         form.statement(tr, la, grouped, o.roots);
-        root_shift = form.ntables() - 1;
+        root_shift = form.nroots() - 1;
     } else {
         if (la == 2) {
             put_be32(abe, la);
@@ -612,7 +644,7 @@ template <class F, class Form> int open_with(const zk_fri_commitment *cm, Form &
     for (size_t j = 0; j < m; j++) tr.append_be<F>(load_host<F>(o.final_table + j * W));
 
     zk_fri_ml_stats st{};
-    if constexpr (Form::kBatch) ZK_TRY((answer_queries_batch<F>(tr, form.cms, form.ntables(), fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, &st.ms_queries, grind_bits, nonce_out)));
+    if constexpr (Form::kBatch) ZK_TRY((answer_queries_batch<F>(tr, form.cws, form.ntables(), form.trees, form.nroots(), fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, &st.ms_queries, grind_bits, nonce_out)));
     else ZK_TRY((answer_queries<F>(tr, fl, sc, Q, o.query_indices, o.query_values, o.query_paths, ev, &st.ms_queries, grind_bits, nonce_out)));
     st.rounds = R;
     st.queries = Q;
@@ -673,7 +705,7 @@ int verify_opening(int field, const uint8_t *root32, uint32_t d, uint32_t log_bl
     if (ml.log_arity == 2 && d - log_final < 2) return ZK_E_ARG;
     if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
     if (d > 32) return ZK_E_RANGE;                           // what sizes the copy below; fri_verify_core repeats these and checks the rest
-    const size_t own = ml.ntables ? ml.ntables : 1;           // the roots the verifier holds itself: root32 has that many
+    const size_t own = ml.ncommit ? ml.ncommit : ml.ntables ? ml.ntables : 1;   // the roots the verifier holds itself: root32 has that many
     std::vector<uint8_t> rs(roots, roots + (size_t)32 * (own - 1 + FriSchedule(d + log_blowup, d - log_final, ml.log_arity).nsteps));
     const bool same_root = memcmp(roots, root32, 32 * own) == 0;
     memcpy(rs.data(), root32, 32 * own);
@@ -724,7 +756,44 @@ FriMlClaim claim_of(const uint64_t *points, uint32_t npoints, const uint64_t *ys
     return ml;
 }
 
+// zk_fri_ml_open_columns_pow's statuses, every ZK_E_ARG and then the device check; *view (may be null) = the first commitment's shape as the
+// driver reads it (d, b, coset; its table, codeword and tree stand for layer 0, which the form supplies), *K = the columns together
+int open_columns_check(const zk_fri_columns *const *cms, uint32_t m, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                       const uint64_t *ys_out, const OpenOut &o, uint32_t grinding_bits, const uint64_t *pow_nonce, zk_fri_commitment *view, uint32_t *K) {
+    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS || (grinding_bits && !pow_nonce)) return ZK_E_ARG;
+    if (!cms || m < 1 || m > ZK_FRI_ML_WIDE_MAX || !cms[0]) return ZK_E_ARG;
+    const zk_fri_columns *c0 = cms[0];
+    uint32_t total = 0;
+    for (uint32_t j = 0; j < m; j++) {                        // one field, size, blow-up and coset; at most ZK_FRI_ML_WIDE_MAX columns
+        const zk_fri_columns *cj = cms[j];
+        if (!cj || cj->field != c0->field || cj->d != c0->d || cj->b != c0->b || cj->has_coset != c0->has_coset) return ZK_E_ARG;
+        if (c0->has_coset && memcmp(cj->coset, c0->coset, sizeof c0->coset) != 0) return ZK_E_ARG;
+        total += cj->k;
+        if (total > ZK_FRI_ML_WIDE_MAX) return ZK_E_ARG;
+    }
+    zk_fri_commitment v{};
+    v.field = c0->field;
+    v.d = c0->d;
+    v.b = c0->b;
+    v.has_coset = c0->has_coset;
+    memcpy(v.coset, c0->coset, sizeof v.coset);
+    v.coeffs = c0->coeffs[0];
+    v.codeword = c0->codeword[0];
+    v.levels = c0->levels;
+    v.log_group = 2;
+    if (view) *view = v;
+    if (K) *K = total;
+    return open_points_check(&v, points, npoints, log_final, nqueries, 2, 2, ys_out, o);
+}
+
 }  // namespace
+
+int zk::fri_ml_open_columns_check(const zk_fri_columns *const *cms, uint32_t m, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                                  const uint64_t *ys_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *query_values,
+                                  uint8_t *query_paths, uint32_t grinding_bits, const uint64_t *pow_nonce) {
+    return open_columns_check(cms, m, points, npoints, log_final, nqueries, ys_out, OpenOut{round_polys, roots, final_table, nullptr, nullptr, query_values, query_paths},
+                              grinding_bits, pow_nonce, nullptr, nullptr);
+}
 
 int zk::fri_ml_open_batch_check(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
                                 uint32_t log_arity, const uint64_t *ys_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *query_values,
@@ -927,6 +996,62 @@ int zk_fri_ml_verify_batch_wide_pow(int field, const uint8_t *roots_of_f, uint32
                                     const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok) {
     return verify_batch_capped(field, roots_of_f, k, ZK_FRI_ML_WIDE_MAX, d, log_blowup, log_final, nqueries, log_arity, log_group, coset, points, npoints, ys, t,
                                round_polys, roots, final_table, query_values, query_paths, grinding_bits, pow_nonce, ok);
+}
+
+// ---- column commitments opened together --------------------------------------------------------------------------------------------
+// m >= 1 widths, each >= 1, together at most ZK_FRI_ML_WIDE_MAX; *K = their sum
+static int widths_check(const uint32_t *widths, uint32_t m, uint32_t *K) {
+    if (!widths || m < 1 || m > ZK_FRI_ML_WIDE_MAX) return ZK_E_ARG;
+    uint32_t total = 0;
+    for (uint32_t i = 0; i < m; i++) {
+        if (widths[i] < 1 || widths[i] > ZK_FRI_COLUMNS_MAX) return ZK_E_ARG;
+        total += widths[i];
+        if (total > ZK_FRI_ML_WIDE_MAX) return ZK_E_ARG;
+    }
+    *K = total;
+    return ZK_OK;
+}
+int zk_fri_ml_sizes_columns(const uint32_t *widths, uint32_t m, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots,
+                            size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround) {
+    uint32_t K = 0;
+    ZK_TRY(widths_check(widths, m, &K));
+    size_t nr = 0, nv = 0, pb = 0;
+    ZK_TRY(zk_fri_ml_sizes_grouped(d, log_blowup, log_final, nqueries, &nr, nfinal, &nv, &pb, nround));
+    const FriSchedule sc(d + log_blowup, d - log_final, 2, true);
+    const size_t v0 = sc.nsteps > 1 ? sc.step[1].val_off : sc.nvalues, d0 = sc.nsteps > 1 ? sc.step[1].path_off : sc.ndigests;   // step 0's share: 4 values, L - 2 digests
+    if (nroots) *nroots = m + nr - 1;
+    if (nvalues) *nvalues = nv + (size_t)(K - 1) * nqueries * v0;
+    if (path_bytes) *path_bytes = pb + (size_t)(m - 1) * nqueries * d0 * 32;
+    return ZK_OK;
+}
+
+int zk_fri_ml_open_columns_pow(const zk_fri_columns *const *cms, uint32_t m, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
+                               uint32_t grinding_bits, zk_transcript *t, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *round_polys, uint8_t *roots,
+                               uint64_t *final_table, uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
+                               uint64_t *pow_nonce) {
+    const OpenOut o{round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
+    zk_fri_commitment view{};
+    uint32_t K = 0, widths[ZK_FRI_ML_WIDE_MAX];
+    ZK_TRY(open_columns_check(cms, m, points, npoints, log_final, nqueries, ys_out, o, grinding_bits, pow_nonce, &view, &K));
+    for (uint32_t i = 0; i < m; i++) widths[i] = cms[i]->k;
+    Transcript fresh;
+    FRI_DISPATCH(view.field, ManyTables<F> form(cms, m, widths, points, npoints, ys_out, gamma_out, view.d);
+                 return open_with<F>(&view, form, log_final, nqueries, 2, true, t ? t->t : fresh, o, grinding_bits, pow_nonce));
+    return ZK_OK;
+}
+
+int zk_fri_ml_verify_columns_pow(int field, const uint8_t *roots_of_f, const uint32_t *widths, uint32_t m, uint32_t d, uint32_t log_blowup, uint32_t log_final,
+                                 uint32_t nqueries, uint32_t grinding_bits, const uint64_t *coset, const uint64_t *points, uint32_t npoints, const uint64_t *ys,
+                                 zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
+                                 const uint8_t *query_paths, uint64_t pow_nonce, int *ok) {
+    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS || npoints < 1 || npoints > 8) return ZK_E_ARG;
+    uint32_t K = 0;
+    ZK_TRY(widths_check(widths, m, &K));
+    FriMlClaim ml = claim_of(points, npoints, ys, round_polys, 2, true, K);
+    ml.widths = widths;
+    ml.ncommit = m;
+    return verify_opening(field, roots_of_f, d, log_blowup, log_final, nqueries, coset, ml, t, roots, final_table, query_values, query_paths, ok, grinding_bits,
+                          pow_nonce, ZK_FRI_ML_WIDE_MAX);
 }
 
 int zk_fri_ml_sizes_grouped(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots, size_t *nfinal, size_t *nvalues,

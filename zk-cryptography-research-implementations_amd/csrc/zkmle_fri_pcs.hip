@@ -304,9 +304,115 @@ int commit_any(const zk_table *coeffs, uint32_t log_blowup, const uint64_t *cose
     return ZK_OK;
 }
 
+thread_local zk_fri_columns_stats g_columns_stats{};
+
+// zk_fri_commit_columns: commit_any's statuses over k tables, then k transforms and ONE tree over the k codewords
+int commit_columns(const zk_table *const *tables, uint32_t k, uint32_t log_blowup, const uint64_t *coset, zk_fri_columns **out) {
+    if (!tables || !out || k < 1 || k > ZK_FRI_COLUMNS_MAX || !tables[0] || log_blowup < 1 || log_blowup > 8) return ZK_E_ARG;
+    const int field = tables[0]->field;
+    if (field_limbs64(field) != 4) return ZK_E_ARG;
+    for (uint32_t c = 1; c < k; c++)
+        if (!tables[c] || tables[c]->field != field) return ZK_E_ARG;
+    if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
+    for (uint32_t c = 0; c < k; c++)
+        if (tables[c]->len == 1) return ZK_E_ARG;
+    for (uint32_t c = 1; c < k; c++)
+        if (tables[c]->len != tables[0]->len) return ZK_E_LEN_MISMATCH;
+    if (!is_pow2(tables[0]->len)) return ZK_E_NOT_POW2;
+    ZK_TRY(shape_check(field, ilog2(tables[0]->len), log_blowup));
+    ZK_TRY(require_device());
+    const auto t0 = std::chrono::steady_clock::now();
+    zk_fri_columns *cm = new zk_fri_columns{};
+    cm->field = field;
+    cm->d = ilog2(tables[0]->len);
+    cm->b = log_blowup;
+    cm->k = k;
+    cm->has_coset = coset != nullptr;
+    if (coset) memcpy(cm->coset, coset, 32);
+    const size_t n = tables[0]->len << log_blowup, leaves = n >> 2;       // N >= 4: d >= 1 and b >= 1
+    int rc = ZK_OK;
+    for (uint32_t c = 0; c < k && rc == ZK_OK; c++) {
+        rc = zk_table_clone(tables[c], &cm->coeffs[c]);
+        if (rc == ZK_OK) rc = zk_table_alloc(field, n, &cm->codeword[c]);
+    }
+    if (rc == ZK_OK) {
+        void *lv = nullptr;
+        if (hipMalloc(&lv, (2 * leaves - 1) * 32) != hipSuccess) { set_last_error("zk_fri_commit_columns: no memory for the tree"); rc = ZK_E_NOMEM; }
+        cm->levels = (uint64_t *)lv;
+    }
+    Events ev;
+    size_t e0 = 0, e1 = 0, e2 = 0, e3 = 0;
+    const auto run = [&]() -> int {
+        ZK_TRY(ev.mark(&e0));
+        for (uint32_t c = 0; c < k; c++) ZK_TRY(ntt_extend_into(cm->coeffs[c], coset, cm->codeword[c]));
+        ZK_TRY(ev.mark(&e1));
+        ZK_TRY(merkle_leaves_columns_device(cm->codeword, k, cm->levels));
+        ZK_TRY(ev.mark(&e2));
+        ZK_TRY(merkle_nodes_device(cm->levels, leaves));
+        ZK_TRY(ev.mark(&e3));
+        return ZK_OK;
+    };
+    if (rc == ZK_OK) rc = run();
+    if (rc == ZK_OK && zk::memcpy_on_stream(cm->root, cm->levels + 4 * (2 * leaves - 2), 32, hipMemcpyDeviceToHost) != hipSuccess) {
+        set_last_error("zk_fri_commit_columns: the transforms or the hash kernels failed");
+        rc = ZK_E_HIP;
+    }
+    if (rc != ZK_OK) {
+        (void)hipStreamSynchronize(cur_stream());
+        zk_fri_columns_free(cm);
+        return rc;
+    }
+    zk_fri_columns_stats st{};
+    st.columns = k;
+    st.ms_extend = ev.ms(e0, e1);
+    st.ms_leaves = ev.ms(e1, e2);
+    st.ms_nodes = ev.ms(e2, e3);
+    st.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    g_columns_stats = st;
+    *out = cm;
+    return ZK_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int zk_fri_commit_columns(const zk_table *const *tables, uint32_t k, uint32_t log_blowup, const uint64_t *coset, zk_fri_columns **out) {
+    return commit_columns(tables, k, log_blowup, coset, out);
+}
+int zk_fri_columns_free(zk_fri_columns *cm) {
+    if (!cm) return ZK_OK;
+    for (uint32_t c = 0; c < ZK_FRI_COLUMNS_MAX; c++) {
+        zk_table_free(cm->coeffs[c]);
+        zk_table_free(cm->codeword[c]);
+    }
+    if (cm->levels) (void)hipFree(cm->levels);
+    delete cm;
+    return ZK_OK;
+}
+int zk_fri_columns_root(const zk_fri_columns *cm, uint8_t root32[32]) {
+    if (!cm || !root32) return ZK_E_ARG;
+    memcpy(root32, cm->root, 32);
+    return ZK_OK;
+}
+uint32_t zk_fri_columns_count(const zk_fri_columns *cm) { return cm ? cm->k : 0; }
+int zk_fri_columns_table(const zk_fri_columns *cm, uint32_t j, const zk_table **out) {
+    if (!cm || !out) return ZK_E_ARG;
+    if (j >= cm->k) return ZK_E_RANGE;
+    *out = cm->coeffs[j];
+    return ZK_OK;
+}
+int zk_fri_columns_codeword(const zk_fri_columns *cm, uint32_t j, const zk_table **out) {
+    if (!cm || !out) return ZK_E_ARG;
+    if (j >= cm->k) return ZK_E_RANGE;
+    *out = cm->codeword[j];
+    return ZK_OK;
+}
+int zk_fri_columns_last_stats(zk_fri_columns_stats *out) {
+    if (!out) return ZK_E_ARG;
+    *out = g_columns_stats;
+    return ZK_OK;
+}
 
 int zk_fri_commit(const zk_table *coeffs, uint32_t log_blowup, const uint64_t *coset, zk_fri_commitment **out) {
     return commit_any(coeffs, log_blowup, coset, 0, out);

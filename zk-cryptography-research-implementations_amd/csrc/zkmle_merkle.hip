@@ -6,7 +6,7 @@
 #include <vector>
 
 #include "host_util.h"
-#include "merkle.cuh"
+#include "merkle_columns.cuh"
 #include "transcript.h"
 
 using namespace zk;
@@ -113,6 +113,53 @@ template <class F> bool host_leaf_grouped(const uint64_t *elements, unsigned lg,
         return false;
     }
 }
+// ---- several columns under one tree (merkle_columns.cuh) ---------------------------------------------------------------------------
+// the leaf launch's grid: a block per 256 leaves, at most 2^14 blocks (64 a CU), the stride loop takes the rest.  ZK_MERKLE_COLUMNS_BLOCKS
+// (read once, here only) lowers the cap, so that a test can put a small tree on the loop's second trip
+inline unsigned merkle_columns_grid(size_t part) {
+    static const size_t cap = [] {
+        const char *e = getenv("ZK_MERKLE_COLUMNS_BLOCKS");
+        const long v = e ? atol(e) : 0;
+        return (size_t)(v >= 1 && v < (1 << 14) ? v : 1 << 14);
+    }();
+    const size_t b = (part + kMerkleBlock - 1) / kMerkleBlock;
+    return (unsigned)(b < 1 ? 1 : b > cap ? cap : b);
+}
+template <class F> int launch_leaves_columns(const zk_table *const *tables, uint32_t k, uint64_t *out) {
+    MerkleColumnsArgs a{};
+    for (uint32_t c = 0; c < k; c++) a.t[c] = tables[c]->dptr;
+    a.k = (int)k;
+    const size_t part = tables[0]->len >> 2;
+    merkle_leaf_columns_kernel<F><<<merkle_columns_grid(part), kMerkleBlock, 0, cur_stream()>>>(a, part, out);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+int root_only_columns(const zk_table *const *tables, uint32_t k, uint8_t root32[32]) {
+    const size_t n = tables[0]->len >> 2;
+    DevBuf buf;
+    ZK_TRY(buf.alloc((2 * n - 1) * 32));
+    ZK_TRY(merkle_levels_columns_device(tables, k, (uint64_t *)buf.p));
+    ZK_HIP(zk::memcpy_on_stream(root32, (uint64_t *)buf.p + 4 * (2 * n - 2), 32, hipMemcpyDeviceToHost));   // the call's one synchronisation
+    return ZK_OK;
+}
+// the leaf over k columns: `elements` = 4 k of them in the leaf's order; false: one of them is not reduced
+template <class F> bool host_leaf_columns(const uint64_t *elements, uint32_t k, uint8_t out[32]) {
+    if constexpr (F::N == 8) {
+        std::vector<uint8_t> msg(1 + (size_t)128 * k);
+        msg[0] = 0x00;
+        for (size_t g = 0; g < (size_t)4 * k; g++) {
+            if (!host::is_reduced<F>(elements + 4 * g)) return false;
+            host_to_bytes_be<F>(host::load_host<F>(elements + 4 * g), msg.data() + 1 + 32 * g);
+        }
+        Keccak256 h;
+        h.update(msg.data(), msg.size());
+        h.finalize_copy(out);
+        return true;
+    } else {
+        return false;
+    }
+}
+
 void host_node(const uint8_t *l, const uint8_t *r, uint8_t out[32]) {
     uint8_t msg[65];
     msg[0] = 0x01;
@@ -141,6 +188,28 @@ int merkle_levels_grouped_device(const zk_table *t, unsigned log_group, uint64_t
     if (log_group == 0) return merkle_levels_device(t, levels);
     ZK_DISPATCH_FIELD(t->field, ZK_TRY(launch_leaves_grouped<F>(t, log_group, levels)));
     return hash_up(levels, t->len >> log_group);
+}
+// the statuses of a tree over the k columns `tables` that need no device
+int merkle_columns_check(const zk_table *const *tables, uint32_t k, size_t min_len) {
+    if (!tables || k < 1 || k > (uint32_t)kMerkleColumnsMax || !tables[0]) return ZK_E_ARG;
+    const int field = tables[0]->field;
+    if (field != ZK_FR381 && field != ZK_BN254_FR) return ZK_E_ARG;
+    for (uint32_t c = 1; c < k; c++)
+        if (!tables[c] || tables[c]->field != field) return ZK_E_ARG;
+    for (uint32_t c = 0; c < k; c++)
+        if (tables[c]->len < min_len) return ZK_E_ARG;
+    for (uint32_t c = 1; c < k; c++)
+        if (tables[c]->len != tables[0]->len) return ZK_E_LEN_MISMATCH;
+    return is_pow2(tables[0]->len) ? ZK_OK : ZK_E_NOT_POW2;
+}
+int merkle_leaves_columns_device(const zk_table *const *tables, uint32_t k, uint64_t *levels) {
+    if (tables[0]->field == ZK_FR381) return launch_leaves_columns<Fr381>(tables, k, levels);
+    return launch_leaves_columns<Bn254Fr>(tables, k, levels);
+}
+int merkle_nodes_device(uint64_t *levels, size_t leaves) { return hash_up(levels, leaves); }
+int merkle_levels_columns_device(const zk_table *const *tables, uint32_t k, uint64_t *levels) {
+    ZK_TRY(merkle_leaves_columns_device(tables, k, levels));
+    return hash_up(levels, tables[0]->len >> 2);
 }
 }  // namespace zk
 
@@ -181,6 +250,26 @@ int zk_merkle_build_grouped(const zk_table *t, uint32_t log_group, zk_merkle_tre
     zk_merkle_tree *m = new zk_merkle_tree{t->field, n, ilog2(n), (uint64_t *)d};
     int rc = merkle_levels_grouped_device(t, log_group, m->levels);
     if (rc == ZK_OK && hipStreamSynchronize(cur_stream()) != hipSuccess) { set_last_error("zk_merkle_build_grouped: the hash kernels failed"); rc = ZK_E_HIP; }
+    if (rc != ZK_OK) { zk_merkle_free(m); return rc; }
+    *out = m;
+    return ZK_OK;
+}
+int zk_mle_merkle_root_columns(const zk_table *const *tables, uint32_t k, uint8_t root32[32]) {
+    if (!root32) return ZK_E_ARG;
+    ZK_TRY(merkle_columns_check(tables, k));
+    ZK_TRY(require_device());
+    return root_only_columns(tables, k, root32);
+}
+int zk_merkle_build_columns(const zk_table *const *tables, uint32_t k, zk_merkle_tree **out) {
+    if (!out) return ZK_E_ARG;
+    ZK_TRY(merkle_columns_check(tables, k));
+    ZK_TRY(require_device());
+    const size_t n = tables[0]->len >> 2;
+    void *d = nullptr;
+    ZK_HIP(hipMalloc(&d, (2 * n - 1) * 32));
+    zk_merkle_tree *m = new zk_merkle_tree{tables[0]->field, n, ilog2(n), (uint64_t *)d};
+    int rc = merkle_levels_columns_device(tables, k, m->levels);
+    if (rc == ZK_OK && hipStreamSynchronize(cur_stream()) != hipSuccess) { set_last_error("zk_merkle_build_columns: the hash kernels failed"); rc = ZK_E_HIP; }
     if (rc != ZK_OK) { zk_merkle_free(m); return rc; }
     *out = m;
     return ZK_OK;
@@ -236,6 +325,24 @@ int zk_merkle_verify_grouped(int field, const uint8_t root32[32], size_t depth, 
     uint8_t cur[32];
     bool reduced = false;
     ZK_DISPATCH_FIELD(field, reduced = host_leaf_grouped<F>(elements, log_group, cur));
+    *ok = 0;
+    if (!reduced) return ZK_OK;
+    for (size_t l = 0; l < depth; l++) {                       // the leaf's sibling first
+        const uint8_t *sib = path + 32 * l;
+        uint8_t nx[32];
+        if ((index >> l) & 1) host_node(sib, cur, nx); else host_node(cur, sib, nx);
+        memcpy(cur, nx, 32);
+    }
+    *ok = memcmp(cur, root32, 32) == 0 ? 1 : 0;
+    return ZK_OK;
+}
+
+int zk_merkle_verify_columns(int field, const uint8_t root32[32], size_t depth, size_t index, uint32_t k, const uint64_t *elements, const uint8_t *path,
+                             int *ok) {
+    if (!root32 || !elements || (!path && depth) || !ok || k < 1 || k > (uint32_t)kMerkleColumnsMax || (field != ZK_FR381 && field != ZK_BN254_FR)) return ZK_E_ARG;
+    if (depth >= 64 || (index >> depth) != 0) return ZK_E_RANGE;
+    uint8_t cur[32];
+    const bool reduced = field == ZK_FR381 ? host_leaf_columns<Fr381>(elements, k, cur) : host_leaf_columns<Bn254Fr>(elements, k, cur);
     *ok = 0;
     if (!reduced) return ZK_OK;
     for (size_t l = 0; l < depth; l++) {                       // the leaf's sibling first

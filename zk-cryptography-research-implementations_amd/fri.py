@@ -573,3 +573,126 @@ def ml_last_stats():
     st = _MlStats()
     L.check(L.lib().zk_fri_ml_last_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _MlStats._fields_}
+
+
+# ---- column commitments: several tables under one tree, opened together --------------------------------------------------------------------
+class _ColumnsStats(C.Structure):
+    _fields_ = [("columns", C.c_uint32), ("ms_extend", C.c_float), ("ms_leaves", C.c_float), ("ms_nodes", C.c_float), ("ms_total", C.c_float)]
+
+
+class FriColumns:
+    """The prover's side of a commitment to k tables under ONE Merkle tree (include/zkmle.h "Column commitments opened together"): device
+    copies of the tables, their codewords and every level of the one tree.  `root` is all a verifier needs.  Use as a context manager, or
+    call free()."""
+
+    def __init__(self, field, d, log_blowup, coset, handle):
+        self.field, self.d, self.log_blowup, self._h = field, d, log_blowup, handle
+        self.k = int(L.lib().zk_fri_columns_count(handle))
+        self.coset = None if coset is None else _elem(field, coset).copy()
+        root = np.zeros(32, np.uint8)
+        L.check(L.lib().zk_fri_columns_root(handle, L.p8(root)))
+        self.root = root.tobytes()
+
+    def _copy(self, fn, j):
+        h, out = C.c_void_p(), C.c_void_p()
+        L.check(fn(self._h, j, C.byref(h)))
+        L.check(L.lib().zk_table_clone(h, C.byref(out)))
+        return MultilinearPolynomial(self.field, _handle=out)
+
+    def codeword(self, j):
+        """a copy of column j's N evaluations f_j(c w^i) as a table of its own"""
+        return self._copy(L.lib().zk_fri_columns_codeword, j)
+
+    def table(self, j):
+        """a copy of column j's committed table"""
+        return self._copy(L.lib().zk_fri_columns_table, j)
+
+    def free(self):
+        if self._h is not None:
+            L.lib().zk_fri_columns_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:      # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+def commit_columns(tables, log_blowup, coset=None):
+    """ONE commitment to the k <= 32 tables (one field, 2^d entries each): leaf j of its tree holds the first fold's coset of every column, so
+    one path answers all of them.  k = 1 has the root of commit(.., log_group=2)"""
+    if not 1 <= len(tables) <= 32:
+        raise L.ZkError(L.ZK_E_ARG, "1 to 32 tables")
+    t0, h = tables[0], C.c_void_p()
+    cs = None if coset is None else L.p64(_elem(t0.field, coset))
+    L.check(L.lib().zk_fri_commit_columns((C.c_void_p * len(tables))(*[t._h for t in tables]), len(tables), log_blowup, cs, C.byref(h)))
+    return FriColumns(t0.field, len(t0).bit_length() - 1, log_blowup, coset, h)
+
+
+def columns_last_stats():
+    """milliseconds of the calling thread's last commit_columns: the k transforms, the leaf launch, the node launches"""
+    st = _ColumnsStats()
+    L.check(L.lib().zk_fri_columns_last_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _ColumnsStats._fields_}
+
+
+def _widths(widths):
+    return (C.c_uint32 * len(widths))(*[int(w) for w in widths])
+
+
+def columns_sizes(widths, d, log_blowup, log_final, nqueries):
+    """(nroots, nfinal, nvalues, path_bytes, nround) of an opening of column commitments of these widths"""
+    out = [C.c_size_t(0) for _ in range(5)]
+    L.check(L.lib().zk_fri_ml_sizes_columns(_widths(widths), len(widths), d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+class FriColumnsOpening(FriMlPointsOpening):
+    """The opening of m column commitments of `widths` (K columns together) at the same P points: ys (K, P, limbs) in global column order;
+    roots (m + nroots - 1, 32), the m commitments' first; query_values (Q, per, limbs) with step 0's 4 K values column-major in front of the
+    later steps'; query_paths with step 0's m paths in front of the later steps'."""
+
+    def __init__(self, field, widths, npoints, d, log_blowup, log_final, nqueries, coset=None, grinding_bits=0):
+        super().__init__(field, npoints, d, log_blowup, log_final, nqueries, coset, 2, True)
+        self.widths, self.k = [int(w) for w in widths], int(sum(widths))
+        self.grinding_bits, self.pow_nonce = grinding_bits, 0
+        nroots, _, nvalues, path_bytes, _ = columns_sizes(widths, d, log_blowup, log_final, nqueries)
+        n = limbs(field)
+        self.ys = np.zeros((self.k, npoints, n), np.uint64)
+        self.roots = np.zeros((nroots, 32), np.uint8)
+        self.query_values = np.zeros((nqueries, nvalues // nqueries, n), np.uint64)
+        self.query_paths = np.zeros(path_bytes, np.uint8)
+
+
+def open_columns(commitments, points, log_final, nqueries, transcript=None, grinding_bits=0):
+    """one proof that every column of the m column commitments (together at most 32 columns; one field, size, blow-up and coset) has the values
+    `.ys[c]` at the same P <= 8 points (P, d, limbs): each query's step 0 carries one path per COMMITMENT"""
+    c0 = commitments[0]
+    pts = _points(c0.field, c0.d, points)
+    op = FriColumnsOpening(c0.field, [c.k for c in commitments], pts.shape[0], c0.d, c0.log_blowup, log_final, nqueries, c0.coset, grinding_bits)
+    nonce = C.c_uint64(0)
+    L.check(L.lib().zk_fri_ml_open_columns_pow(_handles(commitments), len(commitments), L.p64(pts), pts.shape[0], log_final, nqueries, grinding_bits,
+                                               _handle(transcript), *_prover_outputs(op), C.byref(nonce)))
+    op.pow_nonce = int(nonce.value)
+    return op
+
+
+def verify_columns(roots, widths, points, opening, transcript=None):
+    """host only: `roots` = the m commitment roots (32 bytes each) and `widths` their column counts, in the prover's order; the claims checked
+    are evaluate(column_c, points[p]) = opening.ys[c, p]"""
+    op, ok = opening, C.c_int(0)
+    rf, _, ys, proof = _verifier_inputs(op, roots, op.ys, k=len(widths))      # one 32-byte root per width
+    pts = _points(op.field, op.d, points)
+    if ys.shape != (int(sum(widths)), pts.shape[0], limbs(op.field)):
+        raise L.ZkError(L.ZK_E_ARG, "one claim per column and point")
+    L.check(L.lib().zk_fri_ml_verify_columns_pow(op.field, rf, _widths(widths), len(widths), op.d, op.log_blowup, op.log_final, op.nqueries,
+                                                 getattr(op, "grinding_bits", 0), op._coset(), L.p64(pts), pts.shape[0], L.p64(ys), _handle(transcript),
+                                                 *proof, getattr(op, "pow_nonce", 0), C.byref(ok)))
+    return bool(ok.value)

@@ -26,6 +26,14 @@ def merkle_root(poly, log_group=0):
     return out.tobytes()
 
 
+def columns_root(tables):
+    """the 32-byte root of the ONE tree over the k <= 32 tables (one scalar field, one length 2^d >= 4), root-only mode: leaf j holds
+    tables[c][j + s len / 4], s < 4, of every column c (include/zkmle.h "Merkle commitment of several columns")"""
+    out = np.zeros(32, np.uint8)
+    L.check(L.lib().zk_mle_merkle_root_columns((C.c_void_p * len(tables))(*[t._h for t in tables]), len(tables), L.p8(out)))
+    return out.tobytes()
+
+
 class MerkleTree:
     def __init__(self, handle, field, length, log_group=0):
         self._h, self.field, self.length, self.log_group = handle, field, length, log_group
@@ -40,6 +48,30 @@ class MerkleTree:
         else:
             L.check(L.lib().zk_merkle_build_grouped(poly._h, log_group, C.byref(h)))
         return cls(h, poly.field, len(poly), log_group)
+
+    @classmethod
+    def build_columns(cls, tables):
+        """ONE tree over k tables: length >> 2 leaves; open() takes leaf indices and a path authenticates the leaf's 4 k entries"""
+        h = C.c_void_p()
+        L.check(L.lib().zk_merkle_build_columns((C.c_void_p * len(tables))(*[t._h for t in tables]), len(tables), C.byref(h)))
+        tree = cls(h, tables[0].field, len(tables[0]), 2)
+        tree.columns = len(tables)
+        return tree
+
+    @staticmethod
+    def verify_columns(field, root, index, elements, path):
+        """host only: do the (k, 4, limbs) `elements` of leaf `index` -- column, then side -- hash up `path` ((depth, 32) bytes) to `root`?"""
+        root = np.frombuffer(bytes(root), np.uint8).copy()
+        if root.shape[0] != 32:
+            raise L.ZkError(L.ZK_E_ARG, "a Merkle root is 32 bytes")
+        path = np.ascontiguousarray(path, np.uint8).reshape(-1, 32)
+        el = np.ascontiguousarray(elements, np.uint64)
+        if el.ndim != 3 or el.shape[1:] != (4, limbs(field)):
+            raise L.ZkError(L.ZK_E_ARG, "the elements are a (k, 4, limbs) array")
+        ok = C.c_int(0)
+        buf = path if path.size else np.zeros(32, np.uint8)
+        L.check(L.lib().zk_merkle_verify_columns(field, L.p8(root), path.shape[0], int(index), el.shape[0], L.p64(el), L.p8(buf), C.byref(ok)))
+        return bool(ok.value)
 
     def __del__(self):
         if getattr(self, "_h", None):
