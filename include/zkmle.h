@@ -1179,6 +1179,87 @@ int zk_plonk_lookup_verify(int field, const uint8_t *roots_of_fifteen, const uin
 typedef zk_lookup_stats zk_plonk_lookup_stats;
 int zk_plonk_lookup_last_stats(zk_plonk_lookup_stats *out);
 
+/* ---- Plonk with lookups on column commitments (extension; csrc/plonk_helpers.cuh, csrc/plonk_lookup_columns_host.h,
+ *      csrc/zkmle_plonk_lookup_columns.hip) --------------------------------------------------------------------------------------------------------
+ * The proof of the block above for a circuit that was preprocessed ONCE into one commitment: the verifier holds TWO roots, 64 bytes.  Two
+ * column commitments of one shape (field, d <= 31, log_blowup, coset), both made by zk_fri_commit_columns:
+ *     witness   three columns   A, B, C
+ *     circuit   twelve columns  qM, qL, qR, qO, qC, SA, SB, SC, qK, T0, T1, T2
+ * and l <= 2^d public values.
+ *   Statement.  That of "Plonk with lookups: gate, wiring, public inputs and lookup rows in one sumcheck" on the fifteen columns.
+ *   Transcript (t = NULL: a fresh Transcript::new()), plain appends in this order:
+ *     1. 12 bytes in one append: the ASCII tag "ZCLC", then d, then l, each a big-endian u32.  No other protocol here starts with these four
+ *        bytes, so no earlier protocol's transcript is a prefix of this one's;
+ *     2. the witness root, then the circuit root, one append each;
+ *     3. the l public values, each the 32-byte canonical big-endian element;
+ *     4. the table M exactly as step 4 above (the lookup's three kernels), committed as a ONE-column commitment of the same shape; its root;
+ *     5. beta, then gamma: ONE pair;
+ *     6. the four helper tables with that pair, in the SINGLE-DENOMINATOR form, inv0(0) = 0:
+ *            H_j[x] = N_j[x] inv0(Did_j[x] Dsig_j[x]),  N_j = Dsig_j - Did_j = gamma (S_j - id_j),  Did_j = beta + W_j + gamma (j n + x),
+ *                                                       Dsig_j = beta + W_j + gamma S_j,                                    j = 0, 1, 2
+ *            HL[x]  = (qK[x] Dt[x] - M[x] Dw[x]) inv0(Dw[x] Dt[x]),  Dw = beta + A + gamma B + gamma^2 C,  Dt = beta + T0 + gamma T1 + gamma^2 T2
+ *        made together by ONE kernel (plonk_lookup_helpers_kernel) and committed as ONE four-column commitment H0, H1, H2, HL; its one root.
+ *        The proof's h_roots are M's root, then the helpers': 64 bytes.
+ *        Where no denominator is zero these are, as field elements, the tables of step 6 above.  Where a product of two denominators is zero
+ *        the entry is 0, which differs from inv0 per denominator only when exactly ONE of the pair is zero; there the verifier's relation for
+ *        that entry, H Did Dsig - N = 0 (H Dw Dt - qK Dt + M Dw = 0), cannot hold for either definition, since the product is zero and the
+ *        numerator is not.  When both are zero the numerator is zero too and 0 satisfies the relation;
+ *     7. alpha, mu, tau_0 .. tau_{d-1}; E = eq(., tau);
+ *     8. the sumcheck of step 8 above unchanged (plonk_lookup_round_kernel and its launcher as they are, on the columns' tables); the claimed
+ *        sum is alpha^3 PIeval(tau);
+ *     9. the point z, z[d - 1 - l] = r_l;
+ *    10. the whole protocol of zk_fri_ml_open_columns_pow on the transcript as step 8 left it: m = 4 commitments of widths 3, 12, 1, 4 in the
+ *        order witness, circuit, M, helpers, npoints = 1, the point z.  The global column order is A, B, C, qM, qL, qR, qO, qC, SA, SB, SC, qK,
+ *        T0, T1, T2, M, H0, H1, H2, HL: the order of the twenty claims above, so the final relation is that block's on ys as they stand.
+ *   Schedule.  The columns opening's only one: fold by 4 on grouped leaves, d - log_final >= 2.
+ *   Soundness, as a count and not a proof.  The count of the block above holds unchanged: beta and gamma are drawn after the witness root, the
+ *     circuit root and M's root, which between them fix every table that either argument needs before the pair (A, B, C, SA, SB, SC for the
+ *     wiring; A, B, C, qK, T0, T1, T2 and M for the lookup), and nothing that the pair depends on moves after it; the helpers depend on the
+ *     pair and precede alpha, mu and tau as there; alpha^0 .. alpha^4 separate the five zerocheck terms (4 / p), mu and mu^2 the two plain sums
+ *     (2 / p), the rounds are d quartics (4 d / p), tau adds d / p, and the opening its own error.  That a column commitment binds each of its
+ *     columns is the opening's statement ("Column commitments opened together").  Nothing here is proved; DESIGN.md 7s repeats the count.
+ *   Verifier (HOST only).  It replays steps 1 to 9 on a copy of the transcript, checks g_0(0) + g_0(1) = alpha^3 PIeval(tau),
+ *     g_l(0) + g_l(1) = g_{l-1}(r_{l-1}) and the final relation of the block above on the twenty claims, then zk_fri_ml_verify_columns_pow with
+ *     the roots witness, circuit, M, helpers and the widths 3, 12, 1, 4.  *ok is the conjunction; anything unreduced -- a public value >= p
+ *     among it -- gives *ok = 0 with the status ZK_OK.  Every status is decided before the transcript is touched (grinding_bits, a NULL, the
+ *     field, d > 31, zk_fri_ml_sizes_columns' own, a zero coset, ZK_E_RANGE for a field or size without the roots of unity, the public inputs'
+ *     shape); t ends in the prover's state whenever the status is ZK_OK.
+ *   Prover.  It does not check the statement: a false one gives ZK_OK, the rows with qK = 1 that are in no table row in the stats' `misses`,
+ *     and a proof the verifier rejects.  The two helper commitments ADOPT the tables the prover has just made (nothing is cloned) and are freed
+ *     before it returns; no committed table is written.  ZK_E_ARG, with nothing written and the transcript as it was and before
+ *     ZK_E_NO_DEVICE: a NULL, a witness that has not three columns or a circuit that has not twelve, d > 31, two commitments of different
+ *     shape, d - log_final < 2 and the rest of zk_fri_ml_open_columns_pow's own, and the public inputs' shape or an unreduced public value.
+ * Not here: the same move for zk_plonk_prove, zk_wiring_prove and zk_lookup_prove, M inside the witness commitment, a batched transform for
+ * the k columns, several rounds per pass, a sharded prover, and the single-denominator helpers inside the provers above (their protocols define
+ * inv0 per denominator). */
+/* the four helper tables on their own.  tables: A, B, C, SA, SB, SC, qK, T0, T1, T2, M (2 <= len <= 2^31); H[0 .. 3] = H0, H1, H2, HL (new
+ * tables) as step 6 says.  Statuses and their order as zk_lookup_fractions (beta and gamma reduced); ZK_E_ARG also when the four handles H lie
+ * inside the array `tables` (an output that aliases an input). */
+int zk_plonk_lookup_helpers(const zk_table *const tables[11], const uint64_t *beta, const uint64_t *gamma, zk_table *H[4]);
+/* the rows a lane of plonk_lookup_helpers_kernel takes: its tile is 256 times as many */
+uint32_t zk_plonk_lookup_helpers_batch(void);
+/* host: nround = 5 d, nhroots = 2, and zk_fri_ml_sizes_columns' counts for the widths 3, 12, 1, 4 (nroots: the four commitments' first);
+ * d > 31: ZK_E_ARG; any pointer may be NULL */
+int zk_plonk_lookup_sizes_columns(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nround, size_t *nhroots, size_t *nroots,
+                                  size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nopen_round);
+/* h_roots: 64 bytes (M, then the helpers); chal_out (may be NULL): beta, gamma, alpha, mu, tau: 4 + d elements, diagnostic; round_polys: 5 d
+ * elements; challenges: d; ys_out: 20 elements; from gamma_out on, the outputs of zk_fri_ml_open_columns_pow for the four commitments and one
+ * point, sized by zk_plonk_lookup_sizes_columns. */
+int zk_plonk_lookup_prove_columns(const zk_fri_columns *witness, const zk_fri_columns *circuit, const uint64_t *public_inputs, uint32_t npublic,
+                                  uint32_t log_final, uint32_t nqueries, uint32_t grinding_bits, zk_transcript *t, uint8_t *h_roots, uint64_t *chal_out,
+                                  uint64_t *round_polys, uint64_t *challenges, uint64_t *ys_out, uint64_t *gamma_out, uint64_t *open_round_polys, uint8_t *roots,
+                                  uint64_t *final_table, uint64_t *open_challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths,
+                                  uint64_t *pow_nonce);
+/* HOST only.  witness_root, circuit_root: 32 bytes each, as the verifier holds them; h_roots: the proof's two, 64 bytes; ys: the twenty claims */
+int zk_plonk_lookup_verify_columns(int field, const uint8_t *witness_root, const uint8_t *circuit_root, const uint64_t *public_inputs, uint32_t npublic, uint32_t d,
+                                   uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, zk_transcript *t, const uint8_t *h_roots,
+                                   const uint64_t *round_polys, const uint64_t *ys, const uint64_t *open_round_polys, const uint8_t *roots,
+                                   const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits,
+                                   uint64_t pow_nonce, int *ok);
+/* the calling thread's last zk_plonk_lookup_prove_columns: the fields of zk_plonk_lookup_stats; ms_fractions is the ONE helper kernel,
+ * ms_commit the two helper commitments together */
+int zk_plonk_lookup_columns_last_stats(zk_plonk_lookup_stats *out);
+
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */
 int zk_uni_lagrange_interpolate(int field, const uint64_t *xs, const uint64_t *ys, size_t n, uint64_t *out); /* :74 */

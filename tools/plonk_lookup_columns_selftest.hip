@@ -1,0 +1,235 @@
+// plonk_lookup_columns_selftest.hip -- the host verifier of the Plonk proof with lookup rows on column commitments
+// (zk_plonk_lookup_verify_columns: csrc/plonk_lookup_columns_host.h's replay and the columns opening's verifier behind it) as a stand-alone HOST
+// program, for a sanitizer build.  It opens no device and launches nothing; the verifier reaches into most of the library's translation units,
+// so they are all compiled with the host side instrumented and linked in:
+//   for f in zk-cryptography-research-implementations_amd/csrc/*.hip tools/plonk_lookup_columns_selftest.hip; do
+//       hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Wno-pass-failed -c $f -o build/$(basename $f .hip).o; done
+//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined build/*.o -o plonk_lookup_columns_selftest
+//   ./plonk_lookup_columns_selftest tests/golden/plonk_lookup_columns_proof.bin
+// The fixture is one small valid proof written by the Python model (tests/golden/make_plonk_lookup_columns_fixture.py: magic "ZLCX"; BN254 Fr,
+// d = 4, a coset, one public value, 4 bits of proof of work).  Every array is copied into a heap block of exactly its size, so a read past an
+// end is the sanitizer's to report.  Checked: the proof verifies, on a fresh transcript, and with coset = NULL is refused as another statement;
+// every array (the two roots and the two helper roots among them) with one byte changed (first, middle, last) is rejected with ZK_OK, the
+// public value among them; the witness and the circuit root swapped, and M's root and the helpers' swapped, are rejected; no public value,
+// one more (a zero) and an unreduced one are rejected with ZK_OK, more values than rows and no array with npublic > 0 with ZK_E_ARG; the proof
+// shown with one query fewer, with d - 1, with d + 1 and with log_final + 1, its arrays cut or grown to exactly the counts
+// zk_plonk_lookup_sizes_columns gives for those parameters, is rejected without a read past any end; a nonce off by one is rejected; the statuses
+// that precede the transcript leave a caller's transcript as it was.  Exit status 0 = every check held.
+#include <stdio.h>
+#include <string.h>
+
+#include <utility>
+#include <vector>
+
+#include "../include/zkmle.h"
+
+static int failures = 0;
+#define CHECK(cond)                                                          \
+    do {                                                                     \
+        if (!(cond)) {                                                       \
+            fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #cond);       \
+            failures++;                                                      \
+        }                                                                    \
+    } while (0)
+
+enum { OWN, PUB, HROOTS, POLYS, YS, OPEN_POLYS, ROOTS, FINAL, VALUES, PATHS, NARR };
+
+struct Proof {
+    uint32_t field, d, b, f, Q, g;
+    uint64_t nonce, coset[4];
+    std::vector<uint8_t> arr[NARR];
+};
+
+// a heap copy of exactly `n` bytes (at least one, so that the pointer is never NULL)
+struct Exact {
+    uint8_t *p;
+    Exact(const std::vector<uint8_t> &v, size_t n) : p(new uint8_t[n ? n : 1]) {
+        if (!v.empty()) memcpy(p, v.data(), n < v.size() ? n : v.size());   // an empty vector's data() may be NULL: no public value
+    }
+    Exact(const uint8_t *src, size_t n) : p(new uint8_t[n ? n : 1]) { memcpy(p, src, n); }
+    ~Exact() { delete[] p; }
+    Exact(const Exact &) = delete;
+};
+
+static bool read_fixture(const char *path, Proof &pr) {
+    FILE *fh = fopen(path, "rb");
+    if (!fh) return false;
+    char magic[4];
+    uint32_t head[6];
+    bool ok = fread(magic, 1, 4, fh) == 4 && memcmp(magic, "ZLCX", 4) == 0 && fread(head, 4, 6, fh) == 6 && fread(&pr.nonce, 8, 1, fh) == 1 &&
+              fread(pr.coset, 8, 4, fh) == 4;
+    if (ok) {
+        pr.field = head[0]; pr.d = head[1]; pr.b = head[2]; pr.f = head[3]; pr.Q = head[4]; pr.g = head[5];
+    }
+    for (int k = 0; ok && k < NARR; k++) {
+        uint64_t n = 0;
+        ok = fread(&n, 8, 1, fh) == 1 && n < (1u << 24);
+        if (!ok) break;
+        pr.arr[k].resize(n);
+        ok = fread(pr.arr[k].data(), 1, n, fh) == n;
+    }
+    ok = ok && fgetc(fh) == EOF;
+    fclose(fh);
+    return ok;
+}
+
+// the byte counts of the ten arrays (two roots, twenty claims) for the given parameters; false when zk_plonk_lookup_sizes_columns refuses them
+static bool counts(uint32_t d, uint32_t b, uint32_t f, uint32_t Q, size_t npublic, size_t out[NARR]) {
+    size_t nzc, nh, nroots, nfinal, nvalues, pbytes, nround;
+    if (zk_plonk_lookup_sizes_columns(d, b, f, Q, &nzc, &nh, &nroots, &nfinal, &nvalues, &pbytes, &nround) != ZK_OK) return false;
+    out[OWN] = 64; out[PUB] = npublic * 32; out[HROOTS] = nh * 32; out[YS] = 640; out[POLYS] = nzc * 32; out[OPEN_POLYS] = nround * 32; out[ROOTS] = nroots * 32;
+    out[FINAL] = nfinal * 32; out[VALUES] = nvalues * 32; out[PATHS] = pbytes;
+    return true;
+}
+
+// zk_plonk_lookup_verify_columns on exact-size copies of pr's arrays, cut or zero-extended to the counts of the parameters shown; the two roots
+// in heap blocks of 32 bytes each; the public values as they are
+static int verify(const Proof &pr, zk_transcript *t, int *ok, bool with_coset = true, bool null_public = false) {
+    size_t n[NARR];
+    if (!counts(pr.d, pr.b, pr.f, pr.Q, pr.arr[PUB].size() / 32, n)) return ZK_E_ARG;
+    std::vector<uint8_t> grown[NARR];
+    for (int k = 0; k < NARR; k++) {
+        grown[k] = pr.arr[k];
+        grown[k].resize(n[k], 0);
+    }
+    Exact wroot(grown[OWN].data(), 32), croot(grown[OWN].data() + 32, 32), pub(grown[PUB], n[PUB]), hr(grown[HROOTS], n[HROOTS]), polys(grown[POLYS], n[POLYS]),
+        ys(grown[YS], n[YS]), opolys(grown[OPEN_POLYS], n[OPEN_POLYS]), roots(grown[ROOTS], n[ROOTS]), fin(grown[FINAL], n[FINAL]), vals(grown[VALUES], n[VALUES]),
+        paths(grown[PATHS], n[PATHS]);
+    return zk_plonk_lookup_verify_columns((int)pr.field, wroot.p, croot.p, null_public ? nullptr : (const uint64_t *)pub.p, (uint32_t)(n[PUB] / 32), pr.d, pr.b, pr.f, pr.Q,
+                                          with_coset ? pr.coset : nullptr, t, hr.p, (const uint64_t *)polys.p, (const uint64_t *)ys.p, (const uint64_t *)opolys.p, roots.p,
+                                          (const uint64_t *)fin.p, (const uint64_t *)vals.p, paths.p, pr.g, pr.nonce, ok);
+}
+
+int main(int argc, char **argv) {
+    Proof pr;
+    if (argc < 2 || !read_fixture(argv[1], pr)) {
+        fprintf(stderr, "usage: plonk_lookup_columns_selftest tests/golden/plonk_lookup_columns_proof.bin\n");
+        return 2;
+    }
+    size_t n[NARR];
+    CHECK(pr.arr[PUB].size() == 32 && pr.d == 4 && pr.g == 4);
+    CHECK(counts(pr.d, pr.b, pr.f, pr.Q, pr.arr[PUB].size() / 32, n));
+    for (int k = 0; k < NARR; k++) CHECK(pr.arr[k].size() == n[k]);
+    int ok = -1;
+    CHECK(verify(pr, nullptr, &ok) == ZK_OK && ok == 1);
+    ok = -1;
+    CHECK(verify(pr, nullptr, &ok, false) == ZK_OK && ok == 0);
+
+    // one byte changed
+    for (int k = 0; k < NARR; k++) {
+        const size_t len = pr.arr[k].size();
+        for (size_t at : {(size_t)0, len / 2, len - 1}) {
+            Proof bad = pr;
+            bad.arr[k][at] ^= 0x10;
+            ok = -1;
+            CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        }
+    }
+    // the roots in another order: witness and circuit; M and the helpers (with the proof's own copies moved along)
+    {
+        Proof bad = pr;
+        for (int k = 0; k < 32; k++) std::swap(bad.arr[OWN][k], bad.arr[OWN][32 + k]);
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        for (int k = 0; k < 32; k++) std::swap(bad.arr[ROOTS][k], bad.arr[ROOTS][32 + k]);
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        bad = pr;
+        for (int k = 0; k < 32; k++) std::swap(bad.arr[HROOTS][k], bad.arr[HROOTS][32 + k]);
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        for (int k = 0; k < 32; k++) std::swap(bad.arr[ROOTS][64 + k], bad.arr[ROOTS][96 + k]);
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+    }
+    // the public values: another count, an unreduced value, and the refusals
+    {
+        const size_t l = pr.arr[PUB].size() / 32;
+        Proof bad = pr;
+        bad.arr[PUB].resize(32 * (l - 1));
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        bad = pr;
+        bad.arr[PUB].resize(32 * (l + 1), 0);
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        bad = pr;
+        memset(bad.arr[PUB].data() + 32 * (l - 1), 0xFF, 32);
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        bad = pr;
+        bad.arr[PUB].resize(32 * (((size_t)1 << pr.d) + 1), 0);
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_E_ARG && ok == -1);
+        CHECK(verify(pr, nullptr, &ok, true, true) == ZK_E_ARG && ok == -1);
+    }
+    // cut to another statement's counts
+    {
+        Proof cut = pr;
+        cut.Q = pr.Q - 1;
+        ok = -1;
+        CHECK(verify(cut, nullptr, &ok) == ZK_OK && ok == 0);
+        cut = pr;
+        cut.d = pr.d - 1;
+        ok = -1;
+        CHECK(verify(cut, nullptr, &ok) == ZK_OK && ok == 0);
+        cut = pr;
+        cut.f = pr.f + 1;
+        ok = -1;
+        CHECK(verify(cut, nullptr, &ok) == ZK_OK && ok == 0);
+        cut = pr;
+        cut.d = pr.d + 1;                                     // grown with zeros
+        ok = -1;
+        CHECK(verify(cut, nullptr, &ok) == ZK_OK && ok == 0);
+        cut = pr;
+        cut.b = pr.b + 1;
+        ok = -1;
+        CHECK(verify(cut, nullptr, &ok) == ZK_OK && ok == 0);
+    }
+    // the proof of work
+    {
+        Proof bad = pr;
+        bad.nonce = pr.nonce + 1;
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        bad = pr;
+        bad.g = pr.g + 1;
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+        bad = pr;
+        bad.g = 0;
+        ok = -1;
+        CHECK(verify(bad, nullptr, &ok) == ZK_OK && ok == 0);
+    }
+    // a caller's transcript: the statuses leave it alone, ZK_OK moves it, and the proof is bound to what it held
+    {
+        zk_transcript *t = nullptr;
+        CHECK(zk_transcript_new(&t) == ZK_OK);
+        const uint8_t prior[] = "the caller's own";
+        CHECK(zk_transcript_append(t, prior, sizeof prior) == ZK_OK);
+        uint64_t before[25], after[25];
+        uint32_t fb = 0, fa = 0;
+        CHECK(zk_transcript_export_state(t, before, &fb) == ZK_OK);
+        Proof bad = pr;
+        bad.field = 1;
+        ok = -1;
+        CHECK(verify(bad, t, &ok, false) == ZK_E_RANGE && ok == -1);
+        bad = pr;
+        memset(bad.coset, 0, sizeof bad.coset);
+        CHECK(verify(bad, t, &ok) == ZK_E_ARG && ok == -1);
+        bad = pr;
+        bad.g = 33;
+        CHECK(verify(bad, t, &ok) == ZK_E_ARG && ok == -1);
+        bad = pr;
+        bad.f = pr.d - 1;                                     // d - log_final < 2: the size function refuses, and so does the verifier
+        CHECK(verify(bad, t, &ok) == ZK_E_ARG && ok == -1);
+        CHECK(verify(pr, t, nullptr) == ZK_E_ARG);
+        CHECK(zk_transcript_export_state(t, after, &fa) == ZK_OK && fa == fb && memcmp(before, after, sizeof before) == 0);
+        CHECK(verify(pr, t, &ok) == ZK_OK && ok == 0);        // made on a fresh transcript, shown on another
+        CHECK(zk_transcript_export_state(t, after, &fa) == ZK_OK && memcmp(before, after, sizeof before) != 0);
+        zk_transcript_free(t);
+    }
+    if (failures) printf("plonk_lookup_columns_selftest: %d check(s) FAILED\n", failures);
+    else printf("plonk_lookup_columns_selftest ok\n");
+    return failures ? 1 : 0;
+}

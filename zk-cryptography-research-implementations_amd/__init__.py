@@ -29,6 +29,7 @@ from . import lookup  # noqa: F401  (the module: zk.lookup.prove, zk.lookup.veri
 from .lookup import LookupProof  # noqa: F401
 from . import plonk_lookup  # noqa: F401  (the module: zk.plonk_lookup.prove, zk.plonk_lookup.verify, ...)
 from .plonk_lookup import PlonkLookupProof  # noqa: F401
+from .plonk_lookup import PlonkLookupColumnsProof  # noqa: F401
 from . import gkr  # noqa: F401
 from .gkr import Circuit, Gate, Layer, Operator  # noqa: F401
 from . import kzg  # noqa: F401

@@ -235,6 +235,14 @@ def lib():
         "zk_plonk_lookup_verify": [C.c_int, u8p, u64p] + [C.c_uint32] * 7 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
                                                                             C.POINTER(C.c_int)],
         "zk_plonk_lookup_last_stats": [vp],
+        # Plonk with lookups on column commitments
+        "zk_plonk_lookup_helpers": [C.POINTER(vp), u64p, u64p, C.POINTER(vp)],
+        "zk_plonk_lookup_helpers_batch": [],
+        "zk_plonk_lookup_sizes_columns": [C.c_uint32] * 4 + [C.POINTER(sz)] * 7,
+        "zk_plonk_lookup_prove_columns": [vp, vp, u64p] + [C.c_uint32] * 4 + [vp, u8p, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
+        "zk_plonk_lookup_verify_columns": [C.c_int, u8p, u8p, u64p] + [C.c_uint32] * 5 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
+                                                                                       C.POINTER(C.c_int)],
+        "zk_plonk_lookup_columns_last_stats": [vp],
         "zk_sumcheck_basic_prove_succinct": [vp, C.c_uint32, C.c_uint32, vp, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_sumcheck_basic_verify_succinct": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, vp, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u8p,
                                                                                  C.POINTER(C.c_int)],

@@ -151,6 +151,10 @@ struct FriMlClaim {
 int fri_ml_open_columns_check(const zk_fri_columns *const *cms, uint32_t m, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
                               const uint64_t *ys_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *query_values,
                               uint8_t *query_paths, uint32_t grinding_bits, const uint64_t *pow_nonce);
+// zk_fri_commit_columns on k device tables that the caller owns (zk_table_alloc or the pool; not zk_table_wrap) and hands over: with ZK_OK they are
+// the commitment's own tables, freed with it, and nothing is cloned; with any other status they stay the caller's.  The statuses are
+// zk_fri_commit_columns' (zkmle_fri_pcs.hip; the prover on column commitments commits the helper tables it has just made)
+int fri_commit_columns_adopt(zk_table *const *tables, uint32_t k, uint32_t log_blowup, const uint64_t *coset, zk_fri_columns **out);
 // grind_bits > 0: the proof-of-work step (include/zkmle.h "Proof-of-work grinding") with the nonce pow_nonce stands between the final
 // coefficients and the indices; a nonce that fails it gives *ok = 0.  grind_bits > ZK_FRI_GRIND_MAX_BITS: ZK_E_ARG
 int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, Transcript &tr,

@@ -306,8 +306,10 @@ int commit_any(const zk_table *coeffs, uint32_t log_blowup, const uint64_t *cose
 
 thread_local zk_fri_columns_stats g_columns_stats{};
 
-// zk_fri_commit_columns: commit_any's statuses over k tables, then k transforms and ONE tree over the k codewords
-int commit_columns(const zk_table *const *tables, uint32_t k, uint32_t log_blowup, const uint64_t *coset, zk_fri_columns **out) {
+// zk_fri_commit_columns: commit_any's statuses over k tables, then k transforms and ONE tree over the k codewords.  adopt (else null): k device
+// tables the caller owns and hands over, the same objects as `tables`: they become the commitment's own in place of clones when the status is
+// ZK_OK and stay the caller's otherwise
+int commit_columns(const zk_table *const *tables, uint32_t k, uint32_t log_blowup, const uint64_t *coset, zk_fri_columns **out, zk_table *const *adopt = nullptr) {
     if (!tables || !out || k < 1 || k > ZK_FRI_COLUMNS_MAX || !tables[0] || log_blowup < 1 || log_blowup > 8) return ZK_E_ARG;
     const int field = tables[0]->field;
     if (field_limbs64(field) != 4) return ZK_E_ARG;
@@ -332,7 +334,8 @@ int commit_columns(const zk_table *const *tables, uint32_t k, uint32_t log_blowu
     const size_t n = tables[0]->len << log_blowup, leaves = n >> 2;       // N >= 4: d >= 1 and b >= 1
     int rc = ZK_OK;
     for (uint32_t c = 0; c < k && rc == ZK_OK; c++) {
-        rc = zk_table_clone(tables[c], &cm->coeffs[c]);
+        if (adopt) cm->coeffs[c] = adopt[c];
+        else rc = zk_table_clone(tables[c], &cm->coeffs[c]);
         if (rc == ZK_OK) rc = zk_table_alloc(field, n, &cm->codeword[c]);
     }
     if (rc == ZK_OK) {
@@ -359,6 +362,7 @@ int commit_columns(const zk_table *const *tables, uint32_t k, uint32_t log_blowu
     }
     if (rc != ZK_OK) {
         (void)hipStreamSynchronize(cur_stream());
+        for (uint32_t c = 0; adopt && c < k; c++) cm->coeffs[c] = nullptr;   // still the caller's
         zk_fri_columns_free(cm);
         return rc;
     }
@@ -374,6 +378,12 @@ int commit_columns(const zk_table *const *tables, uint32_t k, uint32_t log_blowu
 }
 
 }  // namespace
+
+int zk::fri_commit_columns_adopt(zk_table *const *tables, uint32_t k, uint32_t log_blowup, const uint64_t *coset, zk_fri_columns **out) {
+    for (uint32_t c = 0; tables && c < k && c < ZK_FRI_COLUMNS_MAX; c++)
+        if (tables[c] && (tables[c]->owned == 0 || !tables[c]->dptr)) return ZK_E_ARG;      // a view of the caller's memory cannot change hands
+    return commit_columns(tables, k, log_blowup, coset, out, tables);
+}
 
 extern "C" {
 

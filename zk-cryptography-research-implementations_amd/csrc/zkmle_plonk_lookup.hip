@@ -11,27 +11,15 @@
 #include "eq_table.cuh"
 #include "lookup_driver.cuh"
 #include "plonk_lookup.cuh"
+#include "plonk_lookup_driver.cuh"
 #include "plonk_lookup_host.h"
 #include "wiring_driver.cuh"
 
 using namespace zk;
 using namespace zk::host;
 
-namespace {
-
-thread_local zk_plonk_lookup_stats g_stats{};
-
-constexpr int kTables = kPlonkLookupTables;                  // the twenty opened and E
-static_assert(kTables == kPlonkLookupOpened + 1, "the pass folds the opened tables and E");
-
-// the prover's five helper commitments (M, H0, H1, H2, HL): freed with the call
-struct HelperCommits {
-    zk_fri_commitment *cm[kPlonkLookupHelpers] = {};
-    ~HelperCommits() { for (zk_fri_commitment *c : cm) zk_fri_commitment_free(c); }
-};
-
-// sums (device, 7 elements) of a pass over q pairs whose id tables are c_l + 2^l x + j 2^d.  Launches only.
-template <class F> int launch_round(bool fold, const PlonkLookupTables &t, size_t q, const Fe<F> &r, const WiringChallenges<F> &ch, const Fe<F> &id_base, unsigned log_step,
+// plonk_lookup_driver.cuh's launcher.  Sums (device, 7 elements) of a pass over q pairs whose id tables are c_l + 2^l x + j 2^d.  Launches only.
+template <class F> int zk::host::plonk_lookup_launch_round(bool fold, const PlonkLookupTables &t, size_t q, const Fe<F> &r, const WiringChallenges<F> &ch, const Fe<F> &id_base, unsigned log_step,
                                     unsigned d, void *partials, void *sums) {
     const int grid = reduce_grid_for(q);
     PlonkLookupConsts<F> c;
@@ -53,6 +41,22 @@ template <class F> int launch_round(bool fold, const PlonkLookupTables &t, size_
     ZK_HIP(hipGetLastError());
     return ZK_OK;
 }
+
+template int zk::host::plonk_lookup_launch_round<Fr381>(bool, const PlonkLookupTables &, size_t, const Fe<Fr381> &, const WiringChallenges<Fr381> &, const Fe<Fr381> &, unsigned, unsigned, void *, void *);
+template int zk::host::plonk_lookup_launch_round<Bn254Fr>(bool, const PlonkLookupTables &, size_t, const Fe<Bn254Fr> &, const WiringChallenges<Bn254Fr> &, const Fe<Bn254Fr> &, unsigned, unsigned, void *, void *);
+
+namespace {
+
+thread_local zk_plonk_lookup_stats g_stats{};
+
+constexpr int kTables = kPlonkLookupTables;                  // the twenty opened and E
+static_assert(kTables == kPlonkLookupOpened + 1, "the pass folds the opened tables and E");
+
+// the prover's five helper commitments (M, H0, H1, H2, HL): freed with the call
+struct HelperCommits {
+    zk_fri_commitment *cm[kPlonkLookupHelpers] = {};
+    ~HelperCommits() { for (zk_fri_commitment *c : cm) zk_fri_commitment_free(c); }
+};
 
 template <class F> int round_once(const zk_table *const *in, const WiringChallenges<F> &ch, const uint64_t *id_base, unsigned log_step, const uint64_t *r, zk_table **outs,
                                   uint64_t *gout) {
@@ -78,7 +82,7 @@ template <class F> int round_once(const zk_table *const *in, const WiringChallen
         }
     }
     Fe<F> S[kWiringSums], g[kPlonkNodes];
-    int rc = launch_round<F>(fold, t, q, fold ? load_host<F>(r) : fe_one<F>(), ch, load_host<F>(id_base), log_step, ilog2(2 * q) + log_step, sb.buf.p, sb.sums);
+    int rc = plonk_lookup_launch_round<F>(fold, t, q, fold ? load_host<F>(r) : fe_one<F>(), ch, load_host<F>(id_base), log_step, ilog2(2 * q) + log_step, sb.buf.p, sb.sums);
     for (int j = 0; fold && rc == ZK_OK && j < kTables; j++)
         if (hipMemcpyAsync(o[j]->dptr, (char *)folded.p + (size_t)j * t.ostride, t.ostride, hipMemcpyDeviceToDevice, cur_stream()) != hipSuccess) rc = ZK_E_HIP;
     if (rc == ZK_OK && zk::memcpy_on_stream(S, sb.sums, kWiringSums * ESZ, hipMemcpyDeviceToHost) != hipSuccess) rc = ZK_E_HIP;
@@ -169,7 +173,7 @@ template <class F> int prove_rounds(const zk_fri_commitment *const *cms, const u
             t.ostride = (n >> l) * ESZ;
             id_base = fe_add<F>(id_base, fe_mul<F>(fe_from_u64<F>((uint64_t)1 << (l - 1)), r));
         }
-        ZK_TRY(launch_round<F>(l != 0, t, n >> (l + 1), r, ch, id_base, l, d, sb.buf.p, sb.sums));
+        ZK_TRY(plonk_lookup_launch_round<F>(l != 0, t, n >> (l + 1), r, ch, id_base, l, d, sb.buf.p, sb.sums));
         Fe<F> S[kWiringSums], g[kPlonkNodes];
         ZK_HIP(zk::memcpy_on_stream(S, sb.sums, kWiringSums * ESZ, hipMemcpyDeviceToHost));   // the round's synchronisation
         if (l == 0) eqb.release();

@@ -9,7 +9,13 @@ opening (include/zkmle.h "Plonk with lookups: gate, wiring, public inputs and lo
   (fri.open_multilinear_batch_wide) at the point the rounds leave ends the proof, all on one transcript.  The prover does not check the
   statement: a false one gets a proof that does not verify, and `last_stats()["misses"]` counts the rows whose triple is in no table row.
   `verify` is host code and needs nothing but the fifteen roots and the public values.  `round` is the kernel on its own.  `table_columns` and
-  `sigma_from_cycles` are zk.lookup's and zk.wiring's.  Proving runs on the GPU (there is no CPU path)."""
+  `sigma_from_cycles` are zk.lookup's and zk.wiring's.  Proving runs on the GPU (there is no CPU path).
+
+  `prove_columns(witness, circuit, public_inputs, ..)` is the same statement on TWO column commitments (include/zkmle.h "Plonk with lookups on
+  column commitments"): witness = fri.commit_columns((A, B, C), ..) and circuit = fri.commit_columns((qM, qL, qR, qO, qC, SA, SB, SC, qK, T0, T1,
+  T2), ..), the circuit preprocessed once.  The four helper tables are made by ONE kernel (`helpers` is that kernel on its own) and committed as
+  one four-column commitment, M as a one-column one, and fri.open_columns of the four commitments ends the proof.  `verify_columns` is host code
+  and holds the witness root, the circuit root and the public values."""
 import ctypes as C
 
 import numpy as np
@@ -125,4 +131,96 @@ def last_stats():
     the four helper tables, the five commitments together, the eq table, the rounds, the opening, and the host clock over the call"""
     st = _Stats()
     L.check(L.lib().zk_plonk_lookup_last_stats(C.byref(st)))
+    return {name: getattr(st, name) for name, _ in _Stats._fields_}
+
+
+# ---- on column commitments ------------------------------------------------------------------------------------------------------------------
+WIDTHS = (3, 12, 1, 4)                                       # witness, circuit, M, the helpers: the twenty in the order above
+HELPER_INPUTS = "A, B, C, SA, SB, SC, qK, T0, T1, T2, M"
+
+
+def helpers(tables, beta, gamma):
+    """the four helper tables in one pass; tables = (A, B, C, SA, SB, SC, qK, T0, T1, T2, M) -> (H0, H1, H2, HL) in the single-denominator
+    form: H_j = (Dsig_j - Did_j) inv0(Did_j Dsig_j), HL = (qK Dt - M Dw) inv0(Dw Dt), inv0(0) = 0"""
+    if len(tables) != 11:
+        raise ValueError("the helper pass takes eleven tables: " + HELPER_INPUTS)
+    field = tables[0].field
+    ins, outs = (C.c_void_p * 11)(*[t._h for t in tables]), (C.c_void_p * 4)()
+    L.check(L.lib().zk_plonk_lookup_helpers(ins, L.p64(_elem(field, beta)), L.p64(_elem(field, gamma)), outs))
+    return tuple(MultilinearPolynomial(field, _handle=C.c_void_p(h)) for h in outs)
+
+
+def helpers_batch():
+    """the rows a lane of the helper kernel takes; its tile is 256 times as many"""
+    return int(L.lib().zk_plonk_lookup_helpers_batch())
+
+
+def sizes_columns(d, log_blowup, log_final, nqueries):
+    """-> (nround, nhroots, nroots, nfinal, nvalues, path_bytes, nopen_round): the 5 d elements of the round polynomials, the 2 helper roots,
+    then the counts of fri.columns_sizes((3, 12, 1, 4), ..)"""
+    out = [C.c_size_t(0) for _ in range(7)]
+    L.check(L.lib().zk_plonk_lookup_sizes_columns(d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+class PlonkLookupColumnsProof:
+    """h_roots (2, 32): the roots of M and of the helpers' four-column commitment; round_polys (d, 5, limbs); ys (20, limbs) = the values of the
+    twenty columns at the point, in the order of PlonkLookupProof's; opening: the fri.FriColumnsOpening of the four commitments of widths 3, 12,
+    1, 4 there (its ys are the same array).  drawn and challenges as PlonkLookupProof's.  The public values are the statement's."""
+
+    K, NODES = OPENED, NODES
+
+    def __init__(self, field, d, log_blowup, log_final, nqueries, coset=None, grinding_bits=0):
+        n = limbs(field)
+        self.field, self.d = field, d
+        self.h_roots = np.zeros((2, 32), np.uint8)
+        self.drawn = np.zeros((4 + d, n), np.uint64)
+        self.round_polys = np.zeros((d, self.NODES, n), np.uint64)
+        self.challenges = np.zeros((d, n), np.uint64)
+        self.opening = fri.FriColumnsOpening(field, WIDTHS, 1, d, log_blowup, log_final, nqueries, coset, grinding_bits)
+
+    @property
+    def ys(self):
+        return self.opening.ys[:, 0]
+
+    @property
+    def point(self):
+        """(1, d, limbs): where the columns are opened"""
+        return np.ascontiguousarray(self.challenges[::-1])[None]
+
+
+def prove_columns(witness, circuit, public_inputs, log_final, nqueries, transcript=None, grinding_bits=0):
+    """the proof for the column commitments witness = (A, B, C) and circuit = (qM, qL, qR, qO, qC, SA, SB, SC, qK, T0, T1, T2) of one shape
+    (fri.commit_columns) and the public values public_inputs ((l, limbs), l <= 2^d, or None); d - log_final >= 2"""
+    pub, pp = _public(witness.field, public_inputs)
+    pr = PlonkLookupColumnsProof(witness.field, witness.d, witness.log_blowup, log_final, nqueries, witness.coset, grinding_bits)
+    op, nonce = pr.opening, C.c_uint64(0)
+    L.check(L.lib().zk_plonk_lookup_prove_columns(witness._h, circuit._h, pp, pub.shape[0], log_final, nqueries, grinding_bits, fri._handle(transcript),
+                                                  L.p8(pr.h_roots), L.p64(pr.drawn), L.p64(pr.round_polys), L.p64(pr.challenges), *fri._prover_outputs(op),
+                                                  C.byref(nonce)))
+    op.pow_nonce = int(nonce.value)
+    return pr
+
+
+def verify_columns(witness_root, circuit_root, public_inputs, proof, transcript=None):
+    """host only: the two roots (32 bytes each) as the verifier holds them; public_inputs as for prove_columns"""
+    op, ok = proof.opening, C.c_int(0)
+    hr = np.ascontiguousarray(proof.h_roots, np.uint8)
+    if hr.shape != (2, 32):
+        raise L.ZkError(L.ZK_E_ARG, "two 32-byte helper roots")
+    pub, pp = _public(op.field, public_inputs)
+    # the opening's roots and claims are those of the four commitments; only the first two are the verifier's own
+    rf, _, ys, arrays = fri._verifier_inputs(op, [witness_root, circuit_root, hr[0].tobytes(), hr[1].tobytes()], op.ys, k=len(WIDTHS))
+    own = np.frombuffer(bytes(witness_root) + bytes(circuit_root), np.uint8).copy()
+    rp = np.ascontiguousarray(proof.round_polys, np.uint64)
+    L.check(L.lib().zk_plonk_lookup_verify_columns(op.field, L.p8(own[:32]), L.p8(own[32:]), pp, pub.shape[0], op.d, op.log_blowup, op.log_final, op.nqueries,
+                                                   op._coset(), fri._handle(transcript), L.p8(hr), L.p64(rp), L.p64(ys), *arrays, getattr(op, "grinding_bits", 0),
+                                                   getattr(op, "pow_nonce", 0), C.byref(ok)))
+    return bool(ok.value)
+
+
+def columns_last_stats():
+    """last_stats for the calling thread's last prove_columns: ms_fractions is the one helper kernel, ms_commit the two helper commitments"""
+    st = _Stats()
+    L.check(L.lib().zk_plonk_lookup_columns_last_stats(C.byref(st)))
     return {name: getattr(st, name) for name, _ in _Stats._fields_}
