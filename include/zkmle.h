@@ -330,7 +330,9 @@ uint32_t zk_fri_commitment_log_group(const zk_fri_commitment *cm);              
 int zk_fri_pcs_sizes(uint32_t k, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, size_t *nroots, size_t *nfinal,
                      size_t *nvalues, size_t *path_bytes, size_t *nopened, size_t *opened_path_bytes);
 /* y = sum_i coeffs[i] z^i of a device table of 2^d coefficients (d >= 0), on the device: the element zk_uni_evaluate gives on the host.
- * One lane per run of 8 coefficients, the powers of z from a two-level table, two launches and one 32-byte download. */
+ * One lane per run of 8 coefficients, the powers of z from a two-level table, two launches and one 32-byte download.  At most 512
+ * workgroups; the environment's ZK_FRI_PCS_EVAL_BLOCKS, read per call and clamped to 1 .. 512, lowers that cap (tests: a short table then
+ * takes the later trips of the kernel's loop).  y does not depend on it. */
 int zk_uni_evaluate_device(const zk_table *coeffs, const uint64_t *z, uint64_t *y);
 /* step 3 on its own (as zk_fri_fold is for the fold): a new table of N entries from the k codewords, ys (k elements) and gamma.  The N
  * inversions are Montgomery batch inversions of T entries per lane, T = N / 2^16 between 1 and 16;

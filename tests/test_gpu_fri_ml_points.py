@@ -6,6 +6,8 @@ with the Python model (tests/_fri_ml_points_model.py) or with the library's own 
              table lengths 2^1 .. 2^15 (one lane, under a wave, one workgroup of 256 lanes, two -- a table is a power of two, so "just over
              one" is two -- and up to 64 workgroups per reduction),
              r = 0, 1, p - 1 and random, W all zero and W with entries p - 1
+  stride     the second trip of the grid-stride loops of both round passes, fri_ml_round_w_kernel and the one-point opening's
+             fri_ml_round_kernel: one child process (tests/_fri_ml_worker.py) with ZK_REDUCE_BLOCKS=64
   open       every output equals the model's at d = 1 .. 10, b = 1, 2, P = 1, 2, 3, both fields, with and without a coset (f among 0, 1,
              d - 1); once at d = 15 and once with P = 8; ys = zk_mle_evaluate at each point; a caller's transcript; argument errors
   gkr        sparse_prove_succinct / sparse_verify_succinct on both fields: the reference shape at depth 3 and a random wide circuit with
@@ -14,7 +16,11 @@ with the Python model (tests/_fri_ml_points_model.py) or with the library's own 
              the first root; gkr.sparse_verify on an ordinary proof is unchanged"""
 import copy
 import functools
+import json
+import os
 import random
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -26,6 +32,7 @@ from oracle import pymodel as M
 from test_gpu_fri import hasher_for, table_of, to_mont, zk  # noqa: F401  (zk: the module's fixture)
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = (0, 3)
 
 
@@ -70,6 +77,16 @@ def test_round_pass_at_operands_random_tables_never_reach(zk, field):
         for W in ([0] * n, [p - 1] * n, edge):
             check_round(zk, field, T, W, (p - 1, rng.randrange(2, p - 1)))
         check_round(zk, field, [p - 1] * n, [p - 1] * n, (p - 1, 1))
+
+
+def test_the_second_trip_of_the_grid_stride_loops():
+    e = dict(os.environ, ZK_REDUCE_BLOCKS="64")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_fri_ml_worker.py")], capture_output=True, text=True, env=e, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["blocks"] == 64, out
+    assert out["trips"] == {"round_w round0": 2, "round_w fold": 2, "round round0": 4, "round fold": 2}, out
+    assert out["mismatches"] == [] and out["checked"] == 15, out
 
 
 # ---- the opening -----------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,11 @@ Everything compares byte for byte with the Python models (tests/_fri_pcs_model.p
 tolerance anywhere.
 
   evaluation   zk_uni_evaluate_device against the model and the host zk_uni_evaluate for every 2^0 .. 2^14 (one run of 8 coefficients and
-               its neighbours, one block, several blocks, and 2^13 / 2^14 on both sides of the second power table), z = 0, 1, p - 1, random
+               its neighbours, one block, several blocks, and 2^13 / 2^14 on both sides of the second power table), z = 0, 1, p - 1, random;
+               those launch one lane per run.  The later trips of the kernel's stride loop: with the grid capped at 1 and 2 workgroups
+               (ZK_FRI_PCS_EVAL_BLOCKS) 2^11 .. 2^14 take 1, 2, 4, 8 and 1, 1, 2, 4 trips, on random, all p - 1, zero and delta tables
+               (the delta at both ends of the second trip's first run pins the power that scales it); at the library's own cap 2^20 (512
+               partials: the finishing kernel's second trip) and 2^21 (the main kernel's)
   commit       root = the model's = root_0 of zk_fri_prove; codeword = zk_uni_low_degree_extend
   quotient     every N = 4 .. 2^15 with every T of the batch inversion forced through ZK_FRI_PCS_BATCH (N < 256 T included), k = 1, 2, 5,
                coset or not, a constant polynomial, z = 0, z next to the domain, and the FRI fold witnesses as operands of uni_muladd
@@ -12,6 +16,7 @@ import ctypes as C
 import functools
 import os
 import random
+import re
 
 import numpy as np
 import pytest
@@ -32,22 +37,28 @@ U64P = C.POINTER(C.c_uint64)
 
 class forced_batch:
     """with forced_batch(T): the quotient's batch inversion takes T entries per lane (the library reads the variable per call)"""
+    name = "ZK_FRI_PCS_BATCH"
 
     def __init__(self, t):
         self.t = t
 
     def __enter__(self):
-        self.old = os.environ.get("ZK_FRI_PCS_BATCH")
+        self.old = os.environ.get(self.name)
         if self.t is None:
-            os.environ.pop("ZK_FRI_PCS_BATCH", None)
+            os.environ.pop(self.name, None)
         else:
-            os.environ["ZK_FRI_PCS_BATCH"] = str(self.t)
+            os.environ[self.name] = str(self.t)
 
     def __exit__(self, *exc):
         if self.old is None:
-            os.environ.pop("ZK_FRI_PCS_BATCH", None)
+            os.environ.pop(self.name, None)
         else:
-            os.environ["ZK_FRI_PCS_BATCH"] = self.old
+            os.environ[self.name] = self.old
+
+
+class eval_cap(forced_batch):
+    """with eval_cap(c): the evaluation launches at most c workgroups (read per call); eval_cap(None): the library's own cap"""
+    name = "ZK_FRI_PCS_EVAL_BLOCKS"
 
 
 def elem(zk, field, v):
@@ -83,6 +94,84 @@ def test_evaluation_equals_the_model_and_the_host(zk, field, logn):
         assert host_evaluate(field, host.ctypes.data_as(U64P), n, zm.ctypes.data_as(U64P), ref.ctypes.data_as(U64P)) == 0
         assert np.array_equal(got, ref), (logn, z)
         assert not zk.ntt.evaluate_at(zeros, zm).any()
+
+
+# The lengths above launch one lane per run.  Past the grid cap a lane of pcs_eval_kernel takes a second run, which it scales by a power of z
+# that only that trip reads, and adds to the sum it kept; past 256 partials a lane of pcs_eval_finish_kernel adds a second partial.
+def eval_constants():
+    """the kernel's own constants, read from csrc/fri_pcs.cuh: the trip counts asserted below follow the code, not a copy of its numbers"""
+    src = open(os.path.join(G.PKG_DIR, "csrc", "fri_pcs.cuh")).read()
+    block, run, cap = (int(re.search(r"constexpr \w+ %s = (\d+);" % name, src).group(1)) for name in ("kPcsBlock", "kPcsEvalRun", "kPcsEvalMaxBlocks"))
+    return block, run, cap
+
+
+def eval_trips(n, cap=None):
+    """(trips of pcs_eval_kernel's stride loop, trips of pcs_eval_finish_kernel's loop, runs a stride covers) for n coefficients"""
+    block, run, max_blocks = eval_constants()
+    nruns = -(-n // run)
+    blocks = min(-(-nruns // block), max_blocks if cap is None else max(1, min(cap, max_blocks)))
+    return -(-nruns // (blocks * block)), -(-blocks // block), blocks * block
+
+
+def host_evaluate(zk, field, host, zm):
+    fn = zk.lib().zk_uni_evaluate
+    fn.argtypes, fn.restype = [C.c_int, U64P, C.c_size_t, U64P, U64P], C.c_int
+    ref = np.zeros(4, np.uint64)
+    assert fn(field, host.ctypes.data_as(U64P), len(host), zm.ctypes.data_as(U64P), ref.ctypes.data_as(U64P)) == 0
+    return ref
+
+
+# cap -> log n -> the trips of the stride loop.  Cap 2 at 2^12 is exactly one full trip, and its second trip (2^13) starts at coefficient
+# 4096, the first that reads the power table's `hi` half; cap 1's starts at 2048, inside `lo` (at 2^12 there is no `hi` at all).
+CAPPED_TRIPS = {1: {11: 1, 12: 2, 13: 4, 14: 8}, 2: {11: 1, 12: 1, 13: 2, 14: 4}}
+
+
+@pytest.mark.parametrize("logn", range(11, 15))
+@pytest.mark.parametrize("cap", (1, 2))
+@pytest.mark.parametrize("field", FIELDS)
+def test_evaluation_on_the_later_trips_of_a_capped_grid(zk, field, cap, logn):
+    p, n = NM.MODULUS[field], 1 << logn
+    _, run, _ = eval_constants()
+    trips, finish_trips, stride_runs = eval_trips(n, cap)
+    assert (trips, finish_trips) == (CAPPED_TRIPS[cap][logn], 1)
+    tables = {"random": NM.random_ints(field, n, 620 * field + 10 * logn + cap), "all p - 1": [p - 1] * n, "zero": [0] * n}
+    if trips > 1:                                                        # a delta at both ends of the first run that a second trip takes
+        s = stride_runs * run
+        assert s == 2048 * cap and s + run <= n
+        for name, at in (("delta first", s), ("delta last", s + run - 1)):
+            tables[name] = [0] * at + [1] + [0] * (n - at - 1)
+    zs = (0, 1, p - 1, random.Random(3 * logn + field + cap).randrange(2, p - 1))
+    for name, coeffs in tables.items():
+        table, host = table_of(zk, field, coeffs), to_mont(zk, field, coeffs)
+        for z in zs:
+            zm = elem(zk, field, z)
+            with eval_cap(cap):
+                got = zk.ntt.evaluate_at(table, zm)
+            want = PM.evaluate(field, coeffs, z)
+            if name.startswith("delta"):
+                assert want == pow(z, coeffs.index(1), p)
+            assert zk.to_ints(field, got.reshape(1, -1)) == [want], (name, cap, logn, z)
+            assert np.array_equal(got, host_evaluate(zk, field, host, zm)), (name, cap, logn, z)
+            with eval_cap(None):                                         # the uncapped launch, one run a lane, gives the same element
+                assert np.array_equal(got, zk.ntt.evaluate_at(table, zm)), (name, cap, logn, z)
+
+
+@pytest.mark.parametrize("logn", (20, 21))
+@pytest.mark.parametrize("field", FIELDS)
+def test_evaluation_at_the_default_cap_past_one_trip(zk, field, logn):
+    """2^20 coefficients: the last length of one run a lane, 512 partials, so the finishing kernel's lanes add two each.  2^21: a lane of the
+    main kernel takes two runs.  These are the kernels behind every y of an opening at d >= 20."""
+    p, n = NM.MODULUS[field], 1 << logn
+    assert eval_trips(n)[:2] == {20: (1, 2), 21: (2, 2)}[logn]
+    coeffs = NM.random_ints(field, n, 630 * field + logn)
+    host = to_mont(zk, field, coeffs)
+    table = zk.MultilinearPolynomial.vector(field, host)
+    z = random.Random(630 + logn + field).randrange(2, p - 1)
+    zm = elem(zk, field, z)
+    with eval_cap(None):
+        got = zk.ntt.evaluate_at(table, zm)
+    assert zk.to_ints(field, got.reshape(1, -1)) == [PM.evaluate(field, coeffs, z)], logn
+    assert np.array_equal(got, host_evaluate(zk, field, host, zm)), logn
 
 
 # ---- commit ----------------------------------------------------------------------------------------------------------------------------

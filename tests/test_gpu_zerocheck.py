@@ -5,13 +5,22 @@
             workgroup, two, up to 64 workgroups a reduction), in both forms and both fields, r among 0, 1, p - 1 and random; the folded
             tables equal mle_fold_last, the inputs are unchanged; and at the operands random tables never reach: all four tables all p - 1,
             E all zero, C = A o B exactly (g(0) + g(1) = 0 then, at every length), entries drawn from {0, p - 1, random}
+  stride    the second trip of the grid-stride loop: one child process (tests/_zerocheck_worker.py mul) with ZK_REDUCE_BLOCKS=64 runs round
+            0's form at 2^16 entries and the fold form at 2^17, on random tables and on tables all p - 1 with r = p - 1, against the same
+            model; the child reports the cap it ran with
+  finish    finish_sums_kernel above 256 partials a sum: round 0's form at 2^18 entries under the default cap (512 workgroups), random
+            tables and all p - 1
   prove     with C = A o B in Python integers every output equals the model's: d = 1 .. 10 with both blow-ups, the three schedules, with and
             without a coset, log_final among 0, 1, d - 1 and both fields spread over them; once at d = 15; once with 8 bits of proof of work.
             ys = zk_mle_evaluate of each table at the reversed challenges; verify_mul accepts; a false statement is proved and not verified;
             a caller's transcript ends in the verifier's state
   refusals  commitments of different d, field, blow-up or grouping, and grouped ones at log_arity = 1: ZK_E_ARG, nothing written"""
 import ctypes as C
+import json
+import os
 import random
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -26,6 +35,7 @@ from oracle import pymodel as M
 from test_gpu_fri import table_of, to_mont, zk  # noqa: F401  (zk: the module's fixture)
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = (0, 3)
 Q = 6
 SCHEDULES = [(1, False), (2, False), (2, True)]
@@ -93,6 +103,45 @@ def test_round_at_operands_random_tables_never_reach(zk, field, fold):
             for r in rs:
                 g = check_round(zk, field, [A, B, Cc, E], r, ("C = A o B folded", loglen, r))
                 assert (g[0] + g[1]) % p == ZM.interpolate4(ZM.round_g4(A, B, Cc, E, p), r, p)
+
+
+def run_stride_worker(kernel):
+    """tests/_zerocheck_worker.py for `kernel` ("mul" or "gate") in a fresh process with the reduction grid capped at 64 workgroups"""
+    e = dict(os.environ, ZK_REDUCE_BLOCKS="64")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_zerocheck_worker.py"), kernel], capture_output=True, text=True, env=e, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["kernel"] == kernel and out["blocks"] == 64, out
+    assert out["trips"] == {"round0": 2, "fold": 2}, out
+    assert out["mismatches"] == [] and out["checked"] == 10, out
+
+
+def test_the_second_trip_of_the_grid_stride_loop():
+    run_stride_worker("mul")
+
+
+# The default cap of the reduction grids (mle_kernels.cuh reduce_block_cap, 1536 workgroups of 256 lanes) and the lanes of the one workgroup
+# of finish_sums_kernel, which adds the workgroups' partial sums: past 256 partials a sum, each of its lanes adds a second one.
+REDUCE_BLOCK = 256
+
+
+def reduce_grid_for(work):
+    cap = min(max(int(os.environ.get("ZK_REDUCE_BLOCKS", "1536")), 64), 16384)     # this process's cap, as the library reads it
+    return max(1, min(-(-work // REDUCE_BLOCK), cap))
+
+
+@pytest.mark.parametrize("kind", ("random", "all p - 1"))
+def test_the_finishing_kernel_above_256_partials(zk, kind):
+    """round 0's form at 2^18 entries is 2^17 pairs: 512 workgroups at the default cap, one pair a lane, so what is new here is
+    finish_sums_kernel, every lane of which adds two partials of each of the four sums.  The passes of the wiring, Plonk, lookup and
+    Plonk-with-lookups provers hand their partials to the same kernel in the same layout (partials[sum * grid + block]) with 7 sums for 4:
+    its loop over the sums is the one run here."""
+    field, n = 0, 1 << 18
+    p = NM.MODULUS[field]
+    grid = reduce_grid_for(n // 2)
+    assert grid == 512 and -(-grid // REDUCE_BLOCK) == 2
+    tabs = [NM.random_ints(field, n, 4600 + j) for j in range(4)] if kind == "random" else [[p - 1] * n] * 4
+    check_round(zk, field, tabs, None, kind)
 
 
 # ---- the prover ---------------------------------------------------------------------------------------------------------------------------

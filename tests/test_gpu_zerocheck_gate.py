@@ -7,6 +7,9 @@ anywhere.
             folded tables equal mle_fold_last, the inputs are unchanged; and at 2^10 entries at the operands random tables never reach: all
             nine tables all p - 1, E all zero, all selectors zero (every sum is 0), entries drawn from {0, p - 1, random}, a satisfied circuit
             (g(0) = g(1) = 0 in round 0's form; g(0) + g(1) = the previous quartic at r after a fold)
+  stride    the second trip of the grid-stride loop: one child process (tests/_zerocheck_worker.py gate) with ZK_REDUCE_BLOCKS=64 runs round
+            0's form at 2^16 entries and the fold form at 2^17, on random tables and on tables all p - 1 with r = p - 1, against the same
+            model; the child reports the cap it ran with
   tie       with qM = 1, qO = p - 1, qL = qR = qC = 0 the pass is zk_zerocheck_mul_round's on (A, B, C, E): g5[0 .. 3] = its g4, g5[4] the
             cubic extrapolated
   prove     on a satisfied circuit every output equals the model's: d = 1 .. 8 with both blow-ups, the three schedules, with and without a
@@ -29,6 +32,7 @@ import _ntt_model as NM
 import _zerocheck_gate_model as ZG
 from oracle import pymodel as M
 from test_gpu_fri import table_of, to_mont, zk  # noqa: F401  (zk: the module's fixture)
+from test_gpu_zerocheck import run_stride_worker
 
 pytestmark = pytest.mark.gpu
 FIELDS = (0, 3)
@@ -122,6 +126,10 @@ def test_the_gate_with_the_products_selectors_is_the_mul_round(zk, field, fold):
         if fold:
             for j, k in ((0, 0), (1, 1), (2, 2), (3, 8)):
                 assert np.array_equal(got4[j].evaluated_values, got5[0][k].evaluated_values), (loglen, j)
+
+
+def test_the_second_trip_of_the_grid_stride_loop():
+    run_stride_worker("gate")
 
 
 # ---- the prover ---------------------------------------------------------------------------------------------------------------------------

@@ -65,10 +65,18 @@ template <class F> struct PowTables {
 };
 
 // ---- evaluation ----------------------------------------------------------------------------------------------------------------
+// the grid cap of the evaluation: kPcsEvalMaxBlocks.  ZK_FRI_PCS_EVAL_BLOCKS (environment, read per call; tests) lowers it, clamped to
+// 1 .. kPcsEvalMaxBlocks, so that a short table takes the later trips of the kernel's stride loop.
+unsigned eval_block_cap() {
+    const char *e = getenv("ZK_FRI_PCS_EVAL_BLOCKS");
+    if (!e || !*e) return kPcsEvalMaxBlocks;
+    const long v = atol(e);
+    return v < 1 ? 1u : (v > (long)kPcsEvalMaxBlocks ? kPcsEvalMaxBlocks : (unsigned)v);
+}
 // out[slot] (device) = sum_i coeffs[i] z^i: launches only.  `partials`: room for kPcsEvalMaxBlocks elements.
 template <class F> int launch_evaluate(const zk_table *coeffs, const Fe<F> &z, const PowTables<F> &pw, void *partials, void *out, unsigned slot) {
-    const size_t nruns = (coeffs->len + kPcsEvalRun - 1) / kPcsEvalRun, want = (nruns + kPcsBlock - 1) / kPcsBlock;
-    const unsigned blocks = (unsigned)(want < kPcsEvalMaxBlocks ? want : kPcsEvalMaxBlocks);
+    const size_t nruns = (coeffs->len + kPcsEvalRun - 1) / kPcsEvalRun, want = (nruns + kPcsBlock - 1) / kPcsBlock, cap = eval_block_cap();
+    const unsigned blocks = (unsigned)(want < cap ? want : cap);
     pcs_eval_kernel<F><<<blocks, kPcsBlock, 0, cur_stream()>>>(coeffs->dptr, coeffs->len, pw.lo, pw.hi, z, partials);
     ZK_HIP(hipGetLastError());
     pcs_eval_finish_kernel<F><<<1, kPcsBlock, 0, cur_stream()>>>(partials, blocks, out, slot);
