@@ -1595,6 +1595,25 @@ int zk_gkr_sparse_prove_succinct(int field, const zk_sparse_circuit *c, const zk
 int zk_gkr_sparse_wiring_eval(int field, const zk_gate *layer_gates, size_t ngates, uint32_t out_bits, uint32_t in_bits,
                               const uint64_t *alpha, const uint64_t *pa, const uint64_t *beta, const uint64_t *pb,
                               const uint64_t *rb, const uint64_t *rc, uint64_t *add_r, uint64_t *mul_r);
+/* one phase's table kernel on its own, on tables the caller chooses (a hook for tests: it runs the functions the prover runs per layer --
+ * the conversion of half tables to the products' internal form, the grid, the choice of kernel -- after the same grouping of the gate list).
+ * phase 1: *x = H1, *y = H0 over the left index b,  H1(b) = sum_{g: left_g = b} w_g ([add] + [mul] other[right_g]),  H0(b) = sum_{g add: left_g = b}
+ * w_g other[right_g];  phase 2: *x = C = A + u M, *y = A over the right index c,  A / M(c) = sum_{g add / mul: right_g = c} w_g other[left_g].
+ * Both are new tables of 2^in_bits entries.  The weight w_g of a gate comes either from half tables, w_g = ah[o >> lbits] al[o & (2^lbits - 1)]
+ * (+ bh[..] bl[..]; bh = bl = NULL: one product) at its output index o, with ah, bh of 2^(out_bits - lbits) and al, bl of 2^lbits entries and
+ * 1 <= lbits < out_bits -- any reduced elements, not only eq tables; the kernels then run in the internal form, as the prover's do for layers
+ * of more than 12 output bits -- or from w, ngates weights in gate order (ah .. bl NULL; ngates = 0: w is not read and may be NULL).  The other
+ * table is `other`, 2^in_bits entries (phase 1: the next layer's values; phase 2: eq(rb*, .)), or in phase 2 its halves other_hi of
+ * 2^(in_bits - other_lbits) and other_lo of 2^other_lbits entries, 1 <= other_lbits < in_bits (`other` NULL), which run in the internal form with
+ * weights from half tables and in the stored form with w: the four combinations the prover reaches.  u: one reduced element, phase 2 only.
+ * ZK_E_ARG, with nothing written: a phase other than 1 or 2, half tables AND w or neither (but for ngates = 0), half tables with ngates = 0, bh
+ * without bl, halves of the other table in phase 1 or together with `other`, lbits or other_lbits out of range, out_bits or in_bits outside
+ * 1 .. 30, a table of another field or length, u NULL in phase 2.  Then ZK_E_NO_DEVICE; ZK_E_RANGE for a gate index that does not fit.  The
+ * inputs are not modified.  Extension: no reference counterpart. */
+int zk_gkr_sparse_phase_tables(int field, int phase /* 1 | 2 */, const zk_gate *gates, size_t ngates, uint32_t out_bits, uint32_t in_bits,
+                               const zk_table *ah, const zk_table *al, const zk_table *bh, const zk_table *bl, uint32_t lbits,
+                               const zk_table *w, const zk_table *other, const zk_table *other_hi, const zk_table *other_lo,
+                               uint32_t other_lbits, const uint64_t *u, zk_table **x, zk_table **y);
 /* layer-by-layer evaluation of a sparse circuit on the GPU; evals = layer 0 .. inputs concatenated */
 int zk_sparse_circuit_evaluate(int field, const zk_gate *gates, const size_t *gate_counts, size_t nlayers,
                                const uint32_t *out_bits, const uint64_t *inputs, size_t ninputs, uint64_t *evals);

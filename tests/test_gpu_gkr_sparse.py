@@ -253,3 +253,58 @@ def test_mid_size_proofs_bit_identical_to_the_linear_time_oracle(zk, field, wiri
     circuit = zk.gkr.SparseCircuit(rows, out_bits, n)           # the compiled-circuit path: the same bytes
     again = zk.gkr.sparse_prove(field, None, None, x, circuit=circuit)
     assert np.array_equal(again.coeffs, want["coeffs"]) and np.array_equal(again.challenges, want["challenges"])
+
+
+def _check_whole_proof(zk, field, rows, out_bits, x):
+    want = O.gkr_prove_wide(field, rows, out_bits, x)
+    proof = zk.gkr.sparse_prove(field, rows, out_bits, x)
+    assert np.array_equal(proof.circuit_output, want["circuit_output"])
+    assert np.array_equal(proof.output_challenges, want["output_challenges"])
+    assert np.array_equal(proof.layer_claims, want["layer_claims"])
+    assert np.array_equal(proof.coeffs, want["coeffs"])
+    assert np.array_equal(proof.challenges, want["challenges"])
+    assert np.array_equal(proof.wb_evals, want["wb_evals"]) and np.array_equal(proof.wc_evals, want["wc_evals"])
+    assert np.array_equal(np.asarray(proof.claimed_sum).reshape(-1), want["claimed_sum"])
+    return proof
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("field", [0, 3])
+@pytest.mark.parametrize("shape", [(10, 13, 10, 13), (13, 10, 13, 10)], ids=["10-13-10-in13", "13-10-13-in10"])
+def test_mixed_width_proofs_bit_identical_to_the_linear_time_oracle(zk, field, shape):
+    """The table kernels pick the weights' form by the layer's output width (> 12 bits: half tables in the products' internal form) and the
+    other table's form by its input width, independently.  Equal widths only ever pair internal with internal and table with table; here a
+    wide layer reads a narrow one -- umul_std(weight, eq entry) in phase 2 -- and a narrow layer reads a wide one -- a weight table with the
+    stored halves of eq(rb*, .).  Random wiring, 2^13 gates a layer, the whole proof against oracle/gkr_wide.c (pinned to the dense model on
+    both fields by tests/test_oracle_gkr_wide.py)."""
+    *out_bits, in_last = shape
+    widths = list(out_bits) + [in_last]
+    rng = np.random.default_rng(0x5EED0500 + 13 * field + shape[0])
+    n = 1 << 13
+    rows = []
+    for l in range(len(out_bits)):
+        g = np.zeros((n, 4), np.uint64)
+        g[:, 0] = rng.integers(0, 1 << widths[l + 1], n)
+        g[:, 1] = rng.integers(0, 1 << widths[l + 1], n)
+        g[:, 2] = rng.integers(0, 1 << widths[l], n)              # some outputs fed by several gates, some by none
+        g[:, 3] = rng.integers(0, 2, n)
+        rows.append(g)
+    x = zk.MultilinearPolynomial.random(field, 1 << in_last, 0x5EED0500 + field).evaluated_values
+    x[:4] = zk.from_ints(field, [0, 1, O.modulus(field) - 1, 2])
+    proof = _check_whole_proof(zk, field, rows, out_bits, x)
+    assert zk.gkr.sparse_verify(field, rows, out_bits, proof, x) is True
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("field", [1, 3])
+def test_lg13_proofs_on_the_fields_the_internal_form_had_not_run_on(zk, field):
+    """Layers of 2^13 outputs are the smallest that take the internal-form path; until now only BLS12-381 Fr and BN254 Fq ran it.  BN254 Fr and
+    BLS12-381 Fq (14 limbs of 29 bits: the one L = 14 instance of umul2) against oracle/gkr_wide.c.  The oracle is templated on the field like
+    the prover; the dense big-int model pins it on the 32-byte fields only, so the proof must pass the sparse verifier as well."""
+    lg, depth = 13, 3
+    rows = _layers("random", lg, depth, 0x5EED0600 + field)
+    out_bits = [lg] * depth
+    x = zk.MultilinearPolynomial.random(field, 1 << lg, 0x5EED0600 + field).evaluated_values
+    x[:4] = zk.from_ints(field, [0, 1, O.modulus(field) - 1, 2])
+    proof = _check_whole_proof(zk, field, rows, out_bits, x)
+    assert zk.gkr.sparse_verify(field, rows, out_bits, proof, x) is True

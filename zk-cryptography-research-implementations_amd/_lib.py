@@ -243,6 +243,9 @@ def lib():
         "zk_plonk_lookup_verify_columns": [C.c_int, u8p, u8p, u64p] + [C.c_uint32] * 5 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
                                                                                        C.POINTER(C.c_int)],
         "zk_plonk_lookup_columns_last_stats": [vp],
+        # sparse GKR: one phase's table kernel on caller-chosen tables (a gate array is passed as a void pointer)
+        "zk_gkr_sparse_phase_tables": [C.c_int, C.c_int, vp, sz, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, u64p,
+                                       C.POINTER(vp), C.POINTER(vp)],
         "zk_sumcheck_basic_prove_succinct": [vp, C.c_uint32, C.c_uint32, vp, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p],
         "zk_sumcheck_basic_verify_succinct": [C.c_int, u8p] + [C.c_uint32] * 4 + [u64p, vp, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u8p,
                                                                                  C.POINTER(C.c_int)],

@@ -18,6 +18,7 @@
 
 #include "context.h"
 #include "eq_table.cuh"
+#include "gkr_tables.cuh"
 #include "sumcheck_kernels.cuh"
 #include "transcript.h"
 
@@ -69,42 +70,7 @@ template <class F> __global__ void gate_weights_kernel(const uint32_t *__restric
 // on average (random wiring: 224 +- 15 gates) their gates fit ONE pass of 256 gate lanes 98 % of the time; longer ranges (skewed circuits)
 // take more passes of 256.  Same sums, other order.
 constexpr int kPhaseGroups = kBlock - 32;
-// Where a gate's weight w_g = alpha eq(rb, out_g) + beta eq(rc, out_g) comes from.  Small layers: the table w (gate order), indexed through the
-// group's order list.  Layers of > kEqSmallBits output bits: straight from the HALF tables of the two eq tables (entry o = hi[o >> lbits] *
-// lo[o & mask], eq_table.cuh; the constants ride on the high halves), indexed by the gate's output index stored in grouped order -- four
-// 64 KB tables that live in L2 and two products per gate, instead of building two 2^out_bits tables, adding them up gate by gate into w
-// (three passes over 128 MB at 2^22) and gathering w from HBM.
-struct GateWeights {
-    const void *w;                       // non-null: the table of weights in gate order
-    const void *ah, *al, *bh, *bl;       // else: half tables of alpha eq(rb, .) and (bh non-null) beta eq(rc, .)
-    unsigned lbits;
-    const void *uah, *ual, *ubh, *ubl;   // the same half tables in the products' internal form (UHalves below); uah non-null: the kernels use these
-};
-// the table gathered at a gate's other index: an array (W in phase 1), or the half tables of an eq table (eq(rb*, .) in phase 2)
-struct OtherTable {
-    const void *tab;                     // non-null: the table itself
-    const void *hi, *lo;                 // else its half tables
-    unsigned lbits;
-    const void *uhi, *ulo;               // the half tables in the internal form (with GateWeights::uah)
-};
-// ---- half tables in the products' internal form (r3) ------------------------------------------------------------------------------
-// The table kernels are VALU-bound, and more than half of their VALU work was not multiply-adds but what surrounds a product on stored
-// operands: 32-bit -> 29-bit limbs of one operand, digit extraction of the other, conditional subtraction and 29-bit -> 32-bit limbs of
-// the result -- ~190 instructions around 162 multiply-adds, four products per gate.  The half tables are 2^11 entries each and are
-// built once per layer, so they are converted once: L limbs of 29 bits per entry (ufield.cuh), and the Montgomery factors are chosen so that
-// a gate's chain of products needs no conversion until its result is stored.  With R = 2^(32 N) (the stored form) and U = 2^(29 L):
-//   weights:  ah' = limbs29(ah R), al' = al U  ->  umul2(ah', al', bh', bl') = (ah al + bh bl) R = the weight in the stored form, below 1.06 p;
-//   other:    hi' = hi U, lo' = lo U            ->  umul(hi', lo') = hi lo U;   umul(w R, h U) = w h R, the stored form of the product;
-//   or a stored table entry x R                 ->  umul_std(w R, x R) = w x R  (digits of x: the one conversion left).
-// U / p = 2^6.1, so every one of these is below 1.5 p and one conditional subtraction gives the canonical limbs the old chain gave.
-template <class F> constexpr int u_stride_words() { return (UParams<F>::L + 3) / 4 * 4; }          // 16-byte aligned entries
-template <class F> __device__ __forceinline__ Ufe<F> ufe_load(const void *tab, uint32_t idx) {
-    const uint32_t *p = reinterpret_cast<const uint32_t *>(tab) + (size_t)idx * u_stride_words<F>();
-    Ufe<F> r;
-#pragma unroll
-    for (int j = 0; j < UParams<F>::L; j++) r.l[j] = p[j];
-    return r;
-}
+// (GateWeights, OtherTable, the half tables' internal form and a gate's chain of products: gkr_tables.cuh)
 // out[i] = in[i] as 29-bit limbs: the stored integer itself (mont = 0) or times U / R (mont = 1), fully reduced; two tables per launch
 template <class F> __global__ void halves_to_u_kernel(const void *__restrict__ in0, uint32_t n0, int mont0, void *__restrict__ out0,
                                                       const void *__restrict__ in1, uint32_t n1, int mont1, void *__restrict__ out1) {
@@ -113,7 +79,7 @@ template <class F> __global__ void halves_to_u_kernel(const void *__restrict__ i
     if (second) i -= n0;
     if (second && i >= n1) return;
     const Fe<F> x = fe_load<F>(second ? in1 : in0, i);
-    const Ufe<F> u = (second ? mont1 : mont0) ? u_reduce_once<F>(u_from_std<F>(x)) : u_from_limbs32<F>(x);
+    const Ufe<F> u = half_to_u<F>(x, second ? mont1 : mont0);
     uint32_t *o = reinterpret_cast<uint32_t *>(second ? out1 : out0) + (size_t)i * u_stride_words<F>();
 #pragma unroll
     for (int j = 0; j < u_stride_words<F>(); j++) o[j] = j < UParams<F>::L ? u.l[j] : 0u;
@@ -126,37 +92,6 @@ template <class F> int halves_to_u(const void *hi, int mont_hi, const void *lo, 
     ZK_HIP(hipGetLastError());
     return ZK_OK;
 }
-template <class F> __device__ __forceinline__ Ufe<F> gate_weight_u(const GateWeights &g, uint32_t idx) {        // the weight, stored form, as 29-bit limbs below 1.06 p
-    const uint32_t h = idx >> g.lbits, l = idx & ((1u << g.lbits) - 1u);
-    if (g.ubh) return umul2<F>(ufe_load<F>(g.uah, h), ufe_load<F>(g.ual, l), ufe_load<F>(g.ubh, h), ufe_load<F>(g.ubl, l));
-    return umul<F>(ufe_load<F>(g.uah, h), ufe_load<F>(g.ual, l));
-}
-template <class F> __device__ __forceinline__ Ufe<F> other_times_u(const OtherTable &t, uint32_t idx, const Ufe<F> &wu) {   // w x entry, stored form, below 1.5 p
-    if (t.tab) return umul_std<F>(wu, fe_load<F>(t.tab, idx));
-    return umul<F>(wu, umul<F>(ufe_load<F>(t.uhi, idx >> t.lbits), ufe_load<F>(t.ulo, idx & ((1u << t.lbits) - 1u))));
-}
-template <class F> __device__ __forceinline__ Fe<F> other_entry(const OtherTable &t, uint32_t idx) {
-    if (t.tab) return fe_load<F>(t.tab, idx);
-    return fe_mul<F>(fe_load<F>(t.hi, idx >> t.lbits), fe_load<F>(t.lo, idx & ((1u << t.lbits) - 1u)));
-}
-template <class F> __device__ __forceinline__ Fe<F> gate_weight(const GateWeights &g, uint32_t idx) {
-    if (g.w) return fe_load<F>(g.w, idx);
-    const uint32_t h = idx >> g.lbits, l = idx & ((1u << g.lbits) - 1u);
-    if (g.bh) return fe_mul2_u<F>(fe_load<F>(g.ah, h), fe_load<F>(g.al, l), fe_load<F>(g.bh, h), fe_load<F>(g.bl, l));   // one reduction for both products
-    return fe_mul<F>(fe_load<F>(g.ah, h), fe_load<F>(g.al, l));
-}
-struct Phase1Op {            // per gate: w and t = w W[right]; add gate: H1 += w, H0 += t; mul gate: H1 += t
-    static constexpr bool kNeedsWeight = true;
-    template <class F> static __device__ __forceinline__ void terms(const Fe<F> &wg, const Fe<F> &t, uint32_t op, Fe<F> &x, Fe<F> &y) {
-        if (op == 0) { x = wg; y = t; } else { x = t; y = fe_zero<F>(); }
-    }
-};
-struct Phase2Op {            // per gate: t = w eqL[left]; add gate: A += t; mul gate: M += t
-    static constexpr bool kNeedsWeight = false;
-    template <class F> static __device__ __forceinline__ void terms(const Fe<F> &, const Fe<F> &t, uint32_t op, Fe<F> &x, Fe<F> &y) {
-        if (op == 0) { x = t; y = fe_zero<F>(); } else { x = fe_zero<F>(); y = t; }
-    }
-};
 template <class F, class Op, bool UH>
 __device__ __forceinline__ void grouped_pair_sums(const uint32_t *__restrict__ start, size_t nb, const GateWeights &gw, const uint32_t *__restrict__ order,
                                                   const uint32_t *__restrict__ other, const uint32_t *__restrict__ op, const OtherTable &tab,
@@ -174,16 +109,7 @@ __device__ __forceinline__ void grouped_pair_sums(const uint32_t *__restrict__ s
         const uint32_t e = base + tid;                                                  // one lane per gate
         if (e < e1) {
             const uint32_t oi = order[e], ti = other[e], pi = op[e];
-            if constexpr (UH) {                                                         // half tables in the internal form: no conversions inside the chain
-                const Ufe<F> wu = gate_weight_u<F>(gw, oi);
-                const Fe<F> t = u_to_limbs32<F>(u_reduce_once<F>(other_times_u<F>(tab, ti, wu)));
-                const Fe<F> wg = Op::kNeedsWeight ? u_to_limbs32<F>(u_reduce_once<F>(wu)) : fe_zero<F>();
-                Op::template terms<F>(wg, t, pi, cx[tid], cy[tid]);
-            } else {
-                const Fe<F> x = other_entry<F>(tab, ti);
-                const Fe<F> wg = gate_weight<F>(gw, oi);
-                Op::template terms<F>(wg, fe_mul<F>(wg, x), pi, cx[tid], cy[tid]);
-            }
+            gate_terms<F, Op, UH>(gw, tab, oi, ti, pi, cx[tid], cy[tid]);                // gkr_tables.cuh
         }
         __syncthreads();
         const uint32_t lo = rs > base ? rs : base, hi = re < base + kBlock ? re : base + (uint32_t)kBlock;
@@ -477,6 +403,50 @@ int build_layers(const zk_gate *gates, const size_t *gate_counts, size_t nlayers
     return ZK_OK;
 }
 
+// ---- the table kernels' set-up and launches: what sparse_prove runs per layer, and zk_gkr_sparse_phase_tables on a caller's tables --------
+struct WeightBufs { DevBuf uah, ual, ubh, ubl; };
+struct OtherBufs { DevBuf uhi, ulo; };
+// gw.ah / al (and bh / bl) are the stored half tables: the kernels read them in the products' internal form (gkr_tables.cuh): high halves as
+// they are stored, low halves times U / R
+template <class F> int weights_to_internal(GateWeights &gw, uint32_t out_bits, WeightBufs &b) {
+    ZK_TRY((halves_to_u<F>(gw.ah, 0, gw.al, out_bits, gw.lbits, b.uah, b.ual)));
+    gw.uah = b.uah.p; gw.ual = b.ual.p;
+    if (gw.bh) {
+        ZK_TRY((halves_to_u<F>(gw.bh, 0, gw.bl, out_bits, gw.lbits, b.ubh, b.ubl)));
+        gw.ubh = b.ubh.p; gw.ubl = b.ubl.p;
+    }
+    return ZK_OK;
+}
+// tl.hi / lo are the stored half tables of the other table (k index bits); with internal-form weights both go times U / R: their product is
+// the entry times U
+template <class F> int other_to_internal(OtherTable &tl, uint32_t k, const GateWeights &gw, OtherBufs &b) {
+    if (!gw.uah) return ZK_OK;
+    ZK_TRY((halves_to_u<F>(tl.hi, 1, tl.lo, k, tl.lbits, b.uhi, b.ulo)));
+    tl.uhi = b.uhi.p; tl.ulo = b.ulo.p;
+    return ZK_OK;
+}
+// weights from half tables are indexed by the gates' output indices in grouped order, a weight table by the group's order list
+template <class F> int launch_phase1_tables(const LayerDev &Ly, const GateWeights &gw, const void *W, void *H1, void *H0) {
+    const size_t nk = (size_t)1 << Ly.in_bits;
+    const unsigned grid = (unsigned)((nk + kPhaseGroups - 1) / kPhaseGroups);
+    const uint32_t *st = (const uint32_t *)Ly.st_left.p, *wi = (const uint32_t *)(gw.w ? Ly.ord_left.p : Ly.l_out.p);
+    const uint32_t *oth = (const uint32_t *)Ly.l_right.p, *ops = (const uint32_t *)Ly.l_op.p;
+    if (gw.uah) phase1_tables_kernel<F, true><<<grid, kBlock, 0, cur_stream()>>>(st, nk, gw, wi, oth, ops, W, H1, H0);
+    else phase1_tables_kernel<F, false><<<grid, kBlock, 0, cur_stream()>>>(st, nk, gw, wi, oth, ops, W, H1, H0);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+template <class F> int launch_phase2_tables(const LayerDev &Ly, const GateWeights &gw, const OtherTable &tl, const void *u_dev, void *Cc, void *A) {
+    const size_t nk = (size_t)1 << Ly.in_bits;
+    const unsigned grid = (unsigned)((nk + kPhaseGroups - 1) / kPhaseGroups);
+    const uint32_t *st = (const uint32_t *)Ly.st_right.p, *wi = (const uint32_t *)(gw.w ? Ly.ord_right.p : Ly.r_out.p);
+    const uint32_t *oth = (const uint32_t *)Ly.r_left.p, *ops = (const uint32_t *)Ly.r_op.p;
+    if (gw.uah) phase2_tables_kernel<F, true><<<grid, kBlock, 0, cur_stream()>>>(st, nk, gw, wi, oth, ops, tl, u_dev, Cc, A);
+    else phase2_tables_kernel<F, false><<<grid, kBlock, 0, cur_stream()>>>(st, nk, gw, wi, oth, ops, tl, u_dev, Cc, A);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+
 // the hook of the succinct prover (zk_gkr_sparse_prove_succinct): the transcript's FIRST append is `root32`, the root of a commitment to
 // the inputs, and the inputs are that commitment's device table.  Null everywhere else: nothing is appended, `inputs` is uploaded.
 struct InputBinding {
@@ -538,7 +508,9 @@ template <class F> int sparse_prove(std::vector<LayerDev> &layers, const uint64_
         // gate weights w_g = eq(ra, out_g) (layer 0) or alpha eq(rb, out_g) + beta eq(rc, out_g): the previous layer's challenges and
         // alpha / beta are read from its slots, the constants folded into the eq half tables (eq_table.cuh)
         TablePtr eqA, eqB;
-        DevBuf w, uah, ual, ubh, ubl, uhi, ulo;
+        DevBuf w;
+        WeightBufs wbufs;
+        OtherBufs obufs;
         EqBuilder<F> ebA, ebB;                                 // the half tables live until the layer's kernels are enqueued (stream-ordered pool)
         GateWeights gw{};
         static const bool want_table = [] { const char *e = getenv("ZK_GKR_WEIGHT_TABLE"); return e && e[0] == '1'; }();   // measurements / tests
@@ -552,13 +524,7 @@ template <class F> int sparse_prove(std::vector<LayerDev> &layers, const uint64_
                 ZK_TRY(ebA.halves_dev(ps->slot_ptr(p1 + 3), per, Ly.out_bits, &gw.ah, &gw.al, &gw.lbits, ps->slot_ptr(plk + 2)));   // alpha eq(rb, .)
                 ZK_TRY(ebB.halves_dev(ps->slot_ptr(p2 + 3), per, Ly.out_bits, &gw.bh, &gw.bl, &lb2, ps->slot_ptr(plk + 3)));        // beta eq(rc, .)
             }
-            // the kernels read them in the products' internal form (UHalves above): high halves as they are stored, low halves times U / R
-            ZK_TRY((halves_to_u<F>(gw.ah, 0, gw.al, Ly.out_bits, gw.lbits, uah, ual)));
-            gw.uah = uah.p; gw.ual = ual.p;
-            if (gw.bh) {
-                ZK_TRY((halves_to_u<F>(gw.bh, 0, gw.bl, Ly.out_bits, gw.lbits, ubh, ubl)));
-                gw.ubh = ubh.p; gw.ubl = ubl.p;
-            }
+            ZK_TRY((weights_to_internal<F>(gw, Ly.out_bits, wbufs)));
         } else {
             ZK_TRY(w.alloc((ng ? ng : 1) * esz));
             if (l == 0) {
@@ -577,14 +543,7 @@ template <class F> int sparse_prove(std::vector<LayerDev> &layers, const uint64_
         TablePtr H1, H0;
         ZK_TRY(alloc_table(F::ID, nk, H1));
         ZK_TRY(alloc_table(F::ID, nk, H0));
-        {
-            const unsigned grid = (unsigned)((nk + kPhaseGroups - 1) / kPhaseGroups);
-            const uint32_t *st = (const uint32_t *)Ly.st_left.p, *wi = (const uint32_t *)(halves ? Ly.l_out.p : Ly.ord_left.p);
-            const uint32_t *oth = (const uint32_t *)Ly.l_right.p, *ops = (const uint32_t *)Ly.l_op.p;
-            if (gw.uah) phase1_tables_kernel<F, true><<<grid, kBlock, 0, cur_stream()>>>(st, nk, gw, wi, oth, ops, Wn->dptr, H1->dptr, H0->dptr);
-            else phase1_tables_kernel<F, false><<<grid, kBlock, 0, cur_stream()>>>(st, nk, gw, wi, oth, ops, Wn->dptr, H1->dptr, H0->dptr);
-        }
-        ZK_HIP(hipGetLastError());
+        ZK_TRY((launch_phase1_tables<F>(Ly, gw, Wn->dptr, H1->dptr, H0->dptr)));
         const zk_table *t1[4] = {Wn, H1.get(), H0.get(), nullptr};
         // the layer's claim (alpha wb + beta wc of the previous link, already in its slot) is absorbed in front of round 0
         ZK_TRY(ps->rounds(s1, t1, 2, 2, one, nullptr, l > 0 ? 1 : 0, l > 0 ? base[l - 1] + 2 * (per * layers[l - 1].in_bits + 4) + 4 : 0));
@@ -596,24 +555,14 @@ template <class F> int sparse_prove(std::vector<LayerDev> &layers, const uint64_
         OtherTable tl{};
         if (k > (uint32_t)kEqSmallBits && !want_table) {           // eq(rb*, .) is only gathered once per gate: half tables do (as for the weights)
             ZK_TRY(ebL.halves_dev(ps->slot_ptr(s1 + 3), per, k, &tl.hi, &tl.lo, &tl.lbits));
-            if (gw.uah) {                                           // both halves times U / R: their product is eq(rb*, .) U (UHalves above)
-                ZK_TRY((halves_to_u<F>(tl.hi, 1, tl.lo, k, tl.lbits, uhi, ulo)));
-                tl.uhi = uhi.p; tl.ulo = ulo.p;
-            }
+            ZK_TRY((other_to_internal<F>(tl, k, gw, obufs)));
         } else {
             ZK_TRY((eq_table_dev<F>(ps->slot_ptr(s1 + 3), per, k, eqL)));
             tl.tab = eqL->dptr;
         }
         ZK_TRY(alloc_table(F::ID, nk, Cc));
         ZK_TRY(alloc_table(F::ID, nk, A));
-        {
-            const unsigned grid = (unsigned)((nk + kPhaseGroups - 1) / kPhaseGroups);
-            const uint32_t *st = (const uint32_t *)Ly.st_right.p, *wi = (const uint32_t *)(halves ? Ly.r_out.p : Ly.ord_right.p);
-            const uint32_t *oth = (const uint32_t *)Ly.r_left.p, *ops = (const uint32_t *)Ly.r_op.p;
-            if (gw.uah) phase2_tables_kernel<F, true><<<grid, kBlock, 0, cur_stream()>>>(st, nk, gw, wi, oth, ops, tl, u_dev, Cc->dptr, A->dptr);
-            else phase2_tables_kernel<F, false><<<grid, kBlock, 0, cur_stream()>>>(st, nk, gw, wi, oth, ops, tl, u_dev, Cc->dptr, A->dptr);
-        }
-        ZK_HIP(hipGetLastError());
+        ZK_TRY((launch_phase2_tables<F>(Ly, gw, tl, u_dev, Cc->dptr, A->dptr)));
         const zk_table *t2[4] = {Cc.get(), Wn, A.get(), nullptr};
         const void *cdev[2] = {nullptr, u_dev};
         ZK_TRY(ps->rounds(s2, t2, 2, 2, nullptr, cdev, 0, 0));
@@ -674,6 +623,49 @@ template <class F> int wiring_eval(const zk_gate *g, size_t ngates, uint32_t out
     ZK_HIP(zk::memcpy_on_stream(both, res, esz * 2, hipMemcpyDeviceToHost));
     memcpy(add_r, both, esz);
     memcpy(mul_r, both + F::N / 2, esz);
+    return ZK_OK;
+}
+
+// zk_gkr_sparse_phase_tables: one phase's table kernel on a caller's tables, through the prover's own set-up and launch functions
+struct PhaseTablesArgs {
+    int phase;
+    const zk_table *ah, *al, *bh, *bl, *w, *other, *other_hi, *other_lo;
+    uint32_t lbits, other_lbits;
+    const uint64_t *u;
+};
+template <class F> int phase_tables(const LayerDev &Ly, const PhaseTablesArgs &a, zk_table **x, zk_table **y) {
+    GateWeights gw{};
+    WeightBufs wbufs;
+    OtherBufs obufs;
+    if (a.ah) {
+        gw.ah = a.ah->dptr; gw.al = a.al->dptr; gw.lbits = a.lbits;
+        if (a.bh) { gw.bh = a.bh->dptr; gw.bl = a.bl->dptr; }
+        ZK_TRY((weights_to_internal<F>(gw, Ly.out_bits, wbufs)));
+    } else {
+        gw.w = a.w->dptr;
+    }
+    const size_t nk = (size_t)1 << Ly.in_bits;
+    TablePtr X, Y;
+    ZK_TRY(alloc_table(F::ID, nk, X));
+    ZK_TRY(alloc_table(F::ID, nk, Y));
+    if (a.phase == 1) {
+        ZK_TRY((launch_phase1_tables<F>(Ly, gw, a.other->dptr, X->dptr, Y->dptr)));
+    } else {
+        OtherTable tl{};
+        if (a.other) {
+            tl.tab = a.other->dptr;
+        } else {
+            tl.hi = a.other_hi->dptr; tl.lo = a.other_lo->dptr; tl.lbits = a.other_lbits;
+            ZK_TRY((other_to_internal<F>(tl, Ly.in_bits, gw, obufs)));
+        }
+        DevBuf u_dev;
+        ZK_TRY(u_dev.upload(a.u, 4 * F::N));
+        ZK_TRY((launch_phase2_tables<F>(Ly, gw, tl, u_dev.p, X->dptr, Y->dptr)));
+        ZK_HIP(hipStreamSynchronize(cur_stream()));          // `u_dev` goes back to the pool
+    }
+    ZK_HIP(hipStreamSynchronize(cur_stream()));              // and the converted half tables
+    *x = X.release();
+    *y = Y.release();
     return ZK_OK;
 }
 
@@ -812,6 +804,44 @@ int zk_gkr_sparse_wiring_eval(int field, const zk_gate *layer_gates, size_t ngat
     if (!layer_gates || !pa || !rb || !rc || !add_r || !mul_r || (pb && (!alpha || !beta))) return ZK_E_ARG;
     ZK_TRY(require_device());
     ZK_DISPATCH_FIELD(field, return wiring_eval<F>(layer_gates, ngates, out_bits, in_bits, alpha, pa, beta, pb, rb, rc, add_r, mul_r));
+    return ZK_OK;
+}
+int zk_gkr_sparse_phase_tables(int field, int phase, const zk_gate *gates, size_t ngates, uint32_t out_bits, uint32_t in_bits, const zk_table *ah,
+                               const zk_table *al, const zk_table *bh, const zk_table *bl, uint32_t lbits, const zk_table *w, const zk_table *other,
+                               const zk_table *other_hi, const zk_table *other_lo, uint32_t other_lbits, const uint64_t *u, zk_table **x, zk_table **y) {
+    if (field < 0 || field > 3 || (phase != 1 && phase != 2) || !x || !y || (ngates && !gates)) return ZK_E_ARG;
+    if (out_bits == 0 || out_bits > 30 || in_bits == 0 || in_bits > 30 || ngates >= ((size_t)1 << 31)) return ZK_E_ARG;
+    auto fits = [&](const zk_table *t, size_t len) { return t && t->field == field && t->len == len && t->dptr; };
+    const bool halves = ah || al || bh || bl;
+    if (halves) {                                            // weights from half tables, run in the internal form
+        if (w || ngates == 0 || lbits < 1 || lbits >= out_bits) return ZK_E_ARG;
+        if (!fits(ah, (size_t)1 << (out_bits - lbits)) || !fits(al, (size_t)1 << lbits)) return ZK_E_ARG;
+        if ((bh != nullptr) != (bl != nullptr)) return ZK_E_ARG;
+        if (bh && (!fits(bh, (size_t)1 << (out_bits - lbits)) || !fits(bl, (size_t)1 << lbits))) return ZK_E_ARG;
+    } else if (ngates ? !fits(w, ngates) : (w && w->field != field)) {
+        return ZK_E_ARG;                                     // the weight table in gate order (no gates: it is not read)
+    }
+    const bool other_halves = other_hi || other_lo;
+    if (other_halves) {                                      // phase 2 only: the half tables of eq(rb*, .)
+        if (phase != 2 || other || other_lbits < 1 || other_lbits >= in_bits) return ZK_E_ARG;
+        if (!fits(other_hi, (size_t)1 << (in_bits - other_lbits)) || !fits(other_lo, (size_t)1 << other_lbits)) return ZK_E_ARG;
+    } else if (!fits(other, (size_t)1 << in_bits)) {
+        return ZK_E_ARG;
+    }
+    if (phase == 2 && !u) return ZK_E_ARG;
+    ZK_TRY(require_device());
+    LayerDev Ly;
+    const zk_gate no_gate{};
+    ZK_TRY(upload_layer(ngates ? gates : &no_gate, ngates, out_bits, in_bits, Ly));
+    DevBuf none;                                             // no gates and no weight table: one element that no lane reads
+    zk_table stand_in{field, 1, nullptr, 0};
+    PhaseTablesArgs a{phase, ah, al, bh, bl, w, other, other_hi, other_lo, lbits, other_lbits, u};
+    if (!halves && !w) {
+        ZK_TRY(none.alloc(48));
+        stand_in.dptr = none.p;
+        a.w = &stand_in;
+    }
+    ZK_DISPATCH_FIELD(field, return phase_tables<F>(Ly, a, x, y));
     return ZK_OK;
 }
 int zk_sparse_circuit_evaluate(int field, const zk_gate *gates, const size_t *gate_counts, size_t nlayers, const uint32_t *out_bits,

@@ -357,6 +357,24 @@ def sparse_wiring_eval(field, gate_rows, out_bits, in_bits, pa, rb, rc, alpha=No
     return a, m
 
 
+def sparse_phase_tables(field, phase, gate_rows, out_bits, in_bits, halves=None, lbits=0, w=None, other=None, other_halves=None, other_lbits=0,
+                        u=None):
+    """zk_gkr_sparse_phase_tables (include/zkmle.h): one phase's table kernel of the sparse prover on the caller's tables.  halves = (ah, al) or
+    (ah, al, bh, bl) or w; other or other_halves = (hi, lo); all MultilinearPolynomial.  u: one element (limbs), phase 2.
+    -> (H1, H0) or (C, A), new tables of 2^in_bits entries."""
+    from .mle import MultilinearPolynomial
+    rows = np.ascontiguousarray(gate_rows, np.uint64).reshape(-1, 4)
+    h = lambda t: t._h if t is not None else None
+    hv = tuple(halves) + (None,) * (4 - len(halves)) if halves is not None else (None,) * 4
+    oh = tuple(other_halves) if other_halves is not None else (None, None)
+    x, y = C.c_void_p(), C.c_void_p()
+    up = L.p64(np.ascontiguousarray(u, np.uint64)) if u is not None else None
+    L.check(L.lib().zk_gkr_sparse_phase_tables(field, phase, rows.ctypes.data if rows.shape[0] else None, rows.shape[0], out_bits, in_bits,
+                                               h(hv[0]), h(hv[1]), h(hv[2]), h(hv[3]), lbits, h(w), h(other), h(oh[0]), h(oh[1]), other_lbits, up,
+                                               C.byref(x), C.byref(y)))
+    return MultilinearPolynomial(field, _handle=x), MultilinearPolynomial(field, _handle=y)
+
+
 def _fe_to_bytes_be(field, a):
     out = np.zeros(8 * limbs(field), np.uint8)
     L.check(L.lib().zk_fe_to_bytes_be(field, L.p64(np.ascontiguousarray(a, np.uint64)), L.p8(out)))
