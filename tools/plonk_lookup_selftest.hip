@@ -1,4 +1,4 @@
-// plonk_lookup_selftest.hip -- the host verifier of the Plonk proof with lookup rows (zk_plonk_lookup_verify: csrc/plonk_lookup_host.h's replay and the
+// plonk_lookup_selftest.hip -- the host verifier of the Plonk proof with lookup rows (zk_plonk_lookup_verify: csrc/plonk_lookup_host.h's replay on csrc/zerocheck_host.h's replay_rounds, and the
 // wide opening's verifier behind it) as a stand-alone HOST program, for a sanitizer build.  It opens no device and launches nothing; the verifier
 // reaches into most of the library's translation units, so they are all compiled with the host side instrumented and linked in:
 //   for f in zk-cryptography-research-implementations_amd/csrc/*.hip tools/plonk_lookup_selftest.hip; do

@@ -1,4 +1,4 @@
-// plonk_selftest.hip -- the host verifier of the Plonk proof over FRI commitments (zk_plonk_verify: csrc/plonk_host.h's replay and the opening's
+// plonk_selftest.hip -- the host verifier of the Plonk proof over FRI commitments (zk_plonk_verify: csrc/plonk_host.h's replay on csrc/zerocheck_host.h's replay_rounds, and the opening's
 // verifier behind it) and zk_plonk_public_eval as a stand-alone HOST program, for a sanitizer build.  It opens no device and launches nothing; the verifier
 // reaches into most of the library's translation units, so they are all compiled with the host side instrumented and linked in:
 //   for f in zk-cryptography-research-implementations_amd/csrc/*.hip tools/plonk_selftest.hip; do

@@ -1,4 +1,4 @@
-// wiring_selftest.hip -- the host verifier of the permutation check over FRI commitments (zk_wiring_verify: csrc/wiring_host.h's replay and the
+// wiring_selftest.hip -- the host verifier of the permutation check over FRI commitments (zk_wiring_verify: csrc/wiring_host.h's replay on csrc/zerocheck_host.h's replay_rounds, and the
 // opening's verifier behind it) as a stand-alone HOST program, for a sanitizer build.  It opens no device and launches nothing; the verifier
 // reaches into most of the library's translation units, so they are all compiled with the host side instrumented and linked in:
 //   for f in zk-cryptography-research-implementations_amd/csrc/*.hip tools/wiring_selftest.hip; do

@@ -1,5 +1,5 @@
 // zerocheck_selftest.hip -- the host verifiers of the zerochecks (zk_zerocheck_mul_verify and zk_zerocheck_gate_verify: csrc/zerocheck_host.h's
-// replay and the opening's verifier behind it) as a stand-alone HOST program, for a sanitizer build.  It opens no device and launches nothing; the verifier
+// replay, whose rounds (replay_rounds) every verifier of the family runs, and the opening's verifier behind it) as a stand-alone HOST program, for a sanitizer build.  It opens no device and launches nothing; the verifier
 // reaches into most of the library's translation units, so they are all compiled with the host side instrumented and linked in:
 //   for f in zk-cryptography-research-implementations_amd/csrc/*.hip tools/zerocheck_selftest.hip; do
 //       hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Wno-pass-failed -c $f -o build/$(basename $f .hip).o; done

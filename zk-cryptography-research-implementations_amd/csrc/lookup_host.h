@@ -1,6 +1,6 @@
 // lookup_host.h -- the host side of the lookup argument over FRI commitments (include/zkmle.h "Lookup: rows of a committed table") that prover
 // and verifier share: the statement's absorption, the two helper roots and the challenges behind them, the final relation, and the verifier's
-// replay.  The round message is wiring_host.h's (the same seven sums), the interpolation zerocheck_host.h's.  It touches no device;
+// replay.  The round message is wiring_host.h's (the same seven sums), the interpolation and the rounds' replay zerocheck_host.h's.  It touches no device;
 // tools/lookup_selftest.hip runs it under a sanitizer.  Library-internal; included by .hip files only.
 #pragma once
 #include "wiring_host.h"
@@ -53,38 +53,16 @@ template <class F> Fe<F> lookup_relation(const LookupChallenges<F> &ch, const Fe
 // z[d - 1 - l] = r_l; *good = every check held and every element read is reduced.  The transcript advances the same way whatever *good is.
 template <class F> void lookup_replay(Transcript &tr, const uint8_t *roots, uint32_t d, const uint8_t *h_roots, const uint64_t *round_polys, const uint64_t *ys, uint64_t *z,
                                       bool *good) {
-    constexpr int W = F::N / 2;
     LookupChallenges<F> ch;
     lookup_statement(tr, roots, d);
     lookup_multiplicity_root<F>(tr, h_roots, ch);
     lookup_helper_root<F>(tr, h_roots + 32, d, ch);
     bool ok = true;
-    Fe<F> cur = fe_zero<F>();
-    for (uint32_t l = 0; l < d; l++) {
-        Fe<F> g[kWiringNodes];
-        for (int k = 0; k < kWiringNodes; k++) {
-            const uint64_t *src = round_polys + ((size_t)l * kWiringNodes + k) * W;
-            ok = ok && is_reduced<F>(src);
-            g[k] = load_host<F>(src);
-            tr.append_be<F>(g[k]);
-        }
-        ok = ok && fe_eq<F>(fe_add<F>(g[0], g[1]), cur);
-        const Fe<F> r = tr.random_challenge_as_field_element<F>();
-        store_host<F>(z + (size_t)(d - 1 - l) * W, r);
-        cur = zerocheck_interpolate_at<F, kWiringNodes>(g, r);
-    }
-    const Fe<F> one = fe_one<F>();
-    Fe<F> eq = one;
-    for (uint32_t i = 0; i < d; i++) {
-        const Fe<F> a = load_host<F>(z + (size_t)i * W), b = load_host<F>(ch.tau.data() + (size_t)i * W);
-        eq = fe_mul<F>(eq, fe_add<F>(fe_mul<F>(a, b), fe_mul<F>(fe_sub<F>(one, a), fe_sub<F>(one, b))));
-    }
+    const Fe<F> last = replay_rounds<F, kWiringNodes>(tr, d, fe_zero<F>(), round_polys, z, ok);
+    const Fe<F> eq = eq_at<F>(z, ch.tau.data(), d);
     Fe<F> y[kLookupOpened];
-    for (int j = 0; j < kLookupOpened; j++) {
-        ok = ok && is_reduced<F>(ys + (size_t)j * W);
-        y[j] = load_host<F>(ys + (size_t)j * W);
-    }
-    *good = ok && fe_eq<F>(cur, lookup_relation<F>(ch, y, eq));
+    load_claims<F>(ys, kLookupOpened, y, ok);
+    *good = ok && fe_eq<F>(last, lookup_relation<F>(ch, y, eq));
 }
 
 }  // namespace host

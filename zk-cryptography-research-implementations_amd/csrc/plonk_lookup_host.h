@@ -1,8 +1,8 @@
 // plonk_lookup_host.h -- the host side of the Plonk proof with lookup rows (include/zkmle.h "Plonk with lookups: gate, wiring, public inputs and
 // lookup rows in one sumcheck") that prover and verifier share: the statement's absorption, the roots of M and of the four helper tables with the
 // challenges behind them, the final relation and the verifier's replay.  The public inputs' value, the gate's and the wiring's relation are
-// plonk_host.h's, the lookup's relation lookup_host.h's, the round message wiring_host.h's.  It touches no device;
-// tools/plonk_lookup_selftest.hip runs it under a sanitizer.  Library-internal; included by .hip files only.
+// plonk_host.h's, the lookup's relation lookup_host.h's, the round message wiring_host.h's, the rounds' replay
+// zerocheck_host.h's.  It touches no device; tools/plonk_lookup_selftest.hip runs it under a sanitizer.  Library-internal; included by .hip files only.
 #pragma once
 #include "lookup_host.h"
 #include "plonk_host.h"
@@ -71,32 +71,12 @@ template <class F> void plonk_lookup_replay(Transcript &tr, const uint8_t *roots
     plonk_lookup_multiplicity_root<F>(tr, h_roots, ch);
     plonk_lookup_helpers<F>(tr, h_roots + 32, d, ch);
     const Fe<F> a3 = fe_mul<F>(ch.alpha, fe_mul<F>(ch.alpha, ch.alpha));
-    Fe<F> cur = fe_mul<F>(a3, plonk_public_eval<F>(pub, npublic, ch.tau.data(), d));
-    for (uint32_t l = 0; l < d; l++) {
-        Fe<F> g[kPlonkNodes];
-        for (int k = 0; k < kPlonkNodes; k++) {
-            const uint64_t *src = round_polys + ((size_t)l * kPlonkNodes + k) * W;
-            ok = ok && is_reduced<F>(src);
-            g[k] = load_host<F>(src);
-            tr.append_be<F>(g[k]);
-        }
-        ok = ok && fe_eq<F>(fe_add<F>(g[0], g[1]), cur);
-        const Fe<F> r = tr.random_challenge_as_field_element<F>();
-        store_host<F>(z + (size_t)(d - 1 - l) * W, r);
-        cur = zerocheck_interpolate_at<F, kPlonkNodes>(g, r);
-    }
-    const Fe<F> one = fe_one<F>();
-    Fe<F> eq = one;
-    for (uint32_t i = 0; i < d; i++) {
-        const Fe<F> a = load_host<F>(z + (size_t)i * W), b = load_host<F>(ch.tau.data() + (size_t)i * W);
-        eq = fe_mul<F>(eq, fe_add<F>(fe_mul<F>(a, b), fe_mul<F>(fe_sub<F>(one, a), fe_sub<F>(one, b))));
-    }
+    const Fe<F> claim0 = fe_mul<F>(a3, plonk_public_eval<F>(pub, npublic, ch.tau.data(), d));
+    const Fe<F> last = replay_rounds<F, kPlonkNodes>(tr, d, claim0, round_polys, z, ok);
+    const Fe<F> eq = eq_at<F>(z, ch.tau.data(), d);
     Fe<F> y[kPlonkLookupOpened];
-    for (int j = 0; j < kPlonkLookupOpened; j++) {
-        ok = ok && is_reduced<F>(ys + (size_t)j * W);
-        y[j] = load_host<F>(ys + (size_t)j * W);
-    }
-    *good = ok && fe_eq<F>(cur, plonk_lookup_relation<F>(ch, y, eq, wiring_id_at<F>(z, d), d));
+    load_claims<F>(ys, kPlonkLookupOpened, y, ok);
+    *good = ok && fe_eq<F>(last, plonk_lookup_relation<F>(ch, y, eq, wiring_id_at<F>(z, d), d));
 }
 
 }  // namespace host

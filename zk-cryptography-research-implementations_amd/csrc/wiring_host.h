@@ -1,7 +1,7 @@
 // wiring_host.h -- the host side of the permutation check over FRI commitments (include/zkmle.h "Wiring: a permutation check over committed
 // tables") that prover and verifier share: the statement's absorption and its challenges, the round message from the pass's seven sums, the
-// closed form of the id tables at a point, the final relation, and the verifier's replay.  The round message and the interpolation are
-// zerocheck_host.h's.  It touches no device; tools/wiring_selftest.hip runs it under a sanitizer.  Library-internal; included by .hip files only.
+// closed form of the id tables at a point, the final relation, and the verifier's replay.  The round message, the interpolation and the
+// replay of the rounds themselves (replay_rounds, eq_at, load_claims) are zerocheck_host.h's.  It touches no device; tools/wiring_selftest.hip runs it under a sanitizer.  Library-internal; included by .hip files only.
 #pragma once
 #include "zerocheck_host.h"
 
@@ -76,37 +76,15 @@ template <class F> Fe<F> wiring_relation(const WiringChallenges<F> &ch, const Fe
 // *good = every check held and every element read is reduced.  The transcript advances the same way whatever *good is.  d <= 32.
 template <class F> void wiring_replay(Transcript &tr, const uint8_t *roots, uint32_t d, const uint8_t *h_roots, const uint64_t *round_polys, const uint64_t *ys, uint64_t *z,
                                       bool *good) {
-    constexpr int W = F::N / 2;
     WiringChallenges<F> ch;
     wiring_statement<F>(tr, roots, d, ch);
     wiring_helpers<F>(tr, h_roots, d, ch);
     bool ok = true;
-    Fe<F> cur = fe_zero<F>();
-    for (uint32_t l = 0; l < d; l++) {
-        Fe<F> g[kWiringNodes];
-        for (int k = 0; k < kWiringNodes; k++) {
-            const uint64_t *src = round_polys + ((size_t)l * kWiringNodes + k) * W;
-            ok = ok && is_reduced<F>(src);
-            g[k] = load_host<F>(src);
-            tr.append_be<F>(g[k]);
-        }
-        ok = ok && fe_eq<F>(fe_add<F>(g[0], g[1]), cur);
-        const Fe<F> r = tr.random_challenge_as_field_element<F>();
-        store_host<F>(z + (size_t)(d - 1 - l) * W, r);
-        cur = zerocheck_interpolate_at<F, kWiringNodes>(g, r);
-    }
-    const Fe<F> one = fe_one<F>();
-    Fe<F> eq = one;
-    for (uint32_t i = 0; i < d; i++) {
-        const Fe<F> a = load_host<F>(z + (size_t)i * W), b = load_host<F>(ch.tau.data() + (size_t)i * W);
-        eq = fe_mul<F>(eq, fe_add<F>(fe_mul<F>(a, b), fe_mul<F>(fe_sub<F>(one, a), fe_sub<F>(one, b))));
-    }
+    const Fe<F> last = replay_rounds<F, kWiringNodes>(tr, d, fe_zero<F>(), round_polys, z, ok);
+    const Fe<F> eq = eq_at<F>(z, ch.tau.data(), d);
     Fe<F> y[kWiringOpened];
-    for (int j = 0; j < kWiringOpened; j++) {
-        ok = ok && is_reduced<F>(ys + (size_t)j * W);
-        y[j] = load_host<F>(ys + (size_t)j * W);
-    }
-    *good = ok && fe_eq<F>(cur, wiring_relation<F>(ch, y, eq, wiring_id_at<F>(z, d), d));
+    load_claims<F>(ys, kWiringOpened, y, ok);
+    *good = ok && fe_eq<F>(last, wiring_relation<F>(ch, y, eq, wiring_id_at<F>(z, d), d));
 }
 
 }  // namespace host

@@ -1,6 +1,8 @@
 // zerocheck_host.h -- the host side of the zerochecks over FRI commitments (include/zkmle.h "Zerocheck of a product of committed tables" and
 // "Zerocheck of a Plonk gate over committed tables") that prover and verifier share: the statement's absorption, the round message from the
-// pass's sums, and the verifier's replay of the sumcheck.  The two protocols differ in a statement (ZerocheckMul, ZerocheckGate): the tag, the
+// pass's sums, and the verifier's replay of the sumcheck.  The replay's three parts that do not depend on the protocol (replay_rounds, eq_at,
+// load_claims) serve the whole family: wiring_host.h, plonk_host.h, lookup_host.h, plonk_lookup_host.h and plonk_lookup_columns_host.h call
+// them between their own statement and their own relation.  The two protocols here differ in a statement (ZerocheckMul, ZerocheckGate): the tag, the
 // number of commitments K, the number of nodes a round message is sent at, how the message comes from the pass's sums, and the relation the
 // last check evaluates on the K claims.  It touches no device; tools/zerocheck_selftest.hip runs it under a sanitizer.  Library-internal;
 // included by .hip files only.
@@ -78,19 +80,17 @@ template <class F, class St> void zerocheck_statement(Transcript &tr, const uint
     for (uint32_t i = 0; i < d; i++) store_host<F>(tau + (size_t)i * (F::N / 2), tr.random_challenge_as_field_element<F>());
 }
 
-// The verifier's replay of the statement and the rounds on `tr` and its three checks: g_0(0) + g_0(1) = 0, g_l(0) + g_l(1) = g_{l-1}(r_{l-1}),
-// and g_{d-1}(r_{d-1}) = eq(z, tau) relation(ys).  round_polys: NODES d elements, ys: K.  z (d elements) receives the point,
-// z[d - 1 - l] = r_l; *good = every check held and every element read is reduced.  The transcript advances the same way whatever *good is.
-template <class F, class St> void zerocheck_replay(Transcript &tr, const uint8_t *roots, uint32_t d, const uint64_t *round_polys, const uint64_t *ys, uint64_t *z, bool *good) {
+// The verifier's replay of the d rounds on `tr`, for every protocol of the family: each round's NODES elements are read, checked for reducedness
+// and absorbed, g_l(0) + g_l(1) is checked against the running claim (claim0 at round 0), r_l is drawn and the claim becomes g_l(r_l).  z (d
+// elements) receives the point, z[d - 1 - l] = r_l; a failed check clears `ok`.  Returns g_{d-1}(r_{d-1}).  The transcript advances the same
+// way whatever `ok` is.
+template <class F, int NODES> Fe<F> replay_rounds(Transcript &tr, uint32_t d, const Fe<F> &claim0, const uint64_t *round_polys, uint64_t *z, bool &ok) {
     constexpr int W = F::N / 2;
-    std::vector<uint64_t> tau((size_t)d * W);
-    zerocheck_statement<F, St>(tr, roots, d, tau.data());
-    bool ok = true;
-    Fe<F> cur = fe_zero<F>();
+    Fe<F> cur = claim0;
     for (uint32_t l = 0; l < d; l++) {
-        Fe<F> g[St::NODES];
-        for (int k = 0; k < St::NODES; k++) {
-            const uint64_t *src = round_polys + ((size_t)l * St::NODES + k) * W;
+        Fe<F> g[NODES];
+        for (int k = 0; k < NODES; k++) {
+            const uint64_t *src = round_polys + ((size_t)l * NODES + k) * W;
             ok = ok && is_reduced<F>(src);
             g[k] = load_host<F>(src);
             tr.append_be<F>(g[k]);
@@ -98,20 +98,43 @@ template <class F, class St> void zerocheck_replay(Transcript &tr, const uint8_t
         ok = ok && fe_eq<F>(fe_add<F>(g[0], g[1]), cur);
         const Fe<F> r = tr.random_challenge_as_field_element<F>();
         store_host<F>(z + (size_t)(d - 1 - l) * W, r);
-        cur = zerocheck_interpolate_at<F, St::NODES>(g, r);
+        cur = zerocheck_interpolate_at<F, NODES>(g, r);
     }
+    return cur;
+}
+
+// eq(z, tau) = prod_i (z_i tau_i + (1 - z_i)(1 - tau_i)); z, tau: d elements, u64 limbs
+template <class F> Fe<F> eq_at(const uint64_t *z, const uint64_t *tau, uint32_t d) {
+    constexpr int W = F::N / 2;
     const Fe<F> one = fe_one<F>();
     Fe<F> eq = one;
     for (uint32_t i = 0; i < d; i++) {
-        const Fe<F> a = load_host<F>(z + (size_t)i * W), b = load_host<F>(tau.data() + (size_t)i * W);
+        const Fe<F> a = load_host<F>(z + (size_t)i * W), b = load_host<F>(tau + (size_t)i * W);
         eq = fe_mul<F>(eq, fe_add<F>(fe_mul<F>(a, b), fe_mul<F>(fe_sub<F>(one, a), fe_sub<F>(one, b))));
     }
-    Fe<F> y[St::K];
-    for (int j = 0; j < St::K; j++) {
-        ok = ok && is_reduced<F>(ys + (size_t)j * W);
-        y[j] = load_host<F>(ys + (size_t)j * W);
+    return eq;
+}
+
+// y = the K claims ys; one that is not reduced clears `ok`
+template <class F> void load_claims(const uint64_t *ys, int K, Fe<F> *y, bool &ok) {
+    for (int j = 0; j < K; j++) {
+        ok = ok && is_reduced<F>(ys + (size_t)j * (F::N / 2));
+        y[j] = load_host<F>(ys + (size_t)j * (F::N / 2));
     }
-    *good = ok && fe_eq<F>(cur, fe_mul<F>(eq, St::template relation<F>(y)));
+}
+
+// The verifier's replay of the statement and the rounds on `tr` and its three checks: g_0(0) + g_0(1) = 0, g_l(0) + g_l(1) = g_{l-1}(r_{l-1}),
+// and g_{d-1}(r_{d-1}) = eq(z, tau) relation(ys).  round_polys: NODES d elements, ys: K.  z (d elements) receives the point,
+// z[d - 1 - l] = r_l; *good = every check held and every element read is reduced.  The transcript advances the same way whatever *good is.
+template <class F, class St> void zerocheck_replay(Transcript &tr, const uint8_t *roots, uint32_t d, const uint64_t *round_polys, const uint64_t *ys, uint64_t *z, bool *good) {
+    std::vector<uint64_t> tau((size_t)d * (F::N / 2));
+    zerocheck_statement<F, St>(tr, roots, d, tau.data());
+    bool ok = true;
+    const Fe<F> last = replay_rounds<F, St::NODES>(tr, d, fe_zero<F>(), round_polys, z, ok);
+    const Fe<F> eq = eq_at<F>(z, tau.data(), d);
+    Fe<F> y[St::K];
+    load_claims<F>(ys, St::K, y, ok);
+    *good = ok && fe_eq<F>(last, fe_mul<F>(eq, St::template relation<F>(y)));
 }
 
 }  // namespace host

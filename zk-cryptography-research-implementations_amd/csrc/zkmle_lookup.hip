@@ -1,15 +1,14 @@
 // zkmle_lookup.hip -- C ABI of the lookup argument over FRI commitments (lookup.cuh, lookup_host.h): the multiplicity table, the helper table
 // and one round pass on their own, the prover (the multiplicities and their commitment, the helper table and its commitment, the sumcheck of
 // the logarithmic-derivative relation on the nine coefficient tables and E, then zk_fri_ml_open_batch_pow of the nine commitments at the
-// point the rounds leave, on the same transcript) and its host verifier.  Extension: the protocol is defined in include/zkmle.h "Lookup: rows
+// point the rounds leave, on the same transcript) and its host verifier.  The round loop, the hook's pass, the hooks' table checks and the shells'
+// shared checks are zerocheck_driver.cuh's, by wiring_driver.cuh.  Extension: the protocol is defined in include/zkmle.h "Lookup: rows
 // of a committed table".
 #include <string.h>
 
 #include <chrono>
 #include <vector>
 
-#include "eq_table.cuh"
-#include "fri_host.h"
 #include "lookup.cuh"
 #include "lookup_driver.cuh"
 #include "lookup_host.h"
@@ -23,8 +22,13 @@ namespace {
 thread_local zk_lookup_stats g_lookup_stats{};
 
 constexpr int kTables = LOOKUP_TABLES;                       // A, B, C, qK, T0, T1, T2, M, H, E
-// sums (device, 7 elements) of a pass over q pairs.  Launches only.
-template <class F> int launch_round(bool fold, const LookupTables &t, size_t q, const Fe<F> &r, const LookupChallenges<F> &ch, void *partials, void *sums) {
+// sums (device, 7 elements) of a pass over q pairs; the ten folded to out0 + j ostride.  Launches only.
+template <class F>
+int launch_round(bool fold, const void *const *in, void *out0, size_t ostride, size_t q, const Fe<F> &r, const LookupChallenges<F> &ch, void *partials, void *sums) {
+    LookupTables t{};
+    for (int j = 0; j < kTables; j++) t.in[j] = in[j];
+    t.out0 = out0;
+    t.ostride = ostride;
     const int grid = reduce_grid_for(q);
     LookupConsts<F> c;
     c.beta = ch.beta;
@@ -63,46 +67,21 @@ template <class F> int fractions_once(const zk_table *const *in, const uint64_t 
     return ZK_OK;
 }
 
-template <class F> int round_once(const zk_table *const *in, const LookupChallenges<F> &ch, const uint64_t *r, zk_table **outs, uint64_t *gout) {
-    constexpr size_t ESZ = sizeof(Fe<F>);
-    constexpr int W = F::N / 2;
-    const bool fold = r != nullptr;
-    const size_t len = in[0]->len, q = fold ? len / 4 : len / 2;
-    SumsBuf sb;
-    ZK_TRY(sb.alloc(ESZ));
-    zk_table *o[kTables] = {};
-    const auto drop = [&] { for (zk_table *t : o) zk_table_free(t); };
-    // the pass writes the folded ten into one block; the caller's new tables are copies of its tenths
-    DevBuf folded;
-    LookupTables t{};
-    for (int j = 0; j < kTables; j++) t.in[j] = in[j]->dptr;
-    if (fold) {
-        ZK_TRY(folded.alloc(kTables * (len / 2) * ESZ));
-        t.out0 = folded.p;
-        t.ostride = (len / 2) * ESZ;
-        for (int j = 0; j < kTables; j++) {
-            const int rc = zk_table_alloc(in[0]->field, len / 2, &o[j]);
-            if (rc != ZK_OK) { drop(); return rc; }
-        }
-    }
-    Fe<F> S[kWiringSums], g[kWiringNodes];
-    int rc = launch_round<F>(fold, t, q, fold ? load_host<F>(r) : fe_one<F>(), ch, sb.buf.p, sb.sums);
-    for (int j = 0; fold && rc == ZK_OK && j < kTables; j++)
-        if (hipMemcpyAsync(o[j]->dptr, (char *)folded.p + (size_t)j * t.ostride, t.ostride, hipMemcpyDeviceToDevice, cur_stream()) != hipSuccess) rc = ZK_E_HIP;
-    if (rc == ZK_OK && zk::memcpy_on_stream(S, sb.sums, kWiringSums * ESZ, hipMemcpyDeviceToHost) != hipSuccess) rc = ZK_E_HIP;
-    if (rc != ZK_OK) { drop(); return rc; }
-    wiring_message<F>(S, ch.mu, g);
-    for (int k = 0; k < kWiringNodes; k++) store_host<F>(gout + (size_t)k * W, g[k]);
-    for (int j = 0; fold && j < kTables; j++) outs[j] = o[j];
-    return ZK_OK;
+// zerocheck_driver.cuh's launch and message with the lookup's challenges
+template <class F> auto launch_with(const LookupChallenges<F> &ch) {
+    return [&ch](bool fold, const void *const *in, void *out0, size_t ostride, size_t q, const Fe<F> &r, unsigned, void *partials, void *sums) {
+        return launch_round<F>(fold, in, out0, ostride, q, r, ch, partials, sums);
+    };
+}
+template <class F> auto message_with(const LookupChallenges<F> &ch) {
+    return [&ch](const Fe<F> *S, Fe<F> *g) { wiring_message<F>(S, ch.mu, g); };
 }
 
-// steps 1 to 7 on `tr`: the statement, M and H with their commitments (hc.cm[0], hc.cm[1]; h_roots), E_0 and the d rounds; z (d elements) = the
-// point the opening is made at.  One host synchronisation per round and one for the miss count.
-template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcript &tr, CommitHolder &hc, uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys,
-                                    uint64_t *challenges, uint64_t *z, zk_lookup_stats &st) {
-    constexpr size_t ESZ = sizeof(Fe<F>);
-    constexpr int W = F::N / 2, T = kTables, K = kLookupOpened;
+// steps 1 to 7 on `tr`: the statement, M and H with their commitments (hc.cm[0], hc.cm[1]; h_roots), then E_0 and the d rounds by
+// zerocheck_driver.cuh; z (d elements) = the point the opening is made at.  One host synchronisation for the miss count beside the rounds'.
+template <class F> int prove_steps(const zk_fri_commitment *const *cms, Transcript &tr, CommitHolder &hc, uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys,
+                                   uint64_t *challenges, uint64_t *z, zk_lookup_stats &st) {
+    constexpr int W = F::N / 2, K = kLookupOpened;
     const zk_fri_commitment *c0 = cms[0];
     const unsigned d = c0->d;
     const size_t n = (size_t)1 << d;
@@ -116,7 +95,7 @@ template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcr
     LookupChallenges<F> ch;
 
     Events ev;
-    size_t e0, e1, e2, e3, e4, e5, e6;
+    size_t e0, e1, e2, e3, e4;
     ZK_TRY(ev.mark(&e0));
     {
         TableHolder th;
@@ -144,69 +123,14 @@ template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcr
         memcpy(chal_out + 3 * W, ch.tau.data(), ch.tau.size() * 8);
     }
 
-    // one block: E_0 (n elements), then the two ping-pong halves: the ten tables of an odd round (n / 2 entries each at round 1) and of an
-    // even one (n / 4 each at round 2); a round's tables never outgrow the half they first had
-    DevBuf blk;
-    SumsBuf sb;
-    ZK_TRY(blk.alloc((n + T * (n / 2) + T * (n / 4) + 1) * ESZ));
-    ZK_TRY(sb.alloc(ESZ));
-    char *E0 = (char *)blk.p, *half[2] = {E0 + n * ESZ, E0 + (n + T * (n / 2)) * ESZ};
-    const auto tables_at = [&](unsigned l, const void **out) {   // the nine tables and E at round l: n >> l entries each
-        for (int j = 0; j < T; j++) {
-            const void *own = j < kLookupGiven ? cms[j]->coeffs->dptr : j < K ? hc.cm[j - kLookupGiven]->coeffs->dptr : (void *)E0;
-            out[j] = l == 0 ? own : half[(l - 1) & 1] + (size_t)j * (n >> l) * ESZ;
-        }
-    };
-    EqBuilder<F> eqb;
-    ZK_TRY(eqb.build(ch.tau.data(), d, E0));
-    ZK_TRY(ev.mark(&e5));
-    Fe<F> r = fe_one<F>();
-    for (unsigned l = 0; l < d; l++) {
-        LookupTables t{};
-        if (l == 0) {
-            tables_at(0, t.in);
-        } else {
-            tables_at(l - 1, t.in);
-            t.out0 = half[(l - 1) & 1];
-            t.ostride = (n >> l) * ESZ;
-        }
-        ZK_TRY(launch_round<F>(l != 0, t, n >> (l + 1), r, ch, sb.buf.p, sb.sums));
-        Fe<F> S[kWiringSums], g[kWiringNodes];
-        ZK_HIP(zk::memcpy_on_stream(S, sb.sums, kWiringSums * ESZ, hipMemcpyDeviceToHost));   // the round's synchronisation
-        if (l == 0) eqb.release();
-        wiring_message<F>(S, ch.mu, g);
-        for (int k = 0; k < kWiringNodes; k++) {
-            store_host<F>(round_polys + ((size_t)l * kWiringNodes + k) * W, g[k]);
-            tr.append_be<F>(g[k]);
-        }
-        r = tr.random_challenge_as_field_element<F>();
-        store_host<F>(challenges + (size_t)l * W, r);
-        store_host<F>(z + (size_t)(d - 1 - l) * W, r);
-    }
-    ZK_TRY(ev.mark(&e6));
-    ZK_HIP(hipEventSynchronize(ev.ev[e6]));
+    const void *opened[K];
+    for (int j = 0; j < K; j++) opened[j] = (j < kLookupGiven ? cms[j] : hc.cm[j - kLookupGiven])->coeffs->dptr;
+    ZK_TRY((prove_rounds<F, kTables, kWiringSums, kWiringNodes>(opened, d, ch.tau.data(), tr, launch_with<F>(ch), message_with<F>(ch), round_polys, challenges, z, ev, &e4,
+                                                                &st.ms_eq, &st.ms_rounds)));
     st.rounds = d;
     st.ms_multiplicities = ev.ms(e0, e1);
     st.ms_fractions = ev.ms(e2, e3);
     st.ms_commit = ev.ms(e1, e2) + ev.ms(e3, e4);
-    st.ms_eq = ev.ms(e4, e5);
-    st.ms_rounds = ev.ms(e5, e6);
-    return ZK_OK;
-}
-
-// what the three hooks check alike: `count` tables, none NULL, one of the two scalar fields, one length, a power of two of at least `least`
-int check_tables(const zk_table *const *tables, int count, size_t least) {
-    if (!tables) return ZK_E_ARG;
-    for (int j = 0; j < count; j++)
-        if (!tables[j]) return ZK_E_ARG;
-    const int field = tables[0]->field;
-    if (field != ZK_FR381 && field != ZK_BN254_FR) return ZK_E_ARG;
-    for (int j = 1; j < count; j++)
-        if (tables[j]->field != field) return ZK_E_ARG;
-    for (int j = 1; j < count; j++)
-        if (tables[j]->len != tables[0]->len) return ZK_E_LEN_MISMATCH;
-    if (!is_pow2(tables[0]->len)) return ZK_E_NOT_POW2;
-    if (tables[0]->len < least) return ZK_E_ARG;
     return ZK_OK;
 }
 
@@ -233,9 +157,6 @@ int zk_lookup_fractions(const zk_table *const tables[8], const uint64_t *beta, c
 }
 
 int zk_lookup_round(const zk_table *const tables[10], const uint64_t *beta, const uint64_t *gamma, const uint64_t *mu, const uint64_t *r, zk_table **outs, uint64_t *g5) {
-    if (!tables) return ZK_E_ARG;
-    for (int j = 0; j < kTables; j++)
-        if (!tables[j]) return ZK_E_ARG;
     if (!beta || !gamma || !mu || !g5 || (r && !outs)) return ZK_E_ARG;
     ZK_TRY(check_tables(tables, kTables, r ? 4 : 2));
     const int field = tables[0]->field;
@@ -248,7 +169,7 @@ int zk_lookup_round(const zk_table *const tables[10], const uint64_t *beta, cons
         ch.beta = load_host<F>(beta);
         ch.gamma = load_host<F>(gamma);
         ch.mu = load_host<F>(mu);
-        return round_once<F>(tables, ch, r, outs, g5);
+        return round_once<F, kTables, kWiringSums, kWiringNodes>(tables, r, outs, g5, launch_with<F>(ch), message_with<F>(ch));
     });
     return ZK_OK;
 }
@@ -280,31 +201,22 @@ int zk_lookup_prove(const zk_fri_commitment *const cms[7], uint32_t log_final, u
     zk_transcript *tt = t ? t : &own;
     zk_lookup_stats st{};
     CommitHolder hc;
-    FRI_DISPATCH(cms[0]->field, ZK_TRY((prove_rounds<F>(cms, tt->t, hc, h_roots, chal_out, round_polys, challenges, z.data(), st))));
+    FRI_DISPATCH(cms[0]->field, ZK_TRY((prove_steps<F>(cms, tt->t, hc, h_roots, chal_out, round_polys, challenges, z.data(), st))));
     const zk_fri_commitment *all[kLookupOpened];
     for (int j = 0; j < kLookupOpened; j++) all[j] = j < kLookupGiven ? cms[j] : hc.cm[j - kLookupGiven];
-    ZK_TRY(zk_fri_ml_open_batch_pow(all, kLookupOpened, z.data(), 1, log_final, nqueries, log_arity, tt, ys_out, gamma_out, open_round_polys, roots, final_table,
-                                    open_challenges, query_indices, query_values, query_paths, grinding_bits, pow_nonce));
-    zk_fri_ml_stats ml{};
-    (void)zk_fri_ml_last_stats(&ml);
-    st.ms_opening = ml.ms_total;
-    st.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    g_lookup_stats = st;
-    return ZK_OK;
+    const int opened = zk_fri_ml_open_batch_pow(all, kLookupOpened, z.data(), 1, log_final, nqueries, log_arity, tt, ys_out, gamma_out, open_round_polys, roots, final_table,
+                                                open_challenges, query_indices, query_values, query_paths, grinding_bits, pow_nonce);
+    return prove_finish(opened, t0, st, g_lookup_stats);
 }
 
 int zk_lookup_verify(int field, const uint8_t *roots_of_seven, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
                      const uint64_t *coset, zk_transcript *t, const uint8_t *h_roots, const uint64_t *round_polys, const uint64_t *ys, const uint64_t *open_round_polys,
                      const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce,
                      int *ok) {
-    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
-    if (!roots_of_seven || !h_roots || !round_polys || !ys || !open_round_polys || !roots || !final_table || !query_values || !query_paths || !ok) return ZK_E_ARG;
-    // every status before the transcript is touched: the opening's own on an empty replay; the replay and the opening's verifier run on a copy
-    // that becomes the caller's transcript only with ZK_OK
-    if (field_limbs64(field) < 0) return ZK_E_ARG;
-    ZK_TRY(zk_fri_ml_sizes_batch(kLookupOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, nullptr, nullptr, nullptr, nullptr, nullptr));
-    if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
-    if ((field != ZK_FR381 && field != ZK_BN254_FR) || d + log_blowup > two_adicity(field)) return ZK_E_RANGE;
+    const bool have_all = roots_of_seven && h_roots && round_polys && ys && open_round_polys && roots && final_table && query_values && query_paths && ok;
+    ZK_TRY(verify_check(field, d, log_blowup, coset, grinding_bits, have_all, [&] {
+        return zk_fri_ml_sizes_batch(kLookupOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, nullptr, nullptr, nullptr, nullptr, nullptr);
+    }));
     uint8_t nine[32 * kLookupOpened];
     memcpy(nine, roots_of_seven, 32 * kLookupGiven);
     memcpy(nine + 32 * kLookupGiven, h_roots, 32 * kLookupHelpers);

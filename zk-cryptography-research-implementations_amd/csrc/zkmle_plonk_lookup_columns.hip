@@ -1,19 +1,18 @@
 // zkmle_plonk_lookup_columns.hip -- C ABI of the Plonk proof with lookup rows on COLUMN commitments (plonk_helpers.cuh,
 // plonk_lookup_columns_host.h): the four helper tables in one pass on their own, the prover (the multiplicities as a one-column commitment,
 // the four helper tables by ONE kernel as a four-column commitment, zkmle_plonk_lookup.hip's sumcheck unchanged on the twenty columns and E,
-// then zk_fri_ml_open_columns_pow of the four commitments at the point the rounds leave, on the same transcript) and its host verifier.
+// then zk_fri_ml_open_columns_pow of the four commitments at the point the rounds leave, on the same transcript) and its host verifier.  The
+// rounds are plonk_lookup_driver.cuh's on zerocheck_driver.cuh's round loop, whose table checks and shells' shared checks it uses too.
 // Extension: the protocol is defined in include/zkmle.h "Plonk with lookups on column commitments".
 #include <string.h>
 
 #include <chrono>
 #include <vector>
 
-#include "eq_table.cuh"
 #include "lookup_driver.cuh"
 #include "plonk_helpers.cuh"
 #include "plonk_lookup_columns_host.h"
 #include "plonk_lookup_driver.cuh"
-#include "wiring_driver.cuh"
 
 using namespace zk;
 using namespace zk::host;
@@ -22,7 +21,6 @@ namespace {
 
 thread_local zk_plonk_lookup_stats g_stats{};
 
-constexpr int kTables = kPlonkLookupTables;                  // the twenty opened and E
 // the places of the helper kernel's eleven inputs (A, B, C, SA, SB, SC, qK, T0, T1, T2) among the fifteen given; M is the sixteenth
 constexpr int kHelpersPlace[kPlonkHelpersIn - 1] = {0, 1, 2, 8, 9, 10, 11, 12, 13, 14};
 
@@ -75,12 +73,11 @@ template <class F> int helpers_once(const zk_table *const *in, const uint64_t *b
 }
 
 // steps 1 to 9 on `tr`: the statement, M and its one-column commitment, the four helper tables and their four-column commitment (hc; h_roots: M's
-// root, then the helpers'), E_0 and the d rounds; z (d elements) = the point the opening is made at.  One host synchronisation per round and
-// one for the miss count.
-template <class F> int prove_rounds(const zk_fri_columns *wit, const zk_fri_columns *cir, const uint64_t *pub, uint32_t npublic, Transcript &tr, HelperColumns &hc,
-                                    uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys, uint64_t *challenges, uint64_t *z, zk_plonk_lookup_stats &st) {
-    constexpr size_t ESZ = sizeof(Fe<F>);
-    constexpr int W = F::N / 2, T = kTables, K = kPlonkLookupOpened, G = kPlonkLookupGiven;
+// root, then the helpers'), then E_0 and zkmle_plonk_lookup.hip's d rounds on the columns' tables by plonk_lookup_driver.cuh; z (d elements) =
+// the point the opening is made at.  One host synchronisation for the miss count beside the rounds'.
+template <class F> int prove_steps(const zk_fri_columns *wit, const zk_fri_columns *cir, const uint64_t *pub, uint32_t npublic, Transcript &tr, HelperColumns &hc,
+                                   uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys, uint64_t *challenges, uint64_t *z, zk_plonk_lookup_stats &st) {
+    constexpr int W = F::N / 2, K = kPlonkLookupOpened, G = kPlonkLookupGiven;
     const unsigned d = wit->d;
     const size_t n = (size_t)1 << d;
     const uint64_t *coset = wit->has_coset ? wit->coset : nullptr;
@@ -92,7 +89,7 @@ template <class F> int prove_rounds(const zk_fri_columns *wit, const zk_fri_colu
     plonk_lookup_columns_statement<F>(tr, wit->root, cir->root, d, pub, npublic);
 
     Events ev;
-    size_t e0, e1, e2, e3, e4, e5, e6;
+    size_t e0, e1, e2, e3, e4;
     ZK_TRY(ev.mark(&e0));
     {
         Owned m;
@@ -131,54 +128,13 @@ template <class F> int prove_rounds(const zk_fri_columns *wit, const zk_fri_colu
         memcpy(chal_out + 4 * W, ch.tau.data(), ch.tau.size() * 8);
     }
 
-    // zkmle_plonk_lookup.hip's rounds on the columns' tables: one block holds E_0 (n elements) and the two ping-pong halves of the folded
-    // twenty-one, n + 21 (n / 2 + n / 4) = 16.75 n elements
-    DevBuf blk;
-    SumsBuf sb;
-    ZK_TRY(blk.alloc((n + T * (n / 2) + T * (n / 4) + 1) * ESZ));
-    ZK_TRY(sb.alloc(ESZ));
-    char *E0 = (char *)blk.p, *half[2] = {E0 + n * ESZ, E0 + (n + T * (n / 2)) * ESZ};
-    const auto tables_at = [&](unsigned l, const void **out) {   // the twenty tables and E at round l: n >> l entries each
-        for (int j = 0; j < T; j++) {
-            const void *own = j < G ? given[j] : j == G ? hc.m->coeffs[0]->dptr : j < K ? hc.h->coeffs[j - G - 1]->dptr : (void *)E0;
-            out[j] = l == 0 ? own : half[(l - 1) & 1] + (size_t)j * (n >> l) * ESZ;
-        }
-    };
-    EqBuilder<F> eqb;
-    ZK_TRY(eqb.build(ch.tau.data(), d, E0));
-    ZK_TRY(ev.mark(&e5));
-    Fe<F> r = fe_one<F>(), id_base = fe_zero<F>();             // c_l = sum_{i < l} 2^i r_i
-    for (unsigned l = 0; l < d; l++) {
-        PlonkLookupTables t{};
-        if (l == 0) {
-            tables_at(0, t.in);
-        } else {
-            tables_at(l - 1, t.in);
-            t.out0 = half[(l - 1) & 1];
-            t.ostride = (n >> l) * ESZ;
-            id_base = fe_add<F>(id_base, fe_mul<F>(fe_from_u64<F>((uint64_t)1 << (l - 1)), r));
-        }
-        ZK_TRY(plonk_lookup_launch_round<F>(l != 0, t, n >> (l + 1), r, ch, id_base, l, d, sb.buf.p, sb.sums));
-        Fe<F> S[kWiringSums], g[kPlonkNodes];
-        ZK_HIP(zk::memcpy_on_stream(S, sb.sums, kWiringSums * ESZ, hipMemcpyDeviceToHost));   // the round's synchronisation
-        if (l == 0) eqb.release();
-        wiring_message<F>(S, ch.mu, g);
-        for (int k = 0; k < kPlonkNodes; k++) {
-            store_host<F>(round_polys + ((size_t)l * kPlonkNodes + k) * W, g[k]);
-            tr.append_be<F>(g[k]);
-        }
-        r = tr.random_challenge_as_field_element<F>();
-        store_host<F>(challenges + (size_t)l * W, r);
-        store_host<F>(z + (size_t)(d - 1 - l) * W, r);
-    }
-    ZK_TRY(ev.mark(&e6));
-    ZK_HIP(hipEventSynchronize(ev.ev[e6]));
+    const void *opened[K];
+    for (int j = 0; j < K; j++) opened[j] = j < G ? given[j] : j == G ? hc.m->coeffs[0]->dptr : hc.h->coeffs[j - G - 1]->dptr;
+    ZK_TRY(plonk_lookup_rounds<F>(opened, d, ch, tr, round_polys, challenges, z, ev, &e4, &st.ms_eq, &st.ms_rounds));
     st.rounds = d;
     st.ms_multiplicities = ev.ms(e0, e1);
     st.ms_fractions = ev.ms(e2, e3);
     st.ms_commit = ev.ms(e1, e2) + ev.ms(e3, e4);
-    st.ms_eq = ev.ms(e4, e5);
-    st.ms_rounds = ev.ms(e5, e6);
     return ZK_OK;
 }
 
@@ -194,16 +150,9 @@ int zk_plonk_lookup_helpers(const zk_table *const tables[11], const uint64_t *be
         const char *a = (const char *)tables, *b = (const char *)H;
         if (a < b + kPlonkHelpersOut * sizeof(zk_table *) && b < a + kPlonkHelpersIn * sizeof(zk_table *)) return ZK_E_ARG;
     }
-    for (int j = 0; j < kPlonkHelpersIn; j++)
-        if (!tables[j]) return ZK_E_ARG;
+    ZK_TRY(check_tables(tables, kPlonkHelpersIn, 2));
     const int field = tables[0]->field;
-    if (field != ZK_FR381 && field != ZK_BN254_FR) return ZK_E_ARG;
-    for (int j = 1; j < kPlonkHelpersIn; j++)
-        if (tables[j]->field != field) return ZK_E_ARG;
-    for (int j = 1; j < kPlonkHelpersIn; j++)
-        if (tables[j]->len != tables[0]->len) return ZK_E_LEN_MISMATCH;
-    if (!is_pow2(tables[0]->len)) return ZK_E_NOT_POW2;
-    if (tables[0]->len < 2 || tables[0]->len > ((size_t)1 << kLookupMaxLog)) return ZK_E_ARG;
+    if (tables[0]->len > ((size_t)1 << kLookupMaxLog)) return ZK_E_ARG;
     if (!all_reduced(field, beta, 1) || !all_reduced(field, gamma, 1)) return ZK_E_ARG;
     ZK_TRY(require_device());
     FRI_DISPATCH(field, return helpers_once<F>(tables, beta, gamma, H));
@@ -241,32 +190,22 @@ int zk_plonk_lookup_prove_columns(const zk_fri_columns *witness, const zk_fri_co
     zk_transcript *tt = t ? t : &own;
     zk_plonk_lookup_stats st{};
     HelperColumns hc;
-    FRI_DISPATCH(witness->field, ZK_TRY((prove_rounds<F>(witness, circuit, public_inputs, npublic, tt->t, hc, h_roots, chal_out, round_polys, challenges, z.data(), st))));
+    FRI_DISPATCH(witness->field, ZK_TRY((prove_steps<F>(witness, circuit, public_inputs, npublic, tt->t, hc, h_roots, chal_out, round_polys, challenges, z.data(), st))));
     const zk_fri_columns *all[kPlonkColumnsCommits] = {witness, circuit, hc.m, hc.h};
-    ZK_TRY(zk_fri_ml_open_columns_pow(all, kPlonkColumnsCommits, z.data(), 1, log_final, nqueries, grinding_bits, tt, ys_out, gamma_out, open_round_polys, roots, final_table,
-                                      open_challenges, query_indices, query_values, query_paths, pow_nonce));
-    zk_fri_ml_stats ml{};
-    (void)zk_fri_ml_last_stats(&ml);
-    st.ms_opening = ml.ms_total;
-    st.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    g_stats = st;
-    return ZK_OK;
+    const int opened = zk_fri_ml_open_columns_pow(all, kPlonkColumnsCommits, z.data(), 1, log_final, nqueries, grinding_bits, tt, ys_out, gamma_out, open_round_polys, roots,
+                                                  final_table, open_challenges, query_indices, query_values, query_paths, pow_nonce);
+    return prove_finish(opened, t0, st, g_stats);
 }
 
 int zk_plonk_lookup_verify_columns(int field, const uint8_t *witness_root, const uint8_t *circuit_root, const uint64_t *public_inputs, uint32_t npublic, uint32_t d,
                                    uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, const uint64_t *coset, zk_transcript *t, const uint8_t *h_roots,
                                    const uint64_t *round_polys, const uint64_t *ys, const uint64_t *open_round_polys, const uint8_t *roots, const uint64_t *final_table,
                                    const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok) {
-    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
-    if (!witness_root || !circuit_root || !h_roots || !round_polys || !ys || !open_round_polys || !roots || !final_table || !query_values || !query_paths || !ok)
-        return ZK_E_ARG;
-    // every status before the transcript is touched: the opening's own on an empty replay; the replay and the opening's verifier run on a copy
-    // that becomes the caller's transcript only with ZK_OK
-    if (field_limbs64(field) < 0) return ZK_E_ARG;
-    if (d > kLookupMaxLog) return ZK_E_ARG;
-    ZK_TRY(zk_fri_ml_sizes_columns(kPlonkColumnsWidths, kPlonkColumnsCommits, d, log_blowup, log_final, nqueries, nullptr, nullptr, nullptr, nullptr, nullptr));
-    if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
-    if ((field != ZK_FR381 && field != ZK_BN254_FR) || d + log_blowup > two_adicity(field)) return ZK_E_RANGE;
+    const bool have_all = witness_root && circuit_root && h_roots && round_polys && ys && open_round_polys && roots && final_table && query_values && query_paths && ok;
+    ZK_TRY(verify_check(field, d, log_blowup, coset, grinding_bits, have_all, [&]() -> int {
+        if (d > kLookupMaxLog) return ZK_E_ARG;
+        return zk_fri_ml_sizes_columns(kPlonkColumnsWidths, kPlonkColumnsCommits, d, log_blowup, log_final, nqueries, nullptr, nullptr, nullptr, nullptr, nullptr);
+    }));
     if (!plonk_public_shape_ok(public_inputs, npublic, d)) return ZK_E_ARG;
     uint8_t all[32 * kPlonkColumnsCommits];
     memcpy(all, witness_root, 32);

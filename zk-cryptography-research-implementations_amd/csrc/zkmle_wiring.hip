@@ -1,14 +1,13 @@
 // zkmle_wiring.hip -- C ABI of the permutation check over FRI commitments (wiring.cuh, wiring_host.h): the helper tables of one wire and one
 // round pass on their own, the prover (the three helper tables and their commitments, the sumcheck of the logarithmic-derivative relation on
 // the nine coefficient tables and E, then zk_fri_ml_open_batch_pow of the nine commitments at the point the rounds leave, on the same
-// transcript) and its host verifier.  Extension: the protocol is defined in include/zkmle.h "Wiring: a permutation check over committed tables".
+// transcript) and its host verifier.  The round loop, the hook's pass and the shells' shared checks are zerocheck_driver.cuh's, by
+// wiring_driver.cuh.  Extension: the protocol is defined in include/zkmle.h "Wiring: a permutation check over committed tables".
 #include <string.h>
 
 #include <chrono>
 #include <vector>
 
-#include "eq_table.cuh"
-#include "fri_host.h"
 #include "wiring_driver.cuh"
 
 using namespace zk;
@@ -20,9 +19,13 @@ thread_local zk_wiring_stats g_wiring_stats{};
 
 constexpr int kTables = kWiringOpened + 1;                   // A, B, C, SA, SB, SC, H0, H1, H2, E
 
-// sums (device, 7 elements) of a pass over q pairs whose id tables are c_l + 2^l x + j 2^d.  Launches only.
-template <class F> int launch_round(bool fold, const WiringTables &t, size_t q, const Fe<F> &r, const WiringChallenges<F> &ch, const Fe<F> &id_base, unsigned log_step, unsigned d,
-                                    void *partials, void *sums) {
+// sums (device, 7 elements) of a pass over q pairs whose id tables are c_l + 2^l x + j 2^d; the ten folded to out0 + j ostride.  Launches only.
+template <class F> int launch_round(bool fold, const void *const *in, void *out0, size_t ostride, size_t q, const Fe<F> &r, const WiringChallenges<F> &ch, const Fe<F> &id_base,
+                                    unsigned log_step, unsigned d, void *partials, void *sums) {
+    WiringTables t{};
+    for (int j = 0; j < kTables; j++) t.in[j] = in[j];
+    t.out0 = out0;
+    t.ostride = ostride;
     const int grid = reduce_grid_for(q);
     WiringConsts<F> c;
     c.beta = ch.beta;
@@ -50,47 +53,20 @@ template <class F> int fractions_once(const zk_table *W, const zk_table *S, uint
     return ZK_OK;
 }
 
-template <class F> int round_once(const zk_table *const *in, const WiringChallenges<F> &ch, const uint64_t *id_base, unsigned log_step, const uint64_t *r, zk_table **outs,
+template <class F> int hook_round(const zk_table *const *in, const WiringChallenges<F> &ch, const uint64_t *id_base, unsigned log_step, const uint64_t *r, zk_table **outs,
                                   uint64_t *gout) {
-    constexpr size_t ESZ = sizeof(Fe<F>);
-    constexpr int W = F::N / 2;
-    const bool fold = r != nullptr;
-    const size_t len = in[0]->len, q = fold ? len / 4 : len / 2;
-    SumsBuf sb;
-    ZK_TRY(sb.alloc(ESZ));
-    zk_table *o[kTables] = {};
-    const auto drop = [&] { for (zk_table *t : o) zk_table_free(t); };
-    // the pass writes the folded ten into one block; the caller's new tables are copies of its tenths
-    DevBuf folded;
-    WiringTables t{};
-    for (int j = 0; j < kTables; j++) t.in[j] = in[j]->dptr;
-    if (fold) {
-        ZK_TRY(folded.alloc(kTables * (len / 2) * ESZ));
-        t.out0 = folded.p;
-        t.ostride = (len / 2) * ESZ;
-        for (int j = 0; j < kTables; j++) {
-            const int rc = zk_table_alloc(in[0]->field, len / 2, &o[j]);
-            if (rc != ZK_OK) { drop(); return rc; }
-        }
-    }
-    Fe<F> S[kWiringSums], g[kWiringNodes];
-    int rc = launch_round<F>(fold, t, q, fold ? load_host<F>(r) : fe_one<F>(), ch, load_host<F>(id_base), log_step, ilog2(2 * q) + log_step, sb.buf.p, sb.sums);
-    for (int j = 0; fold && rc == ZK_OK && j < kTables; j++)
-        if (hipMemcpyAsync(o[j]->dptr, (char *)folded.p + (size_t)j * t.ostride, t.ostride, hipMemcpyDeviceToDevice, cur_stream()) != hipSuccess) rc = ZK_E_HIP;
-    if (rc == ZK_OK && zk::memcpy_on_stream(S, sb.sums, kWiringSums * ESZ, hipMemcpyDeviceToHost) != hipSuccess) rc = ZK_E_HIP;
-    if (rc != ZK_OK) { drop(); return rc; }
-    wiring_message<F>(S, ch.mu, g);
-    for (int k = 0; k < kWiringNodes; k++) store_host<F>(gout + (size_t)k * W, g[k]);
-    for (int j = 0; fold && j < kTables; j++) outs[j] = o[j];
-    return ZK_OK;
+    const Fe<F> id0 = load_host<F>(id_base);
+    const auto launch = [&](bool fold, const void *const *ip, void *out0, size_t ostride, size_t q, const Fe<F> &rr, unsigned, void *partials, void *sums) {
+        return launch_round<F>(fold, ip, out0, ostride, q, rr, ch, id0, log_step, ilog2(2 * q) + log_step, partials, sums);
+    };
+    return round_once<F, kTables, kWiringSums, kWiringNodes>(in, r, outs, gout, launch, [&](const Fe<F> *S, Fe<F> *g) { wiring_message<F>(S, ch.mu, g); });
 }
 
-// steps 1 to 6 on `tr`: the statement, the helper tables and their commitments (hc, h_roots), E_0 and the d rounds; z (d elements) = the point
-// the opening is made at.  One host synchronisation per round.
-template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcript &tr, CommitHolder &hc, uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys,
-                                    uint64_t *challenges, uint64_t *z, zk_wiring_stats &st) {
-    constexpr size_t ESZ = sizeof(Fe<F>);
-    constexpr int W = F::N / 2, T = kTables, K = kWiringOpened;
+// steps 1 to 6 on `tr`: the statement, the helper tables and their commitments (hc, h_roots), then E_0 and the d rounds by zerocheck_driver.cuh;
+// z (d elements) = the point the opening is made at.
+template <class F> int prove_steps(const zk_fri_commitment *const *cms, Transcript &tr, CommitHolder &hc, uint8_t *h_roots, uint64_t *chal_out, uint64_t *round_polys,
+                                   uint64_t *challenges, uint64_t *z, zk_wiring_stats &st) {
+    constexpr int W = F::N / 2, K = kWiringOpened;
     const zk_fri_commitment *c0 = cms[0];
     const unsigned d = c0->d;
     const size_t n = (size_t)1 << d;
@@ -100,7 +76,7 @@ template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcr
     wiring_statement<F>(tr, roots, d, ch);
 
     Events ev;
-    size_t e0, e1, e2, e3, e4;
+    size_t e0, e1, e2;
     ZK_TRY(ev.mark(&e0));
     {
         TableHolder th;
@@ -126,53 +102,17 @@ template <class F> int prove_rounds(const zk_fri_commitment *const *cms, Transcr
         memcpy(chal_out + 4 * W, ch.tau.data(), ch.tau.size() * 8);
     }
 
-    // one block: E_0 (n elements), then the two ping-pong halves: the ten tables of an odd round (n / 2 entries each at round 1) and of an
-    // even one (n / 4 each at round 2); a round's tables never outgrow the half they first had
-    DevBuf blk;
-    SumsBuf sb;
-    ZK_TRY(blk.alloc((n + T * (n / 2) + T * (n / 4) + 1) * ESZ));
-    ZK_TRY(sb.alloc(ESZ));
-    char *E0 = (char *)blk.p, *half[2] = {E0 + n * ESZ, E0 + (n + T * (n / 2)) * ESZ};
-    const auto tables_at = [&](unsigned l, const void **out) {   // the nine tables and E at round l: n >> l entries each
-        for (int j = 0; j < T; j++) {
-            const void *own = j < kWiringGiven ? cms[j]->coeffs->dptr : j < K ? hc.cm[j - kWiringGiven]->coeffs->dptr : (void *)E0;
-            out[j] = l == 0 ? own : half[(l - 1) & 1] + (size_t)j * (n >> l) * ESZ;
-        }
+    const void *opened[K];
+    for (int j = 0; j < K; j++) opened[j] = (j < kWiringGiven ? cms[j] : hc.cm[j - kWiringGiven])->coeffs->dptr;
+    IdBase<F> idb;
+    const auto launch = [&](bool fold, const void *const *in, void *out0, size_t ostride, size_t q, const Fe<F> &r, unsigned l, void *partials, void *sums) {
+        return launch_round<F>(fold, in, out0, ostride, q, r, ch, idb.at(l, r), l, d, partials, sums);
     };
-    EqBuilder<F> eqb;
-    ZK_TRY(eqb.build(ch.tau.data(), d, E0));
-    ZK_TRY(ev.mark(&e3));
-    Fe<F> r = fe_one<F>(), id_base = fe_zero<F>();             // c_l = sum_{i < l} 2^i r_i
-    for (unsigned l = 0; l < d; l++) {
-        WiringTables t{};
-        if (l == 0) {
-            tables_at(0, t.in);
-        } else {
-            tables_at(l - 1, t.in);
-            t.out0 = half[(l - 1) & 1];
-            t.ostride = (n >> l) * ESZ;
-            id_base = fe_add<F>(id_base, fe_mul<F>(fe_from_u64<F>((uint64_t)1 << (l - 1)), r));
-        }
-        ZK_TRY(launch_round<F>(l != 0, t, n >> (l + 1), r, ch, id_base, l, d, sb.buf.p, sb.sums));
-        Fe<F> S[kWiringSums], g[kWiringNodes];
-        ZK_HIP(zk::memcpy_on_stream(S, sb.sums, kWiringSums * ESZ, hipMemcpyDeviceToHost));   // the round's synchronisation
-        if (l == 0) eqb.release();
-        wiring_message<F>(S, ch.mu, g);
-        for (int k = 0; k < kWiringNodes; k++) {
-            store_host<F>(round_polys + ((size_t)l * kWiringNodes + k) * W, g[k]);
-            tr.append_be<F>(g[k]);
-        }
-        r = tr.random_challenge_as_field_element<F>();
-        store_host<F>(challenges + (size_t)l * W, r);
-        store_host<F>(z + (size_t)(d - 1 - l) * W, r);
-    }
-    ZK_TRY(ev.mark(&e4));
-    ZK_HIP(hipEventSynchronize(ev.ev[e4]));
+    ZK_TRY((prove_rounds<F, kTables, kWiringSums, kWiringNodes>(opened, d, ch.tau.data(), tr, launch, [&](const Fe<F> *S, Fe<F> *g) { wiring_message<F>(S, ch.mu, g); },
+                                                                round_polys, challenges, z, ev, &e2, &st.ms_eq, &st.ms_rounds)));
     st.rounds = d;
     st.ms_fractions = ev.ms(e0, e1);
     st.ms_commit = ev.ms(e1, e2);
-    st.ms_eq = ev.ms(e2, e3);
-    st.ms_rounds = ev.ms(e3, e4);
     return ZK_OK;
 }
 
@@ -192,30 +132,8 @@ int zk_wiring_fractions(const zk_table *W, const zk_table *S, uint64_t first, co
 
 int zk_wiring_round(const zk_table *const tables[10], const uint64_t *beta, const uint64_t *gamma, const uint64_t *alpha, const uint64_t *mu, const uint64_t *id_base,
                     uint32_t log_step, const uint64_t *r, zk_table **outs, uint64_t *g5) {
-    if (!tables) return ZK_E_ARG;
-    for (int j = 0; j < kTables; j++)
-        if (!tables[j]) return ZK_E_ARG;
-    const int field = tables[0]->field;
-    if (!beta || !gamma || !alpha || !mu || !id_base || !g5 || (r && !outs) || (field != ZK_FR381 && field != ZK_BN254_FR)) return ZK_E_ARG;
-    for (int j = 1; j < kTables; j++)
-        if (tables[j]->field != field) return ZK_E_ARG;
-    const size_t len = tables[0]->len;
-    for (int j = 1; j < kTables; j++)
-        if (tables[j]->len != len) return ZK_E_LEN_MISMATCH;
-    if (!is_pow2(len)) return ZK_E_NOT_POW2;
-    if (len < (r ? 4u : 2u) || (r && !all_reduced(field, r, 1))) return ZK_E_ARG;
-    for (const uint64_t *e : {beta, gamma, alpha, mu, id_base})
-        if (!all_reduced(field, e, 1)) return ZK_E_ARG;
-    if (log_step > 32 || ilog2(r ? len / 2 : len) + log_step > 32) return ZK_E_ARG;
-    ZK_TRY(require_device());
-    FRI_DISPATCH(field, {
-        WiringChallenges<F> ch;
-        ch.beta = load_host<F>(beta);
-        ch.gamma = load_host<F>(gamma);
-        ch.alpha = load_host<F>(alpha);
-        ch.mu = load_host<F>(mu);
-        return round_once<F>(tables, ch, id_base, log_step, r, outs, g5);
-    });
+    ZK_TRY(wiring_round_check(tables, kTables, beta, gamma, alpha, mu, id_base, log_step, r, outs, g5));
+    FRI_DISPATCH(tables[0]->field, return hook_round<F>(tables, wiring_challenges<F>(beta, gamma, alpha, mu), id_base, log_step, r, outs, g5));
     return ZK_OK;
 }
 
@@ -246,31 +164,22 @@ int zk_wiring_prove(const zk_fri_commitment *const cms[6], uint32_t log_final, u
     zk_transcript *tt = t ? t : &own;
     zk_wiring_stats st{};
     CommitHolder hc;
-    FRI_DISPATCH(cms[0]->field, ZK_TRY((prove_rounds<F>(cms, tt->t, hc, h_roots, chal_out, round_polys, challenges, z.data(), st))));
+    FRI_DISPATCH(cms[0]->field, ZK_TRY((prove_steps<F>(cms, tt->t, hc, h_roots, chal_out, round_polys, challenges, z.data(), st))));
     const zk_fri_commitment *all[kWiringOpened];
     for (int j = 0; j < kWiringOpened; j++) all[j] = j < kWiringGiven ? cms[j] : hc.cm[j - kWiringGiven];
-    ZK_TRY(zk_fri_ml_open_batch_pow(all, kWiringOpened, z.data(), 1, log_final, nqueries, log_arity, tt, ys_out, gamma_out, open_round_polys, roots, final_table,
-                                    open_challenges, query_indices, query_values, query_paths, grinding_bits, pow_nonce));
-    zk_fri_ml_stats ml{};
-    (void)zk_fri_ml_last_stats(&ml);
-    st.ms_opening = ml.ms_total;
-    st.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    g_wiring_stats = st;
-    return ZK_OK;
+    const int opened = zk_fri_ml_open_batch_pow(all, kWiringOpened, z.data(), 1, log_final, nqueries, log_arity, tt, ys_out, gamma_out, open_round_polys, roots, final_table,
+                                                open_challenges, query_indices, query_values, query_paths, grinding_bits, pow_nonce);
+    return prove_finish(opened, t0, st, g_wiring_stats);
 }
 
 int zk_wiring_verify(int field, const uint8_t *roots_of_six, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
                      const uint64_t *coset, zk_transcript *t, const uint8_t *h_roots, const uint64_t *round_polys, const uint64_t *ys, const uint64_t *open_round_polys,
                      const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce,
                      int *ok) {
-    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
-    if (!roots_of_six || !h_roots || !round_polys || !ys || !open_round_polys || !roots || !final_table || !query_values || !query_paths || !ok) return ZK_E_ARG;
-    // every status before the transcript is touched: the opening's own on an empty replay; the replay and the opening's verifier run on a copy
-    // that becomes the caller's transcript only with ZK_OK
-    if (field_limbs64(field) < 0) return ZK_E_ARG;
-    ZK_TRY(zk_fri_ml_sizes_batch(kWiringOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, nullptr, nullptr, nullptr, nullptr, nullptr));
-    if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
-    if ((field != ZK_FR381 && field != ZK_BN254_FR) || d + log_blowup > two_adicity(field)) return ZK_E_RANGE;
+    const bool have_all = roots_of_six && h_roots && round_polys && ys && open_round_polys && roots && final_table && query_values && query_paths && ok;
+    ZK_TRY(verify_check(field, d, log_blowup, coset, grinding_bits, have_all, [&] {
+        return zk_fri_ml_sizes_batch(kWiringOpened, d, log_blowup, log_final, nqueries, log_arity, log_group, nullptr, nullptr, nullptr, nullptr, nullptr);
+    }));
     uint8_t nine[32 * kWiringOpened];
     memcpy(nine, roots_of_six, 32 * kWiringGiven);
     memcpy(nine + 32 * kWiringGiven, h_roots, 32 * kWiringWires);

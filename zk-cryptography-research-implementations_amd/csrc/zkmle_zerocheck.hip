@@ -1,18 +1,16 @@
 // zkmle_zerocheck.hip -- C ABI of the zerochecks over FRI commitments (zerocheck.cuh, zerocheck_host.h): the product A o B = C over three
 // commitments and the Plonk gate qM A B + qL A + qR B + qO C + qC = 0 over eight.  For each: one round pass on its own, the prover (the
 // sumcheck of sum_x eq(x, tau) relation(x) = 0 on the commitments' coefficient tables, then zk_fri_ml_open_batch_pow of the K commitments at
-// the point the rounds leave, on the same transcript) and its host verifier.  One round driver, one prover and one verifier serve both,
-// parametrised by zerocheck_host.h's statement.  Extension: the protocols are defined in include/zkmle.h "Zerocheck of a product of
+// the point the rounds leave, on the same transcript) and its host verifier.  One launch, one prover and one verifier serve both, parametrised
+// by zerocheck_host.h's statement; the round loop, the hook's pass and the shells' shared checks are zerocheck_driver.cuh's.  Extension: the protocols are defined in include/zkmle.h "Zerocheck of a product of
 // committed tables" and "Zerocheck of a Plonk gate over committed tables".
 #include <string.h>
 
 #include <chrono>
 #include <vector>
 
-#include "eq_table.cuh"
-#include "fri_host.h"
 #include "zerocheck.cuh"
-#include "zerocheck_host.h"
+#include "zerocheck_driver.cuh"
 
 using namespace zk;
 using namespace zk::host;
@@ -36,8 +34,15 @@ template <> struct Pass<ZerocheckGate> {
     }
 };
 
-// sums (device, NODES elements) = the pass's sums at the nodes 0 .. NODES - 2 and infinity.  Launches only.
-template <class F, class St> int launch_round(bool fold, const typename Pass<St>::Tables &t, size_t q, const Fe<F> &r, void *partials, void *sums) {
+// zerocheck_driver.cuh's launch for the statement: sums (device, NODES elements) = the pass's sums at the nodes 0 .. NODES - 2 and infinity.
+// The kernels take one output per table: out0 + j ostride, as the driver lays them out.  Launches only.
+template <class F, class St>
+int launch_round(bool fold, const void *const *in, void *out0, size_t ostride, size_t q, const Fe<F> &r, unsigned, void *partials, void *sums) {
+    typename Pass<St>::Tables t{};
+    for (int j = 0; j < St::K + 1; j++) {
+        t.in[j] = in[j];
+        if (fold) t.out[j] = (char *)out0 + (size_t)j * ostride;
+    }
     const int grid = reduce_grid_for(q);
     if (fold) Pass<St>::template launch<F, true>(grid, t, q, r, partials);
     else Pass<St>::template launch<F, false>(grid, t, q, r, partials);
@@ -47,119 +52,36 @@ template <class F, class St> int launch_round(bool fold, const typename Pass<St>
     return ZK_OK;
 }
 
-// room for the workgroups' partial sums and the `nsums` sums behind them
-struct SumsBuf {
-    DevBuf buf;
-    void *sums = nullptr;
-    int alloc(size_t esz, size_t nsums) {
-        const size_t cap = (size_t)reduce_block_cap();
-        ZK_TRY(buf.alloc((nsums * cap + nsums) * esz));
-        sums = (char *)buf.p + nsums * cap * esz;
-        return ZK_OK;
-    }
-};
-
 // the checks of a round hook on its T = K + 1 tables, in the order of zk_zerocheck_mul_round's statuses
 inline int round_check(const zk_table *const *in, int T, const uint64_t *r, zk_table **outs, const uint64_t *g) {
-    for (int j = 0; j < T; j++)
-        if (!in[j]) return ZK_E_ARG;
-    if (!g || (r && !outs) || (in[0]->field != ZK_FR381 && in[0]->field != ZK_BN254_FR)) return ZK_E_ARG;
-    for (int j = 1; j < T; j++)
-        if (in[j]->field != in[0]->field) return ZK_E_ARG;
-    for (int j = 1; j < T; j++)
-        if (in[j]->len != in[0]->len) return ZK_E_LEN_MISMATCH;
-    if (!is_pow2(in[0]->len)) return ZK_E_NOT_POW2;
-    if (in[0]->len < (r ? 4u : 2u) || (r && !all_reduced(in[0]->field, r, 1))) return ZK_E_ARG;
+    if (!g || (r && !outs)) return ZK_E_ARG;
+    ZK_TRY(check_tables(in, T, r ? 4 : 2));
+    if (r && !all_reduced(in[0]->field, r, 1)) return ZK_E_ARG;
     return require_device();
 }
 
-template <class F, class St> int round_once(const zk_table *const *in, const uint64_t *r, zk_table **outs, uint64_t *gout) {
-    constexpr size_t ESZ = sizeof(Fe<F>);
-    constexpr int W = F::N / 2, T = St::K + 1, NS = St::NODES;
-    const bool fold = r != nullptr;
-    const size_t len = in[0]->len, q = fold ? len / 4 : len / 2;
-    SumsBuf sb;
-    ZK_TRY(sb.alloc(ESZ, NS));
-    zk_table *o[T] = {};
-    const auto drop = [&] { for (zk_table *t : o) zk_table_free(t); };
-    typename Pass<St>::Tables t{};
-    for (int j = 0; j < T; j++) {
-        t.in[j] = in[j]->dptr;
-        if (!fold) continue;
-        const int rc = zk_table_alloc(in[0]->field, len / 2, &o[j]);
-        if (rc != ZK_OK) { drop(); return rc; }
-        t.out[j] = o[j]->dptr;
-    }
-    Fe<F> S[NS], g[NS];
-    int rc = launch_round<F, St>(fold, t, q, fold ? load_host<F>(r) : fe_one<F>(), sb.buf.p, sb.sums);
-    if (rc == ZK_OK && zk::memcpy_on_stream(S, sb.sums, NS * ESZ, hipMemcpyDeviceToHost) != hipSuccess) rc = ZK_E_HIP;
-    if (rc != ZK_OK) { drop(); return rc; }
-    St::template message<F>(S, g);
-    for (int k = 0; k < NS; k++) store_host<F>(gout + (size_t)k * W, g[k]);
-    for (int j = 0; fold && j < T; j++) outs[j] = o[j];
-    return ZK_OK;
+template <class F, class St> int hook_round(const zk_table *const *in, const uint64_t *r, zk_table **outs, uint64_t *gout) {
+    return round_once<F, St::K + 1, St::NODES, St::NODES>(in, r, outs, gout, launch_round<F, St>, St::template message<F>);
 }
 
-// the statement, E_0 and the d rounds on `tr`; z (d elements) = the point the opening is made at.  One host synchronisation per round: the
-// sums down, the transcript's step on the host, r_l up as the next pass's argument.
-template <class F, class St> int prove_rounds(const zk_fri_commitment *const *cms, Transcript &tr, uint64_t *tau_out, uint64_t *round_polys, uint64_t *challenges,
-                                              uint64_t *z, zk_zerocheck_stats &st) {
-    constexpr size_t ESZ = sizeof(Fe<F>);
-    constexpr int W = F::N / 2, K = St::K, T = St::K + 1, NS = St::NODES;
+// the statement and, by zerocheck_driver.cuh, E_0 and the d rounds on `tr`; z (d elements) = the point the opening is made at
+template <class F, class St> int prove_steps(const zk_fri_commitment *const *cms, Transcript &tr, uint64_t *tau_out, uint64_t *round_polys, uint64_t *challenges,
+                                             uint64_t *z, zk_zerocheck_stats &st) {
+    constexpr int K = St::K;
     const unsigned d = cms[0]->d;
-    const size_t n = (size_t)1 << d;
     uint8_t roots[32 * K];
-    for (int j = 0; j < K; j++) memcpy(roots + 32 * j, cms[j]->root, 32);
-    std::vector<uint64_t> tau((size_t)d * W);
+    const void *opened[K];
+    for (int j = 0; j < K; j++) {
+        memcpy(roots + 32 * j, cms[j]->root, 32);
+        opened[j] = cms[j]->coeffs->dptr;
+    }
+    std::vector<uint64_t> tau((size_t)d * (F::N / 2));
     zerocheck_statement<F, St>(tr, roots, d, tau.data());
     if (tau_out) memcpy(tau_out, tau.data(), tau.size() * 8);
-
-    // one block: E_0 (n elements), then the two ping-pong halves: the T tables of an odd round (n / 2 entries each at round 1) and of an
-    // even one (n / 4 each at round 2); a round's tables never outgrow the half they first had
-    DevBuf blk;
-    SumsBuf sb;
-    ZK_TRY(blk.alloc((n + T * (n / 2) + T * (n / 4) + 1) * ESZ));
-    ZK_TRY(sb.alloc(ESZ, NS));
-    char *E0 = (char *)blk.p, *half[2] = {E0 + n * ESZ, E0 + (n + T * (n / 2)) * ESZ};
-    const auto tables_at = [&](unsigned l, const void **out) {   // the K tables and E at round l: n >> l entries each
-        for (int j = 0; j < T; j++) out[j] = l == 0 ? (j < K ? cms[j]->coeffs->dptr : (void *)E0) : half[(l - 1) & 1] + (size_t)j * (n >> l) * ESZ;
-    };
     Events ev;
-    size_t e0, e1, e2;
-    ZK_TRY(ev.mark(&e0));
-    EqBuilder<F> eqb;
-    ZK_TRY(eqb.build(tau.data(), d, E0));
-    ZK_TRY(ev.mark(&e1));
-    Fe<F> r = fe_one<F>();
-    for (unsigned l = 0; l < d; l++) {
-        typename Pass<St>::Tables t{};
-        if (l == 0) {
-            tables_at(0, t.in);
-        } else {
-            const void *to[T];
-            tables_at(l - 1, t.in);
-            tables_at(l, to);
-            for (int j = 0; j < T; j++) t.out[j] = const_cast<void *>(to[j]);
-        }
-        ZK_TRY((launch_round<F, St>(l != 0, t, n >> (l + 1), r, sb.buf.p, sb.sums)));
-        Fe<F> S[NS], g[NS];
-        ZK_HIP(zk::memcpy_on_stream(S, sb.sums, NS * ESZ, hipMemcpyDeviceToHost));   // the round's synchronisation
-        if (l == 0) eqb.release();
-        St::template message<F>(S, g);
-        for (int k = 0; k < NS; k++) {
-            store_host<F>(round_polys + ((size_t)l * NS + k) * W, g[k]);
-            tr.append_be<F>(g[k]);
-        }
-        r = tr.random_challenge_as_field_element<F>();
-        store_host<F>(challenges + (size_t)l * W, r);
-        store_host<F>(z + (size_t)(d - 1 - l) * W, r);
-    }
-    ZK_TRY(ev.mark(&e2));
-    ZK_HIP(hipEventSynchronize(ev.ev[e2]));
     st.rounds = d;
-    st.ms_eq = ev.ms(e0, e1);
-    st.ms_rounds = ev.ms(e1, e2);
-    return ZK_OK;
+    return prove_rounds<F, K + 1, St::NODES, St::NODES>(opened, d, tau.data(), tr, launch_round<F, St>, St::template message<F>, round_polys, challenges, z, ev, nullptr,
+                                                        &st.ms_eq, &st.ms_rounds);
 }
 
 // zk_zerocheck_mul_prove / zk_zerocheck_gate_prove on the statement's K commitments
@@ -179,15 +101,10 @@ template <class St> int prove(const zk_fri_commitment *const *cms, uint32_t log_
     zk_transcript own;
     zk_transcript *tt = t ? t : &own;
     zk_zerocheck_stats st{};
-    FRI_DISPATCH(cms[0]->field, ZK_TRY((prove_rounds<F, St>(cms, tt->t, tau_out, round_polys, challenges, z.data(), st))));
-    ZK_TRY(zk_fri_ml_open_batch_pow(cms, St::K, z.data(), 1, log_final, nqueries, log_arity, tt, ys_out, gamma_out, open_round_polys, roots, final_table, open_challenges,
-                                    query_indices, query_values, query_paths, grinding_bits, pow_nonce));
-    zk_fri_ml_stats ml{};
-    (void)zk_fri_ml_last_stats(&ml);
-    st.ms_opening = ml.ms_total;
-    st.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    g_zc_stats = st;
-    return ZK_OK;
+    FRI_DISPATCH(cms[0]->field, ZK_TRY((prove_steps<F, St>(cms, tt->t, tau_out, round_polys, challenges, z.data(), st))));
+    const int opened = zk_fri_ml_open_batch_pow(cms, St::K, z.data(), 1, log_final, nqueries, log_arity, tt, ys_out, gamma_out, open_round_polys, roots, final_table,
+                                                open_challenges, query_indices, query_values, query_paths, grinding_bits, pow_nonce);
+    return prove_finish(opened, t0, st, g_zc_stats);
 }
 
 // zk_zerocheck_mul_verify / zk_zerocheck_gate_verify; own_roots: the statement's K roots as the verifier holds them
@@ -195,14 +112,10 @@ template <class St> int verify(int field, const uint8_t *own_roots, uint32_t d, 
                                uint32_t log_group, const uint64_t *coset, zk_transcript *t, const uint64_t *round_polys, const uint64_t *ys,
                                const uint64_t *open_round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
                                const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok) {
-    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
-    if (!own_roots || !round_polys || !ys || !open_round_polys || !roots || !final_table || !query_values || !query_paths || !ok) return ZK_E_ARG;
-    // every status before the transcript is touched: the opening's own on an empty replay, as zk_sumcheck_basic_verify_succinct; and the replay
-    // and the opening's verifier run on a copy that becomes the caller's transcript only with ZK_OK
-    if (field_limbs64(field) < 0) return ZK_E_ARG;
-    ZK_TRY(zk_fri_ml_sizes_batch(St::K, d, log_blowup, log_final, nqueries, log_arity, log_group, nullptr, nullptr, nullptr, nullptr, nullptr));
-    if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
-    if ((field != ZK_FR381 && field != ZK_BN254_FR) || d + log_blowup > two_adicity(field)) return ZK_E_RANGE;
+    const bool have_all = own_roots && round_polys && ys && open_round_polys && roots && final_table && query_values && query_paths && ok;
+    ZK_TRY(verify_check(field, d, log_blowup, coset, grinding_bits, have_all, [&] {
+        return zk_fri_ml_sizes_batch(St::K, d, log_blowup, log_final, nqueries, log_arity, log_group, nullptr, nullptr, nullptr, nullptr, nullptr);
+    }));
     zk_transcript work;
     if (t) work.t = t->t;
     std::vector<uint64_t> z((size_t)d * 4);
@@ -223,14 +136,13 @@ extern "C" {
 int zk_zerocheck_mul_round(const zk_table *A, const zk_table *B, const zk_table *C, const zk_table *E, const uint64_t *r, zk_table **outs, uint64_t *g4) {
     const zk_table *in[4] = {A, B, C, E};
     ZK_TRY(round_check(in, 4, r, outs, g4));
-    FRI_DISPATCH(A->field, return (round_once<F, ZerocheckMul>(in, r, outs, g4)));
+    FRI_DISPATCH(A->field, return (hook_round<F, ZerocheckMul>(in, r, outs, g4)));
     return ZK_OK;
 }
 
 int zk_zerocheck_gate_round(const zk_table *const tables[9], const uint64_t *r, zk_table **outs, uint64_t *g5) {
-    if (!tables) return ZK_E_ARG;
     ZK_TRY(round_check(tables, 9, r, outs, g5));
-    FRI_DISPATCH(tables[0]->field, return (round_once<F, ZerocheckGate>(tables, r, outs, g5)));
+    FRI_DISPATCH(tables[0]->field, return (hook_round<F, ZerocheckGate>(tables, r, outs, g5)));
     return ZK_OK;
 }
 
