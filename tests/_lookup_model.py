@@ -21,19 +21,15 @@ of the sum is then 0 and the sum of H is not) and hides that from the first chec
 first check passes, a later one fails, and the opening alone verifies.
 `instance(field, d, seed, rows, looked)` builds a satisfied instance from a list of table rows and a choice of looked-up rows.
 Everything is Python integers; nothing here knows how the library works."""
+import functools
 import random
 
-import numpy as np
-
 import _fri_ml_batch_model as BM
-import _fri_ml_model as ML
-import _grind_model as GR
 import _ntt_model as NM
-import _wiring_model as WM
+import _zerocheck_family_model as F
 from oracle import pymodel as M
 
-be32 = ML.be32
-inv0, interpolate5, eq_at, commit_like = WM.inv0, WM.interpolate5, WM.eq_at, WM.commit_like
+be32, inv0, eq_at, commit_like, interpolate5 = F.be32, F.inv0, F.eq_at, F.commit_like, F.interpolate
 GIVEN, HELPERS, K, NODES = 7, 2, 9, 5
 
 
@@ -125,121 +121,34 @@ def round_g5(tabs, ch, p):
     return [v % p for v in g]
 
 
-def pow_transcript(d, f, bits, nonce=None, prefix=b""):
-    """the transcript of a proof with the proof-of-work step: it stands in front of the first index, sample number 2 (beta, gamma) + 1 (mu) + d
-    (tau) + d (the rounds) + 1 (the opening's gamma) + R (its rounds)"""
-    tr = GR.PowTranscript(bits, 3 + 2 * d + 1 + (d - f), nonce)
-    tr.append(prefix)
-    return tr
+def helper_phase(i, tabs, ch, p, cheat):
+    """the family's helper phases: M from the seven (a cheating prover credits every miss to row 0), then H from the eight and beta, gamma"""
+    if i == 1:
+        return [fractions(tabs, ch[0], ch[1], p)], {}
+    m, misses = multiplicities(tabs, p)
+    if cheat:
+        m[0] = (m[0] + misses) % p
+    return [m], {"misses": misses, "M": m}
+
+
+PROTO = F.Proto(tag, GIVEN, NODES, 0, ((1, 2), (1, 1)), helper_phase, lambda v, ids, ch: summand(v[:K], v[K], ch),
+                lambda tabs, extra, ch, p: (round_g5(tabs, ch, p), None), opening=BM)
+pow_transcript, sizes, flat = (functools.partial(fn, PROTO) for fn in (F.pow_transcript, F.sizes, F.flat))
+_helpers = functools.partial(F.helpers, PROTO)               # -> [beta, gamma, mu, tau]
 
 
 def _statement(tr, roots, d):
-    tr.append(tag(d))
-    for r in roots:
-        tr.append(r)
-
-
-def _helpers(tr, h_roots, d, p):
-    tr.append(h_roots[0])
-    beta, gamma = tr.challenge(p), tr.challenge(p)
-    tr.append(h_roots[1])
-    mu = tr.challenge(p)
-    return beta, gamma, mu, [tr.challenge(p) for _ in range(d)]
+    F.statement(PROTO, tr, roots, d, None)
 
 
 def prove(cms, f, Q, a=1, tr=None, hasher=M.keccak256, cheat=False, commit=None):
     """-> the proof as a dict; `cms`: the model commitments of the seven (tests/_fri_pcs_model.py, or _fri_ml_grouped_model.py's, all alike);
     `commit(table)`: the model commitment of a helper table with their shape (commit_like on the first by default); `tr` is advanced.  The
     statement is not checked."""
-    field, d = cms[0]["field"], cms[0]["d"]
-    assert len(cms) == GIVEN
-    p = NM.MODULUS[field]
-    tr = M.Transcript() if tr is None else tr
-    roots = [c["root"] for c in cms]
-    commit = (lambda t: commit_like(cms[0], t, hasher)) if commit is None else commit
-    _statement(tr, roots, d)
-    given = [list(c["coeffs"]) for c in cms]
-    m, misses = multiplicities(given, p)
-    if cheat:
-        m[0] = (m[0] + misses) % p
-    mcm = commit(m)
-    tr.append(mcm["root"])
-    beta, gamma = tr.challenge(p), tr.challenge(p)
-    h = fractions(given + [m], beta, gamma, p)
-    hcm = commit(h)
-    tr.append(hcm["root"])
-    mu = tr.challenge(p)
-    tau = [tr.challenge(p) for _ in range(d)]
-    ch = (beta, gamma, mu)
-    tabs = given + [m, h, ML.eq_table(tau, p)]
-    polys, rs = [], []
-    for l in range(d):
-        g = round_g5(tabs, ch, p)
-        if cheat and l == 0:
-            g[1] = -g[0] % p
-        polys.append(g)
-        for e in g:
-            tr.append(be32(e))
-        r = tr.challenge(p)
-        rs.append(r)
-        tabs = [ML.mle_fold_last(field, t, r) for t in tabs]
-    z = rs[::-1]
-    op = BM.open_batch(list(cms) + [mcm, hcm], [z], f, Q, a, tr, hasher)
-    assert [row[0] for row in op["ys"]] == [t[0] for t in tabs[:K]] and tabs[K][0] == eq_at(z, tau, p)
-    return {"field": field, "d": d, "roots": roots, "h_roots": [mcm["root"], hcm["root"]], "drawn": [beta, gamma, mu] + tau, "polys": polys, "challenges": rs,
-            "opening": op, "misses": misses, "M": m, "nonce": getattr(tr, "nonce", None) or 0}
+    return F.prove_rounds(PROTO, cms, (), f, Q, a, tr, hasher, cheat, commit)
 
 
 def verify(pr, roots=None, tr=None, hasher=M.keccak256):
     """`roots`: the verifier's own seven, the proof's unless given -> (ok, the number of the first check that failed or None): 0 the first
     round's sum, l >= 1 round l's, d the last claim, d + 1 the opening"""
-    field, d, op = pr["field"], pr["d"], pr["opening"]
-    p = NM.MODULUS[field]
-    tr = M.Transcript() if tr is None else tr
-    roots = pr["roots"] if roots is None else roots
-    _statement(tr, roots, d)
-    beta, gamma, mu, tau = _helpers(tr, pr["h_roots"], d, p)
-    cur, rs, failed = 0, [], None
-    for l in range(d):
-        g = pr["polys"][l]
-        for e in g:
-            tr.append(be32(e % p))
-        if failed is None and (any(not 0 <= e < p for e in g) or (g[0] + g[1]) % p != cur):
-            failed = l
-        rs.append(tr.challenge(p))
-        cur = interpolate5(g, rs[l], p)
-    z = rs[::-1]
-    ys = [row[0] for row in op["ys"]]
-    want = summand(ys, eq_at(z, tau, p), (beta, gamma, mu)) % p
-    if failed is None and cur != want:
-        failed = d
-    good = BM.verify(dict(op, own_roots=list(roots) + list(pr["h_roots"]), points=[z]), tr, hasher) and getattr(tr, "pow_ok", None) is not False
-    if failed is None and not good:
-        failed = d + 1
-    return failed is None, failed
-
-
-def sizes(d, b, f, Q, a=1, grouped=False):
-    """(nround, nhroots) + the batch model's five counts at k = 9"""
-    return (NODES * d, HELPERS) + BM.sizes(K, d, b, f, Q, a, grouped)
-
-
-def flat(zk, pr):
-    """the proof as the C outputs: drawn (3 + d, 4), polys (d, 5, 4), challenges (d, 4), own_roots (7, 32), h_roots (2, 32), and the opening's
-    arrays of _fri_ml_batch_model.flat under their names there with ys as (9, 4) and the opening's round polynomials as open_polys /
-    open_challenges"""
-    field, d = pr["field"], pr["d"]
-
-    def mont(ints):
-        canon = np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in ints), np.uint64).reshape(-1, 4).copy()
-        out = np.zeros_like(canon)
-        assert zk.lib().zk_vec_from_canonical(field, canon.ctypes.data_as(zk._lib.u64p), canon.shape[0], out.ctypes.data_as(zk._lib.u64p)) == 0
-        return out
-
-    fl = BM.flat(zk, pr["opening"])
-    fl["open_polys"], fl["open_challenges"] = fl.pop("polys"), fl.pop("challenges")
-    fl["ys"] = fl["ys"].reshape(K, 4)
-    fl["own_roots"] = np.frombuffer(b"".join(pr["roots"]), np.uint8).reshape(GIVEN, 32).copy()
-    fl["h_roots"] = np.frombuffer(b"".join(pr["h_roots"]), np.uint8).reshape(HELPERS, 32).copy()
-    fl.update(drawn=mont(pr["drawn"]), polys=mont([e for g in pr["polys"] for e in g]).reshape(d, NODES, 4), challenges=mont(pr["challenges"]))
-    return fl
+    return F.replay(PROTO, pr, roots, None, tr, hasher)

@@ -20,21 +20,21 @@ helper tables, the wiring's summand, the id tables), _zerocheck_gate_model (the 
 `prove(.., cheat=True)` is _wiring_model's cheating prover here: it commits H = 0 and sends g_0(1) = c - g_0(0).
 `circuit(field, d, seed, l, ..)` builds a small wired circuit whose first l rows are public-input rows.
 Everything is Python integers; nothing here knows how the library works."""
+import functools
 import random
-
-import numpy as np
 
 import _fri_ml_batch_model as BM
 import _fri_ml_model as ML
 import _ntt_model as NM
 import _wiring_model as WM
+import _zerocheck_family_model as F
 import _zerocheck_gate_model as ZG
 from oracle import pymodel as M
 
-be32 = ML.be32
+be32, mont = F.be32, F.mont
 WIRES, GIVEN, K, NODES, TABLES = 3, 11, 14, 5, 15
 W_PLACES, Q_PLACES, S_PLACES, H_PLACES, E_PLACE = (0, 1, 2), (3, 4, 5, 6, 7), (8, 9, 10), (11, 12, 13), 14
-interpolate5, eq_at, id_at, pow_transcript, commit_like = WM.interpolate5, WM.eq_at, WM.id_at, WM.pow_transcript, WM.commit_like
+interpolate5, eq_at, id_at, commit_like = F.interpolate, F.eq_at, F.id_at, F.commit_like
 
 
 def tag(d, l):
@@ -105,9 +105,9 @@ def summand(v, ids, ch, pi=0):
     return WM.summand(ws, ss, hs, ids, e, ch) + e * alpha ** 3 * (ZG.gate(*ws, *qs) - pi)
 
 
-def round_g5(tabs, ids, ch, p, pi=None):
+def round_g5(tabs, ids, ch, p, pi=None, summand=summand, E_PLACE=E_PLACE):
     """-> (the message g(0) .. g(4) as the protocol sends it, the round polynomial of F itself at the five nodes), straight from the definition;
-    tabs: the fifteen; ids: the three id tables; pi: the PI table (all zero when None)"""
+    tabs: the fifteen; ids: the three id tables; pi: the PI table (all zero when None).  summand, E_PLACE: a wider relation's, _plonk_lookup_model's"""
     alpha = ch[2]
     pi = [0] * len(tabs[0]) if pi is None else pi
     line = lambda t, x, X: t[2 * x] + X * (t[2 * x + 1] - t[2 * x])
@@ -120,111 +120,30 @@ def round_g5(tabs, ids, ch, p, pi=None):
     return [(a + b) % p for a, b in zip(f, moved)], [a % p for a in f]
 
 
-def _statement(tr, roots, d, pub, p):
-    tr.append(tag(d, len(pub)))
-    for r in roots:
-        tr.append(r)
-    for v in pub:
-        tr.append(be32(v % p))
-    return tr.challenge(p), tr.challenge(p)
+def claimed_sum(pub, tau, ch, p):
+    """alpha^3 sum_x PI[x] E[x] on the explicit tables, which is alpha^3 public_eval"""
+    out = ch[2] ** 3 * sum(a * b for a, b in zip(pi_table(pub, len(tau)), ML.eq_table(tau, p))) % p
+    assert out == ch[2] ** 3 * public_eval(pub, tau, p) % p
+    return out
+
+
+def explicit_tables(d, pub):
+    return F.id_tables(d) + [pi_table(pub, d)]
+
+
+PROTO = F.Proto(tag, GIVEN, NODES, 2, ((WIRES, 2),), lambda i, tabs, ch, p, cheat: WM.helper_phase(i, tabs[:3] + tabs[8:11], ch, p, cheat), summand,
+                lambda tabs, x, ch, p: round_g5(tabs, x[:WIRES], ch, p, x[WIRES]), explicit_tables, claimed_sum, BM)
+pow_transcript, sizes, flat = (functools.partial(fn, PROTO) for fn in (F.pow_transcript, F.sizes, F.flat))
+_statement = lambda tr, roots, d, pub, p: F.statement(PROTO, tr, roots, d, p, pub)      # -> [beta, gamma]
 
 
 def prove(cms, pub, f, Q, a=1, tr=None, hasher=M.keccak256, cheat=False):
     """-> the proof as a dict; `cms`: the model commitments of the eleven (all alike); `pub`: the public values; `tr` is advanced.  The
     statement is not checked."""
-    field, d = cms[0]["field"], cms[0]["d"]
-    assert len(cms) == GIVEN and len(pub) <= 1 << d
-    p, n = NM.MODULUS[field], 1 << d
-    tr = M.Transcript() if tr is None else tr
-    roots = [c["root"] for c in cms]
-    beta, gamma = _statement(tr, roots, d, pub, p)
-    given = [list(c["coeffs"]) for c in cms]
-    ws, ss = given[0:3], given[8:11]
-    hs = [[0] * n for _ in range(WIRES)] if cheat else [WM.fractions(ws[j], ss[j], j * n, beta, gamma, p) for j in range(WIRES)]
-    hcms = [commit_like(cms[0], h, hasher) for h in hs]
-    h_roots = [c["root"] for c in hcms]
-    alpha, mu, tau = WM._helpers(tr, h_roots, d, p)
-    ch = (beta, gamma, alpha, mu)
-    tabs, ids, pi = given + hs + [ML.eq_table(tau, p)], WM.id_tables(d), pi_table(pub, d)
-    claimed = alpha ** 3 * sum(a_ * b_ for a_, b_ in zip(pi, tabs[E_PLACE])) % p
-    assert claimed == alpha ** 3 * public_eval(pub, tau, p) % p
-    polys, rs, own_sums = [], [], []
-    for l in range(d):
-        g, own = round_g5(tabs, ids, ch, p, pi)
-        own_sums.append((own[0] + own[1]) % p)
-        if cheat and l == 0:
-            g[1] = (claimed - g[0]) % p
-        polys.append(g)
-        for e in g:
-            tr.append(be32(e))
-        r = tr.challenge(p)
-        rs.append(r)
-        tabs = [ML.mle_fold_last(field, t, r) for t in tabs]
-        ids = [ML.mle_fold_last(field, t, r) for t in ids]
-        pi = ML.mle_fold_last(field, pi, r)
-    z = rs[::-1]
-    op = BM.open_batch(list(cms) + hcms, [z], f, Q, a, tr, hasher)
-    assert [row[0] for row in op["ys"]] == [t[0] for t in tabs[:K]] and tabs[K][0] == eq_at(z, tau, p)
-    assert [t[0] for t in ids] == [id_at(j, z, d, p) for j in range(WIRES)]
-    return {"field": field, "d": d, "roots": roots, "pub": list(pub), "h_roots": h_roots, "drawn": [beta, gamma, alpha, mu] + tau, "polys": polys, "challenges": rs,
-            "opening": op, "nonce": getattr(tr, "nonce", None) or 0, "own_first_sum": own_sums[0] if own_sums else 0}
+    return F.prove_rounds(PROTO, cms, pub, f, Q, a, tr, hasher, cheat)
 
 
 def verify(pr, roots=None, pub=None, tr=None, hasher=M.keccak256):
     """`roots`, `pub`: the verifier's own eleven and its public values, the proof's unless given -> (ok, the number of the first check that failed
     or None): 0 the first round's sum (or a public value outside the field), l >= 1 round l's, d the last claim, d + 1 the opening"""
-    field, d, op = pr["field"], pr["d"], pr["opening"]
-    p = NM.MODULUS[field]
-    tr = M.Transcript() if tr is None else tr
-    roots = pr["roots"] if roots is None else roots
-    pub = pr["pub"] if pub is None else pub
-    beta, gamma = _statement(tr, roots, d, pub, p)
-    alpha, mu, tau = WM._helpers(tr, pr["h_roots"], d, p)
-    failed = 0 if any(not 0 <= v < p for v in pub) or len(pub) > 1 << d else None
-    moved = alpha ** 3 * sum(a * b for a, b in zip(pi_table(pub, d), ML.eq_table(tau, p))) % p if len(pub) <= 1 << d else 0
-    cur, rs = moved, []
-    for l in range(d):
-        g = pr["polys"][l]
-        for e in g:
-            tr.append(be32(e % p))
-        if failed is None and (any(not 0 <= e < p for e in g) or (g[0] + g[1] - cur) % p != 0):
-            failed = l
-        rs.append(tr.challenge(p))
-        cur = interpolate5(g, rs[l], p)
-    z = rs[::-1]
-    ys = [row[0] for row in op["ys"]]
-    want = summand(ys + [eq_at(z, tau, p)], [id_at(j, z, d, p) for j in range(WIRES)], (beta, gamma, alpha, mu)) % p
-    if failed is None and cur != want:
-        failed = d
-    good = BM.verify(dict(op, own_roots=list(roots) + list(pr["h_roots"]), points=[z]), tr, hasher) and getattr(tr, "pow_ok", None) is not False
-    if failed is None and not good:
-        failed = d + 1
-    return failed is None, failed
-
-
-def sizes(d, b, f, Q, a=1, grouped=False):
-    """(nround, nhroots) + the batch model's five counts at k = 14"""
-    return (NODES * d, WIRES) + BM.sizes(K, d, b, f, Q, a, grouped)
-
-
-def mont(zk, field, ints):
-    canon = np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in ints), np.uint64).reshape(-1, 4).copy()
-    out = np.zeros_like(canon)
-    if canon.shape[0]:
-        assert zk.lib().zk_vec_from_canonical(field, canon.ctypes.data_as(zk._lib.u64p), canon.shape[0], out.ctypes.data_as(zk._lib.u64p)) == 0
-    return out
-
-
-def flat(zk, pr):
-    """the proof as the C outputs: drawn (4 + d, 4), polys (d, 5, 4), challenges (d, 4), own_roots (11, 32), h_roots (3, 32), pub (l, 4), and the
-    opening's arrays of _fri_ml_batch_model.flat under their names there with ys as (14, 4) and the opening's round polynomials as open_polys /
-    open_challenges"""
-    field, d = pr["field"], pr["d"]
-    fl = BM.flat(zk, pr["opening"])
-    fl["open_polys"], fl["open_challenges"] = fl.pop("polys"), fl.pop("challenges")
-    fl["ys"] = fl["ys"].reshape(K, 4)
-    fl["own_roots"] = np.frombuffer(b"".join(pr["roots"]), np.uint8).reshape(GIVEN, 32).copy()
-    fl["h_roots"] = np.frombuffer(b"".join(pr["h_roots"]), np.uint8).reshape(WIRES, 32).copy()
-    fl.update(drawn=mont(zk, field, pr["drawn"]), polys=mont(zk, field, [e for g in pr["polys"] for e in g]).reshape(d, NODES, 4),
-              challenges=mont(zk, field, pr["challenges"]), pub=mont(zk, field, pr["pub"]))
-    return fl
+    return F.replay(PROTO, pr, roots, pub, tr, hasher)

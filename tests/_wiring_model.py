@@ -19,33 +19,21 @@ because the zerocheck part of the sum is then not 0 unless S = id, hides that fr
 sends g_0(1) = -g_0(0) and is honest afterwards.  The first check passes, a later one fails, and the opening alone verifies.
 `wiring(field, d, seed)` draws a random permutation of the 3 n cells and one random value per cycle.
 Everything is Python integers; nothing here knows how the library works."""
+import functools
 import random
 
-import numpy as np
-
 import _fri_ml_batch_model as BM
-import _fri_ml_grouped_model as GM
-import _fri_ml_model as ML
-import _fri_pcs_model as PM
-import _grind_model as GR
 import _ntt_model as NM
+import _zerocheck_family_model as F
 from oracle import pymodel as M
 
-be32 = ML.be32
+be32, eq_at, inv0, id_tables, id_at, commit_like = F.be32, F.eq_at, F.inv0, F.id_tables, F.id_at, F.commit_like
+interpolate5 = F.interpolate                                 # the quartic through (0, g[0]) .. (4, g[4]) at r
 WIRES, GIVEN, K, NODES = 3, 6, 9, 5
 
 
 def tag(d):
     return b"ZCPW" + int(d).to_bytes(4, "big")
-
-
-def inv0(a, p):
-    return 0 if a % p == 0 else pow(a, -1, p)
-
-
-def id_tables(d):
-    n = 1 << d
-    return [[j * n + x for x in range(n)] for j in range(WIRES)]
 
 
 def cycles_of(sigma):
@@ -113,146 +101,26 @@ def round_g5(tabs, ids, ch, p):
     return [v % p for v in g]
 
 
-def interpolate5(g, r, p):
-    """the quartic through (0, g[0]) .. (4, g[4]) at r, by Lagrange's formula"""
-    out = 0
-    for i in range(NODES):
-        num, den = 1, 1
-        for j in range(NODES):
-            if j != i:
-                num, den = num * (r - j) % p, den * (i - j) % p
-        out += g[i] * num * pow(den, -1, p)
-    return out % p
+def helper_phase(i, tabs, ch, p, cheat):
+    """the family's helper phase: H0, H1, H2 from A, B, C, SA, SB, SC at the first places of `tabs` and beta, gamma; all zero when cheating"""
+    n = len(tabs[0])
+    return [[0] * n if cheat else fractions(tabs[j], tabs[GIVEN - WIRES + j], j * n, ch[0], ch[1], p) for j in range(WIRES)], {}
 
 
-def eq_at(z, tau, p):
-    out = 1
-    for a, b in zip(z, tau):
-        out = out * ML.eq1(a, b, p) % p
-    return out
-
-
-def id_at(j, z, d, p):
-    """the closed form of the multilinear extension of id_j at z: variable 0 is the most significant index bit"""
-    return (j * (1 << d) + sum((1 << (d - 1 - i)) * zi for i, zi in enumerate(z))) % p
-
-
-def _statement(tr, roots, d, p):
-    tr.append(tag(d))
-    for r in roots:
-        tr.append(r)
-    return tr.challenge(p), tr.challenge(p)
-
-
-def _helpers(tr, h_roots, d, p):
-    for r in h_roots:
-        tr.append(r)
-    alpha, mu = tr.challenge(p), tr.challenge(p)
-    return alpha, mu, [tr.challenge(p) for _ in range(d)]
-
-
-def pow_transcript(d, f, bits, nonce=None, prefix=b""):
-    """the transcript of a proof with the proof-of-work step: it stands in front of the first index, sample number 2 (beta, gamma) + 2 (alpha,
-    mu) + d (tau) + d (the rounds) + 1 (the opening's gamma) + R (its rounds)"""
-    tr = GR.PowTranscript(bits, 4 + 2 * d + 1 + (d - f), nonce)
-    tr.append(prefix)
-    return tr
-
-
-def commit_like(cm, table, hasher):
-    """the model commitment of `table` with the shape of the model commitment `cm`"""
-    mod = GM if cm.get("log_group", 0) else PM
-    return mod.commit(cm["field"], table, cm["b"], cm["coset"], hasher)
+PROTO = F.Proto(tag, GIVEN, NODES, 2, ((WIRES, 2),), helper_phase, lambda v, ids, ch: summand(v[0:3], v[3:6], v[6:9], ids, v[9], ch),
+                lambda tabs, ids, ch, p: (round_g5(tabs, ids, ch, p), None), lambda d, pub: id_tables(d), opening=BM)
+pow_transcript, sizes, flat = (functools.partial(fn, PROTO) for fn in (F.pow_transcript, F.sizes, F.flat))
+_statement, _helpers = functools.partial(F.statement, PROTO), functools.partial(F.helpers, PROTO)      # -> [beta, gamma]; -> [alpha, mu, tau]
 
 
 def prove(cms, f, Q, a=1, tr=None, hasher=M.keccak256, cheat=False, commit=None):
     """-> the proof as a dict; `cms`: the model commitments of the six (tests/_fri_pcs_model.py, or _fri_ml_grouped_model.py's, all alike);
     `commit(table)`: the model commitment of a helper table with their shape (commit_like on the first by default); `tr` is advanced.  The
     statement is not checked."""
-    field, d = cms[0]["field"], cms[0]["d"]
-    assert len(cms) == GIVEN
-    p, n = NM.MODULUS[field], 1 << d
-    tr = M.Transcript() if tr is None else tr
-    roots = [c["root"] for c in cms]
-    beta, gamma = _statement(tr, roots, d, p)
-    ws, ss = [list(c["coeffs"]) for c in cms[:3]], [list(c["coeffs"]) for c in cms[3:]]
-    hs = [[0] * n for _ in range(WIRES)] if cheat else [fractions(ws[j], ss[j], j * n, beta, gamma, p) for j in range(WIRES)]
-    commit = (lambda t: commit_like(cms[0], t, hasher)) if commit is None else commit
-    hcms = [commit(h) for h in hs]
-    h_roots = [c["root"] for c in hcms]
-    alpha, mu, tau = _helpers(tr, h_roots, d, p)
-    ch = (beta, gamma, alpha, mu)
-    tabs, ids = ws + ss + hs + [ML.eq_table(tau, p)], id_tables(d)
-    polys, rs = [], []
-    for l in range(d):
-        g = round_g5(tabs, ids, ch, p)
-        if cheat and l == 0:
-            g[1] = -g[0] % p
-        polys.append(g)
-        for e in g:
-            tr.append(be32(e))
-        r = tr.challenge(p)
-        rs.append(r)
-        tabs = [ML.mle_fold_last(field, t, r) for t in tabs]
-        ids = [ML.mle_fold_last(field, t, r) for t in ids]
-    z = rs[::-1]
-    op = BM.open_batch(list(cms) + hcms, [z], f, Q, a, tr, hasher)
-    assert [row[0] for row in op["ys"]] == [t[0] for t in tabs[:K]] and tabs[K][0] == eq_at(z, tau, p)
-    assert [t[0] for t in ids] == [id_at(j, z, d, p) for j in range(WIRES)]
-    return {"field": field, "d": d, "roots": roots, "h_roots": h_roots, "drawn": [beta, gamma, alpha, mu] + tau, "polys": polys, "challenges": rs, "opening": op,
-            "nonce": getattr(tr, "nonce", None) or 0}
+    return F.prove_rounds(PROTO, cms, (), f, Q, a, tr, hasher, cheat, commit)
 
 
 def verify(pr, roots=None, tr=None, hasher=M.keccak256):
     """`roots`: the verifier's own six, the proof's unless given -> (ok, the number of the first check that failed or None): 0 the first
     round's sum, l >= 1 round l's, d the last claim, d + 1 the opening"""
-    field, d, op = pr["field"], pr["d"], pr["opening"]
-    p = NM.MODULUS[field]
-    tr = M.Transcript() if tr is None else tr
-    roots = pr["roots"] if roots is None else roots
-    beta, gamma = _statement(tr, roots, d, p)
-    alpha, mu, tau = _helpers(tr, pr["h_roots"], d, p)
-    cur, rs, failed = 0, [], None
-    for l in range(d):
-        g = pr["polys"][l]
-        for e in g:
-            tr.append(be32(e % p))
-        if failed is None and (any(not 0 <= e < p for e in g) or (g[0] + g[1]) % p != cur):
-            failed = l
-        rs.append(tr.challenge(p))
-        cur = interpolate5(g, rs[l], p)
-    z = rs[::-1]
-    ys = [row[0] for row in op["ys"]]
-    want = summand(ys[0:3], ys[3:6], ys[6:9], [id_at(j, z, d, p) for j in range(WIRES)], eq_at(z, tau, p), (beta, gamma, alpha, mu)) % p
-    if failed is None and cur != want:
-        failed = d
-    good = BM.verify(dict(op, own_roots=list(roots) + list(pr["h_roots"]), points=[z]), tr, hasher) and getattr(tr, "pow_ok", None) is not False
-    if failed is None and not good:
-        failed = d + 1
-    return failed is None, failed
-
-
-def sizes(d, b, f, Q, a=1, grouped=False):
-    """(nround, nhroots) + the batch model's five counts at k = 9"""
-    return (NODES * d, WIRES) + BM.sizes(K, d, b, f, Q, a, grouped)
-
-
-def flat(zk, pr):
-    """the proof as the C outputs: drawn (4 + d, 4), polys (d, 5, 4), challenges (d, 4), own_roots (6, 32), h_roots (3, 32), and the opening's
-    arrays of _fri_ml_batch_model.flat under their names there with ys as (9, 4) and the opening's round polynomials as open_polys /
-    open_challenges"""
-    field, d = pr["field"], pr["d"]
-
-    def mont(ints):
-        canon = np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in ints), np.uint64).reshape(-1, 4).copy()
-        out = np.zeros_like(canon)
-        assert zk.lib().zk_vec_from_canonical(field, canon.ctypes.data_as(zk._lib.u64p), canon.shape[0], out.ctypes.data_as(zk._lib.u64p)) == 0
-        return out
-
-    fl = BM.flat(zk, pr["opening"])
-    fl["open_polys"], fl["open_challenges"] = fl.pop("polys"), fl.pop("challenges")
-    fl["ys"] = fl["ys"].reshape(K, 4)
-    fl["own_roots"] = np.frombuffer(b"".join(pr["roots"]), np.uint8).reshape(GIVEN, 32).copy()
-    fl["h_roots"] = np.frombuffer(b"".join(pr["h_roots"]), np.uint8).reshape(WIRES, 32).copy()
-    fl.update(drawn=mont(pr["drawn"]), polys=mont([e for g in pr["polys"] for e in g]).reshape(d, NODES, 4), challenges=mont(pr["challenges"]))
-    return fl
+    return F.replay(PROTO, pr, roots, None, tr, hasher)

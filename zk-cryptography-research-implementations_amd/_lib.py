@@ -56,6 +56,13 @@ def lib():
     L.zk_merkle_depth.restype = sz
     L.zk_fri_commitment_log_group.restype = C.c_uint32
     L.zk_fri_columns_count.restype = C.c_uint32
+    # the zerocheck family (zerocheck .. plonk_lookup below): what stands behind an entry's own leading arguments
+    opened = [u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p]         # ys, gamma, round polys, roots, final, challenges, indices, values, paths
+    zc_prove = [vp, u64p, u64p, u64p] + opened + [u64p]                    # transcript, tau, round polys, challenges; the opening; the nonce
+    zh_prove = [vp, u8p, u64p, u64p, u64p] + opened + [u64p]               # transcript, helper roots, drawn, round polys, challenges; ..
+    checked = [u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64, C.POINTER(C.c_int)]   # round polys, ys, the opening; bits, nonce; ok
+    zc_verify = [u64p, vp] + checked                                       # coset, transcript; ..
+    zh_verify = [u64p, vp, u8p] + checked                                  # coset, transcript, helper roots; ..
     sigs = {
         "zk_device_count": [C.POINTER(C.c_int)],
         "zk_init": [C.c_int],
@@ -193,55 +200,48 @@ def lib():
         # zerocheck of a product of committed tables
         "zk_zerocheck_mul_round": [vp, vp, vp, vp, u64p, C.POINTER(vp), u64p],
         "zk_zerocheck_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 6,
-        "zk_zerocheck_mul_prove": [vp, vp, vp] + [C.c_uint32] * 4 + [vp, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
-        "zk_zerocheck_mul_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + [u64p, vp, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
-                                                                       C.POINTER(C.c_int)],
+        "zk_zerocheck_mul_prove": [vp, vp, vp] + [C.c_uint32] * 4 + zc_prove,
+        "zk_zerocheck_mul_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + zc_verify,
         "zk_zerocheck_last_stats": [vp],
         # zerocheck of a Plonk gate over committed tables
         "zk_zerocheck_gate_round": [C.POINTER(vp), u64p, C.POINTER(vp), u64p],
         "zk_zerocheck_gate_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 6,
-        "zk_zerocheck_gate_prove": [C.POINTER(vp)] + [C.c_uint32] * 4 + [vp, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
-        "zk_zerocheck_gate_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + [u64p, vp, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
-                                                                       C.POINTER(C.c_int)],
+        "zk_zerocheck_gate_prove": [C.POINTER(vp)] + [C.c_uint32] * 4 + zc_prove,
+        "zk_zerocheck_gate_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + zc_verify,
         # wiring: a permutation check over committed tables
         "zk_wiring_fractions": [vp, vp, C.c_uint64, u64p, u64p, C.POINTER(vp)],
         "zk_wiring_round": [C.POINTER(vp), u64p, u64p, u64p, u64p, u64p, C.c_uint32, u64p, C.POINTER(vp), u64p],
         "zk_wiring_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 7,
-        "zk_wiring_prove": [C.POINTER(vp)] + [C.c_uint32] * 4 + [vp, u8p, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
-        "zk_wiring_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
-                                                                C.POINTER(C.c_int)],
+        "zk_wiring_prove": [C.POINTER(vp)] + [C.c_uint32] * 4 + zh_prove,
+        "zk_wiring_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + zh_verify,
         "zk_wiring_last_stats": [vp],
         # Plonk: gate, wiring and public inputs in one sumcheck
         "zk_plonk_round": [C.POINTER(vp), u64p, u64p, u64p, u64p, u64p, C.c_uint32, u64p, C.POINTER(vp), u64p],
         "zk_plonk_public_eval": [C.c_int, u64p, C.c_uint32, u64p, C.c_uint32, u64p],
         "zk_plonk_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 7,
-        "zk_plonk_prove": [C.POINTER(vp), u64p] + [C.c_uint32] * 5 + [vp, u8p, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
-        "zk_plonk_verify": [C.c_int, u8p, u64p] + [C.c_uint32] * 7 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
-                                                                       C.POINTER(C.c_int)],
+        "zk_plonk_prove": [C.POINTER(vp), u64p] + [C.c_uint32] * 5 + zh_prove,
+        "zk_plonk_verify": [C.c_int, u8p, u64p] + [C.c_uint32] * 7 + zh_verify,
         "zk_plonk_last_stats": [vp],
         # lookup: rows of a committed table
         "zk_lookup_multiplicities": [C.POINTER(vp), C.POINTER(vp), u64p],
         "zk_lookup_fractions": [C.POINTER(vp), u64p, u64p, C.POINTER(vp)],
         "zk_lookup_round": [C.POINTER(vp), u64p, u64p, u64p, u64p, C.POINTER(vp), u64p],
         "zk_lookup_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 7,
-        "zk_lookup_prove": [C.POINTER(vp)] + [C.c_uint32] * 4 + [vp, u8p, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
-        "zk_lookup_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
-                                                                C.POINTER(C.c_int)],
+        "zk_lookup_prove": [C.POINTER(vp)] + [C.c_uint32] * 4 + zh_prove,
+        "zk_lookup_verify": [C.c_int, u8p] + [C.c_uint32] * 6 + zh_verify,
         "zk_lookup_last_stats": [vp],
         # Plonk with lookups: gate, wiring, public inputs and lookup rows in one sumcheck
         "zk_plonk_lookup_round": [C.POINTER(vp), u64p, u64p, u64p, u64p, u64p, C.c_uint32, u64p, C.POINTER(vp), u64p],
         "zk_plonk_lookup_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 7,
-        "zk_plonk_lookup_prove": [C.POINTER(vp), u64p] + [C.c_uint32] * 5 + [vp, u8p, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
-        "zk_plonk_lookup_verify": [C.c_int, u8p, u64p] + [C.c_uint32] * 7 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
-                                                                            C.POINTER(C.c_int)],
+        "zk_plonk_lookup_prove": [C.POINTER(vp), u64p] + [C.c_uint32] * 5 + zh_prove,
+        "zk_plonk_lookup_verify": [C.c_int, u8p, u64p] + [C.c_uint32] * 7 + zh_verify,
         "zk_plonk_lookup_last_stats": [vp],
         # Plonk with lookups on column commitments
         "zk_plonk_lookup_helpers": [C.POINTER(vp), u64p, u64p, C.POINTER(vp)],
         "zk_plonk_lookup_helpers_batch": [],
         "zk_plonk_lookup_sizes_columns": [C.c_uint32] * 4 + [C.POINTER(sz)] * 7,
-        "zk_plonk_lookup_prove_columns": [vp, vp, u64p] + [C.c_uint32] * 4 + [vp, u8p, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
-        "zk_plonk_lookup_verify_columns": [C.c_int, u8p, u8p, u64p] + [C.c_uint32] * 5 + [u64p, vp, u8p, u64p, u64p, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
-                                                                                       C.POINTER(C.c_int)],
+        "zk_plonk_lookup_prove_columns": [vp, vp, u64p] + [C.c_uint32] * 4 + zh_prove,
+        "zk_plonk_lookup_verify_columns": [C.c_int, u8p, u8p, u64p] + [C.c_uint32] * 5 + zh_verify,
         "zk_plonk_lookup_columns_last_stats": [vp],
         # sparse GKR: one phase's table kernel on caller-chosen tables (a gate array is passed as a void pointer)
         "zk_gkr_sparse_phase_tables": [C.c_int, C.c_int, vp, sz, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, u64p,

@@ -18,12 +18,11 @@ opening (include/zkmle.h "Plonk with lookups: gate, wiring, public inputs and lo
   and holds the witness root, the circuit root and the public values."""
 import ctypes as C
 
-import numpy as np
-
 from . import _lib as L
+from . import _zerocheck_family as F
 from . import fri
 from .lookup import _Stats, table_columns  # noqa: F401
-from .mle import MultilinearPolynomial, _elem, limbs
+from .mle import MultilinearPolynomial, _elem
 from .plonk import _public
 from .wiring import sigma_from_cycles  # noqa: F401
 
@@ -34,11 +33,7 @@ ORDER = "A, B, C, qM, qL, qR, qO, qC, SA, SB, SC, qK, T0, T1, T2"
 def sizes(d, log_blowup, log_final, nqueries, log_arity=1, grouped=False):
     """-> (nround, nhroots, nroots, nfinal, nvalues, path_bytes, nopen_round): the 5 d elements of the round polynomials, the 5 helper roots,
     then the counts of fri.ml_sizes_wide(.., k=20), the opening of the twenty commitments"""
-    out = [C.c_size_t(0) for _ in range(7)]
-    if grouped and log_arity != 2:
-        raise ValueError("grouped leaves need log_arity=2")
-    L.check(L.lib().zk_plonk_lookup_sizes(d, log_blowup, log_final, nqueries, log_arity, 2 if grouped else 0, *[C.byref(o) for o in out]))
-    return tuple(int(o.value) for o in out)
+    return F.sizes_of(L.lib().zk_plonk_lookup_sizes, 7, d, log_blowup, log_final, nqueries, log_arity, grouped)
 
 
 def round(tables, beta, gamma, alpha, mu, id_base=0, log_step=0, r=None):
@@ -47,43 +42,16 @@ def round(tables, beta, gamma, alpha, mu, id_base=0, log_step=0, r=None):
     last variable, g5 of the folded ones).  The id tables are those of zk.wiring.round."""
     if len(tables) != TABLES:
         raise ValueError("the pass takes twenty-one tables: " + ORDER + ", M, H0, H1, H2, HL, E")
-    field = tables[0].field
-    g5 = np.zeros((NODES, limbs(field)), np.uint64)
-    ins = (C.c_void_p * TABLES)(*[t._h for t in tables])
-    ch = [L.p64(_elem(field, v)) for v in (beta, gamma, alpha, mu, id_base)]
-    if r is None:
-        L.check(L.lib().zk_plonk_lookup_round(ins, *ch, log_step, None, None, L.p64(g5)))
-        return g5
-    outs = (C.c_void_p * TABLES)()
-    L.check(L.lib().zk_plonk_lookup_round(ins, *ch, log_step, L.p64(_elem(field, r)), outs, L.p64(g5)))
-    return tuple(MultilinearPolynomial(field, _handle=C.c_void_p(h)) for h in outs), g5
+    return F.round_pass(L.lib().zk_plonk_lookup_round, tables, (beta, gamma, alpha, mu, id_base), log_step, r, NODES)
 
 
-class PlonkLookupProof:
+class PlonkLookupProof(F.Proof):
     """h_roots (5, 32): the roots of M, H0, H1, H2, HL; round_polys (d, 5, limbs); ys (20, limbs) = the values of the fifteen and of M, H0, H1,
     H2, HL at the point; opening: the fri.FriMlWideOpening of the twenty commitments there (its ys are the same array).  drawn (4 + d, limbs) =
     beta, gamma, alpha, mu, tau and challenges (d, limbs) are what the prover's transcript gave (diagnostic: the verifier derives its own; the
     opening's point is the challenges reversed).  The public values are the statement's, not the proof's."""
 
-    K, NODES = OPENED, NODES
-
-    def __init__(self, field, d, log_blowup, log_final, nqueries, coset=None, log_arity=1, grouped=False, grinding_bits=0):
-        n = limbs(field)
-        self.field, self.d = field, d
-        self.h_roots = np.zeros((HELPERS, 32), np.uint8)
-        self.drawn = np.zeros((4 + d, n), np.uint64)
-        self.round_polys = np.zeros((d, self.NODES, n), np.uint64)
-        self.challenges = np.zeros((d, n), np.uint64)
-        self.opening = fri.FriMlWideOpening(field, self.K, 1, d, log_blowup, log_final, nqueries, coset, log_arity, grouped, grinding_bits)
-
-    @property
-    def ys(self):
-        return self.opening.ys[:, 0]
-
-    @property
-    def point(self):
-        """(1, d, limbs): where the tables are opened"""
-        return np.ascontiguousarray(self.challenges[::-1])[None]
+    K, NODES, HELPER_ROOTS, DRAWN, OPENING = OPENED, NODES, HELPERS, 4, fri.FriMlWideOpening
 
 
 def prove(wires, selectors, sigmas, lookup_selector, table, public_inputs, log_final, nqueries, log_arity=1, transcript=None, grinding_bits=0):
@@ -93,45 +61,23 @@ def prove(wires, selectors, sigmas, lookup_selector, table, public_inputs, log_f
     if len(wires) != WIRES or len(selectors) != SELECTORS or len(sigmas) != WIRES or len(table) != COLUMNS:
         raise ValueError("the proof takes three wires, five selectors, three permutation tables, the lookup selector and three table columns: " + ORDER)
     cms = tuple(wires) + tuple(selectors) + tuple(sigmas) + (lookup_selector,) + tuple(table)
-    c0 = cms[0]
-    grouped = getattr(c0, "log_group", 0) != 0
-    if grouped and log_arity != 2:
-        raise ValueError("commitments with grouped leaves are opened with log_arity=2")
-    pub, pp = _public(c0.field, public_inputs)
-    pr = PlonkLookupProof(c0.field, c0.d, c0.log_blowup, log_final, nqueries, c0.coset, log_arity, grouped, grinding_bits)
-    op, nonce = pr.opening, C.c_uint64(0)
-    arr = (C.c_void_p * GIVEN)(*[c._h for c in cms])
-    L.check(L.lib().zk_plonk_lookup_prove(arr, pp, pub.shape[0], log_final, nqueries, log_arity, grinding_bits, fri._handle(transcript), L.p8(pr.h_roots),
-                                          L.p64(pr.drawn), L.p64(pr.round_polys), L.p64(pr.challenges), *fri._prover_outputs(op), C.byref(nonce)))
-    op.pow_nonce = int(nonce.value)
-    return pr
+    fn, arr = L.lib().zk_plonk_lookup_prove, (C.c_void_p * GIVEN)(*[c._h for c in cms])
+    return F.prove_with(PlonkLookupProof, lambda *rest: fn(arr, *rest), cms[0], log_final, nqueries, log_arity, transcript, grinding_bits,
+                        lambda: _public(cms[0].field, public_inputs))
 
 
 def verify(roots, public_inputs, proof, transcript=None):
     """host only: `roots` = the fifteen roots (32 bytes each) in the order A, B, C, qM, qL, qR, qO, qC, SA, SB, SC, qK, T0, T1, T2;
     public_inputs as for prove"""
-    op, ok = proof.opening, C.c_int(0)
     if len(roots) != GIVEN:
         raise L.ZkError(L.ZK_E_ARG, "one 32-byte Merkle root per commitment: " + ORDER)
-    hr = np.ascontiguousarray(proof.h_roots, np.uint8)
-    if hr.shape != (HELPERS, 32):
-        raise L.ZkError(L.ZK_E_ARG, "five 32-byte helper roots")
-    pub, pp = _public(op.field, public_inputs)
-    # the opening's roots and claims are those of the twenty; only the fifteen are the verifier's own
-    rf, _, ys, arrays = fri._verifier_inputs(op, list(roots) + [hr[j].tobytes() for j in range(HELPERS)], op.ys, k=proof.K)
-    rp = np.ascontiguousarray(proof.round_polys, np.uint64)
-    L.check(L.lib().zk_plonk_lookup_verify(op.field, rf, pp, pub.shape[0], op.d, op.log_blowup, op.log_final, op.nqueries, op.log_arity, 2 if op.grouped else 0,
-                                           op._coset(), fri._handle(transcript), L.p8(hr), L.p64(rp), L.p64(ys), *arrays, getattr(op, "grinding_bits", 0),
-                                           getattr(op, "pow_nonce", 0), C.byref(ok)))
-    return bool(ok.value)
+    return F.verify_with(L.lib().zk_plonk_lookup_verify, proof, roots, transcript, lambda: _public(proof.opening.field, public_inputs))
 
 
 def last_stats():
     """the calling thread's last prove: `misses` (rows with qK = 1 whose triple is in no table row) and milliseconds of the multiplicity count,
     the four helper tables, the five commitments together, the eq table, the rounds, the opening, and the host clock over the call"""
-    st = _Stats()
-    L.check(L.lib().zk_plonk_lookup_last_stats(C.byref(st)))
-    return {name: getattr(st, name) for name, _ in _Stats._fields_}
+    return F.stats_of(L.lib().zk_plonk_lookup_last_stats, _Stats)
 
 
 # ---- on column commitments ------------------------------------------------------------------------------------------------------------------
@@ -158,69 +104,34 @@ def helpers_batch():
 def sizes_columns(d, log_blowup, log_final, nqueries):
     """-> (nround, nhroots, nroots, nfinal, nvalues, path_bytes, nopen_round): the 5 d elements of the round polynomials, the 2 helper roots,
     then the counts of fri.columns_sizes((3, 12, 1, 4), ..)"""
-    out = [C.c_size_t(0) for _ in range(7)]
-    L.check(L.lib().zk_plonk_lookup_sizes_columns(d, log_blowup, log_final, nqueries, *[C.byref(o) for o in out]))
-    return tuple(int(o.value) for o in out)
+    return F.sizes_of(L.lib().zk_plonk_lookup_sizes_columns, 7, d, log_blowup, log_final, nqueries)
 
 
-class PlonkLookupColumnsProof:
+class PlonkLookupColumnsProof(F.Proof):
     """h_roots (2, 32): the roots of M and of the helpers' four-column commitment; round_polys (d, 5, limbs); ys (20, limbs) = the values of the
     twenty columns at the point, in the order of PlonkLookupProof's; opening: the fri.FriColumnsOpening of the four commitments of widths 3, 12,
     1, 4 there (its ys are the same array).  drawn and challenges as PlonkLookupProof's.  The public values are the statement's."""
 
-    K, NODES = OPENED, NODES
+    K, NODES, HELPER_ROOTS, DRAWN, OPENING = OPENED, NODES, 2, 4, fri.FriColumnsOpening
 
     def __init__(self, field, d, log_blowup, log_final, nqueries, coset=None, grinding_bits=0):
-        n = limbs(field)
-        self.field, self.d = field, d
-        self.h_roots = np.zeros((2, 32), np.uint8)
-        self.drawn = np.zeros((4 + d, n), np.uint64)
-        self.round_polys = np.zeros((d, self.NODES, n), np.uint64)
-        self.challenges = np.zeros((d, n), np.uint64)
-        self.opening = fri.FriColumnsOpening(field, WIDTHS, 1, d, log_blowup, log_final, nqueries, coset, grinding_bits)
-
-    @property
-    def ys(self):
-        return self.opening.ys[:, 0]
-
-    @property
-    def point(self):
-        """(1, d, limbs): where the columns are opened"""
-        return np.ascontiguousarray(self.challenges[::-1])[None]
+        self._allocate(field, d, fri.FriColumnsOpening(field, WIDTHS, 1, d, log_blowup, log_final, nqueries, coset, grinding_bits))
 
 
 def prove_columns(witness, circuit, public_inputs, log_final, nqueries, transcript=None, grinding_bits=0):
     """the proof for the column commitments witness = (A, B, C) and circuit = (qM, qL, qR, qO, qC, SA, SB, SC, qK, T0, T1, T2) of one shape
     (fri.commit_columns) and the public values public_inputs ((l, limbs), l <= 2^d, or None); d - log_final >= 2"""
-    pub, pp = _public(witness.field, public_inputs)
-    pr = PlonkLookupColumnsProof(witness.field, witness.d, witness.log_blowup, log_final, nqueries, witness.coset, grinding_bits)
-    op, nonce = pr.opening, C.c_uint64(0)
-    L.check(L.lib().zk_plonk_lookup_prove_columns(witness._h, circuit._h, pp, pub.shape[0], log_final, nqueries, grinding_bits, fri._handle(transcript),
-                                                  L.p8(pr.h_roots), L.p64(pr.drawn), L.p64(pr.round_polys), L.p64(pr.challenges), *fri._prover_outputs(op),
-                                                  C.byref(nonce)))
-    op.pow_nonce = int(nonce.value)
-    return pr
+    fn = L.lib().zk_plonk_lookup_prove_columns
+    return F.prove_with(PlonkLookupColumnsProof, lambda *rest: fn(witness._h, circuit._h, *rest), witness, log_final, nqueries, None, transcript, grinding_bits,
+                        lambda: _public(witness.field, public_inputs))
 
 
 def verify_columns(witness_root, circuit_root, public_inputs, proof, transcript=None):
     """host only: the two roots (32 bytes each) as the verifier holds them; public_inputs as for prove_columns"""
-    op, ok = proof.opening, C.c_int(0)
-    hr = np.ascontiguousarray(proof.h_roots, np.uint8)
-    if hr.shape != (2, 32):
-        raise L.ZkError(L.ZK_E_ARG, "two 32-byte helper roots")
-    pub, pp = _public(op.field, public_inputs)
-    # the opening's roots and claims are those of the four commitments; only the first two are the verifier's own
-    rf, _, ys, arrays = fri._verifier_inputs(op, [witness_root, circuit_root, hr[0].tobytes(), hr[1].tobytes()], op.ys, k=len(WIDTHS))
-    own = np.frombuffer(bytes(witness_root) + bytes(circuit_root), np.uint8).copy()
-    rp = np.ascontiguousarray(proof.round_polys, np.uint64)
-    L.check(L.lib().zk_plonk_lookup_verify_columns(op.field, L.p8(own[:32]), L.p8(own[32:]), pp, pub.shape[0], op.d, op.log_blowup, op.log_final, op.nqueries,
-                                                   op._coset(), fri._handle(transcript), L.p8(hr), L.p64(rp), L.p64(ys), *arrays, getattr(op, "grinding_bits", 0),
-                                                   getattr(op, "pow_nonce", 0), C.byref(ok)))
-    return bool(ok.value)
+    return F.verify_with(L.lib().zk_plonk_lookup_verify_columns, proof, [witness_root, circuit_root], transcript,
+                         lambda: _public(proof.opening.field, public_inputs))
 
 
 def columns_last_stats():
     """last_stats for the calling thread's last prove_columns: ms_fractions is the one helper kernel, ms_commit the two helper commitments"""
-    st = _Stats()
-    L.check(L.lib().zk_plonk_lookup_columns_last_stats(C.byref(st)))
-    return {name: getattr(st, name) for name, _ in _Stats._fields_}
+    return F.stats_of(L.lib().zk_plonk_lookup_columns_last_stats, _Stats)
