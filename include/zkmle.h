@@ -1071,6 +1071,13 @@ int zk_plonk_last_stats(zk_plonk_stats *out);
 /* the multiplicity table on its own.  tables: A, B, C, qK, T0, T1, T2 (len >= 2, at most 2^31: the counts are 32 bits); *M (a new table) as
  * step 2 says, *misses = the number of rows with qK = 1 whose triple is in no table row.  Statuses and their order as zk_wiring_fractions. */
 int zk_lookup_multiplicities(const zk_table *const tables[7], zk_table **M, uint64_t *misses);
+/* TEST HOOK: the hash table as the insert pass of zk_lookup_multiplicities and of the provers leaves it (the same set-up and launch).  T: T0,
+ * T1, T2 (len = n >= 2, at most 2^31); slots: 2 n words of HOST memory.  Slot s holds the index of a table row or all ones (empty); a row's home
+ * is murmur3_x86_32 (seed 0x5EED) of its 96 stored bytes, T0 then T1 then T2, masked with 2 n - 1, and it sits at the first slot from there, cyclically,
+ * that was empty or held an equal row when it arrived; the slot of a repeated row ends at its smallest index.  Which row sits in which slot of a
+ * chain depends on the arrival order; the set of occupied slots does not.  Statuses and their order as zk_lookup_multiplicities; nothing is
+ * written unless the status is ZK_OK. */
+int zk_lookup_hash_slots(const zk_table *const T[3], uint32_t *slots);
 /* the helper table on its own.  tables: A, B, C, qK, T0, T1, T2, M; *H (a new table) as step 4 says; len >= 2.  Statuses and their order as
  * zk_wiring_fractions (beta and gamma reduced). */
 int zk_lookup_fractions(const zk_table *const tables[8], const uint64_t *beta, const uint64_t *gamma, zk_table **H);

@@ -37,7 +37,7 @@ zk = G.import_package()
 P64, P8 = C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
 p64 = lambda a: a.ctypes.data_as(P64) if a is not None else None
 p8 = lambda a: a.ctypes.data_as(P8) if a is not None else None
-NEW_NAMES = ("zk_lookup_multiplicities", "zk_lookup_fractions", "zk_lookup_round", "zk_lookup_sizes", "zk_lookup_prove", "zk_lookup_verify", "zk_lookup_last_stats")
+NEW_NAMES = ("zk_lookup_multiplicities", "zk_lookup_hash_slots", "zk_lookup_fractions", "zk_lookup_round", "zk_lookup_sizes", "zk_lookup_prove", "zk_lookup_verify", "zk_lookup_last_stats")
 SCHEDULES = [(1, False), (2, False), (2, True)]              # (log_arity, grouped)
 # (field, d, b, f, coset): d = 1 .. 4 on both fields, f = 0 and f = d - 1 among them; log_arity 2 runs where R = d - f >= 2
 CASES = [(0, 1, 1, 0, False), (3, 1, 2, 0, True), (0, 2, 2, 0, True), (3, 2, 1, 1, False), (3, 2, 1, 0, False), (0, 3, 1, 1, False), (3, 3, 2, 0, True),
@@ -123,7 +123,7 @@ def test_new_exports_are_present():
         assert hasattr(lib, name), name
         assert name + "(" in header, name
     assert "Lookup: rows of a committed table" in header and "zk_lookup_stats" in header
-    for name in ("prove", "verify", "multiplicities", "fractions", "round", "sizes", "last_stats", "LookupProof", "table_columns"):
+    for name in ("prove", "verify", "multiplicities", "hash_slots", "fractions", "round", "sizes", "last_stats", "LookupProof", "table_columns"):
         assert hasattr(zk.lookup, name), name
     assert zk.LookupProof is zk.lookup.LookupProof
 
@@ -430,11 +430,27 @@ def test_prover_and_hook_statuses_without_a_device():
             assert mu(tabs) == L.ZK_E_LEN_MISMATCH
     assert mu([h[1, 8]] * 7) == L.ZK_E_ARG and mu([h[0, 6]] * 7) == L.ZK_E_NOT_POW2 and mu([h[0, 1]] * 7) == L.ZK_E_ARG
     assert mu([h[0, 1 << 32]] * 7) == L.ZK_E_ARG              # the counts are 32 bits: d > 31 is refused
+    # the hash table's slots (a test hook)
+    slots = np.full(16, 7, np.uint32)
+    hs = lambda tabs, out=slots: lib.zk_lookup_hash_slots(None if tabs is None else arr(tabs), None if out is None else out.ctypes.data_as(C.POINTER(C.c_uint32)))
+    assert hs(None) == L.ZK_E_ARG and hs([t4] * 3, out=None) == L.ZK_E_ARG
+    for i in range(3):
+        tabs = [t4] * 3
+        tabs[i] = None
+        assert hs(tabs) == L.ZK_E_ARG
+        tabs[i] = h[3, 4]
+        assert hs(tabs) == L.ZK_E_ARG
+        if i:
+            tabs[i] = t8
+            assert hs(tabs) == L.ZK_E_LEN_MISMATCH
+    assert hs([h[1, 8]] * 3) == L.ZK_E_ARG and hs([h[0, 6]] * 3) == L.ZK_E_NOT_POW2 and hs([h[0, 1]] * 3) == L.ZK_E_ARG
+    assert hs([h[0, 1 << 32]] * 3) == L.ZK_E_ARG              # the slots hold 32-bit indices: n > 2^31 is refused
     import torch
     if not torch.cuda.is_available():
         assert rnd([h[0, 2]] * 10) == L.ZK_E_NO_DEVICE and rnd([t4] * 10, r=one) == L.ZK_E_NO_DEVICE and fr([t4] * 8) == L.ZK_E_NO_DEVICE
         assert mu([t4] * 7) == L.ZK_E_NO_DEVICE and mu([h[0, 1 << 31]] * 7) == L.ZK_E_NO_DEVICE
-    assert (g5 == 7).all() and not any(outs) and not H and not Mt and misses.value == 7
+        assert hs([t4] * 3) == L.ZK_E_NO_DEVICE and hs([h[0, 1 << 31]] * 3) == L.ZK_E_NO_DEVICE
+    assert (g5 == 7).all() and not any(outs) and not H and not Mt and misses.value == 7 and (slots == 7).all()
     w = lambda n: np.full(n, 7, np.uint64)
     bufs = [w(64) for _ in range(9)]
     r8, hr = np.full(64 * 32, 7, np.uint8), np.full(64, 7, np.uint8)

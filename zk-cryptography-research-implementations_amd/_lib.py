@@ -224,6 +224,7 @@ def lib():
         "zk_plonk_last_stats": [vp],
         # lookup: rows of a committed table
         "zk_lookup_multiplicities": [C.POINTER(vp), C.POINTER(vp), u64p],
+        "zk_lookup_hash_slots": [C.POINTER(vp), C.POINTER(C.c_uint32)],
         "zk_lookup_fractions": [C.POINTER(vp), u64p, u64p, C.POINTER(vp)],
         "zk_lookup_round": [C.POINTER(vp), u64p, u64p, u64p, u64p, C.POINTER(vp), u64p],
         "zk_lookup_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 7,

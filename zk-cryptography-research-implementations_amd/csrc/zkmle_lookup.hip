@@ -147,6 +147,16 @@ int zk_lookup_multiplicities(const zk_table *const tables[7], zk_table **M, uint
     return ZK_OK;
 }
 
+int zk_lookup_hash_slots(const zk_table *const T[3], uint32_t *slots) {
+    if (!slots) return ZK_E_ARG;
+    ZK_TRY(check_tables(T, 3, 2));
+    if (T[0]->len > ((size_t)1 << kLookupMaxLog)) return ZK_E_ARG;
+    ZK_TRY(require_device());
+    const void *p[3] = {T[0]->dptr, T[1]->dptr, T[2]->dptr};
+    FRI_DISPATCH(T[0]->field, return hash_slots_into<F>(p, T[0]->len, slots));
+    return ZK_OK;
+}
+
 int zk_lookup_fractions(const zk_table *const tables[8], const uint64_t *beta, const uint64_t *gamma, zk_table **H) {
     if (!beta || !gamma || !H) return ZK_E_ARG;
     ZK_TRY(check_tables(tables, kLookupGiven + 1, 2));

@@ -13,6 +13,8 @@
   `table_columns(d, rows)` pads a list of triples to 2^d rows by repeating the last one and returns the three columns."""
 import ctypes as C
 
+import numpy as np
+
 from . import _lib as L
 from . import _zerocheck_family as F
 from .mle import MultilinearPolynomial, _elem
@@ -50,6 +52,17 @@ def multiplicities(tables):
     ins = (C.c_void_p * GIVEN)(*[t._h for t in tables])
     L.check(L.lib().zk_lookup_multiplicities(ins, C.byref(m), C.byref(misses)))
     return MultilinearPolynomial(tables[0].field, _handle=m), int(misses.value)
+
+
+def hash_slots(tables):
+    """zk_lookup_hash_slots (include/zkmle.h), a test hook: tables = (T0, T1, T2) of n rows -> the 2 n slots of the hash table as the insert pass
+    of `multiplicities` and of the provers leaves it, a uint32 array; a slot holds the index of a table row or 0xFFFFFFFF (empty)"""
+    if len(tables) != 3:
+        raise ValueError("the hash table takes three tables: T0, T1, T2")
+    slots = np.empty(2 * len(tables[0]), np.uint32)
+    ins = (C.c_void_p * 3)(*[t._h for t in tables])
+    L.check(L.lib().zk_lookup_hash_slots(ins, slots.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return slots
 
 
 def fractions(tables, beta, gamma):
