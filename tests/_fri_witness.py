@@ -1,6 +1,6 @@
 """The committed operands of the FRI fold's last step that need the SECOND subtraction of fe_from_u_below_2p
-(tests/golden/fri_fold_witnesses.json, found by tools/find_fold_witness.hip), as Python integers.  Helper of tests/test_fri_arith_cpu.py
-and tests/test_gpu_fri_edges.py.
+(tests/golden/fri_fold_witnesses.json, found by tools/find_fold_witness.hip), as Python integers.  Helper of tests/test_fri_arith_cpu.py,
+tests/test_gpu_fri_edges.py and, through tests/_fri_ml_edges.py, of tests/test_fri_ml_edges_cpu.py and tests/test_gpu_fri_ml_edges.py.
 
 Everything in the file is in the stored (Montgomery) form x R mod p, R = 2^256; `real` leaves it."""
 import json

@@ -4,7 +4,9 @@ compares byte for byte with the library's own independent paths and with the Pyt
   fold       zk_fri_ml_fold = zk_uni_low_degree_extend(zk_mle_fold(T, last, r), b, c^2) for every codeword length 8 .. 2^15 (ntt_pow2t's
              switch from a table read to a product at 2^13 included), both fields, with and without a coset, r = 0, 1, p - 1 and random;
              r = 0 and r = 1 give the extensions of the even and the odd entries; lengths 2 .. 64 (2 and 4 have no table of two variables
-             behind them) against the model's integers, whose layers tests/test_fri_ml_cpu.py ties to the same extension
+             behind them) against the model's integers, whose layers tests/test_fri_ml_cpu.py ties to the same extension.  The
+             operands uniform tables never reach (the second subtraction of the fold's last step, structured tables, cosets that are
+             roots of unity), against the model's integers up to 2^14: tests/test_gpu_fri_ml_edges.py
   open       every output equals the model's at d = 1 .. 10, b = 1, 2, f = 0, 1, d - 1, Q = 8, and at d = 14, b = 2, f = 3 (several
              workgroups per reduction); y = zk_mle_evaluate; root_0 = the commitment's root; the host verifier accepts; the commitment's
              tables are unchanged

@@ -4,7 +4,9 @@
   fold4      zk_fri_ml_fold4 = two zk_fri_ml_fold calls, both fields, with and without a coset, at the lengths 4 and 8 (one and two lanes),
              2^10 (one workgroup of 256 lanes), 2^11 (two: a table is a power of two, so "one more than a workgroup" is two) and 2^15 (the
              power tables' second level: a product instead of a table read); challenges random and r0, r1 in {0, 1, p - 1}; tables random,
-             all p - 1 and all 0; at 4 and 8 also the model's four-point formula
+             all p - 1 and all 0; at 4 and 8 also the model's four-point formula.  The operands uniform tables never reach (the second
+             subtraction in either pair of the first stage, u0 = u1, u0 + u1 = p, c^2 = p - 1), against two folds of the model up to
+             2^14: tests/test_gpu_fri_ml_edges.py
   open       zk_fri_ml_open_points_arity(log_arity = 2) equals the model of tests/_fri_ml_arity_model.py in every output and passes the host
              verifier: d in {3, 4, 6, 10} with f chosen for R = 2, 3, 4, 5, 6, 8 and 9, b in {1, 2}, with and without a coset, P in {1, 2, 8}
   arity 1    through the new entry point: zk_fri_ml_open_points' bytes at d = 6

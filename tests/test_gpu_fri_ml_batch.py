@@ -5,7 +5,9 @@ is byte for byte; no tolerance anywhere.
   fold      zk_fri_ml_fold_batch equals zk_fri_ml_fold4 (r1 = None: zk_fri_ml_fold) of zk_mle_linear_combination of the codewords: both fields,
             with and without a coset, every length 2^2 .. 2^15 (fold by 2: from 2^1), k in {1, 2, 4, 5, 16} (one group of the lazy sum's four
             products, one past it, the maximum); 2^20 with k = 3 (the grid-stride loop runs more than once); and the operands random tables
-            never reach: every entry and coefficient p - 1 at k = 16, all zeros, one table passed twice, r0 and r1 in {0, 1, p - 1}
+            never reach: every entry and coefficient p - 1 at k = 16, all zeros, one table passed twice, r0 and r1 in {0, 1, p - 1}.
+            Against the model's integers, in the lanes where the single-table kernels need their second subtraction and on structured
+            tables, at k = 2 and 16: tests/test_gpu_fri_ml_edges.py
   opening   equals the model of tests/_fri_ml_batch_model.py in every output on the cases of tests/test_fri_ml_batch_cpu.py (k in {1, 2, 5}, the
             three schedules) and passes zk_fri_ml_verify_batch; a caller's transcript ends in the verifier's state
   k = 1     the claims are those of zk_fri_ml_open_points_arity on the same commitment.  The round polynomials, later roots and final table

@@ -5,7 +5,9 @@ over BLS12-381 Fr and BN254 Fr.  Everything is byte for byte; no tolerance anywh
   fold      zk_fri_ml_fold_batch_wide at k = 17, 20 and 32 equals zk_fri_ml_fold4 (r1 = None: zk_fri_ml_fold) of zk_mle_linear_combination of
             the codewords: both fields, with and without a coset, every codeword length 2^2 .. 2^12, fold by 2 and by 4; at k = 1, 9 and 16 it
             equals zk_fri_ml_fold_batch; every entry and coefficient p - 1 at k = 32 (the one reduction's bound), and zeros; once at length
-            2^20 with k = 17 built from three distinct tables repeated: the second trip of the kernel's grid-stride loop at 768 blocks
+            2^20 with k = 17 built from three distinct tables repeated: the second trip of the kernel's grid-stride loop at 768 blocks.
+            Against the model's integers, in the lanes where the single-table kernels need their second subtraction and on structured
+            tables, at k = 17 and 32: tests/test_gpu_fri_ml_edges.py
   opening   zk_fri_ml_open_batch_wide_pow at k = 17, 20 and 32, d = 4 .. 8, the three schedules, equals the model of
             tests/_fri_ml_wide_model.py in every output and passes zk_fri_ml_verify_batch_wide_pow; once with 8 bits of proof of work; at k = 9
             it equals zk_fri_ml_open_batch_pow byte for byte

@@ -1,7 +1,8 @@
 // find_fold_witness.hip -- host program: a seeded search for operands of the FRI fold's last step (csrc/fri.cuh uni_muladd) whose value
 // before the reduction reaches 2 p, so that fe_from_u_below_2p (csrc/ufield.cuh) needs its SECOND conditional subtraction.  Uniform tables
 // reach that branch about once in 2^28 outputs; tests/golden/fri_fold_witnesses.json holds what this tool found, and the suite replays it
-// (tests/test_fri_arith_cpu.py on the host, tests/test_gpu_fri_edges.py through fri_fold_kernel).  Not run by the suite.
+// (tests/test_fri_arith_cpu.py on the host, tests/test_gpu_fri_edges.py through fri_fold_kernel, tests/test_fri_ml_edges_cpu.py and
+// tests/test_gpu_fri_ml_edges.py through the multilinear folds of csrc/fri_ml.cuh).  Not run by the suite.
 //
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 -pthread tools/find_fold_witness.hip -o find_fold_witness
 //   find_fold_witness <field: 0 = BLS12-381 Fr, 3 = BN254 Fr> <seed> [want = 3] [max_rounds = 40] [threads = 16] [mode = muladd | ufold]
