@@ -760,6 +760,45 @@ int zk_fri_ml_verify_columns_pow(int field, const uint8_t *roots_of_f, const uin
                                  uint32_t npoints, const uint64_t *ys, zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots,
                                  const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint64_t pow_nonce, int *ok);
 
+/* ---- FRI commitment opened against a weight table (extension; csrc/fri_ml.cuh fri_ml_round_w_kernel, csrc/zkmle_fri_ml.hip) --------------------------
+ * The proof of an inner product of a committed table with ANY table: for a commitment of 2^d entries T and a device table W_0 of 2^d entries,
+ *     sum_x T[x] W_0[x] = c.
+ * It is "FRI commitment opened at several points" with the points taken out: that protocol's sumcheck already runs on a weight table,
+ * W_0 = sum_p gamma^p eq(., z^p), and here the caller hands W_0 over.  Everything else -- fields, d, b, f, Q, the coset, the rounds binding
+ * the LAST variable, the three schedules (log_arity 1; 2; 2 on a commitment with grouped leaves), the proof-of-work step -- is as there, in
+ * "... with a fold arity", "... with grouped leaves" and "Proof-of-work grinding".
+ * Transcript (t = NULL: a fresh Transcript::new()): the several-point protocol's with its steps 3 to 7 replaced:
+ *   1. FRI's 48-byte header; at log_arity 2 the 4-byte arity line (and its second word on grouped leaves), as in those protocols;
+ *   2. root_0;
+ *   3. the 4 ASCII bytes "WGHT";
+ *   4. c as the 32-byte canonical big-endian element: c = g_0(0) + g_0(1) comes out of round 0's pass and is appended before g_0;
+ *   5. for l = 0 .. R - 1: g_l(0), g_l(1), g_l(2); r_l; the next committed layer's root where the schedule has one;
+ *   6. the m = 2^f entries of T_R; the proof-of-work step if grinding_bits > 0; the Q indices.
+ * THE WEIGHT TABLE IS NOT ABSORBED.  The statement is only as binding as the caller makes it: W_0, or everything it is computed from, must be
+ * in the transcript before the call (a prover whose rounds produce the table passes the transcript those rounds ran on).
+ * Prover: W_0 is copied into the opening's block (the caller's table is not modified) and folded there beside T; the passes are the
+ * several-point form's, fri_ml_round_w_kernel.  ZK_E_ARG: a NULL (challenges and, with grinding_bits > 0, pow_nonce are required), log_arity
+ * outside 1 .. 2, grouped leaves without log_arity 2, R < 2 at log_arity 2, Q or f out of range, a table of another field;
+ * ZK_E_LEN_MISMATCH: a table of another length; then ZK_E_NO_DEVICE.  Sizes: zk_fri_ml_sizes_weighted = zk_fri_ml_sizes_batch at k = 1.
+ * Verifier (HOST only): zk_fri_ml_verify_points_arity's arguments (and log_group, grinding_bits, pow_nonce) with the points and claims replaced
+ * by c, `challenges` (R elements, as the proof carries them) and w_final (m elements): the caller's W_R, that is W_0 folded over the last
+ * variable R times by those challenges.  fri_verify_core's FriMlClaim switch is extended, not copied.  It replays the rounds and sets *ok = 0
+ * if any replayed r_l differs from challenges[l] -- this is what makes a w_final computed from the proof's own copy of the challenges sound,
+ * and no callback crosses the C ABI -- then checks g_0(0) + g_0(1) = c, the chain claim = g_l(r_l), and
+ * sum_j T_R[j] w_final[j] = g_{R-1}(r_{R-1}), then FRI's query checks unchanged.  Anything unreduced gives *ok = 0; the statuses and "t ends in
+ * the prover's state whenever the status is ZK_OK" are zk_fri_ml_verify's. */
+int zk_fri_ml_sizes_weighted(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
+                             size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround);
+int zk_fri_ml_open_weighted(const zk_fri_commitment *cm, const zk_table *weights, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                            uint32_t grinding_bits, zk_transcript *t, uint64_t *c_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table,
+                            uint64_t *challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths, uint64_t *pow_nonce);
+/* HOST only. */
+int zk_fri_ml_verify_weighted(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries,
+                              uint32_t log_arity, uint32_t log_group, const uint64_t *coset, const uint64_t *c, const uint64_t *challenges,
+                              const uint64_t *w_final, zk_transcript *t, const uint64_t *round_polys, const uint8_t *roots,
+                              const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits,
+                              uint64_t pow_nonce, int *ok);
+
 /* ---- Zerocheck of a product of committed tables (extension; csrc/zerocheck.cuh, csrc/zerocheck_host.h, csrc/zkmle_zerocheck.hip) --------------------
  * The simplest non-linear statement over the commitment above: three commitments cmA, cmB, cmC (zk_fri_commit / zk_fri_commit_grouped; one
  * field, d, log_blowup, coset and log_group) whose tables, read as evaluations over the cube {0,1}^d, satisfy  A[x] B[x] - C[x] = 0  for all x.
@@ -1268,6 +1307,95 @@ int zk_plonk_lookup_verify_columns(int field, const uint8_t *witness_root, const
 /* the calling thread's last zk_plonk_lookup_prove_columns: the fields of zk_plonk_lookup_stats; ms_fractions is the ONE helper kernel,
  * ms_commit the two helper commitments together */
 int zk_plonk_lookup_columns_last_stats(zk_plonk_lookup_stats *out);
+
+/* ---- R1CS instance: sparse matrices times a table (extension; csrc/r1cs.cuh, csrc/r1cs_host.h, csrc/zkmle_r1cs.hip) ----------------------------------
+ * A rank-1 constraint system (A z) o (B z) = C z over ZK_FR381 or ZK_BN254_FR: three sparse matrices of 2^s rows and 2^d columns, s >= 1,
+ * d >= 2, both at most 28.  The handle is what a Spartan prover and its verifier hold of a circuit; here it carries the two sparse passes such
+ * a prover runs, each behind a function of its own: the products feed its first sumcheck (zk_zerocheck_mul_round's pass on A z, B z, C z), and
+ * the bound rows are the weight table of its second, which "FRI commitment opened against a weight table" runs as the opening of the witness.
+ * "R1CS satisfiability" below chains them.  A handle belongs to the device of its first pass (ZK_E_ARG on another).
+ * z = (w || x): the witness w in the columns below 2^(d-1) -- the most significant index bit 0, variable 0 being the most
+ * significant bit as everywhere -- and the public half x above.
+ *
+ * zk_r1cs_create takes, for each of A, B, C, nnz[k] entries in any order: row, column and the value as a reduced element in the host layout
+ * (Montgomery limbs).  Zero values and empty matrices are allowed.  ZK_E_ARG, before any device work: a field other than the two, s or d out
+ * of range, a row or column out of range, an unreduced value, the same (row, column) twice in one matrix, more than 2^32 - 1 entries.  The
+ * handle sorts the entries by (row, column) and builds, on the host, a CSR form of the three matrices for the products and a CSC form (a
+ * counting sort) for the bound rows, with the rows and columns binned by length: up to ZK_R1CS_ROW_SPLIT entries one to a lane, above it one
+ * to a workgroup (a column's length is that of the three matrices together).  This is preprocessing, once per circuit.  Creating a handle
+ * needs no device; the forms are copied to the device when zk_r1cs_matvec or zk_r1cs_bind_rows first needs them, and stay there.
+ *
+ * zk_r1cs_digest = Keccak-256 of: the 7 ASCII bytes "R1CSMAT"; the field id, s, d as big-endian u32; then for A, B, C in turn nnz as a
+ * big-endian u64 and the entries sorted by (row, column), each as row (big-endian u32), column (big-endian u32) and the value as its 32
+ * canonical big-endian bytes.  It does not depend on the order the entries were given in.
+ * zk_r1cs_shape: any output may be NULL; block_items = how many rows (of the 3 2^s) and columns (of the 2^d) lie above ZK_R1CS_ROW_SPLIT.
+ *
+ * zk_r1cs_matvec: out[0 .. 3) = new tables of 2^s entries, A z, B z, C z for the device table z of 2^d entries: one launch sequence over
+ * the rows of all three matrices.  ZK_E_ARG for another field, ZK_E_LEN_MISMATCH for another length, then ZK_E_NO_DEVICE.
+ * zk_r1cs_bind_rows: with E = eq(rx, .) over the 2^s rows (rx: s reduced elements, rx[0] the most significant index bit) and rho (one reduced
+ * element; unreduced: ZK_E_ARG),
+ *     M[y] = sum over the entries (x, y) of A, B, C of rho^k val E[x],   k = 0, 1, 2 for A, B, C,
+ * one pass over the three CSC forms that writes M once.  *out = a new table of the 2^(d-1) witness columns, or with full != 0 of all 2^d.
+ * Every product val * operand of both passes is accumulated as a plain integer and reduced at the latest every 68 (ZK_FR381) or 168
+ * (ZK_BN254_FR) terms; all results are canonical.  The grids are capped by ZK_R1CS_BLOCKS workgroups (1 .. 65536, read at every call). */
+#define ZK_R1CS_ROW_SPLIT 32
+typedef struct zk_r1cs zk_r1cs;
+int zk_r1cs_create(int field, uint32_t log_rows, uint32_t log_cols, const uint32_t *const rows[3], const uint32_t *const cols[3],
+                   const uint64_t *const vals[3], const size_t nnz[3], zk_r1cs **out);
+int zk_r1cs_free(zk_r1cs *inst);
+int zk_r1cs_digest(const zk_r1cs *inst, uint8_t digest32[32]);                                  /* HOST only */
+int zk_r1cs_shape(const zk_r1cs *inst, int *field, uint32_t *log_rows, uint32_t *log_cols, uint64_t nnz[3], uint64_t block_items[2]);   /* HOST only */
+int zk_r1cs_matvec(zk_r1cs *inst, const zk_table *z, zk_table *out[3]);
+int zk_r1cs_bind_rows(zk_r1cs *inst, const uint64_t *rx, const uint64_t *rho, int full, zk_table **out);
+/* ---- R1CS satisfiability: Spartan over a FRI commitment (extension; csrc/r1cs_host.h, csrc/zkmle_r1cs.hip) ------------------------------------------
+ * The proof that (A z) o (B z) = C z for z = (w || x): w the table of 2^(d-1) entries that cmW commits to (cmW->d = d - 1, else ZK_E_ARG; any
+ * leaf grouping the weighted opening accepts), x = (1, pi_1 .. pi_l, 0, ..) the public half, 0 <= l < 2^(d-1).  Two sumchecks from existing
+ * parts: the product zerocheck's rounds over the tables A z, B z, C z, and the opening of w against the weight table of the bound rows, which
+ * IS the second sumcheck sum_y M[y] z[y].  The prover does not check the relation: on a false statement it returns ZK_OK and a proof the
+ * verifier rejects.  This is the Spartan-NIZK form: the verifier is linear in the circuit (no Spark), and nothing is zero knowledge.
+ * Transcript (t = NULL: a fresh one), plain appends in this order:
+ *   1. 16 bytes in one append: "R1CS", then s, d, l as big-endian u32; the 32-byte digest (zk_r1cs_digest); cmW's root; pi_1 .. pi_l, each as the
+ *      32-byte canonical big-endian element, one append each;
+ *   2. tau_0 .. tau_{s-1} by random_challenge_as_field_element();
+ *   3. (nothing is appended) z on the device, the three products (zk_r1cs_matvec's launch), E_0 = eq(., tau);
+ *   4. the s rounds of step 4 of zk_zerocheck_mul_prove on (A z, B z, C z, E): a cubic at the nodes 0 .. 3 per round, then r_l; rx[s-1-l] = r_l;
+ *   5. va, vb, vc = zk_mle_evaluate(A z | B z | C z, rx), appended in that order;
+ *   6. rho = random_challenge_as_field_element();
+ *   7. (nothing is appended) M = zk_r1cs_bind_rows(rx, rho) over the witness half;
+ *   8. the whole protocol of zk_fri_ml_open_weighted on the transcript as it stands, byte for byte: cmW, the weight table M, the caller's
+ *      log_final, nqueries, log_arity, grinding_bits; its claim is c.
+ * Verifier (HOST only; it holds the instance, the 32-byte root and the public values): replays 1, 2, 4, 6 and checks g_0(0) + g_0(1) = 0,
+ * g_l(0) + g_l(1) = g_{l-1}(r_{l-1}), g_{s-1}(r_{s-1}) = eq(rx, tau) (va vb - vc); c = va + rho vb + rho^2 vc - c_pub with
+ *   c_pub = sum over the entries (x, y), y >= 2^(d-1), of rho^k val eq(rx, x) x[y - 2^(d-1)];
+ * then zk_fri_ml_verify_weighted with c, the proof's opening challenges and
+ *   w_final[j] = sum over the entries with y < 2^(d-1), (y >> R) = j, of rho^k val eq(rx, x) prod_{l<R} eq1(r_l, bit l of y),  R = d - 1 - f,
+ * bit 0 the least significant (round l of the opening binds the last variable): two host eq tables and one walk over the entries.  *ok is the
+ * conjunction; anything unreduced gives *ok = 0.  Every status is decided before the transcript moves, and t ends in the prover's state
+ * whenever the status is ZK_OK.  zk_r1cs_public_terms returns c_pub and (w_final not NULL) w_final on their own; nchallenges = R.
+ * Sizes: nzc_round = 4 s elements of round polynomials; the rest zk_fri_ml_sizes_weighted at d - 1.  vs: three elements; tau_out (s elements)
+ * and rho_out are diagnostic and may be NULL; challenges: the s r_l. */
+int zk_r1cs_sizes(uint32_t log_rows, uint32_t log_cols, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group,
+                  size_t *nzc_round, size_t *nroots, size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround);
+int zk_r1cs_prove(zk_r1cs *inst, const zk_fri_commitment *cmW, const uint64_t *public_inputs, uint32_t l, uint32_t log_final, uint32_t nqueries,
+                  uint32_t log_arity, uint32_t grinding_bits, zk_transcript *t, uint64_t *tau_out, uint64_t *round_polys, uint64_t *challenges,
+                  uint64_t *vs_out, uint64_t *rho_out, uint64_t *c_out, uint64_t *open_round_polys, uint8_t *roots, uint64_t *final_table,
+                  uint64_t *open_challenges, uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths, uint64_t *pow_nonce);
+/* HOST only. */
+int zk_r1cs_verify(const zk_r1cs *inst, const uint8_t *root32, const uint64_t *public_inputs, uint32_t l, uint32_t log_blowup, uint32_t log_final,
+                   uint32_t nqueries, uint32_t log_arity, uint32_t log_group, const uint64_t *coset, zk_transcript *t, const uint64_t *round_polys,
+                   const uint64_t *vs, const uint64_t *c, const uint64_t *open_round_polys, const uint8_t *roots, const uint64_t *final_table,
+                   const uint64_t *open_challenges, const uint64_t *query_values, const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce,
+                   int *ok);
+/* HOST only. */
+int zk_r1cs_public_terms(const zk_r1cs *inst, const uint64_t *public_inputs, uint32_t l, const uint64_t *rx, const uint64_t *rho,
+                         const uint64_t *open_challenges, uint32_t nchallenges, uint64_t *c_pub, uint64_t *w_final);
+/* the calling thread's last zk_r1cs_prove: the products (with z's assembly), E_0, the rounds, the row binding (with eq(rx, .)), the opening and
+ * the total, in ms.  zk_r1cs_matvec sets ms_products and zk_r1cs_bind_rows ms_eq (its table eq(rx, .)) and ms_bind: device events around the
+ * launches alone */
+typedef struct {
+    float ms_products, ms_eq, ms_rounds, ms_bind, ms_opening, ms_total;
+} zk_r1cs_stats;
+int zk_r1cs_last_stats(zk_r1cs_stats *out);
 
 /* ---- univariate helpers (host; polynomials/src/univariate/dense_univariate.rs) ------------------ */
 int zk_uni_evaluate(int field, const uint64_t *coeffs, size_t n, const uint64_t *x, uint64_t *out);        /* :57 */

@@ -19,7 +19,7 @@ from .merkle import MerkleTree, merkle_root  # noqa: F401
 from . import ntt  # noqa: F401  (the module, like merkle and kzg: the transform itself is zk.ntt.ntt)
 from .ntt import two_adicity, root_of_unity, ntt_inplace, low_degree_extend, poly_mul, evaluate_at  # noqa: F401
 from . import fri  # noqa: F401  (the module: zk.fri.prove, zk.fri.verify, ...)
-from .fri import FriProof, FriCommitment, FriOpening, FriMlOpening  # noqa: F401
+from .fri import FriProof, FriCommitment, FriOpening, FriMlOpening, FriMlWeightedOpening  # noqa: F401
 from . import zerocheck  # noqa: F401  (the module: zk.zerocheck.prove_mul, zk.zerocheck.verify_mul, ...)
 from . import wiring  # noqa: F401  (the module: zk.wiring.prove, zk.wiring.verify, ...)
 from .wiring import WiringProof  # noqa: F401
@@ -30,6 +30,8 @@ from .lookup import LookupProof  # noqa: F401
 from . import plonk_lookup  # noqa: F401  (the module: zk.plonk_lookup.prove, zk.plonk_lookup.verify, ...)
 from .plonk_lookup import PlonkLookupProof  # noqa: F401
 from .plonk_lookup import PlonkLookupColumnsProof  # noqa: F401
+from . import r1cs  # noqa: F401  (the module: zk.r1cs.matvec, zk.r1cs.bind_rows, ...)
+from .r1cs import R1CS, R1CSProof  # noqa: F401
 from . import gkr  # noqa: F401
 from .gkr import Circuit, Gate, Layer, Operator  # noqa: F401
 from . import kzg  # noqa: F401

@@ -197,6 +197,11 @@ def lib():
         "zk_fri_ml_open_columns_pow": [C.POINTER(vp), C.c_uint32, u64p] + [C.c_uint32] * 4 + [vp, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
         "zk_fri_ml_verify_columns_pow": [C.c_int, u8p, C.POINTER(C.c_uint32)] + [C.c_uint32] * 6 + [u64p, u64p, C.c_uint32, u64p, vp, u64p, u8p, u64p, u64p, u8p,
                                                                                                    C.c_uint64, C.POINTER(C.c_int)],
+        # a FRI commitment opened against a caller's weight table
+        "zk_fri_ml_sizes_weighted": [C.c_uint32] * 6 + [C.POINTER(sz)] * 5,
+        "zk_fri_ml_open_weighted": [vp, vp] + [C.c_uint32] * 4 + [vp, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
+        "zk_fri_ml_verify_weighted": [C.c_int, u8p] + [C.c_uint32] * 6 + [u64p, u64p, u64p, u64p, vp, u64p, u8p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
+                                                                         C.POINTER(C.c_int)],
         # zerocheck of a product of committed tables
         "zk_zerocheck_mul_round": [vp, vp, vp, vp, u64p, C.POINTER(vp), u64p],
         "zk_zerocheck_sizes": [C.c_uint32] * 6 + [C.POINTER(sz)] * 6,
@@ -244,6 +249,20 @@ def lib():
         "zk_plonk_lookup_prove_columns": [vp, vp, u64p] + [C.c_uint32] * 4 + zh_prove,
         "zk_plonk_lookup_verify_columns": [C.c_int, u8p, u8p, u64p] + [C.c_uint32] * 5 + zh_verify,
         "zk_plonk_lookup_columns_last_stats": [vp],
+        # R1CS instance: three sparse matrices, their products with a table and their rows bound at a point
+        "zk_r1cs_create": [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(u64p),
+                           C.POINTER(sz), C.POINTER(vp)],
+        "zk_r1cs_free": [vp],
+        "zk_r1cs_digest": [vp, u8p],
+        "zk_r1cs_shape": [vp, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64p, u64p],
+        "zk_r1cs_matvec": [vp, vp, C.POINTER(vp)],
+        "zk_r1cs_bind_rows": [vp, u64p, u64p, C.c_int, C.POINTER(vp)],
+        "zk_r1cs_last_stats": [vp],
+        "zk_r1cs_sizes": [C.c_uint32] * 7 + [C.POINTER(sz)] * 6,
+        "zk_r1cs_prove": [vp, vp, u64p] + [C.c_uint32] * 5 + [vp, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u64p, u8p, u64p],
+        "zk_r1cs_verify": [vp, u8p, u64p] + [C.c_uint32] * 6 + [u64p, vp, u64p, u64p, u64p, u64p, u8p, u64p, u64p, u64p, u8p, C.c_uint32, C.c_uint64,
+                                                               C.POINTER(C.c_int)],
+        "zk_r1cs_public_terms": [vp, u64p, C.c_uint32, u64p, u64p, u64p, C.c_uint32, u64p, u64p],
         # sparse GKR: one phase's table kernel on caller-chosen tables (a gate array is passed as a void pointer)
         "zk_gkr_sparse_phase_tables": [C.c_int, C.c_int, vp, sz, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, u64p,
                                        C.POINTER(vp), C.POINTER(vp)],

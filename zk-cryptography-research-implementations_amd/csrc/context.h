@@ -145,6 +145,10 @@ struct FriMlClaim {
     // holds the ntables columns' values as ever but ONE path per commitment, whose leaf is hashed from that commitment's 4 w_i values
     const uint32_t *widths = nullptr;
     uint32_t ncommit = 0;
+    // weighted_c != null: the opening against a caller's weight table ("FRI commitment opened against a weight table"; needs npoints = 0 and
+    // ntables = 0; z and y are not read): "WGHT" and the claim c follow root_0 (and the arity line), the sumcheck starts from c and ends in
+    // sum_j T_R[j] w_final[j], and every replayed r_l must equal challenges[l] (R elements, as the proof carries them)
+    const uint64_t *weighted_c = nullptr, *challenges = nullptr, *w_final = nullptr;
 };
 // zk_fri_ml_open_columns_pow's own statuses (zkmle_fri_ml.hip), every ZK_E_ARG and then ZK_E_NO_DEVICE, as fri_ml_open_batch_check for a prover
 // that runs rounds of its own before it opens column commitments
@@ -166,6 +170,11 @@ int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_fin
 int fri_ml_open_batch_check(const zk_fri_commitment *const *cms, uint32_t k, const uint64_t *points, uint32_t npoints, uint32_t log_final, uint32_t nqueries,
                             uint32_t log_arity, const uint64_t *ys_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *query_values,
                             uint8_t *query_paths, uint32_t grinding_bits, const uint64_t *pow_nonce, uint32_t max_tables = ZK_FRI_ML_BATCH_MAX);   // ZK_FRI_ML_WIDE_MAX: zk_fri_ml_open_batch_wide_pow's
+// zk_fri_ml_open_weighted's own statuses (zkmle_fri_ml.hip), every ZK_E_ARG, ZK_E_LEN_MISMATCH and then ZK_E_NO_DEVICE, for a prover that runs
+// rounds of its own on the transcript before it opens against a weight table those rounds produce
+int fri_ml_open_weighted_check(const zk_fri_commitment *cm, const zk_table *weights, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                               const uint64_t *c_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, const uint64_t *challenges,
+                               uint64_t *query_values, uint8_t *query_paths, uint32_t grinding_bits, const uint64_t *pow_nonce);
 // steps 1-3 of the proof-of-work step on `tr` with the search on the GPU (zkmle_grind.hip): zk_transcript_grind's checks and body
 int transcript_grind(Transcript &tr, uint32_t bits, uint64_t start, uint32_t log_batch, uint64_t *nonce);
 // Prover::prove (prover.rs:35-71) on a caller's Transcript whose binding append (:38-39) is the 32 bytes `bound` -- a commitment the caller

@@ -206,7 +206,10 @@ template <class F> Replayed<F> replay(uint32_t d, uint32_t b, uint32_t f, uint32
         }
         tr.append(roots, 32);
     }
-    if (ml && ml->npoints == 0) {                            // z_0 .. z_{d-1}, then y
+    if (ml && ml->weighted_c) {                              // "WGHT", then the claim c; the weight table is the caller's to bind
+        tr.append((const uint8_t *)"WGHT", 4);
+        absorb(ml->weighted_c);
+    } else if (ml && ml->npoints == 0) {                     // z_0 .. z_{d-1}, then y
         for (unsigned i = 0; i < d; i++) absorb(ml->z + (size_t)i * W);
         absorb(ml->y);
     } else if (ml) {                                         // P, the points (point-major), the claims, then gamma
@@ -234,11 +237,39 @@ template <class F> Replayed<F> replay(uint32_t d, uint32_t b, uint32_t f, uint32
 
 // the sumcheck of sum_x T[x] W[x] = sum_p gamma^p y_p beside the folds, on the same challenges; the single-point form is one point with gamma^0.
 // k tables together: T = sum_j alpha^j T_j, alpha = gamma^P, so only the first claim differs: sum_j sum_p gamma^(j P + p) y_{j,p}
+// g(r) from g's values at 0, 1, 2:  g0 (r - 1)(r - 2) / 2 - g1 r (r - 2) + g2 r (r - 1) / 2
+template <class F> Fe<F> g3_at(const Fe<F> &g0, const Fe<F> &g1, const Fe<F> &g2, const Fe<F> &r) {
+    const Fe<F> one = fe_one<F>(), two = fe_from_u64<F>(2), r1 = fe_sub<F>(r, one), r2 = fe_sub<F>(r, two);
+    const Fe<F> outer = fe_mul<F>(fe_inv<F>(two), fe_add<F>(fe_mul<F>(g0, fe_mul<F>(r1, r2)), fe_mul<F>(g2, fe_mul<F>(r, r1))));
+    return fe_sub<F>(outer, fe_mul<F>(g1, fe_mul<F>(r, r2)));
+}
+
+// the same sumcheck against a caller's weight table (ml.weighted_c): the first claim is c, every r_l must be the challenge the proof carries --
+// the caller folded its table by those -- and the end is sum_j T_R[j] w_final[j]
+template <class F> bool weighted_sumcheck_holds(uint32_t d, uint32_t f, const FriMlClaim &ml, const Replayed<F> &rp) {
+    constexpr int W = F::N / 2;
+    const unsigned R = d - f;
+    const size_t m = (size_t)1 << f;
+    for (size_t i = 0; i < R + m; i++)                        // the carried challenges, then w_final: reduced
+        if (!is_reduced<F>(i < R ? ml.challenges + i * W : ml.w_final + (i - R) * W)) return false;
+    Fe<F> claim = load_host<F>(ml.weighted_c);
+    for (unsigned l = 0; l < R; l++) {
+        const uint64_t *g = ml.round_polys + (size_t)l * 3 * W;
+        const Fe<F> g0 = load_host<F>(g), g1 = load_host<F>(g + W), g2 = load_host<F>(g + 2 * W);
+        if (!fe_eq<F>(rp.beta[l], load_host<F>(ml.challenges + (size_t)l * W)) || !fe_eq<F>(fe_add<F>(g0, g1), claim)) return false;
+        claim = g3_at<F>(g0, g1, g2, rp.beta[l]);
+    }
+    Fe<F> end = fe_zero<F>();
+    for (size_t j = 0; j < m; j++) end = fe_add<F>(end, fe_mul<F>(rp.h[j], load_host<F>(ml.w_final + j * W)));
+    return fe_eq<F>(end, claim);
+}
+
 template <class F> bool sumcheck_holds(uint32_t d, uint32_t f, const FriMlClaim &ml, const Replayed<F> &rp) {
     constexpr int W = F::N / 2;
+    if (ml.weighted_c) return weighted_sumcheck_holds<F>(d, f, ml, rp);
     const unsigned R = d - f, np = ml.npoints ? ml.npoints : 1;
     const size_t m = (size_t)1 << f;
-    const Fe<F> one = fe_one<F>(), two = fe_from_u64<F>(2), inv2 = fe_inv<F>(two);
+    const Fe<F> one = fe_one<F>(), two = fe_from_u64<F>(2);
     std::vector<Fe<F>> A(np, one);                            // per point p: gamma^p A^p_l
     Fe<F> claim = fe_zero<F>();
     for (unsigned p = 1; p < np; p++) A[p] = fe_mul<F>(A[p - 1], rp.gamma);
@@ -251,10 +282,7 @@ template <class F> bool sumcheck_holds(uint32_t d, uint32_t f, const FriMlClaim 
         const uint64_t *g = ml.round_polys + (size_t)l * 3 * W;
         const Fe<F> g0 = load_host<F>(g), g1 = load_host<F>(g + W), g2 = load_host<F>(g + 2 * W), r = rp.beta[l];
         if (!fe_eq<F>(fe_add<F>(g0, g1), claim)) return false;
-        // g_l(r) from its values at 0, 1, 2:  g0 (r - 1)(r - 2) / 2 - g1 r (r - 2) + g2 r (r - 1) / 2
-        const Fe<F> r1 = fe_sub<F>(r, one), r2 = fe_sub<F>(r, two);
-        const Fe<F> outer = fe_mul<F>(inv2, fe_add<F>(fe_mul<F>(g0, fe_mul<F>(r1, r2)), fe_mul<F>(g2, fe_mul<F>(r, r1))));
-        claim = fe_sub<F>(outer, fe_mul<F>(g1, fe_mul<F>(r, r2)));
+        claim = g3_at<F>(g0, g1, g2, r);
         for (unsigned p = 0; p < np; p++) {
             const Fe<F> zv = load_host<F>(ml.z + ((size_t)p * d + d - 1 - l) * W);   // eq1(r_l, z_v) = 1 - r - z + 2 r z
             A[p] = fe_mul<F>(A[p], fe_add<F>(fe_sub<F>(fe_sub<F>(one, r), zv), fe_mul<F>(two, fe_mul<F>(r, zv))));
@@ -376,8 +404,10 @@ int fri_verify_core(int field, uint32_t d, uint32_t log_blowup, uint32_t log_fin
                     const uint8_t *roots, const uint64_t *final_coeffs, const uint64_t *query_values, const uint8_t *query_paths, int *ok,
                     uint64_t *indices_out, const FriMlClaim *ml, uint32_t grind_bits, uint64_t pow_nonce, uint32_t max_tables) {
     if (grind_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
-    if (ml && (!ml->z || !ml->y || !ml->round_polys || ml->npoints > 8)) return ZK_E_ARG;
-    if (ml && (ml->log_arity < 1 || ml->log_arity > 2 || (ml->log_arity == 2 && (ml->npoints < 1 || log_final >= d || d - log_final < 2)))) return ZK_E_ARG;
+    const bool weighted = ml && ml->weighted_c;               // a weight table stands where the points do
+    if (weighted && (!ml->challenges || !ml->w_final || !ml->round_polys || ml->npoints || ml->ntables)) return ZK_E_ARG;
+    if (ml && !weighted && (!ml->z || !ml->y || !ml->round_polys || ml->npoints > 8)) return ZK_E_ARG;
+    if (ml && (ml->log_arity < 1 || ml->log_arity > 2 || (ml->log_arity == 2 && ((ml->npoints < 1 && !weighted) || log_final >= d || d - log_final < 2)))) return ZK_E_ARG;
     if (ml && ml->grouped && ml->log_arity != 2) return ZK_E_ARG;
     if (ml && (ml->ntables > max_tables || (ml->ntables && ml->npoints < 1))) return ZK_E_ARG;
     if (ml && ml->ncommit) {                                 // column commitments: grouped leaves, and the widths make up the tables

@@ -324,6 +324,40 @@ template <class F> struct ManyPoints {
     void bind(unsigned, const Fe<F> &) {}
 };
 
+// a caller's weight table W_0 of n entries ("FRI commitment opened against a weight table"): ManyPoints without points.  Nothing of the table
+// enters the transcript; the claim c = g_0(0) + g_0(1) comes out of round 0's pass and is appended before g_0, as OnePoint's y is
+template <class F> struct Weighted {
+    static constexpr int W = F::N / 2;
+    static constexpr unsigned kSums = 3;
+    static constexpr bool kBatch = false;
+    const void *w0;                                          // device, n elements; not modified
+    uint64_t *c_out;
+    unsigned d;
+
+    size_t weight_room(size_t n) const { return 2 * n; }     // W_0 .. W_{R-1}
+    size_t weight_off(size_t n, unsigned l) const { return 2 * n - ((2 * n) >> l); }
+    void absorb(Transcript &tr) const { tr.append((const uint8_t *)"WGHT", 4); }
+    // W_0 = the caller's table, copied into the weights' room (the later rounds fold it there); round 0's pass writes nothing
+    int start(const zk_fri_commitment *, Transcript &, const PassMem &m) {
+        const size_t n = (size_t)1 << d;
+        ZK_HIP(hipMemcpyAsync(m.weights, w0, n * sizeof(Fe<F>), hipMemcpyDeviceToDevice, cur_stream()));
+        return pass(false, m.T0, m.weights, nullptr, nullptr, n / 2, fe_one<F>(), m.partials, m.sums);
+    }
+    void release() {}
+    static int pass(bool fold, const void *tin, const void *win, void *tout, void *wout, size_t q, const Fe<F> &r, void *partials, void *sums) {
+        return launch_round_w<F>(fold, tin, win, tout, wout, q, r, partials, sums);
+    }
+    void round_poly(unsigned l, const Fe<F> *S, Transcript &tr, Fe<F> g[3]) const {
+        nodes_to_g3<F>(S, g);
+        if (l == 0) {
+            const Fe<F> c = fe_add<F>(g[0], g[1]);
+            store_host<F>(c_out, c);
+            tr.append_be<F>(c);
+        }
+    }
+    void bind(unsigned, const Fe<F> &) {}
+};
+
 // k commitments at the same P points ("FRI commitments opened together"): ManyPoints on T = sum_j alpha^j T_j, alpha = gamma^P.  T_0 is
 // written into n further elements behind the weights (round 1 reads it anyway); f_0 = sum_j alpha^j f_j is never stored: the first step's
 // fold forms it in registers (fri_ml_fold_batch_kernel), and a query's step-0 answers come from the k commitments' own codewords and trees.
@@ -700,7 +734,8 @@ int verify_opening(int field, const uint8_t *root32, uint32_t d, uint32_t log_bl
                    const FriMlClaim &ml, zk_transcript *t, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
                    const uint8_t *query_paths, int *ok, uint32_t grind_bits = 0, uint64_t pow_nonce = 0, uint32_t max_tables = ZK_FRI_ML_BATCH_MAX) {
     if (grind_bits > ZK_FRI_GRIND_MAX_BITS) return ZK_E_ARG;
-    if (!root32 || !ml.z || !ml.y || !ml.round_polys || !roots || !final_table || !query_values || !query_paths || !ok) return ZK_E_ARG;
+    if (ml.weighted_c ? (!ml.challenges || !ml.w_final) : (!ml.z || !ml.y)) return ZK_E_ARG;
+    if (!root32 || !ml.round_polys || !roots || !final_table || !query_values || !query_paths || !ok) return ZK_E_ARG;
     if (field_limbs64(field) < 0 || log_blowup < 1 || log_blowup > 8 || nqueries < 1 || nqueries > 4096 || d < 1 || log_final >= d) return ZK_E_ARG;
     if (ml.log_arity == 2 && d - log_final < 2) return ZK_E_ARG;
     if (coset && is_zero_element(field, coset)) return ZK_E_ARG;
@@ -800,6 +835,19 @@ int zk::fri_ml_open_batch_check(const zk_fri_commitment *const *cms, uint32_t k,
                                 uint8_t *query_paths, uint32_t grinding_bits, const uint64_t *pow_nonce, uint32_t max_tables) {
     return open_batch_check(cms, k, points, npoints, log_final, nqueries, log_arity, ys_out, OpenOut{round_polys, roots, final_table, nullptr, nullptr, query_values, query_paths},
                             grinding_bits, pow_nonce, max_tables);
+}
+
+int zk::fri_ml_open_weighted_check(const zk_fri_commitment *cm, const zk_table *weights, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                                   const uint64_t *c_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, const uint64_t *challenges,
+                                   uint64_t *query_values, uint8_t *query_paths, uint32_t grinding_bits, const uint64_t *pow_nonce) {
+    if (grinding_bits > ZK_FRI_GRIND_MAX_BITS || (grinding_bits && !pow_nonce)) return ZK_E_ARG;
+    if (!cm || !weights || !c_out || !round_polys || !roots || !final_table || !challenges || !query_values || !query_paths) return ZK_E_ARG;
+    if (log_arity < 1 || log_arity > 2 || (cm->log_group != 0 && cm->log_group != 2) || (cm->log_group == 2 && log_arity != 2)) return ZK_E_ARG;
+    ZK_TRY(open_check(cm, nullptr, log_final, nqueries, cm->log_group));
+    if (log_arity == 2 && cm->d - log_final < 2) return ZK_E_ARG;
+    if (weights->field != cm->field) return ZK_E_ARG;
+    if (weights->len != (size_t)1 << cm->d) return ZK_E_LEN_MISMATCH;
+    return require_device();
 }
 
 extern "C" {
@@ -1084,6 +1132,38 @@ int zk_fri_ml_verify_points(int field, const uint8_t *root32, uint32_t d, uint32
                             const uint64_t *final_table, const uint64_t *query_values, const uint8_t *query_paths, int *ok) {
     return zk_fri_ml_verify_points_arity(field, root32, d, log_blowup, log_final, nqueries, 1, coset, points, npoints, ys, t, round_polys, roots, final_table,
                                          query_values, query_paths, ok);
+}
+
+// ---- the opening against a weight table ----------------------------------------------------------------------------------------------
+int zk_fri_ml_sizes_weighted(uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t log_group, size_t *nroots,
+                             size_t *nfinal, size_t *nvalues, size_t *path_bytes, size_t *nround) {
+    return zk_fri_ml_sizes_batch(1, d, log_blowup, log_final, nqueries, log_arity, log_group, nroots, nfinal, nvalues, path_bytes, nround);
+}
+
+int zk_fri_ml_open_weighted(const zk_fri_commitment *cm, const zk_table *weights, uint32_t log_final, uint32_t nqueries, uint32_t log_arity, uint32_t grinding_bits,
+                            zk_transcript *t, uint64_t *c_out, uint64_t *round_polys, uint8_t *roots, uint64_t *final_table, uint64_t *challenges,
+                            uint64_t *query_indices, uint64_t *query_values, uint8_t *query_paths, uint64_t *pow_nonce) {
+    const OpenOut o{round_polys, roots, final_table, challenges, query_indices, query_values, query_paths};
+    ZK_TRY(zk::fri_ml_open_weighted_check(cm, weights, log_final, nqueries, log_arity, c_out, round_polys, roots, final_table, challenges, query_values, query_paths,
+                                          grinding_bits, pow_nonce));
+    Transcript fresh;
+    FRI_DISPATCH(cm->field, Weighted<F> form{weights->dptr, c_out, cm->d};
+                 return open_with<F>(cm, form, log_final, nqueries, log_arity, cm->log_group == 2, t ? t->t : fresh, o, grinding_bits, pow_nonce));
+    return ZK_OK;
+}
+
+int zk_fri_ml_verify_weighted(int field, const uint8_t *root32, uint32_t d, uint32_t log_blowup, uint32_t log_final, uint32_t nqueries, uint32_t log_arity,
+                              uint32_t log_group, const uint64_t *coset, const uint64_t *c, const uint64_t *challenges, const uint64_t *w_final, zk_transcript *t,
+                              const uint64_t *round_polys, const uint8_t *roots, const uint64_t *final_table, const uint64_t *query_values,
+                              const uint8_t *query_paths, uint32_t grinding_bits, uint64_t pow_nonce, int *ok) {
+    if (!c || log_arity < 1 || log_arity > 2 || (log_group != 0 && log_group != 2) || (log_group == 2 && log_arity != 2)) return ZK_E_ARG;
+    FriMlClaim ml{nullptr, nullptr, round_polys};
+    ml.log_arity = log_arity;
+    ml.grouped = log_group == 2;
+    ml.weighted_c = c;
+    ml.challenges = challenges;
+    ml.w_final = w_final;
+    return verify_opening(field, root32, d, log_blowup, log_final, nqueries, coset, ml, t, roots, final_table, query_values, query_paths, ok, grinding_bits, pow_nonce);
 }
 
 int zk_fri_ml_last_stats(zk_fri_ml_stats *out) {

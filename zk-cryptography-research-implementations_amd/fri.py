@@ -501,6 +501,55 @@ def verify_multilinear_batch(roots, points, opening, transcript=None):
     return bool(ok.value)
 
 
+# ---- the opening against a weight table ---------------------------------------------------------------------------------------------------
+class FriMlWeightedOpening(FriMlOpening):
+    """The opening of sum_x T[x] W[x] = c against a caller's weight table: FriMlOpening with c (limbs,) in place of y; challenges (R, limbs) are
+    part of the proof here (the verifier compares them with its own); query_values (Q, per, limbs); grinding_bits and pow_nonce as a batch's."""
+
+    def __init__(self, field, d, log_blowup, log_final, nqueries, coset=None, log_arity=1, grouped=False, grinding_bits=0):
+        super().__init__(field, d, log_blowup, log_final, nqueries, coset, log_arity, grouped)
+        del self.y
+        self.log_arity, self.grouped, self.grinding_bits, self.pow_nonce = log_arity, grouped, grinding_bits, 0
+        self.c = np.zeros(limbs(field), np.uint64)
+        self.query_values = self.query_values.reshape(nqueries, -1, limbs(field))
+
+
+def ml_sizes_weighted(d, log_blowup, log_final, nqueries, log_arity=1, grouped=False):
+    """-> (nroots, nfinal, nvalues, path_bytes, nround) of an opening against a weight table: ml_sizes' counts of one table"""
+    out = [C.c_size_t(0) for _ in range(5)]
+    L.check(L.lib().zk_fri_ml_sizes_weighted(d, log_blowup, log_final, nqueries, log_arity, 2 if grouped else 0, *[C.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+def open_weighted(commitment, weights, log_final, nqueries, log_arity=1, transcript=None, grinding_bits=0):
+    """the proof that the committed table T and the device table `weights` (2^d entries, not modified) have the inner product `.c`.  The weight
+    table does NOT enter the transcript: the caller has bound it (or what it is computed from) to `transcript` already.  A commitment with
+    grouped leaves needs log_arity=2."""
+    grouped = getattr(commitment, "log_group", 0) != 0
+    if grouped and log_arity != 2:
+        raise ValueError("a commitment with grouped leaves is opened with log_arity=2")
+    op = FriMlWeightedOpening(commitment.field, commitment.d, commitment.log_blowup, log_final, nqueries, commitment.coset, log_arity, grouped, grinding_bits)
+    nonce = C.c_uint64(0)
+    L.check(L.lib().zk_fri_ml_open_weighted(commitment._h, weights._h, log_final, nqueries, log_arity, grinding_bits, _handle(transcript), L.p64(op.c),
+                                            L.p64(op.round_polys), L.p8(op.roots), L.p64(op.final_table), L.p64(op.challenges), L.p64(op.query_indices),
+                                            L.p64(op.query_values), L.p8(op.query_paths), C.byref(nonce)))
+    op.pow_nonce = int(nonce.value)
+    return op
+
+
+def verify_weighted(root, w_final, opening, transcript=None):
+    """host only: `root` = the commitment's 32 bytes; w_final (2^log_final, limbs) = the caller's weight table folded over its last variable by
+    opening.challenges, one after the other.  The verifier refuses an opening whose carried challenges are not the transcript's."""
+    op, ok = opening, C.c_int(0)
+    rf, _, c, proof = _verifier_inputs(op, [root], op.c)
+    wf, ch = np.ascontiguousarray(w_final, np.uint64), np.ascontiguousarray(op.challenges, np.uint64)
+    if wf.shape != (1 << op.log_final, limbs(op.field)) or ch.shape != (op.d - op.log_final, limbs(op.field)):
+        raise L.ZkError(L.ZK_E_ARG, "w_final has 2^log_final elements and the opening one challenge per round")
+    L.check(L.lib().zk_fri_ml_verify_weighted(op.field, rf, op.d, op.log_blowup, op.log_final, op.nqueries, op.log_arity, 2 if op.grouped else 0, op._coset(),
+                                              L.p64(c), L.p64(ch), L.p64(wf), _handle(transcript), *proof, op.grinding_bits, op.pow_nonce, C.byref(ok)))
+    return bool(ok.value)
+
+
 # ---- several commitments opened together, wide: up to 32 ----------------------------------------------------------------------------------
 # The narrow functions above keep their cap of 16.  These are the same protocol byte for byte, for k <= 32.
 def ml_sizes_wide(d, log_blowup, log_final, nqueries, log_arity=1, grouped=False, k=1):
